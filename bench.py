@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- samples/sec of DLPM's reverse-sampling loop at T=1000 on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1: started under torch.distributed.run (RANK / WORLD_SIZE set) the process is one rank; started
 plainly, it spawns the N ranks itself (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -13,12 +13,22 @@ state [1024, 3, 32, 32], the reference's cifar10.yml UNet (39.6 M parameters, at
 alpha = 1.7, clamp_a = 10, clamp_eps = 50, fp32, Philox noise keyed by the global sample index.
 
 A "step" is ONE reverse step (UNet forward + fused update) over the whole batch: W warm-up steps,
-then exactly K timed steps between barrier + synchronize pairs, max over ranks -> `ms_per_step`.
-`value` [samples/s at T=1000] is then MEASURED, not extrapolated: one whole trajectory -- init (A
-draws, tables, x_T) + all T-1 = 999 reverse steps + the final RCCL all-gather (N > 1) -- is timed
-between barriers in the same run (`full_trajectory_s`, max over ranks) and value = B_total / that.
-`--no-full-trajectory` skips it; value is then init + 999 * ms_per_step + gather and says so
-(`value_source`).  With --steps 999 --warmup 0 the K-step region is itself a whole trajectory.
+then exactly K timed steps between barrier + synchronize pairs, max over ranks -> `ms_per_step`
+(W + K <= 999, the steps of one trajectory).  `value` [samples/s at T=1000] = B_total / (init (A
+draws, tables, x_T) + 999 * ms_per_step + the final RCCL all-gather (N > 1)), and `value_source`
+says so.  With --steps 999 --warmup 0 the K-step region is itself a whole trajectory, and `value`
+is measured from it.
+
+A plain run does only that.  --full adds, after the headline figure, everything else the line
+reports: one whole trajectory timed between barriers (`full_trajectory_s`, max over ranks; `value`
+is then B_total / that, MEASURED), rocm-smi board power / clock samples, the instrumented eager
+pass behind `roofline` and the per-kernel figures, and the CPU baseline (N = 1).  --no-full-trajectory,
+--no-board-sampler, --no-prof and --no-cpu-baseline switch single parts of a --full run off.
+
+--dump-outputs DIR writes the samples' state after the last timed step (what dlpm_sampler_copy_state
+hands a caller; the gathered batch for N > 1) as DIR/state.npy, float32.  Every input is seeded, so
+the same arguments give the same inputs on every run; a state beyond 64 MB is cut to a fixed, seeded
+sample of whole samples (rows of the batch).
 """
 import os as _os
 # (before torch is imported: the CPU-baseline leg's OpenMP barriers wait passively -- spinning threads lose whole steps to any
@@ -93,6 +103,21 @@ def parse_prof(txt):
         name, n, ms, fl, by = line.split()
         out[name] = dict(launches=int(n), ms=float(ms), flops=float(fl), bytes=float(by))
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, name, x, limit=DUMP_LIMIT_BYTES):
+    """x (a batch, samples along dim 0) -> d/<name>.npy as float32.  Beyond `limit` bytes: a fixed, seeded sample of whole
+    rows, in batch order, so that two builds run with the same arguments write comparable files."""
+    import numpy as np
+    a = x.detach().float().cpu().numpy()
+    if a.nbytes > limit:
+        keep = max(1, limit // a[0].nbytes)
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a))
 
 
 def physical_cores():
@@ -558,7 +583,14 @@ def main():
     ap.add_argument('--lim', action='store_true',
                     help='LIM sampler variant (--method lim of the reference, SDE updates): T network evaluations; '
                          'not the headline config')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline figure, also time one whole trajectory (value measured from it), sample board power, '
+                         'run the instrumented per-kernel pass (roofline) and the CPU baseline; a plain run does none of these')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the state after the last timed step as DIR/state.npy (float32; a seeded sample of rows beyond 64 MB)')
     args = ap.parse_args()
+    if not args.full:
+        args.no_full_trajectory = args.no_board_sampler = args.no_prof = args.no_cpu_baseline = True
 
     if args.cpu_baseline_only:
         cfg_name, _, T, alpha = WORKLOADS[args.workload]
@@ -657,6 +689,8 @@ def main():
         full = x
     finite = bool(torch.isfinite(full).all().item())
     assert full.shape[0] == B * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, 'state', full)
     # ---- who ran: one record per rank (rank, device index, UUID / PCI address, its own step time, a checksum of ITS shard and of
     # the same rows of the gathered batch), collected with ONE all_gather_object -- so that the line proves N distinct devices and
     # that the collective of the stated backend delivered every rank's shard

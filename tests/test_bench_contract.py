@@ -6,7 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
 
@@ -14,6 +16,52 @@ TOP_KEYS = {'metric': str, 'value': float, 'unit': str, 'n_gpus': int, 'steps': 
             'higher_is_better': bool, 'scaling': str, 'dtype': str, 'data': str, 'config': dict}
 ROOFLINE_KEYS = ('bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')
 CPU_KEYS = ('value', 'unit', 'cores', 'kind', 'sample')
+
+
+FULL_ONLY_KEYS = ('full_trajectory_s', 'roofline', 'board', 'cpu_baseline', 'ms_per_step_by_kernel_class')
+
+
+def _bench(argv, extra_env=None, timeout=600):
+    """One `bench.py` process -> its one JSON line."""
+    env = dict(os.environ, **(extra_env or {}))
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + argv, env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_lean_and_dumps_the_last_timed_state(tmp_path):
+    """A plain `bench.py --steps K --warmup W` (stub sampler, DLPM_BENCH_DRY_RUN) times its K steps and nothing else: `value`
+    from init + 999 x ms_per_step, every --full part null.  --dump-outputs writes the state after the last timed step, the same
+    on every run with the same arguments."""
+    for d in ('a', 'b'):
+        j = _bench(['--gpus', '1', '--steps', '3', '--warmup', '2', '--batch', '4', '--dump-outputs', str(tmp_path / d)],
+                   {'DLPM_BENCH_DRY_RUN': '1'})
+    assert j['steps'] == 3 and j['warmup'] == 2 and j['value_source'].startswith('extrapolated') and j['value'] == j['extrapolated_value']
+    for k in FULL_ONLY_KEYS:
+        assert j[k] is None, k
+    a, b = np.load(tmp_path / 'a' / 'state.npy'), np.load(tmp_path / 'b' / 'state.npy')
+    assert a.dtype == np.float32 and a.shape == (4, 3, 4, 4) and np.array_equal(a, b)
+    assert np.array_equal(a[:, 0, 0, 0], np.arange(4) + 5.0)           # the stub's state: sample index + steps taken (W + K)
+    assert float(a.astype(np.float64).sum()) == j['ranks'][0]['shard_checksum']
+
+
+def test_dump_outputs_keeps_a_seeded_sample_of_rows_beyond_the_limit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.arange(10 * 6, dtype=torch.float64).view(10, 2, 3)
+    bench.dump_outputs(str(tmp_path), 'small', x)
+    small = np.load(tmp_path / 'small.npy')
+    assert small.dtype == np.float32 and np.array_equal(small, x.float().numpy())
+    for name in ('big', 'big_again'):
+        bench.dump_outputs(str(tmp_path), name, x, limit=4 * 6 * 4)     # room for 4 of the 10 rows
+    a = np.load(tmp_path / 'big.npy')
+    assert a.dtype == np.float32 and a.shape == (4, 2, 3) and np.array_equal(a, np.load(tmp_path / 'big_again.npy'))
+    rows = (a[:, 0, 0] / 6).astype(int)
+    assert list(rows) == sorted(set(rows)) and np.array_equal(a, x.float().numpy()[rows])
 
 
 def test_cpu_baseline_block_structure():
@@ -37,7 +85,7 @@ def test_bench_prints_one_line_with_the_contracts_keys():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'mnist_unet_b256_T1000', '--steps', '5', '--warmup', '2',
-                        '--no-cpu-baseline', '--no-full-trajectory'], env=env, capture_output=True, text=True, timeout=600)
+                        '--full', '--no-cpu-baseline', '--no-full-trajectory'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -67,6 +115,23 @@ def test_bench_prints_one_line_with_the_contracts_keys():
         assert 0 < j['sclk_mhz']['min'] <= j['sclk_mhz']['mean'] < 4000
     assert 'algorithmic_tflops_over_fp32_peak' in j and 'whole_step_frac_of_fp32_peak' not in j
     assert 'update_kernel_unfused' in j
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_the_state_its_timed_steps_computed(tmp_path):
+    """The plain line on the GPU (MNIST net, K = 5, W = 2): the contract's keys, no --full part, and --dump-outputs' state.npy is
+    the state the timed path left (the line's own checksum of it)."""
+    j = _bench(['--workload', 'mnist_unet_b256_T1000', '--steps', '5', '--warmup', '2', '--dump-outputs', str(tmp_path)])
+    for k, typ in TOP_KEYS.items():
+        assert isinstance(j[k], (int, float) if typ is float else typ), (k, j[k])
+    assert j['steps'] == 5 and j['warmup'] == 2 and j['value'] > 0 and j['ms_per_step'] > 0 and j['samples_finite'] is True
+    assert j['value_source'].startswith('extrapolated') and j['value'] == j['extrapolated_value']
+    for k in FULL_ONLY_KEYS:
+        assert j[k] is None, k
+    a = np.load(tmp_path / 'state.npy')
+    assert a.dtype == np.float32 and list(a.shape) == j['config']['state_shape_per_gpu'] and np.isfinite(a).all()
+    want = j['ranks'][0]['shard_checksum']
+    assert abs(float(a.astype(np.float64).sum()) - want) <= 1e-9 * float(np.abs(a).astype(np.float64).sum())
 
 
 def test_board_sampler_parses_rocm_smi_and_tolerates_its_absence():

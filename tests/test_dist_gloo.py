@@ -79,7 +79,7 @@ def test_bench_spawns_its_own_ranks_and_propagates_failure():
     """`python bench.py --gpus 2` started plainly launches its two ranks itself (torch.distributed.run, 127.0.0.1),
     runs the barrier / max-over-ranks / all-gather control flow and prints ONE JSON line; a failing rank makes the
     parent exit non-zero.  DLPM_BENCH_DRY_RUN swaps the sampler for a CPU stub (gloo): control flow only."""
-    r, out = _run_bench({'DLPM_BENCH_DRY_RUN': '1'}, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '6')
+    r, out = _run_bench({'DLPM_BENCH_DRY_RUN': '1'}, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '6', '--full')
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(out) == 1, r.stdout
     j = out[0]
@@ -96,11 +96,11 @@ def test_bench_spawns_its_own_ranks_and_propagates_failure():
 
 @pytest.mark.parametrize('workload,per_gpu', [('cifar10_unet_b1024_T1000', 1024), ('celeba64_unet_b256_T1000', 256)])
 def test_bench_eight_rank_control_flow_of_the_driver_commands(workload, per_gpu):
-    """BASELINE configs 4 and 5 as the driver would launch them (`bench.py --gpus 8 [--workload ...]`), unattended: eight
-    spawned ranks, gloo, stub sampler (DLPM_BENCH_DRY_RUN) -- rendezvous, barriers, max-over-ranks, ONE all-gather of the
-    per-GPU shards, one JSON line whose batch is 8 x the per-GPU batch of the workload."""
+    """BASELINE configs 4 and 5 as the driver would launch them (`bench.py --gpus 8 [--workload ...]`, here with --full: the
+    whole trajectory too), unattended: eight spawned ranks, gloo, stub sampler (DLPM_BENCH_DRY_RUN) -- rendezvous, barriers,
+    max-over-ranks, ONE all-gather of the per-GPU shards, one JSON line whose batch is 8 x the per-GPU batch of the workload."""
     r, out = _run_bench({'DLPM_BENCH_DRY_RUN': '1', 'OMP_NUM_THREADS': '1'}, '--gpus', '8', '--steps', '4', '--warmup', '1',
-                        '--workload', workload, timeout=600)
+                        '--workload', workload, '--full', timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(out) == 1, r.stdout
     j = out[0]
@@ -130,12 +130,12 @@ def test_bench_rank_dying_mid_trajectory_fails_the_parent_within_the_deadline():
     import time
     env = {'DLPM_BENCH_DRY_RUN': '1', 'DLPM_BENCH_DIE_RANK': '1', 'DLPM_BENCH_DIE_AT': '40', 'OMP_NUM_THREADS': '1'}
     t0 = time.time()
-    r, out = _run_bench(env, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '4', '--rank-timeout', '200', timeout=400)
+    r, out = _run_bench(env, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '4', '--rank-timeout', '200', '--full', timeout=400)
     assert r.returncode not in (0, 124) and not out, (r.returncode, r.stdout)
     assert time.time() - t0 < 150
     env['DLPM_BENCH_DIE_MODE'] = 'hang'
     t0 = time.time()
-    r, out = _run_bench(env, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '4', '--rank-timeout', '25', timeout=400)
+    r, out = _run_bench(env, '--gpus', '2', '--steps', '5', '--warmup', '2', '--batch', '4', '--rank-timeout', '25', '--full', timeout=400)
     assert r.returncode == 124 and not out, (r.returncode, r.stdout)
     assert time.time() - t0 < 120
 
