@@ -175,6 +175,7 @@ int launch_gn_coeffs_from_stats(const float2 *st0, const float2 *st1, int C0, in
                                 const float *gamma, const float *beta, const float *ss, int64_t ss_stride,
                                 int64_t ss_offset, float *coefA, float *coefB, hipStream_t st);
 int launch_attention(const float *qkv, float *out, int B, int T, int C, int heads, hipStream_t st);
+int launch_attention_general(const float *qkv, float *out, int B, int T, int C, int heads, hipStream_t st);   // always k_attention_any
 
 // Whole blocks of small images in one launch, activations resident in LDS (block_small.hip): 64-output-channel ResBlocks on
 // 8x8 / 4x4 images, one workgroup per image.

@@ -1334,6 +1334,12 @@ extern "C" int dlpm_attention_f32(const float *qkv, float *out, int32_t B, int32
     return launch_attention(qkv, out, B, T, C, heads, as_stream(stream));
 }
 
+extern "C" int dlpm_attention_general_f32(const float *qkv, float *out, int32_t B, int32_t T, int32_t C, int32_t heads,
+                                          dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(qkv && out && B > 0, "dlpm_attention_general_f32: null argument");
+    return launch_attention_general(qkv, out, B, T, C, heads, as_stream(stream));
+}
+
 extern "C" int dlpm_resblock_small_f32(const dlpm_resblock_args *a, float *scratch_dev, int64_t scratch_floats, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(a && a->x0 && a->conv1_w && a->conv2_w && a->ss && a->out && scratch_dev, "dlpm_resblock_small_f32: null argument");
     // every parameter the kernel reads at entry (it has no optional ones but the skip convolution and the statistics)

@@ -439,9 +439,16 @@ int dlpm_groupnorm_coeffs_f32(const float *src0, const float *src1, int32_t C0, 
 
 /* QKVAttention over qkv[B,T,3C] (NHWC; channel layout head-major [head][q|k|v][C/heads] as produced
  * by the reference's reshape) -> out[B,T,C].  QK^T and PV on the fp32 MFMA, softmax in fp32.
+ * Any sequence length T in 1..4096 and head dim C/heads in 1..256 (larger: DLPM_ERR_UNSUPPORTED).
+ * T in {16, 64, 256} with head dim in {16, 32, 64, 128} (K/V of a head within 160 KiB of LDS) runs the
+ * whole-head kernel; every other shape runs the flash-style general kernel (online softmax over key blocks).
  * Replaces QKVAttention.forward: unet.py:236-250. */
 int dlpm_attention_f32(const float *qkv_dev, float *out_dev, int32_t B, int32_t T, int32_t C, int32_t heads,
                        dlpm_stream_t stream);
+
+/* Same arguments and result as dlpm_attention_f32, but always runs the general kernel (A/B checks, tests). */
+int dlpm_attention_general_f32(const float *qkv_dev, float *out_dev, int32_t B, int32_t T, int32_t C, int32_t heads,
+                               dlpm_stream_t stream);
 
 /* Whole blocks of SMALL images in one launch, activations resident in LDS, one workgroup per image (round 4; the UNet handle
  * takes them for its 64-channel blocks on 8x8 / 4x4 images under DLPM_CONV_AUTO).  Weights arrive in the reference's layouts

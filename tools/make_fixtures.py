@@ -20,6 +20,7 @@ Fixture families:
   F10 LIM sampler        VPSDE, LIM_sampler sde/ode updates        dlpm/methods/LIM/functions/{sde,sampler}.py
   F13 small blocks       ResBlock / AttentionBlock at the fused kernels' shapes     dlpm/models/unet.py:105-250
   F14 16x16 / 32x32 blocks  AttentionBlock at T = 256, ResBlocks of the MNIST-sized net's fine levels   dlpm/models/unet.py:105-250
+  F15 any geometry      QKVAttention at any T / head dim, the 28x28 MNIST UNet (forward, bounded T=1000 sample)   dlpm/models/unet.py
   F12 mean types         p_mean_variance: START_X / Z / PREVIOUS_X, denoised_fn, model_kwargs   GenerativeLevyProcess.py:154-219
   F11 image quantisation PIL's float -> 8-bit path (torchvision absent)  bem/evaluate/EvaluationManager.py:188-190
   F9 checkpoints         TrainingManager.save/load, EMAHelper,    bem/TrainingManager.py:240-285, bem/utils_ema.py,
@@ -818,6 +819,106 @@ def f14_blocks16():
     save('f14_blocks16', **arrs)
 
 
+def f15_geometry():
+    """Shapes the four shipped configs never reach: QKVAttention at any token count / head dim, and the UNet of BASELINE
+    configs[1] as written (MNIST at 28x28: channel_mult (1, 2, 2), attention at 14x14 and 7x7, i.e. T = 196 / 49, head dim 16).
+    Only NEW files are written; an existing one must be reproduced bit for bit."""
+    def save_new(name, **arrs):
+        path = os.path.join(OUT, name + '.npz')
+        if os.path.exists(path):
+            old = np.load(path)
+            for k, v in arrs.items():
+                v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+                assert np.array_equal(old[k], v), '%s: this run does not reproduce the committed %s' % (name, k)
+            print('kept %s (reproduced)' % name)
+            return
+        save(name, **arrs)
+
+    # ---- QKVAttention (unet.py:230-250) on qkv [heads, 3 ch, T]; inputs are fp16-representable (stored as fp16: the file stays
+    # small; exact in fp32), outputs fp32
+    g = torch.Generator().manual_seed(15)
+    att = ref_unet.QKVAttention()
+    arrs = {}
+    for ch, T, heads in [(16, 49, 2), (16, 196, 2), (8, 784, 2), (8, 4, 2), (32, 1024, 1), (24, 100, 2), (256, 64, 1)]:
+        qkv = torch.randn(heads, 3 * ch, T, generator=g).half().float()
+        tag = 'ch%d_T%d' % (ch, T)
+        arrs[tag + '_in'] = qkv.half()
+        arrs[tag + '_out'] = att(qkv)
+    save_new('f15_attention_any', **arrs)
+    if os.environ.get('F15_ONLY') == 'attention':
+        return
+
+    # ---- the mnist28 net (dlpm_amd/configs/mnist28.yml): forward at B = 2, weights seeded and re-randomised as in F6
+    mc, mult, attn, heads, res, hw, B = 32, [1, 2, 2], [2, 4], 4, 2, 28, 2
+    torch.manual_seed(1234)
+    net = make_unet(1, mc, mult, attn, heads, res).eval()
+    rerandomize(net, 4321)
+    g = torch.Generator().manual_seed(77)
+    x = torch.randn(B, 1, hw, hw, generator=g)
+    t = torch.rand(B, generator=g)
+    with torch.inference_mode():
+        y = net(x, t)
+        t_same = torch.full((B,), 0.37)
+        y_same = net(x, t_same)
+    sd = net.state_dict()
+    keys = list(sd.keys())
+    shapes = np.full((len(keys), 4), -1, dtype=np.int64)
+    for i, k in enumerate(keys):
+        shapes[i, :sd[k].dim()] = sd[k].shape
+    save_new('f15_unet_mnist28', x=x, t=t, y=y, y_same_t=y_same, t_same=t_same,
+             cfg=np.array([1, mc, heads, res, hw, B]), mult=np.array(mult), attn=np.array(attn),
+             digest_final=np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8),
+             keys=np.array(keys), shapes=shapes)
+
+    # ---- a bounded (clip_denoised) reference sample() of that net at T = 1000, B = 2, alpha = 1.7, mnist.yml's clamps.  The head
+    # convolution is scaled (as f5b does for the 32x32 MNIST net) by the first factor that makes the fixture informative:
+    # sensitivity >= 0.4 and >= 70 % of the final pixels inside (-1, 1)
+    T, B, every, alpha, ca, ce = 1000, 2, 100, 1.7, 20, 200
+    shape = [B, 1, hw, hw]
+
+    class Perturbed(torch.nn.Module):   # net(x, t) * (1 + rel * N(0, 1)), drawn from a generator of its own
+        def __init__(self, net, rel, seed):
+            super().__init__()
+            self.net, self.rel, self.g = net, rel, torch.Generator().manual_seed(seed)
+
+        def forward(self, x, t, **kw):
+            y = self.net(x, t, **kw)
+            return y * (1 + self.rel * torch.randn(y.shape, generator=self.g))
+
+    def post(x):
+        return (x.clamp(-1, 1) + 1) / 2
+
+    def run(model):
+        np.random.seed(0)
+        torch.manual_seed(0)
+        meth = GenerativeLevyProcess(alpha=alpha, device='cpu', reverse_steps=T, rescale_timesteps=True)
+        return meth.sample({'default': model}, shape, T, clamp_a=ca, clamp_eps=ce, clip_denoised=True, get_sample_history=True)
+
+    name = 'f15_traj_unet_mnist28_clip_T1000'
+    REL = 1e-4
+    for head_scale in [float(v) for v in os.environ.get('F15_HEAD_SCALES', '5 4 6 3').split()]:
+        torch.manual_seed(1234)
+        net = make_unet(1, mc, mult, attn, heads, res).eval()
+        rerandomize(net, 4321)
+        with torch.no_grad():
+            net.out[2].weight.mul_(head_scale)
+            net.out[2].bias.mul_(head_scale)
+        x, hist = run(net)
+        inside = float((x.abs() < 1).float().mean())
+        xp, _ = run(Perturbed(net, REL, 77))
+        sens = float((post(xp) - post(x)).abs().max()) / REL
+        sens_state = float((xp - x).abs().max()) / REL
+        print('%s head x %g: %.1f %% of the final pixels inside (-1, 1), max |state| %.4g, sensitivity %.3g (state %.3g)'
+              % (name, head_scale, 100 * inside, float(hist.abs().max()), sens, sens_state))
+        if inside >= 0.7 and sens >= 0.4:
+            break
+    assert inside >= 0.7 and sens >= 0.4, name
+    save_new(name, final=x, history_sub=hist[::every], every=np.array(every), meta=np.array([T, alpha, ca, ce]),
+             mean_type=np.array('EPSILON'), shape=np.array(shape), inside=np.array(inside), head_scale=np.array(head_scale),
+             arch=np.array('mnist28'), sensitivity=np.array(sens), sensitivity_state=np.array(sens_state), sensitivity_rel=np.array(REL),
+             digest=np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8), state_900=hist[900])
+
+
 def f8_generation_manager():
     class FakeMethod:
         device = 'cpu'
@@ -1007,9 +1108,9 @@ def f10_lim():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14']
+    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15']
     table = dict(f12=f12_mean_types, f11=f11_image_quantise, f10=f10_lim, f1=f1_schedule, f2=f2_noise, f3=f3_tables, f4=f4_single_step, f5=f5_trajectories, f5u=f5_unet_trajectory, f5w=f5_wide_unet_trajectory, f5k=f5_unet_trajectories_T1000, f5b=f5_bounded_unet_trajectories, f5c=f5_cifar_teacher_forced,
-                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f8=f8_generation_manager, f9=f9_checkpoints)
+                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f8=f8_generation_manager, f9=f9_checkpoints)
     with torch.no_grad():
         for w in which:
             table[w]()
