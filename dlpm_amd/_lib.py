@@ -103,6 +103,8 @@ SIGNATURES = {
     'dlpm_png_encode_rgb8': (C.c_int, [vp, i32, i32, i32, vp, i64, C.POINTER(i64)]),
     'dlpm_png_write_rgb8': (C.c_int, [vp, i64, i32, i32, C.c_char_p, i64, i32, i32]),
     'dlpm_unet_create': (C.c_int, [C.POINTER(UNetConfig), C.POINTER(vp)]),
+    'dlpm_unet_create_conditional': (C.c_int, [C.POINTER(UNetConfig), i32, C.POINTER(vp)]),
+    'dlpm_unet_num_classes': (i32, [vp]),
     'dlpm_unet_set_param': (C.c_int, [vp, C.c_char_p, vp, i64]),
     'dlpm_unet_num_params': (C.c_int, [vp]),
     'dlpm_unet_param_key': (C.c_char_p, [vp, C.c_int, C.POINTER(i64)]),
@@ -110,6 +112,8 @@ SIGNATURES = {
     'dlpm_unet_workspace_bytes': (i64, [vp, i64]),
     'dlpm_unet_forward': (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp]),
     'dlpm_unet_forward_uniform_t': (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp]),
+    'dlpm_unet_forward_labels': (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, vp]),
+    'dlpm_unet_forward_uniform_t_labels': (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, vp]),
     'dlpm_unet_forward_update': (C.c_int, [vp, vp, vp, C.POINTER(UpdateArgs), vp, i64, vp, i64, vp]),
     'dlpm_unet_time_embedding_width': (i64, [vp]),
     'dlpm_unet_time_embeddings_scratch_bytes': (i64, [vp, i64]),
@@ -149,6 +153,7 @@ SIGNATURES = {
     'dlpm_sampler_step_injected': (C.c_int, [vp, vp, vp]),
     'dlpm_sampler_steps': (C.c_int, [vp, i32, vp]),
     'dlpm_sampler_set_history': (C.c_int, [vp, vp, vp]),
+    'dlpm_sampler_set_labels': (C.c_int, [vp, vp, vp]),
     'dlpm_sampler_copy_state': (C.c_int, [vp, vp, vp]),
     'dlpm_sampler_state': (vp, [vp]),
     'dlpm_sampler_t': (i32, [vp]),

@@ -2,6 +2,7 @@
 
 Covers the reference flags that reach the sampler (script_utils.py:11-12,35-39,56-67,82-83,155-221):
   --config --method --generate --reverse_steps --deterministic --clip --alpha --non_iso --scale --input_scaling --set_seed/--random_seed
+  (--class_labels cycle|K: labels of a class-conditional net, i.e. a config with model.class_cond and data.num_classes)
 plus the checkpoint to evaluate, resolved like eval.py does (eval.py:21, bem/utils_exp.py:96-139):
   --name N [--models_dir models] [--epoch E]  ->  models/N/<dataset>/model_<exphash>[_<E>].pt
 or given directly with --checkpoint FILE; --ema_eval [--ema_index I] evaluates an EMA shadow.
@@ -16,6 +17,22 @@ import torch
 
 import dlpm_amd
 from dlpm_amd.config import sample_shape
+
+
+def class_labels(spec, num_classes, n):
+    """--class_labels: None, 'cycle' (sample i -> i % K) or an integer k (every sample -> k), as an int64 [n] tensor."""
+    if spec is None:
+        if num_classes is not None:
+            raise SystemExit('the net is class-conditional (model.class_cond): give --class_labels cycle|K')
+        return None
+    if num_classes is None:
+        raise SystemExit('--class_labels needs a class-conditional net (model.class_cond: true, data.num_classes: K)')
+    if spec == 'cycle':
+        return torch.arange(n, dtype=torch.int64) % num_classes
+    k = int(spec)
+    if not 0 <= k < num_classes:
+        raise SystemExit('--class_labels %d outside [0, %d)' % (k, num_classes))
+    return torch.full((n,), k, dtype=torch.int64)
 
 
 def main(argv=None):
@@ -57,6 +74,9 @@ def main(argv=None):
                     help='with --gen_data_path and --rng philox: sample in chunks of at least this many images (pixels do not '
                          'depend on the chunking).  auto (default) = up to 1024, as many as free HBM holds; 0 = eval.batch_size '
                          'chunks exactly as the reference')
+    ap.add_argument('--class_labels', default=None, metavar='cycle|K',
+                    help='labels of a class-conditional net (model.class_cond): cycle = sample i gets i %% num_classes, an integer k = '
+                         'every sample gets k.  With --gen_data_path they are written to labels.npy next to the images')
     a = ap.parse_args(argv)
 
     p = dlpm_amd.load_config(a.config)
@@ -108,19 +128,22 @@ def main(argv=None):
         model.set_gemm_policy(a.gemm)
     method = dlpm_amd.init_method_by_parameter(p, rng=a.rng, seed=seed or 0)
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
+    labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
     if a.gen_data_path:
         assert is_image, '--gen_data_path dumps images; 2-D data has no image form'
         ev = dlpm_amd.EvaluationManager(method, gm, None, is_image=True, gen_data_path=a.gen_data_path,
                                         device_batch=a.device_batch if a.device_batch == 'auto' else int(a.device_batch))
         r = ev.evaluate_model({'default': model}, data_to_generate=p['eval']['data_to_generate'],
-                              batch_size=p['eval']['batch_size'])
+                              batch_size=p['eval']['batch_size'], class_labels=labels)
         print('wrote %d png files to %s' % (r['generated'], r['gen_data_path']))
         return r
     remaining, chunks = p['eval']['data_to_generate'], []
     while remaining > 0:                                    # EvaluationManager.py:181-193
         n = min(p['eval']['batch_size'], remaining)
-        chunks.append(gm.generate({'default': model}, n).clone())
+        done = p['eval']['data_to_generate'] - remaining
+        extra = {} if labels is None else {'model_kwargs': {'y': labels[done:done + n]}}
+        chunks.append(gm.generate({'default': model}, n, **extra).clone())
         remaining -= n
         print('generated %d, %d to go' % (n, remaining), file=sys.stderr)
     samples = torch.cat(chunks)

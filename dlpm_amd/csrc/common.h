@@ -43,6 +43,15 @@ int ensure_dynamic_lds(const void *kernel, int bytes);
 // t <- t - 1 on the device step counter (noise.hip): what DLPM_UPD_ADVANCE does after an update
 int launch_step_advance(int32_t *t_dev, hipStream_t st);
 
+// Class-conditional UNets inside the sampler (unet.hip): the time-MLP rows time_embed(timestep_embedding(t)) of M timesteps
+// ([M][4 * model_channels], scratch as dlpm_unet_time_embeddings_scratch_bytes), and dlpm_unet_forward_update with labels y_dev[B]
+int64_t unet_time_mlp_width(const dlpm_unet *net);
+int unet_time_mlp_rows(dlpm_unet *net, const float *t_dev, int64_t M, float *out_dev, void *scratch_dev, int64_t scratch_bytes,
+                       hipStream_t st);
+int unet_forward_update_labels(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const int64_t *y_dev,
+                               const dlpm_update_args *upd, float *eps_scratch_dev, int64_t B, void *workspace_dev,
+                               int64_t workspace_bytes, hipStream_t stream);
+
 // Optional per-launch timing (dlpm_prof_enable): brackets one launch with HIP events on its stream.
 bool prof_enabled();
 bool prof_detail();   // DLPM_PROF_DETAIL=1: one class per distinct launch shape

@@ -217,6 +217,10 @@ int relayout_weight_small(const float *oihw_dev, float *dst_dev, int Cout, int C
 bool res_small_ok(const ResSmallLaunch &r);
 int launch_resblock_small(const ResSmallLaunch &r, hipStream_t st);
 int launch_timestep_embedding(const float *t, float *emb, int64_t B, int dim, hipStream_t st);
+// out[b] = src[row(b)] + w[y[b]] over `dim` columns (embed.hip): row(b) = (row_dev ? *row_dev : 0) + b * src_row_stride; a label
+// outside [0, K) gives a NaN row and no read of w
+int launch_label_embedding_add(const float *src, const int32_t *row_dev, int src_row_stride, const float *w, const int64_t *y, int64_t K,
+                               int64_t B, int dim, float *out, hipStream_t st);
 
 __device__ __forceinline__ float silu_f(float v) {
     // x * sigmoid(x), sigmoid = 1/(1+exp(-x))  (nn.py:12-14).  v_exp_f32 + v_rcp_f32 (1 ulp each): the IEEE

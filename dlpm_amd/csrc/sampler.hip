@@ -27,7 +27,11 @@ struct dlpm_sampler {
     float **hist_cell = nullptr;   // device cell with the history base (see dlpm_update_args::hist_pp)
     float *hist = nullptr;         // its current value (caller-owned [T,B,D] buffer or null)
     float *x = nullptr, *eps = nullptr, *tvec = nullptr;
-    float *emb_tab = nullptr;      // UNet, DLPM loop: the time path's output for every step, [T][emb width] (dlpm_unet_time_embeddings)
+    float *emb_tab = nullptr;      // UNet, DLPM loop: the time path's output for every step, [T][emb width] (dlpm_unet_time_embeddings);
+                                   // class-conditional net: the time MLP's output for every step, [T][4 * model_channels]
+    bool cond = false;             // the UNet is class-conditional: every forward reads `labels`
+    int64_t *labels = nullptr;     // [B] class labels (dlpm_sampler_set_labels), read by the captured graph
+    bool labels_set = false;
     int32_t *t_dev = nullptr;
     uint64_t *key_dev = nullptr;   // {seed, sample_offset}: read by the update kernel, so reseeding keeps the graph
     int graph_steps = 0;           // steps inside the captured graph
@@ -72,7 +76,9 @@ __global__ void k_set_ptr(float **cell, float *v) {
 int build_time_table(dlpm_sampler *s) {
     if (!s->cfg.unet || s->lim) return DLPM_OK;
     const char *nt = getenv("DLPM_NO_TIME_TABLE");
-    const int64_t ew = dlpm_unet_time_embedding_width(s->cfg.unet);
+    // a conditional net's emb rows depend on the label: the table holds the time MLP's rows, the label term and the emb linears
+    // run in every step (per sample, as in every other forward of such a net)
+    const int64_t ew = s->cond ? unet_time_mlp_width(s->cfg.unet) : dlpm_unet_time_embedding_width(s->cfg.unet);
     if ((nt && nt[0] == '1') || ew <= 0) return DLPM_OK;
     const int T = s->cfg.T;
     std::vector<float> tv(T);
@@ -86,7 +92,8 @@ int build_time_table(dlpm_sampler *s) {
     if (e == hipSuccess) e = hipMalloc(&scr, (size_t)scr_bytes);
     if (e == hipSuccess && !s->emb_tab) e = hipMalloc(&s->emb_tab, (size_t)T * ew * sizeof(float));
     if (e == hipSuccess) {
-        r = dlpm_unet_time_embeddings(s->cfg.unet, tv_dev, T, s->emb_tab, scr, scr_bytes, nullptr);
+        r = s->cond ? unet_time_mlp_rows(s->cfg.unet, tv_dev, T, s->emb_tab, scr, scr_bytes, nullptr)
+                    : dlpm_unet_time_embeddings(s->cfg.unet, tv_dev, T, s->emb_tab, scr, scr_bytes, nullptr);
         e = hipDeviceSynchronize();
     }
     if (tv_dev) (void)hipFree(tv_dev);
@@ -143,6 +150,8 @@ int model_forward(dlpm_sampler *s, hipStream_t st) {
         TRY(dlpm_scale_by_table_f32(s->x, s->xin, s->cfg.B * s->D, s->t_dev, s->in_scale, st));
         xin = s->xin;
     }
+    if (s->cond)
+        return dlpm_unet_forward_uniform_t_labels(s->cfg.unet, xin, s->tvec, s->labels, s->eps, s->cfg.B, s->ws, s->ws_bytes, st);
     if (s->cfg.unet)
         return dlpm_unet_forward_uniform_t(s->cfg.unet, xin, s->tvec, s->eps, s->cfg.B, s->ws, s->ws_bytes, st);   // t = [i] * B
     return dlpm_mlp_forward(s->cfg.mlp, xin, s->tvec, s->eps, s->cfg.B, st);
@@ -196,7 +205,8 @@ int one_step(dlpm_sampler *s, const float *z, bool advance, hipStream_t st) {
             xin = s->xin;
         }
         TimeTableBinding bound(s);
-        return dlpm_unet_forward_update(s->cfg.unet, xin, s->tvec, &a, s->eps, s->cfg.B, s->ws, s->ws_bytes, st);
+        return unet_forward_update_labels(s->cfg.unet, xin, s->tvec, s->cond ? s->labels : nullptr, &a, s->eps, s->cfg.B, s->ws,
+                                          s->ws_bytes, st);
     }
     TRY(model_forward(s, st));
     return dlpm_update_f32(&a, st);
@@ -208,6 +218,13 @@ int flush_key(dlpm_sampler *s, hipStream_t st) {
     DLPM_LAUNCH_CHECK();
     s->key_dirty = false;
     return DLPM_OK;
+}
+
+// a conditional net samples nothing before dlpm_sampler_set_labels
+int need_labels(const dlpm_sampler *s) {
+    if (!s->cond || s->labels_set) return DLPM_OK;
+    set_error("dlpm_sampler: the net is class-conditional: call dlpm_sampler_set_labels first");
+    return DLPM_ERR_STATE;
 }
 
 int build_tables(dlpm_sampler *s, hipStream_t st) {
@@ -241,8 +258,14 @@ extern "C" int dlpm_sampler_create(const dlpm_sampler_config *cfg, dlpm_sampler 
     DLPM_CHECK_ARG(!is_lim || cfg->mean_type == DLPM_MEAN_EPSILON, "LIM only supports epsilon prediction, fixed variance and rescaled timesteps");
     DLPM_CHECK_ARG(!is_lim || !(cfg->flags & (DLPM_UPD_CLIP | DLPM_UPD_ELEMENTWISE)),
                    "dlpm_sampler_create: the LIM sampler has no clip_denoised / non-isotropic variant (the reference's are commented out)");
+    const bool cond = cfg->unet && dlpm_unet_num_classes(cfg->unet) > 0;
+    if (cond && is_lim) {
+        set_error("dlpm_sampler_create: the LIM sampler does not take class labels (class-conditional nets sample with the DLPM loop)");
+        return DLPM_ERR_UNSUPPORTED;
+    }
     dlpm_sampler *s = new dlpm_sampler();
     s->cfg = *cfg;
+    s->cond = cond;
     s->D = (int64_t)cfg->C * cfg->H * cfg->W;
     s->lim = is_lim;
     s->elem = (cfg->flags & DLPM_UPD_ELEMENTWISE) != 0;
@@ -322,6 +345,7 @@ extern "C" int dlpm_sampler_create(const dlpm_sampler_config *cfg, dlpm_sampler 
     if ((e = hipMalloc(&s->eps, (size_t)B * s->D * sizeof(float))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&s->tvec, (size_t)B * sizeof(float))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&s->t_dev, sizeof(int32_t))) != hipSuccess) return fail(e);
+    if (cond && (e = hipMalloc(&s->labels, (size_t)B * sizeof(int64_t))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&s->key_dev, 2 * sizeof(uint64_t))) != hipSuccess) return fail(e);
     {
         uint64_t key[2] = {cfg->seed, (uint64_t)cfg->sample_offset};
@@ -360,6 +384,7 @@ extern "C" int dlpm_sampler_reseed(dlpm_sampler *s, uint64_t seed, int64_t sampl
 
 extern "C" int dlpm_sampler_begin(dlpm_sampler *s, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(s, "dlpm_sampler_begin: null handle");
+    TRY(need_labels(s));
     hipStream_t st = as_stream(stream);
     const dlpm_sampler_config &c = s->cfg;
     if (s->lim) {
@@ -379,6 +404,7 @@ extern "C" int dlpm_sampler_begin(dlpm_sampler *s, dlpm_stream_t stream) {
 
 extern "C" int dlpm_sampler_begin_injected(dlpm_sampler *s, const float *A_dev, const float *xT_dev, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(s && A_dev && xT_dev, "dlpm_sampler_begin_injected: null argument");
+    TRY(need_labels(s));
     hipStream_t st = as_stream(stream);
     DLPM_HIP(hipMemcpyAsync(s->A, A_dev, (size_t)(s->lim ? s->cfg.T - 1 : s->cfg.T) * s->cols * sizeof(float),
                             hipMemcpyDeviceToDevice, st));
@@ -402,6 +428,7 @@ extern "C" int dlpm_sampler_set_state(dlpm_sampler *s, const float *x_dev, int32
 extern "C" int dlpm_sampler_step_injected(dlpm_sampler *s, const float *z_dev, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(s, "dlpm_sampler_step_injected: null handle");
     if (s->t_host < 1) return DLPM_OK;
+    TRY(need_labels(s));
     TRY(sync_plan(s));
     TRY(flush_key(s, as_stream(stream)));
     TRY(one_step(s, z_dev, true, as_stream(stream)));
@@ -453,6 +480,7 @@ extern "C" int dlpm_sampler_steps(dlpm_sampler *s, int32_t nsteps, dlpm_stream_t
     hipStream_t st = as_stream(stream);
     if (nsteps > s->t_host) nsteps = s->t_host;
     if (nsteps == 0) return DLPM_OK;
+    TRY(need_labels(s));
     TRY(sync_plan(s));
     TRY(flush_key(s, st));   // one thread, stream-ordered before the (replayed) steps; free when the key is clean
     // toy net, plain stochastic DLPM steps: the whole run of steps is one launch (state in registers)
@@ -480,6 +508,16 @@ extern "C" int dlpm_sampler_steps(dlpm_sampler *s, int32_t nsteps, dlpm_stream_t
     DLPM_HIP(hipEventRecord(s->ev_out, s->own));
     DLPM_HIP(hipStreamWaitEvent(st, s->ev_out, 0));    // and the caller's later work follows them
     return r;
+}
+
+extern "C" int dlpm_sampler_set_labels(dlpm_sampler *s, const int64_t *y_dev, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(s && y_dev, "dlpm_sampler_set_labels: null argument");
+    DLPM_CHECK_ARG(s->cond, "dlpm_sampler_set_labels: the sampler's net is not class-conditional");
+    // into the buffer the captured graph reads: new labels never force a recapture.  Stream-ordered behind every earlier replay
+    // (dlpm_sampler_steps fences its private stream back into the caller's) and ahead of the next one
+    DLPM_HIP(hipMemcpyAsync(s->labels, y_dev, (size_t)s->cfg.B * sizeof(int64_t), hipMemcpyDeviceToDevice, as_stream(stream)));
+    s->labels_set = true;
+    return DLPM_OK;
 }
 
 extern "C" int dlpm_sampler_set_history(dlpm_sampler *s, float *hist_dev, dlpm_stream_t stream) {
@@ -521,7 +559,7 @@ extern "C" void dlpm_sampler_destroy(dlpm_sampler *s) {
     if (s->own) (void)hipStreamDestroy(s->own);
     void *bufs[] = {s->g, s->bg, s->s, s->bs, s->A, s->c_eps == s->A ? nullptr : s->c_eps, s->c_noise, s->x, s->eps, s->tvec, s->emb_tab,
                     s->t_dev, s->key_dev, s->ws, s->hist_cell, s->lim_ts, s->lim_tmp, s->lim_cx, s->lim_cs, s->lim_cn,
-                    s->in_scale, s->xin};
+                    s->in_scale, s->xin, s->labels};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete s;

@@ -175,6 +175,8 @@ struct dlpm_unet {
     int p_head_gn_w = -1, p_head_gn_b = -1;
     float *embcat_w = nullptr, *embcat_b = nullptr;
     int emb_total = 0, ted = 0, final_ch = 0;
+    int num_classes = 0;             // dlpm_unet_create_conditional: K > 0 adds label_emb.weight [K][ted]
+    int p_label = -1;
     bool finalized = false;
     std::vector<Tensor4> feats;      // block outputs of the last forward
     int64_t flops = 0;
@@ -247,6 +249,7 @@ void build_arch(dlpm_unet *u) {
     u->ted = 4 * mc;
     u->te0 = u->conv("time_embed.0.", u->ted, mc, 1);
     u->te2 = u->conv("time_embed.2.", u->ted, u->ted, 1);
+    if (u->num_classes > 0) u->p_label = u->add("label_emb.weight", (int64_t)u->num_classes * u->ted);   // unet.py:341-342
     {
         Layer L;
         L.kind = L_STEM; L.pre = "input_blocks.0.0."; L.cin = c.in_channels; L.cout = mc;
@@ -436,6 +439,9 @@ struct Ctx {
     hipStream_t st;
     float *embout = nullptr;
     bool uniform_t = false;      // every sample has the same timestep: the time MLP and the emb linears run on ONE row
+    const int64_t *y = nullptr;  // class labels [B] (int64) of a conditional net: B emb rows whatever uniform_t says
+    // row pitch of the per-ResBlock scale/shift rows: 0 when all samples read the one row of a uniform-t unconditional forward
+    int64_t emb_pitch() const { return (uniform_t && !y) ? 0 : u->emb_total; }
     const HeadUpdate *hu = nullptr;   // the sampler's reverse update, fused into the head convolution (dlpm_unet_forward_update)
     bool dry() const { return ws.dry; }
 };
@@ -494,7 +500,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
             r.gn2_w = u->params[L.p_gn2_w].dev; r.gn2_b = u->params[L.p_gn2_b].dev;
             r.b1 = u->params[L.c1.p_b].dev; r.b2 = u->params[L.c2.p_b].dev;
             r.bs = L.has_skip ? u->params[L.skip.p_b].dev : nullptr;
-            r.emb = cx.embout; r.emb_stride = cx.uniform_t ? 0 : u->emb_total; r.emb_off = L.emb_off;
+            r.emb = cx.embout; r.emb_stride = cx.emb_pitch(); r.emb_off = L.emb_off;
             r.out = o; r.stats_out = out->stats;
             return launch_resblock_small(r, cx.st);
         }
@@ -535,7 +541,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
             r.gn1_w = u->params[L.p_gn1_w].dev; r.gn1_b = u->params[L.p_gn1_b].dev;
             r.gn2_w = u->params[L.p_gn2_w].dev; r.gn2_b = u->params[L.p_gn2_b].dev;
             r.b1 = u->params[L.c1.p_b].dev; r.b2 = u->params[L.c2.p_b].dev;
-            r.emb = cx.embout; r.emb_stride = cx.uniform_t ? 0 : u->emb_total; r.emb_off = L.emb_off;
+            r.emb = cx.embout; r.emb_stride = cx.emb_pitch(); r.emb_off = L.emb_off;
             r.out = o; r.stats_out = out->stats;
             TRY(launch_resblock_img(r, cx.st));
             done();
@@ -569,7 +575,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
     a.bias = u->params[L.c1.p_b].dev; a.coefA = cA1; a.coefB = cB1; a.act_silu = 1; a.out = h1.p; a.stats_out = h1.stats;
     TRY(run_conv3(cx, L.c1, a));
     TRY(gn_any(h1, Tensor4(), B, G2, u->params[L.p_gn2_w].dev, u->params[L.p_gn2_b].dev, cx.embout,
-               cx.uniform_t ? 0 : u->emb_total, L.emb_off, cA2, cB2, cx.st));   // row pitch 0: all samples read the one emb row
+               cx.emb_pitch(), L.emb_off, cA2, cB2, cx.st));   // row pitch 0: all samples read the one emb row
     ConvLaunch b;
     b.src0 = h1.p; b.C0 = Co; b.B = B; b.Hin = b.Hout = H; b.Win = b.Wout = W;
     b.bias = u->params[L.c2.p_b].dev; b.coefA = cA2; b.coefB = cB2; b.act_silu = 1; b.out = o; b.stats_out = out->stats;
@@ -709,8 +715,8 @@ __global__ void k_table_row(const float *__restrict__ table, const int32_t *__re
     if (i < n) out[i] = table[(int64_t)(*row) * n + i];
 }
 
-// time embedding -> time MLP -> the row-concatenated per-ResBlock emb linears, for M rows of t (unet.py:147-150, 336-338, 470)
-int time_path(dlpm_unet *u, const float *t, int M, float *e0, float *e1, float *e2, float *out, hipStream_t st) {
+// time embedding -> time MLP, for M rows of t: e2[M][ted] = time_embed(timestep_embedding(t)) (unet.py:336-338, 470)
+int time_mlp(dlpm_unet *u, const float *t, int M, float *e0, float *e1, float *e2, hipStream_t st) {
     const int mc = u->cfg.model_channels, ted = u->ted;
     TRY(launch_timestep_embedding(t, e0, M, mc, st));
     ConvLaunch g;
@@ -718,9 +724,21 @@ int time_path(dlpm_unet *u, const float *t, int M, float *e0, float *e1, float *
     g.src0 = e0; g.C0 = mc; g.bias = u->params[u->te0.p_b].dev; g.out = e1;
     TRY(run_conv(u, u->te0, g, st));
     g.src0 = e1; g.C0 = ted; g.bias = u->params[u->te2.p_b].dev; g.out = e2; g.act_silu = 1;
-    TRY(run_conv(u, u->te2, g, st));
-    g.src0 = e2; g.bias = u->embcat_b; g.out = out;
+    return run_conv(u, u->te2, g, st);
+}
+
+// the row-concatenated per-ResBlock emb linears (SiLU on the input) of M rows emb[M][ted] (unet.py:147-150)
+int emb_linears(dlpm_unet *u, const float *emb, int M, float *out, hipStream_t st) {
+    ConvLaunch g;
+    g.B = M; g.Hin = g.Win = g.Hout = g.Wout = 1;
+    g.src0 = emb; g.C0 = u->ted; g.bias = u->embcat_b; g.out = out; g.act_silu = 1;
     return run_conv(u, u->embcat, g, st);
+}
+
+// time embedding -> time MLP -> the row-concatenated per-ResBlock emb linears, for M rows of t (unet.py:147-150, 336-338, 470)
+int time_path(dlpm_unet *u, const float *t, int M, float *e0, float *e1, float *e2, float *out, hipStream_t st) {
+    TRY(time_mlp(u, t, M, e0, e1, e2, st));
+    return emb_linears(u, e2, M, out, st);
 }
 
 // optional [T][emb_total] table of the time path's output (time embedding -> time MLP -> the per-ResBlock emb linears) and the device
@@ -737,7 +755,22 @@ int walk(dlpm_unet *u, Ctx &cx, const float *x, const float *t, float *eps) {
     const int Bt = cx.uniform_t ? 1 : B;
     float *e0 = cx.ws.alloc((int64_t)B * mc), *e1 = cx.ws.alloc((int64_t)B * ted), *e2 = cx.ws.alloc((int64_t)B * ted);
     cx.embout = cx.ws.alloc((int64_t)B * u->emb_total);
-    if (!cx.dry()) {
+    if (!cx.dry() && u->num_classes > 0) {
+        // class-conditional: emb = time_embed(t) + label_emb(y) per sample (unet.py:470-473), then the emb linears over B rows.  The
+        // time-MLP row comes from the bound [T][ted] table (the sampler's), from one row (uniform t) or from B rows; the rows a GEMM
+        // produces do not depend on how many it has, so a sample's emb row has the same bits on all three paths
+        const float *src = e2;
+        const int32_t *row = nullptr;
+        int stride = cx.uniform_t ? 0 : 1;
+        if (cx.uniform_t && tl_time_net == u && tl_time_table) {
+            src = tl_time_table;
+            row = tl_time_index;
+        } else {
+            TRY(time_mlp(u, t, Bt, e0, e1, e2, cx.st));
+        }
+        TRY(launch_label_embedding_add(src, row, stride, u->params[u->p_label].dev, cx.y, u->num_classes, B, ted, e1, cx.st));
+        TRY(emb_linears(u, e1, B, cx.embout, cx.st));
+    } else if (!cx.dry()) {
         if (cx.uniform_t && tl_time_net == u && tl_time_table) {
             // the whole time path is a function of the step index alone: its output for every step was computed once
             // (dlpm_unet_time_embeddings, same kernels, one row per step -- same bits) and the step reads its row
@@ -829,7 +862,7 @@ int64_t count_flops(dlpm_unet *u) {
 
 }  // namespace
 
-extern "C" int dlpm_unet_create(const dlpm_unet_config *cfg, dlpm_unet **out) {
+static int create_net(const dlpm_unet_config *cfg, int32_t num_classes, dlpm_unet **out) {
     DLPM_CHECK_ARG(cfg && out, "dlpm_unet_create: null argument");
     DLPM_CHECK_ARG(cfg->in_channels > 0 && cfg->model_channels > 0 && cfg->out_channels > 0 && cfg->num_res_blocks > 0,
                    "dlpm_unet_create: channels / res blocks must be positive");
@@ -841,10 +874,20 @@ extern "C" int dlpm_unet_create(const dlpm_unet_config *cfg, dlpm_unet **out) {
                    cfg->image_size, cfg->n_mult - 1);
     dlpm_unet *u = new dlpm_unet();
     u->cfg = *cfg;
+    u->num_classes = num_classes;
     build_arch(u);
     *out = u;
     return DLPM_OK;
 }
+
+extern "C" int dlpm_unet_create(const dlpm_unet_config *cfg, dlpm_unet **out) { return create_net(cfg, 0, out); }
+
+extern "C" int dlpm_unet_create_conditional(const dlpm_unet_config *cfg, int32_t num_classes, dlpm_unet **out) {
+    DLPM_CHECK_ARG(num_classes > 0, "dlpm_unet_create_conditional: num_classes must be positive, got %d", num_classes);
+    return create_net(cfg, num_classes, out);
+}
+
+extern "C" int32_t dlpm_unet_num_classes(const dlpm_unet *net) { return net ? net->num_classes : 0; }
 
 extern "C" int dlpm_unet_num_params(const dlpm_unet *net) { return net ? (int)net->params.size() : 0; }
 
@@ -1047,6 +1090,10 @@ extern "C" int64_t dlpm_unet_time_embeddings_scratch_bytes(const dlpm_unet *u, i
 extern "C" int dlpm_unet_time_embeddings(dlpm_unet *net, const float *t_dev, int64_t M, float *out_dev, void *scratch_dev, int64_t scratch_bytes,
                                          dlpm_stream_t stream) {
     DLPM_CHECK_ARG(net && t_dev && out_dev && scratch_dev && M > 0 && M < (1 << 24), "dlpm_unet_time_embeddings: bad argument");
+    if (net->num_classes > 0) {
+        set_error("dlpm_unet_time_embeddings: the emb rows of a class-conditional net depend on the label, not on t alone");
+        return DLPM_ERR_UNSUPPORTED;
+    }
     if (!net->finalized) {
         set_error("dlpm_unet_time_embeddings: call dlpm_unet_finalize first");
         return DLPM_ERR_STATE;
@@ -1058,6 +1105,24 @@ extern "C" int dlpm_unet_time_embeddings(dlpm_unet *net, const float *t_dev, int
     }
     float *e0 = static_cast<float *>(scratch_dev), *e1 = e0 + M * net->cfg.model_channels, *e2 = e1 + M * net->ted;
     return time_path(net, t_dev, (int)M, e0, e1, e2, out_dev, as_stream(stream));
+}
+
+int64_t dlpm::unet_time_mlp_width(const dlpm_unet *net) { return net ? net->ted : -1; }
+
+// the time-MLP rows of a conditional net (before the label term): out_dev[M][4 * model_channels], same scratch as above
+int dlpm::unet_time_mlp_rows(dlpm_unet *net, const float *t_dev, int64_t M, float *out_dev, void *scratch_dev, int64_t scratch_bytes,
+                             hipStream_t st) {
+    DLPM_CHECK_ARG(net && t_dev && out_dev && scratch_dev && M > 0 && M < (1 << 24), "unet_time_mlp_rows: bad argument");
+    if (!net->finalized) {
+        set_error("unet_time_mlp_rows: call dlpm_unet_finalize first");
+        return DLPM_ERR_STATE;
+    }
+    if (scratch_bytes < dlpm_unet_time_embeddings_scratch_bytes(net, M)) {
+        set_error("unet_time_mlp_rows: scratch too small");
+        return DLPM_ERR_NOMEM;
+    }
+    float *e0 = static_cast<float *>(scratch_dev), *e1 = e0 + M * net->cfg.model_channels;
+    return time_mlp(net, t_dev, (int)M, e0, e1, out_dev, st);
 }
 
 extern "C" int dlpm_unet_bind_time_table(dlpm_unet *net, const float *table_dev, const int32_t *row_index_dev) {
@@ -1090,16 +1155,30 @@ extern "C" int64_t dlpm_unet_workspace_bytes(const dlpm_unet *net, int64_t B) {
 }
 
 static int unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, void *workspace_dev,
-                        int64_t workspace_bytes, dlpm_stream_t stream, bool uniform_t, const HeadUpdate *hu = nullptr);
+                        int64_t workspace_bytes, dlpm_stream_t stream, bool uniform_t, const int64_t *y_dev,
+                        const HeadUpdate *hu = nullptr);
 
 extern "C" int dlpm_unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B,
                                  void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream) {
-    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, false);
+    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, false, nullptr);
 }
 
 extern "C" int dlpm_unet_forward_uniform_t(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B,
                                            void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream) {
-    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, true);
+    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, true, nullptr);
+}
+
+extern "C" int dlpm_unet_forward_labels(dlpm_unet *net, const float *x_dev, const float *t_dev, const int64_t *y_dev, float *eps_dev,
+                                        int64_t B, void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(y_dev, "dlpm_unet_forward_labels: null labels");
+    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, false, y_dev);
+}
+
+extern "C" int dlpm_unet_forward_uniform_t_labels(dlpm_unet *net, const float *x_dev, const float *t_dev, const int64_t *y_dev,
+                                                  float *eps_dev, int64_t B, void *workspace_dev, int64_t workspace_bytes,
+                                                  dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(y_dev, "dlpm_unet_forward_uniform_t_labels: null labels");
+    return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, true, y_dev);
 }
 
 // Whether this net's head convolution runs on the kernel that can carry the update (a property of the architecture).
@@ -1118,6 +1197,14 @@ static bool head_fusable(const dlpm_unet *u) {
 extern "C" int dlpm_unet_forward_update(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const dlpm_update_args *upd,
                                         float *eps_scratch_dev, int64_t B, void *workspace_dev, int64_t workspace_bytes,
                                         dlpm_stream_t stream) {
+    return dlpm::unet_forward_update_labels(net, x_in_dev, t_dev, nullptr, upd, eps_scratch_dev, B, workspace_dev, workspace_bytes,
+                                            as_stream(stream));
+}
+
+// dlpm_unet_forward_update with the class labels of a conditional net (dlpm_sampler's step; y_dev null for an unconditional net)
+int dlpm::unet_forward_update_labels(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const int64_t *y_dev,
+                                     const dlpm_update_args *upd, float *eps_scratch_dev, int64_t B, void *workspace_dev,
+                                     int64_t workspace_bytes, hipStream_t stream) {
     DLPM_CHECK_ARG(net && x_in_dev && t_dev && upd && upd->x_dev && upd->t_dev && upd->g_dev && upd->c_eps_dev && upd->c_noise_dev,
                    "dlpm_unet_forward_update: null argument");
     DLPM_CHECK_ARG(upd->B == B, "dlpm_unet_forward_update: update batch %lld != %lld", (long long)upd->B, (long long)B);
@@ -1129,7 +1216,7 @@ extern "C" int dlpm_unet_forward_update(dlpm_unet *net, const float *x_in_dev, c
                       !(upd->flags & (DLPM_UPD_DLIM | DLPM_UPD_CLIP | DLPM_UPD_ELEMENTWISE));
     if (!fuse) {   // the variants the head's epilogue does not carry: eps through HBM, then the update kernels
         DLPM_CHECK_ARG(eps_scratch_dev, "dlpm_unet_forward_update: this update variant needs the eps scratch buffer");
-        int r = unet_forward(net, x_in_dev, t_dev, eps_scratch_dev, B, workspace_dev, workspace_bytes, stream, true);
+        int r = unet_forward(net, x_in_dev, t_dev, eps_scratch_dev, B, workspace_dev, workspace_bytes, stream, true, y_dev);
         if (r != DLPM_OK) return r;
         dlpm_update_args a = *upd;
         a.eps_dev = eps_scratch_dev;
@@ -1140,15 +1227,21 @@ extern "C" int dlpm_unet_forward_update(dlpm_unet *net, const float *x_in_dev, c
     hu.key = upd->key_dev; hu.seed = upd->seed; hu.sample_offset = upd->sample_offset; hu.hist_pp = upd->hist_pp;
     hu.T = upd->T; hu.B = B;
     float dummy;   // walk() wants a non-null eps pointer; the fused head never writes it
-    int r = unet_forward(net, x_in_dev, t_dev, eps_scratch_dev ? eps_scratch_dev : &dummy, B, workspace_dev, workspace_bytes, stream, true, &hu);
+    int r = unet_forward(net, x_in_dev, t_dev, eps_scratch_dev ? eps_scratch_dev : &dummy, B, workspace_dev, workspace_bytes, stream, true,
+                         y_dev, &hu);
     if (r != DLPM_OK) return r;
-    if (upd->flags & DLPM_UPD_ADVANCE) return launch_step_advance(const_cast<int32_t *>(upd->t_dev), as_stream(stream));
+    if (upd->flags & DLPM_UPD_ADVANCE) return launch_step_advance(const_cast<int32_t *>(upd->t_dev), stream);
     return DLPM_OK;
 }
 
 static int unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, void *workspace_dev,
-                        int64_t workspace_bytes, dlpm_stream_t stream, bool uniform_t, const HeadUpdate *hu) {
+                        int64_t workspace_bytes, dlpm_stream_t stream, bool uniform_t, const int64_t *y_dev, const HeadUpdate *hu) {
     DLPM_CHECK_ARG(net && x_dev && t_dev && eps_dev && workspace_dev, "dlpm_unet_forward: null argument");
+    // the reference asserts that labels are given iff the net is class-conditional (unet.py:463-466)
+    DLPM_CHECK_ARG(net->num_classes == 0 || y_dev, "dlpm_unet_forward: must specify y if and only if the model is class-conditional "
+                   "(this net has %d classes: call the *_labels forward)", net->num_classes);
+    DLPM_CHECK_ARG(net->num_classes > 0 || !y_dev, "dlpm_unet_forward: must specify y if and only if the model is class-conditional "
+                   "(labels given to an unconditional net)");
     DLPM_CHECK_ARG(B > 0 && B < (1 << 24), "dlpm_unet_forward: bad batch %lld", (long long)B);
     if (!net->finalized) {
         set_error("dlpm_unet_forward: call dlpm_unet_finalize first");
@@ -1168,6 +1261,7 @@ static int unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, 
     cx.ws.reuse = !net->keep_feats;
     cx.st = as_stream(stream);
     cx.uniform_t = uniform_t;
+    cx.y = y_dev;
     cx.hu = hu;
     return walk(net, cx, x_dev, t_dev, eps_dev);
 }

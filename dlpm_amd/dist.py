@@ -42,10 +42,14 @@ def sample_sharded(make_method, models, shape, reverse_steps, group=None, **samp
     """Every rank samples its shard of `shape[0]` and all ranks return the full batch.
 
     `make_method(sample_offset)` builds the rank-local GenerativeLevyProcess (same seed on every
-    rank, shard-specific offset)."""
+    rank, shard-specific offset).  `model_kwargs={'y': labels}` gives the labels of the whole batch; each rank samples
+    with its shard's slice."""
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     lo, hi = shard_range(shape[0], rank, world)
     method = make_method(lo)
+    mk = sample_kwargs.get('model_kwargs')
+    if mk and 'y' in mk:          # class labels are per sample: this rank's shard of them
+        sample_kwargs = dict(sample_kwargs, model_kwargs=dict(mk, y=mk['y'][lo:hi]))
     local = method.sample(models, [hi - lo] + list(shape[1:]), reverse_steps, **sample_kwargs)
     return all_gather_samples(local, shape[0], group)

@@ -159,8 +159,19 @@ class EvaluationManager:
         tmp_kwargs.update(kwargs)
         return self._evaluate_model(models, **tmp_kwargs)
 
-    def _evaluate_model(self, models, data_to_generate, batch_size, fig_lim=1.5, callback_on_logging=None, **kwargs):
+    def _evaluate_model(self, models, data_to_generate, batch_size, fig_lim=1.5, callback_on_logging=None, class_labels=None,
+                        **kwargs):
+        """`class_labels`: for a class-conditional net, the [data_to_generate] labels in global sample order; every chunk samples with
+        its slice (model_kwargs={'y': ...}), so neither pixels nor labels depend on the chunking, and the image dump writes them to
+        `<gen_data_path>/labels.npy` (int64, index i = image i)."""
+        if class_labels is not None:
+            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+            assert class_labels.numel() >= data_to_generate, 'class_labels: %d labels for %d samples' % (
+                class_labels.numel(), data_to_generate)
+            class_labels = class_labels[:data_to_generate]
         if not self.is_image:
+            if class_labels is not None:
+                kwargs['model_kwargs'] = {'y': class_labels}
             self.gen_manager.generate(models, data_to_generate, **kwargs)          # EvaluationManager.py:135
             return {'generated': data_to_generate, 'gen_data_path': None}
         assert self.gen_data_path is not None, 'gen_data_path is needed to save the generated images'
@@ -194,6 +205,8 @@ class EvaluationManager:
                 with ctx:
                     while remaining > 0:                                           # EvaluationManager.py:181-193
                         n = min(batch_size, remaining)
+                        if class_labels is not None:
+                            kwargs['model_kwargs'] = {'y': class_labels[total:total + n]}
                         try:
                             self.gen_manager.generate(models, n, to_host=False, declare_batch=False, **kwargs)
                         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
@@ -215,6 +228,8 @@ class EvaluationManager:
             finally:
                 dump.close()
             assert data_to_generate == total == dump.written
+            if class_labels is not None:
+                np.save(os.path.join(self.gen_data_path, 'labels.npy'), class_labels.numpy())
             if self.verbose:
                 print('saved generated data in {}.'.format(self.gen_data_path))
         return {'generated': total, 'gen_data_path': self.gen_data_path}

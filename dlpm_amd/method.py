@@ -5,7 +5,8 @@ dlpm/methods/GenerativeLevyProcess.py:48-90,512-569 (what `GenerationManager.gen
 `eval.py --generate` call).  The loop itself runs in libdlpm_amd:
 
   * `models['default']` is a dlpm_amd.UNetModel / MLPModel  -> dlpm_sampler_* (one reverse step
-    captured as a hipGraph and replayed T-1 times);
+    captured as a hipGraph and replayed T-1 times); a class-conditional UNetModel with
+    `model_kwargs={'y': labels}` takes the same path (the labels sit in a device buffer the graph reads);
   * any other callable `model(x, t)` on the GPU                -> the same noise / table / update
     kernels, with the model called from Python between them.
 
@@ -255,13 +256,21 @@ class GenerativeLevyProcess:
             e = torch.clamp(e, -clamp_eps, clamp_eps)
         return a0, e.contiguous()
 
-    def _run_native(self, model, shape, flags, eta, clamp_a, clamp_eps, noise, history, progress):
+    def _run_native(self, model, shape, flags, eta, clamp_a, clamp_eps, noise, history, progress, labels=None):
         L, st = _lib.lib(), _lib.stream_ptr()
         lim = bool(flags & _lib.SMP_LIM)
         T = self.reverse_steps + (1 if lim else 0)      # LIM runs `reverse_steps` updates, DLPM reverse_steps - 1
         seed, offset = self._philox_key()
+        if getattr(model, 'num_classes', None) is not None:
+            if lim:
+                raise NotImplementedError('the LIM sampler does not take class labels')
+            labels = model._check_labels(shape[0], labels)      # the reference's checks, before any device work
         h = self._native_sampler(model, shape, flags, eta, clamp_a, clamp_eps, seed, offset)
         dev = torch.device(self.device)
+        if labels is not None:
+            # into the sampler's own buffer: its captured graph reads them from there, so new labels need no recapture
+            y_d = labels.to(dev, torch.int64).contiguous()
+            _lib.check(L.dlpm_sampler_set_labels(h, y_d.data_ptr(), st))
         x = torch.empty(shape, dtype=torch.float32, device=dev)
         # the update kernel stores every intermediate state into this buffer (row T - t), inside the graph
         hist = torch.empty([T] + list(shape), dtype=torch.float32, device=dev) if history else None
@@ -465,10 +474,12 @@ class GenerativeLevyProcess:
             model.eval()
         clamp_a = self.dlpm.gen_a.kwargs.get('clamp_a')
         clamp_eps = self.dlpm.gen_eps.kwargs.get('clamp_eps')
-        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and not model_kwargs
+        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and \
+            _native_kwargs(model, model_kwargs)
         with torch.inference_mode():
             if native:
-                out = self._run_native(model, list(shape), flags, eta, clamp_a, clamp_eps, noise, history, progress)
+                out = self._run_native(model, list(shape), flags, eta, clamp_a, clamp_eps, noise, history, progress,
+                                       labels=(model_kwargs or {}).get('y'))
             else:
                 out = self._run_callable(model, list(shape), flags, eta, clamp_a, clamp_eps, noise, history, progress,
                                          denoised_fn=denoised_fn, model_kwargs=model_kwargs)
@@ -498,8 +509,9 @@ class GenerativeLevyProcess:
     # -------------------------------------------------------------------------------- BEM: SAMPLING
     def sample(self, models, shape, reverse_steps, time_spacing=None, initial_data=None, clip_denoised=False,
                deterministic=False, dlim_eta=1.0, print_progression=False, get_sample_history=False, clamp_a=None,
-               clamp_eps=None):
-        """GenerativeLevyProcess.sample: dlpm/methods/GenerativeLevyProcess.py:512-569."""
+               clamp_eps=None, model_kwargs=None):
+        """GenerativeLevyProcess.sample: dlpm/methods/GenerativeLevyProcess.py:512-569.  `model_kwargs` (this build's addition, passed on
+        to the model as the reference's loops do, :601): {'y': labels} for a class-conditional UNetModel."""
         from .unet import UNetModel
         from .mlp import MLPModel
         self.dlpm.gen_a.setParams(clamp_a=clamp_a)          # stateful, as in the reference (:526-527)
@@ -517,9 +529,11 @@ class GenerativeLevyProcess:
         noise = initial_data if deterministic else None
         flags = (_lib.UPD_DLIM if deterministic else 0) | (_lib.UPD_CLIP if clip_denoised else 0)
         eta = dlim_eta if deterministic else 0.0
-        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps
-        run = self._run_native if native else self._run_callable
+        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and _native_kwargs(model, model_kwargs)
+        labels = (model_kwargs or {}).get('y')
         with torch.inference_mode():
+            if self.LIM and (model_kwargs or getattr(model, 'num_classes', None) is not None):
+                raise NotImplementedError('the LIM sampler does not take model_kwargs / class labels')
             if self.LIM:
                 # lim_sample (GenerativeLevyProcess.py:454-507): `deterministic` selects the ODE; clip_denoised and
                 # initial_data are accepted and ignored, as in the reference
@@ -528,8 +542,12 @@ class GenerativeLevyProcess:
                     out = self._run_native(model, shape, flags, 0.0, None, clamp_eps, None, get_sample_history, print_progression)
                 else:
                     out = self._run_callable_lim(model, shape, flags, clamp_eps, get_sample_history, print_progression)
+            elif native:
+                out = self._run_native(model, shape, flags, eta, clamp_a, clamp_eps, noise, get_sample_history, print_progression,
+                                       labels=labels)
             else:
-                out = run(model, shape, flags, eta, clamp_a, clamp_eps, noise, get_sample_history, print_progression)
+                out = self._run_callable(model, shape, flags, eta, clamp_a, clamp_eps, noise, get_sample_history, print_progression,
+                                         model_kwargs=model_kwargs)
         if self._dataset is not None:
             self._dataset['next'] += shape[0]
         else:
@@ -538,6 +556,14 @@ class GenerativeLevyProcess:
 
     def training_losses(self, *a, **k):
         raise NotImplementedError('training is outside the sampling hot path this build covers (SURVEY.md 2b)')
+
+
+def _native_kwargs(model, model_kwargs):
+    """Whether the native sampler carries these model_kwargs: none for an unconditional net, exactly {'y': labels} for a
+    class-conditional UNetModel.  Anything else runs the model from Python (model(x, t, **model_kwargs))."""
+    if getattr(model, 'num_classes', None) is not None:
+        return set(model_kwargs or {}) == {'y'}
+    return not model_kwargs
 
 
 def init_method_by_parameter(p, **kw):

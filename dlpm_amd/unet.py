@@ -5,7 +5,8 @@ dlpm/dlpm_experiment.py:38-56 and exposes the SAME `state_dict` keys/shapes (so 
 checkpoints load with `load_state_dict`) and, because the torch modules are instantiated in the
 reference's construction order (unet.py:334-436), the SAME default initialisation under a given
 `torch.manual_seed`.  `forward(x, timesteps)` runs entirely in libdlpm_amd (HIP, gfx950); there is
-no PyTorch compute path and it raises if the library is unavailable.
+no PyTorch compute path and it raises if the library is unavailable.  `num_classes=K` builds the reference's
+class-conditional net (`label_emb`, unet.py:341-342): `forward(x, timesteps, y)` then takes int64 labels.
 """
 import ctypes as C
 import weakref
@@ -56,9 +57,9 @@ class UNetModel(nn.Module):
                  use_checkpoint=False, num_heads=1, num_heads_upsample=-1, use_scale_shift_norm=False,
                  image_size=None):
         super().__init__()
-        if dims != 2 or num_classes is not None or not conv_resample or not use_scale_shift_norm:
+        if dims != 2 or not conv_resample or not use_scale_shift_norm:
             raise NotImplementedError('dlpm_amd.UNetModel implements the configuration DLPM instantiates '
-                                      '(dims=2, unconditional, conv_resample, use_scale_shift_norm=True)')
+                                      '(dims=2, conv_resample, use_scale_shift_norm=True)')
         if num_heads_upsample not in (-1, num_heads):
             raise NotImplementedError('num_heads_upsample must equal num_heads')
         if dropout:
@@ -68,10 +69,13 @@ class UNetModel(nn.Module):
         self.attention_resolutions = tuple(attention_resolutions)
         self.channel_mult = tuple(channel_mult)
         self.num_heads = num_heads
+        self.num_classes = num_classes
         self.image_size = image_size
         mc, ted = model_channels, 4 * model_channels
 
         self.time_embed = _holder([('0', nn.Linear(mc, ted)), ('2', nn.Linear(ted, ted))])
+        if num_classes is not None:
+            self.label_emb = nn.Embedding(num_classes, ted)                 # unet.py:341-342: right after time_embed
         blocks = [_holder([('0', nn.Conv2d(in_channels, mc, 3, padding=1))])]
         chans, ch, ds = [mc], mc, 1
         for level, mult in enumerate(self.channel_mult):
@@ -183,7 +187,10 @@ class UNetModel(nn.Module):
         for i, a in enumerate(self.attention_resolutions):
             cfg.attention_resolutions[i] = a
         h = C.c_void_p()
-        _lib.check(L.dlpm_unet_create(C.byref(cfg), C.byref(h)))
+        if self.num_classes is None:
+            _lib.check(L.dlpm_unet_create(C.byref(cfg), C.byref(h)))
+        else:
+            _lib.check(L.dlpm_unet_create_conditional(C.byref(cfg), int(self.num_classes), C.byref(h)))
         sd = self.state_dict()
         n = L.dlpm_unet_num_params(h)
         if n != len(sd):
@@ -217,9 +224,23 @@ class UNetModel(nn.Module):
         return _lib.lib().dlpm_unet_flops_per_sample(self.native_handle(image_size))
 
     # ------------------------------------------------------------------ model(x, t) protocol
+    def _check_labels(self, B, y):
+        """The reference's argument checks (unet.py:463-473), before any device work: y iff conditional, y.shape == (B,), and
+        labels in [0, K) (nn.Embedding raises IndexError).  Returns the labels as contiguous int64 on x's device, or None."""
+        assert (y is not None) == (self.num_classes is not None), \
+            'must specify y if and only if the model is class-conditional'
+        if y is None:
+            return None
+        assert y.shape == (B,)
+        if y.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise TypeError('class labels must be an integer tensor, got %s' % y.dtype)
+        if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
+            raise IndexError('class label out of range [0, %d): min %d, max %d' % (self.num_classes, int(y.min()), int(y.max())))
+        return y
+
     def forward(self, x, timesteps, y=None):
-        """eps = model(x[B,C,H,W] fp32 on the GPU, t[B] floats) -- GenerativeLevyProcess.py:180."""
-        assert y is None, 'class conditioning is not part of the DLPM path'
+        """eps = model(x[B,C,H,W] fp32 on the GPU, t[B] floats[, y[B] class labels]) -- GenerativeLevyProcess.py:180."""
+        y = self._check_labels(x.shape[0], y)
         if not x.is_cuda:
             raise _lib.DlpmError('dlpm_amd.UNetModel.forward runs on the MI355X only (x is on %s); '
                                  'there is no CPU fallback' % x.device)
@@ -231,17 +252,23 @@ class UNetModel(nn.Module):
         assert t.shape == (B,)
         out = torch.empty((B, self.out_channels, H, W), dtype=torch.float32, device=x.device)
         ws = self.workspace(B, x.device)
-        _lib.check(_lib.lib().dlpm_unet_forward(h, x.data_ptr(), t.data_ptr(), out.data_ptr(), B, ws.data_ptr(),
-                                               ws.numel(), _lib.stream_ptr()))
+        if y is None:
+            _lib.check(_lib.lib().dlpm_unet_forward(h, x.data_ptr(), t.data_ptr(), out.data_ptr(), B, ws.data_ptr(),
+                                                   ws.numel(), _lib.stream_ptr()))
+        else:
+            y = y.to(x.device, torch.int64).contiguous()
+            _lib.check(_lib.lib().dlpm_unet_forward_labels(h, x.data_ptr(), t.data_ptr(), y.data_ptr(), out.data_ptr(), B,
+                                                          ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
         return out
 
     def get_feature_vectors(self, x, timesteps, y=None):
         """Block outputs of a forward as NCHW tensors: {'down': [...], 'middle': t, 'up': [...]}
         (same structure as the reference's UNetModel.get_feature_vectors, unet.py:494-524)."""
+        self._check_labels(x.shape[0], y)
         L = _lib.lib()
         _lib.check(L.dlpm_unet_keep_features(self.native_handle(x.shape[2]), 1))   # no arena recycling for this forward
         try:
-            self.forward(x, timesteps)
+            self.forward(x, timesteps, y)
             return self._collect_features(x)
         finally:
             _lib.check(L.dlpm_unet_keep_features(self._handle, 0))
@@ -261,10 +288,16 @@ class UNetModel(nn.Module):
 
 
 def unet_from_config(p):
-    """_unet_model(p): dlpm/dlpm_experiment.py:24-57 (reference YAML schema)."""
+    """_unet_model(p): dlpm/dlpm_experiment.py:24-57 (reference YAML schema).  `model.class_cond: true` with `data.num_classes: K`
+    builds the class-conditional net (the reference's commented `num_classes=(NUM_CLASSES if class_cond else None)`, :51)."""
     m = p['model']
+    num_classes = None
+    if m.get('class_cond', False):
+        num_classes = p['data'].get('num_classes')
+        assert num_classes, 'model.class_cond needs data.num_classes'
+        num_classes = int(num_classes)
     return UNetModel(in_channels=p['data']['channels'], model_channels=m['model_channels'],
                      out_channels=p['data']['channels'], num_res_blocks=m['num_res_blocks'],
                      attention_resolutions=m['attn_resolutions'], dropout=m['dropout'], channel_mult=m['channel_mult'],
-                     dims=2, num_classes=None, use_checkpoint=False, num_heads=m['num_heads'], num_heads_upsample=-1,
+                     dims=2, num_classes=num_classes, use_checkpoint=False, num_heads=m['num_heads'], num_heads_upsample=-1,
                      use_scale_shift_norm=True, image_size=p['data'].get('image_size'))

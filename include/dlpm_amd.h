@@ -296,6 +296,14 @@ typedef struct dlpm_unet_config {
 typedef struct dlpm_unet dlpm_unet; /* opaque; owns device copies of the weights */
 
 int dlpm_unet_create(const dlpm_unet_config *cfg, dlpm_unet **out);
+/* A class-conditional net (UNetModel(num_classes=K), unet.py:341-342): the parameter list gains "label_emb.weight" [K][4 *
+ * model_channels] right after the time_embed tensors (the reference's state_dict order), and the time path becomes
+ * emb = time_embed(t) + label_emb(y) per sample (unet.py:470-473).  Such a net takes labels on every forward: the forwards
+ * without labels (dlpm_unet_forward / _uniform_t / _update) return DLPM_ERR_ARG on it, as the reference asserts
+ * (unet.py:463-466), and dlpm_unet_time_embeddings returns DLPM_ERR_UNSUPPORTED (its rows depend on the label).
+ * dlpm_unet_num_classes: K, 0 for an unconditional net. */
+int dlpm_unet_create_conditional(const dlpm_unet_config *cfg, int32_t num_classes, dlpm_unet **out);
+int32_t dlpm_unet_num_classes(const dlpm_unet *net);
 /* Upload one tensor by its reference state_dict key (e.g. "input_blocks.7.1.qkv.weight"), from a
  * host fp32 buffer in the reference's layout (OIHW conv weights etc.); the library re-lays it out. */
 int dlpm_unet_set_param(dlpm_unet *net, const char *key, const float *host_data, int64_t numel);
@@ -330,6 +338,14 @@ int dlpm_unet_bind_time_table(dlpm_unet *net, const float *table_dev, const int3
  * (unet.py:147-150, 336-338) are evaluated for one row instead of B identical ones.  Same bits as dlpm_unet_forward. */
 int dlpm_unet_forward_uniform_t(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B,
                                 void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream);
+/* The forwards of a class-conditional net: y_dev[B] int64 labels on the device (torch.long), one per sample.  The emb rows are
+ * computed per sample (B rows whatever t is), so a sample's row has the same bits from either call and from dlpm_sampler.  A label
+ * outside [0, num_classes) is never used as an index: its sample's emb row is NaN (so is its output).  Check labels before the call
+ * (UNetModel.forward raises IndexError, as nn.Embedding does).  DLPM_ERR_ARG on an unconditional net. */
+int dlpm_unet_forward_labels(dlpm_unet *net, const float *x_dev, const float *t_dev, const int64_t *y_dev, float *eps_dev, int64_t B,
+                             void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream);
+int dlpm_unet_forward_uniform_t_labels(dlpm_unet *net, const float *x_dev, const float *t_dev, const int64_t *y_dev, float *eps_dev,
+                                       int64_t B, void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream);
 /* One network evaluation AND the reverse update of the sampler in one call: x_in_dev is what the net reads (the state, or its
  * input-scaled copy), upd describes the update of upd->x_dev exactly as for dlpm_update_f32 except that upd->eps_dev is ignored --
  * eps is what this forward computes.  For the stochastic DLPM step without clipping / DLIM / element-wise tables, on nets whose
@@ -556,6 +572,11 @@ int dlpm_sampler_steps(dlpm_sampler *s, int32_t nsteps, dlpm_stream_t stream);
  * `torch.stack(x_hist)` the reference returns with get_sample_history (GenerativeLevyProcess.py:274-288) --
  * written by the update kernel inside the captured graph, no per-step host round trip.  Call before begin. */
 int dlpm_sampler_set_history(dlpm_sampler *s, float *hist_dev, dlpm_stream_t stream);
+/* Class-conditional net: copy the B int64 labels y_dev (device, one per sample of this shard) into a buffer the sampler owns and its
+ * captured graph reads -- new labels take effect at the next step without a recapture.  Required before dlpm_sampler_begin* on such
+ * a net (DLPM_ERR_STATE otherwise); DLPM_ERR_ARG for an unconditional net.  Labels must lie in [0, num_classes) (see
+ * dlpm_unet_forward_labels).  The LIM loop (DLPM_SMP_LIM) does not take labels: dlpm_sampler_create refuses a conditional net there. */
+int dlpm_sampler_set_labels(dlpm_sampler *s, const int64_t *y_dev, dlpm_stream_t stream);
 
 /* Copy the current state x[B,C,H,W] into a caller buffer (device to device, on `stream`). */
 int dlpm_sampler_copy_state(dlpm_sampler *s, float *out_dev, dlpm_stream_t stream);

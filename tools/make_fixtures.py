@@ -21,6 +21,7 @@ Fixture families:
   F13 small blocks       ResBlock / AttentionBlock at the fused kernels' shapes     dlpm/models/unet.py:105-250
   F14 16x16 / 32x32 blocks  AttentionBlock at T = 256, ResBlocks of the MNIST-sized net's fine levels   dlpm/models/unet.py:105-250
   F15 any geometry      QKVAttention at any T / head dim, the 28x28 MNIST UNet (forward, bounded T=1000 sample)   dlpm/models/unet.py
+  F16 class-conditional  UNetModel(num_classes=10) forwards, p_sample_loop / ddim_sample_loop with model_kwargs={'y': y}   unet.py:341-342, 463-481
   F12 mean types         p_mean_variance: START_X / Z / PREVIOUS_X, denoised_fn, model_kwargs   GenerativeLevyProcess.py:154-219
   F11 image quantisation PIL's float -> 8-bit path (torchvision absent)  bem/evaluate/EvaluationManager.py:188-190
   F9 checkpoints         TrainingManager.save/load, EMAHelper,    bem/TrainingManager.py:240-285, bem/utils_ema.py,
@@ -96,11 +97,11 @@ def rerandomize(model, seed, std=0.02, perturb_norm=True):
     return model
 
 
-def make_unet(in_ch, mc, mult, attn, heads, res):
+def make_unet(in_ch, mc, mult, attn, heads, res, num_classes=None):
     # constructor arguments as dlpm/dlpm_experiment.py:38-56
     return ref_unet.UNetModel(in_channels=in_ch, model_channels=mc, out_channels=in_ch,
                               num_res_blocks=res, attention_resolutions=attn, dropout=0.0,
-                              channel_mult=mult, dims=2, num_classes=None, use_checkpoint=False,
+                              channel_mult=mult, dims=2, num_classes=num_classes, use_checkpoint=False,
                               num_heads=heads, num_heads_upsample=-1, use_scale_shift_norm=True)
 
 
@@ -919,6 +920,99 @@ def f15_geometry():
              digest=np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8), state_900=hist[900])
 
 
+F16_NETS = {
+    # name: (in_ch, mc, mult, attn, heads, res); 32x32 images, K = 10 classes
+    'mnist': (1, 32, [1, 2, 2, 2], [2, 4], 4, 2),
+    'cifar_narrow': (3, 32, [1, 2, 2, 2], [4, 8, 16], 4, 2),    # the CIFAR net's block structure at a narrow width
+}
+F16_K, F16_Y = 10, [0, 9, 3, 3, 7, 0]     # mixed labels: repeats, 0 and K - 1
+
+
+def f16_conditional():
+    """Class-conditional UNets (num_classes = 10): forwards of two nets at per-sample t and at one t for the whole batch, and a bounded
+    DLPM p_sample_loop / DLIM ddim_sample_loop of the MNIST-shaped net with model_kwargs={'y': y} on the reference's CPU streams.
+    Weights: torch.manual_seed(1234) init (digest stored), then rerandomize(net, 4321) -- label_emb keeps its N(0, 1) init."""
+    y = torch.tensor(F16_Y, dtype=torch.int64)
+    B = len(F16_Y)
+    for name, (in_ch, mc, mult, attn, heads, res) in F16_NETS.items():
+        torch.manual_seed(1234)
+        net = make_unet(in_ch, mc, mult, attn, heads, res, num_classes=F16_K).eval()
+        digest_init = weight_digest(net)
+        rerandomize(net, 4321)
+        g = torch.Generator().manual_seed(16)
+        x = torch.randn(B, in_ch, 32, 32, generator=g)
+        t = torch.rand(B, generator=g)
+        t_same = torch.full((B,), 0.37)
+        with torch.inference_mode():
+            out = net(x, t, y)
+            out_same = net(x, t_same, y)
+        sd = net.state_dict()
+        keys = list(sd.keys())
+        shapes = np.full((len(keys), 4), -1, dtype=np.int64)
+        for i, k in enumerate(keys):
+            shapes[i, :sd[k].dim()] = sd[k].shape
+        save('f16_cond_%s' % name, x=x, t=t, y=y, out=out, out_same_t=out_same, t_same=t_same,
+             cfg=np.array([in_ch, mc, heads, res, 32, F16_K]), mult=np.array(mult), attn=np.array(attn),
+             digest_init=np.frombuffer(bytes.fromhex(digest_init), dtype=np.uint8),
+             digest_final=np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8), keys=np.array(keys), shapes=shapes)
+
+    # ---- bounded trajectories of the MNIST-shaped net (head convolution x 5, as f5b's MNIST net): clip_denoised, mnist.yml's clamps
+    in_ch, mc, mult, attn, heads, res = F16_NETS['mnist']
+    alpha, ca, ce, REL = 1.7, 20, 200, 1e-4
+    shape = [B, in_ch, 32, 32]
+
+    class Perturbed(torch.nn.Module):   # net(x, t, y) * (1 + rel * N(0, 1)), drawn from a generator of its own
+        def __init__(self, net, rel, seed):
+            super().__init__()
+            self.net, self.rel, self.g = net, rel, torch.Generator().manual_seed(seed)
+
+        def forward(self, x, t, **kw):
+            o = self.net(x, t, **kw)
+            return o * (1 + self.rel * torch.randn(o.shape, generator=self.g))
+
+    def post(v):
+        return (v.clamp(-1, 1) + 1) / 2
+
+    # Stochastic loop: T = 200, head x 5 (sensitivity 1.3, 63 % of the pixels in range).  The deterministic DLIM loop amplifies far more
+    # and drives most pixels of this random net onto the clip bound (T = 200: sensitivity 24 at head x 5, 54 at x 1; T = 50 / 30 / 20:
+    # 14..46; at every setting tried <= 19 % of the pixels end inside (-1, 1)): the first (T, head scale) of F16_DLIM whose sensitivity
+    # stays checkable at 1e-4 (<= 3) -- T = 10 at the reference init's head: 2.9, 7 % inside
+    dlim_choices = [tuple(float(v) for v in c.split(':')) for c in os.environ.get('F16_DLIM', '10:1').split()]
+    for tag, dlim, T, head_scale in [('dlpm', False, 200, 5.0)] + [('dlim', True, int(c[0]), c[1]) for c in dlim_choices]:
+        torch.manual_seed(1234)
+        net = make_unet(in_ch, mc, mult, attn, heads, res, num_classes=F16_K).eval()
+        rerandomize(net, 4321)
+        with torch.no_grad():
+            net.out[2].weight.mul_(head_scale)
+            net.out[2].bias.mul_(head_scale)
+
+        def run(model):
+            np.random.seed(0)
+            torch.manual_seed(0)
+            meth = GenerativeLevyProcess(alpha=alpha, device='cpu', reverse_steps=T, rescale_timesteps=True)
+            meth.dlpm.gen_a.setParams(clamp_a=ca)          # what sample() sets before its loop (GenerativeLevyProcess.py:526-527)
+            meth.dlpm.gen_eps.setParams(clamp_eps=ce)
+            loop = meth.ddim_sample_loop if dlim else meth.p_sample_loop
+            return loop(model, shape, clip_denoised=True, model_kwargs={'y': y}, get_sample_history=True)
+        x, hist = run(net)
+        xp, _ = run(Perturbed(net, REL, 77))
+        sens = float((post(xp) - post(x)).abs().max()) / REL
+        sens_state = float((xp - x).abs().max()) / REL
+        inside = float((x.abs() < 1).float().mean())
+        print('f16 %s T = %d head x %g: %.1f %% of the final pixels inside (-1, 1), sensitivity %.3g (state %.3g)'
+              % (tag, T, head_scale, 100 * inside, sens, sens_state))
+        if dlim and not sens <= 3.0:
+            continue
+        save('f16_traj_cond_mnist_%s_clip' % tag, final=x, history_sub=hist[::T // 10], every=np.array(T // 10), y=y,
+             meta=np.array([T, alpha, ca, ce]), shape=np.array(shape), head_scale=np.array(head_scale), inside=np.array(inside),
+             sensitivity=np.array(sens), sensitivity_state=np.array(sens_state), sensitivity_rel=np.array(REL),
+             digest=np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8))
+        if dlim:
+            break
+    else:
+        raise AssertionError('f16: no DLIM setting of F16_DLIM gives an informative, checkable trajectory')
+
+
 def f8_generation_manager():
     class FakeMethod:
         device = 'cpu'
@@ -1108,9 +1202,9 @@ def f10_lim():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15']
+    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16']
     table = dict(f12=f12_mean_types, f11=f11_image_quantise, f10=f10_lim, f1=f1_schedule, f2=f2_noise, f3=f3_tables, f4=f4_single_step, f5=f5_trajectories, f5u=f5_unet_trajectory, f5w=f5_wide_unet_trajectory, f5k=f5_unet_trajectories_T1000, f5b=f5_bounded_unet_trajectories, f5c=f5_cifar_teacher_forced,
-                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f8=f8_generation_manager, f9=f9_checkpoints)
+                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f8=f8_generation_manager, f9=f9_checkpoints)
     with torch.no_grad():
         for w in which:
             table[w]()
