@@ -31,8 +31,6 @@ struct ConvLaunch {
     float *out = nullptr;
     int Cout = 0;
     int in_nchw = 0, out_nchw = 0;  // boundary layouts
-    int ws_gemm = 0;                // 1x1 only: use the weight-streaming kernel (TAPS = 1) instead of k_conv_igemm
-    int abl = 0;                    // timing-only ablation bits (DLPM_ABL env, only in builds with -DDLPM_IGEMM_ABLATIONS; results are wrong when set)
     // Which kernel generation a 3x3 stride-1 launch takes is a function of the LAYER (geometry + this policy), never of the
     // batch the launch happens to carry: the generations round differently, and a sample must not depend on how its batch
     // was sharded or chunked.  gen = DLPM_CONV_AUTO / _F4 / _F2 / _IGEMM (include/dlpm_amd.h); dispatch_B > 0 lets AUTO
@@ -44,7 +42,6 @@ struct ConvLaunch {
     // [s Cin / ksplit, (s + 1) Cin / ksplit) and writing its partial outputs to out + s B Hout Wout Cout (bias / residual / statistics
     // are null in such a launch: launch_splitk_reduce adds them).  Taken by the narrow F(4x4) shapes and the F(2x2) kernel only.
     int ksplit = 0;
-    int pers_total = 0;             // persistent form of the 8-wave F(4x4) shape (DLPM_WINO4_PERSIST): tiles of the launch (the grid is one workgroup per CU)
     // Optional fused GroupNorm statistics of the OUTPUT: per (image, pixel tile, channel) the
     // pair (mean, centred sum of squares) over the tile's pixels, written by the MFMA kernels'
     // epilogue when the tile lies inside one image.  [B][HW/tile][Cout] float2 with tile =
@@ -98,8 +95,6 @@ int64_t wino_weight_floats(int Cout, int Cin);
 int relayout_weight_wino(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 // Winograd F(4x4,3x3) path (conv_wino4.hip): 16 tiles of 4x4 outputs x 128 channels per workgroup
 bool wino4_enabled();                  // DLPM_WINO_F4
-bool wino4_vsplit();                   // DLPM_WINO_VS: waves = position halves x channel quarters (weight fragment order follows)
-bool wino4_image_stats(int cout);      // this layer's epilogue emits per-image statistics for blocks of four 8x8 images
 bool wino4_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg);
 bool wino4_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg);   // geometry + dispatch policy
 int launch_conv_wino4(const ConvLaunch &c, hipStream_t st);
@@ -148,7 +143,6 @@ int conv_stats_pixels(const ConvLaunch &c);
 int conv_ksplit_for(const ConvLaunch &c);
 int wino4_launch_nq(const ConvLaunch &c);      // the n-tile width launch_conv_wino4 would use
 int64_t wino_grid_at(const ConvLaunch &c, int64_t B);   // workgroups of the F(2x2) kernel at batch B
-int wino_chunk_channels(const ConvLaunch &c);            // input channels per chunk of its K loop (8; 16 under DLPM_WINO_KC=16)
 // out = bias + sum_s part[s] (+ residual [res0 | res1]) over n = B Hout Wout pixels x Cout channels, partials summed in ascending s
 int launch_splitk_reduce(const float *part, int S, int64_t npix, int Cout, const float *bias, const float *res0, const float *res1, int R0,
                          float *out, hipStream_t st);
@@ -163,8 +157,8 @@ inline int launch_conv_fallback(const ConvLaunch &L, hipStream_t st) {
 // weight re-layout kernels: OIHW -> [tap][Cout][Cin] (igemm) or [tap][Cin][Cout] (direct)
 int relayout_weight(const float *oihw_dev, float *dst_dev, int Cout, int Cin, int ks, bool for_igemm, hipStream_t st);
 // OIHW 3x3 -> fragment order for k_conv3x3_halo_ws; dst holds frag_weight_floats(Cout, Cin) floats
-int64_t frag_weight_floats(int Cout, int Cin, int taps = 9);
-int relayout_weight_frag(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st, int taps = 9);
+int64_t frag_weight_floats(int Cout, int Cin);
+int relayout_weight_frag(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 
 int launch_gn_coeffs(const float *src0, const float *src1, int C0, int C1, int B, int HW, int groups,
                      const float *gamma, const float *beta, const float *ss, int64_t ss_stride, int64_t ss_offset,

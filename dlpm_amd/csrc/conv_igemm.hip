@@ -66,7 +66,7 @@ __device__ __forceinline__ void epilogue_rows(const ConvLaunch &p, floatx16 (&ac
                     const float4 b = *reinterpret_cast<const float4 *>(p.bias + n);
                     v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
                 }
-                if (p.res0 && !(p.abl & 2)) {
+                if (p.res0) {
                     const float4 q = (n < p.R0) ? *reinterpret_cast<const float4 *>(p.res0 + m * p.R0 + n)
                                                 : *reinterpret_cast<const float4 *>(p.res1 + m * R1 + (n - p.R0));
                     v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
@@ -80,7 +80,6 @@ __device__ __forceinline__ void epilogue_rows(const ConvLaunch &p, floatx16 (&ac
                     d = v.w - K.w; s1.w += d; s2.w = fmaf(d, d, s2.w);
                     cnt++;
                 }
-                if ((p.abl & 1) && v.x == v.x) continue;  // timing ablation only
                 *reinterpret_cast<float4 *>(p.out + m * p.Cout + n) = v;
             }
         }
@@ -410,7 +409,7 @@ __global__ void __launch_bounds__(256) k_conv3x3_halo(ConvLaunch p, int th, int 
                     x.z = fmaf(x.z, ca.z, cb.z);
                     x.w = fmaf(x.w, ca.w, cb.w);
                 }
-                if (p.act_silu && !(p.abl & 4)) {
+                if (p.act_silu) {
                     x.x = silu_f(x.x);
                     x.y = silu_f(x.y);
                     x.z = silu_f(x.z);
@@ -467,14 +466,14 @@ __global__ void __launch_bounds__(256) k_conv3x3_halo(ConvLaunch p, int th, int 
     __syncthreads();
 
     int s = 0;
-    for (int chunk = 0; chunk < ((p.abl & 64) ? 0 : nch); chunk++) {
+    for (int chunk = 0; chunk < nch; chunk++) {
 #pragma unroll 1
         for (int tap = 0; tap < 9; tap++, s++) {
             const int buf = s & 1;
             const bool last_tap = tap == 8, more = (chunk + 1 < nch);
             // one UNCONDITIONAL weight prefetch per tap (harmlessly redundant on the very last step):
             // two call sites would make hipcc merge their results with copies behind a vmcnt(0)
-            if (!(p.abl & 32)) load_w(last_tap ? min(chunk + 1, nch - 1) : chunk, last_tap ? 0 : tap + 1);
+            load_w(last_tap ? min(chunk + 1, nch - 1) : chunk, last_tap ? 0 : tap + 1);
             if (last_tap && more) load_halo(chunk + 1);
 
             const int ky = tap / 3, kx = tap - ky * 3;
@@ -497,13 +496,13 @@ __global__ void __launch_bounds__(256) k_conv3x3_halo(ConvLaunch p, int th, int 
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
                     }
             }
-            if ((!last_tap || more) && !(p.abl & 8)) store_w(buf ^ 1);
+            if (!last_tap || more) store_w(buf ^ 1);
             if (last_tap && more) {
                 store_coef();     // (the previous chunk's coefficients were consumed before its first tap)
                 __syncthreads();  // every wave has finished reading this chunk's halo; coefficients visible
                 store_halo();
             }
-            if (!(p.abl & 16)) __syncthreads();
+            __syncthreads();
         }
     }
 
@@ -547,26 +546,22 @@ __global__ void __launch_bounds__(256) k_conv3x3_halo(ConvLaunch p, int th, int 
 // 1-KB pieces per n-block -- and each wave reads its stream with fully coalesced 1-KB loads,
 // prefetching one group (1024 MFMA cycles) ahead in a small register ring.  LDS then holds only
 // the activation halo, and the per-tap workgroup barrier disappears: waves synchronise twice per
-// 32-channel chunk instead of nine times.  Measured motivation (DLPM_ABL ablations, MFMA
+// 32-channel chunk instead of nine times.  Measured motivation (timing ablations, MFMA
 // micro-benchmark tools/mb/mfma_loop.hip): the LDS weight staging + per-tap barrier cost ~8 % of the
 // kernel.
 // ---------------------------------------------------------------------------------------------
-// TAPS = 9: the 3x3 convolution.  TAPS = 1: the same kernel as a plain GEMM over pixels for 1x1 convolutions / conv1d /
-// Linear (no halo, 4 fragment groups per chunk) -- weights from registers instead of through LDS.
-template <int BN, int WAVES_M, int WAVES_N, int RM, int RN, int RING, bool UPS, int TAPS = 9>
+template <int BN, int WAVES_M, int WAVES_N, int RM, int RN, int RING, bool UPS>
 __global__ void __launch_bounds__(256, 2) k_conv3x3_halo_ws(ConvLaunch p, int th, int nimg) {
     // UPS: the conv runs on the nearest-x2 upsampled input (Upsample, unet.py:73-75).  The halo tile then holds
     // the SOURCE-resolution patch ((th/2+2) x (W/2+2) pixels) and each lane's tap address is
     // row_offset[ky] + col_offset[kx], which depend on the parity of its output pixel.
     static_assert(WAVES_M * WAVES_N == 4 && WAVES_M * RM * 32 == BM && WAVES_N * RN * 32 == BN, "tile shape");
-    static_assert(TAPS == 9 || (TAPS == 1 && !UPS), "taps");
-    constexpr int NG = TAPS * 4;  // fragment groups per chunk: taps x 4 k-groups
-    constexpr int PADW = TAPS == 9 ? 1 : 0;
+    constexpr int NG = 36;  // fragment groups per chunk: 9 taps x 4 k-groups
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     const int W = p.Wout, H = p.Hout;
     const int Ws = UPS ? (W >> 1) : W, Hs = UPS ? (H >> 1) : H;   // source (staged) resolution
-    const int Wp = Ws + 2 * PADW;
-    const int hpi = ((UPS ? (th >> 1) : th) + 2 * PADW) * Wp;
+    const int Wp = Ws + 2;
+    const int hpi = ((UPS ? (th >> 1) : th) + 2) * Wp;
     const int hp = nimg * hpi;
     float *Ah = hsm;
     float *Cf = hsm + ((hp + 3) & ~3) * LDS_LD;
@@ -593,7 +588,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_halo_ws(ConvLaunch p, int th
         const int hpix = it * 32 + (tid >> 3);
         const int img = hpix / hpi, hr = hpix - img * hpi;
         const int hy = hr / Wp, hx = hr - hy * Wp;
-        const int iy = (UPS ? (y0 >> 1) : y0) + hy - PADW, ix = hx - PADW;
+        const int iy = (UPS ? (y0 >> 1) : y0) + hy - 1, ix = hx - 1;
         const bool pad = iy < 0 || iy >= Hs || ix < 0 || ix >= Ws || (pb + img) >= p.B;
         off[it] = (it >= nit || hpix >= hp) ? -2 : (pad ? -1 : (((pb + img) * Hs + iy) * Ws + ix));
     }
@@ -702,7 +697,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_halo_ws(ConvLaunch p, int th
                 bq[(g + AHEAD) % RING][j] = wbase[woff[j] + AHEAD * 64];
                 woff[j] += 64;
             }
-            if (g == (TAPS == 9 ? 24 : 0) && more) load_halo(chunk + 1);  // 3x3: at tap 6, two taps of MFMAs cover its latency
+            if (g == 24 && more) load_halo(chunk + 1);  // at tap 6: two taps of MFMAs cover its latency
             // pin the prefetch HERE: left alone, the scheduler sinks each load to just before its first
             // use (two groups later) to save registers and then waits for it with vmcnt(0)
             __builtin_amdgcn_sched_barrier(0);
@@ -764,9 +759,9 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_halo_ws(ConvLaunch p, int th
 
 // OIHW (3x3) -> Wf[nb][chunk][tap][kk][lane][4]:  lane = kh*32 + l31 holds
 // W[cout = nb*32 + l31][cin = chunk*32 + kk*8 + kh*4 + e][tap], zero beyond Cout.
-__global__ void k_relayout_weight_frag(const float *oihw, float *dst, int Cout, int Cin, int taps) {
+__global__ void k_relayout_weight_frag(const float *oihw, float *dst, int Cout, int Cin) {
     const int nbk = (Cout + 31) / 32, nch = Cin / 32;
-    const int64_t n = (int64_t)nbk * nch * taps * 4 * 64 * 4;
+    const int64_t n = (int64_t)nbk * nch * 9 * 4 * 64 * 4;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int e = (int)(i & 3);
@@ -774,12 +769,12 @@ __global__ void k_relayout_weight_frag(const float *oihw, float *dst, int Cout, 
     int64_t r = i >> 8;
     const int kk = (int)(r & 3);
     r >>= 2;
-    const int tap = (int)(r % taps);
-    r /= taps;
+    const int tap = (int)(r % 9);
+    r /= 9;
     const int chunk = (int)(r % nch);
     const int nb = (int)(r / nch);
     const int co = nb * 32 + (lane & 31), ci = chunk * 32 + kk * 8 + (lane >> 5) * 4 + e;
-    dst[i] = (co < Cout) ? oihw[((int64_t)co * Cin + ci) * taps + tap] : 0.f;
+    dst[i] = (co < Cout) ? oihw[((int64_t)co * Cin + ci) * 9 + tap] : 0.f;
 }
 
 // stem: Cin = image channels read from the caller's NCHW state, 3x3 stride 1, writes NHWC.
@@ -1042,24 +1037,23 @@ static bool halo_ok(const ConvLaunch &c, int *th, int *nimg) {
         *th = c.Hout;
         *nimg = BM / HW;
     }
-    if (c.ups && ((*th & 1) || (c.C0 + c.C1) % KC != 0 || c.abl)) return false;
+    if (c.ups && ((*th & 1) || (c.C0 + c.C1) % KC != 0)) return false;
     return *nimg * (*th + 2) * (W + 2) * 8 <= HALO_NIT * 256;
 }
 
-template <int BN, int WAVES_M, int WAVES_N, int RM, int RN, int RING, bool UPS, int TAPS = 9>
+template <int BN, int WAVES_M, int WAVES_N, int RM, int RN, int RING, bool UPS>
 static int launch_halo_ws_r(const ConvLaunch &c, int th, int nimg, int64_t grid, hipStream_t st) {
-    constexpr int PADW = TAPS == 9 ? 1 : 0;
-    const int hp = nimg * ((UPS ? th / 2 : th) + 2 * PADW) * ((UPS ? c.Wout / 2 : c.Wout) + 2 * PADW);
+    const int hp = nimg * ((UPS ? th / 2 : th) + 2) * ((UPS ? c.Wout / 2 : c.Wout) + 2);
     size_t shmem = (size_t)((hp + 3) & ~3) * LDS_LD * sizeof(float) + (size_t)nimg * 64 * sizeof(float);
     const size_t epi = (size_t)(RM * 32) * (BN + 4) * sizeof(float);   // epilogue_rows' row image
     const size_t stats = (size_t)(256 / (BN / 4)) * BN * 2 * sizeof(float);
     if (shmem < epi) shmem = epi;
     if (shmem < stats) shmem = stats;
     {
-        int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_halo_ws<BN, WAVES_M, WAVES_N, RM, RN, RING, UPS, TAPS>), 64 * 1024);
+        int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_halo_ws<BN, WAVES_M, WAVES_N, RM, RN, RING, UPS>), 64 * 1024);
         if (r != DLPM_OK) return r;
     }
-    k_conv3x3_halo_ws<BN, WAVES_M, WAVES_N, RM, RN, RING, UPS, TAPS><<<(unsigned)grid, 256, shmem, st>>>(c, th, nimg);
+    k_conv3x3_halo_ws<BN, WAVES_M, WAVES_N, RM, RN, RING, UPS><<<(unsigned)grid, 256, shmem, st>>>(c, th, nimg);
     return DLPM_OK;
 }
 
@@ -1068,32 +1062,6 @@ static int launch_halo_ws(const ConvLaunch &c, int th, int nimg, int64_t grid, h
     // ring depth 2 = one fragment group (16 MFMAs = 1024 cycles) of prefetch distance; 3 measured equal
     if (c.ups) return launch_halo_ws_r<BN, WAVES_M, WAVES_N, RM, RN, 2, true>(c, th, nimg, grid, st);
     return launch_halo_ws_r<BN, WAVES_M, WAVES_N, RM, RN, 2, false>(c, th, nimg, grid, st);
-}
-
-// 1x1 / Linear through the weight-streaming kernel (TAPS = 1): geometry of the 128-pixel tile
-static bool gemm_ws_ok(const ConvLaunch &c, int *th, int *nimg) {
-    // opt-in (ConvLaunch::ws_gemm): measured on the CIFAR net it is 1-10 % SLOWER than k_conv_igemm for every 1x1 shape
-    // (91 vs 101 TFLOP/s at H32, 128+128 -> 128): with one tap there are only 64 MFMAs per wave between two barriers,
-    // and the LDS weight staging it removes was not what limits these launches
-    if (!c.ws_gemm || ws_disabled() || !c.w_frag || c.ks != 1 || c.stride != 1 || c.ups || c.in_nchw || c.abl) return false;
-    if ((c.C0 + c.C1) % KC != 0 || (c.C0 & 3) || c.Hin != c.Hout || c.Win != c.Wout) return false;
-    const int W = c.Wout, HW = c.Hout * c.Wout;
-    if (HW >= BM) {
-        if (HW % BM != 0 || BM % W != 0) return false;
-        *th = BM / W;
-        *nimg = 1;
-    } else {
-        if (BM % HW != 0) return false;
-        *th = c.Hout;
-        *nimg = BM / HW;
-        if (c.coefA && *nimg > 16) return false;   // 16 threads per image load the GroupNorm coefficients
-    }
-    return true;
-}
-
-template <int BN, int WAVES_M, int WAVES_N, int RM, int RN>
-static int launch_gemm_ws(const ConvLaunch &c, int th, int nimg, int64_t grid, hipStream_t st) {
-    return launch_halo_ws_r<BN, WAVES_M, WAVES_N, RM, RN, 2, false, 1>(c, th, nimg, grid, st);
 }
 
 template <int BN, int WAVES_M, int WAVES_N, int RM, int RN>
@@ -1154,12 +1122,12 @@ int conv_stats_pixels(const ConvLaunch &c) {
     if (conv_ksplit_for(c) > 1) return 0;      // a split-K launch emits partial outputs: no statistics (the consumer's GroupNorm reads the tensor)
     if (c.in_nchw) return stem_stats_ok(c) ? 1024 : 0;
     // same order as launch_conv_igemm's dispatch: a launch that carries split weights runs k_conv_split whatever else it carries
-    // (k_conv_split: per 128-pixel tile through the 4-wave row epilogue, or per whole 8x8 image from the registers of the 8 / 16-wave shapes)
+    // (k_conv_split: per 128-pixel tile through the 4-wave row epilogue, or per whole 8x8 image from the registers of the 8-wave shape)
     if (conv_split_ok(c)) {
         const int64_t hw = (int64_t)c.Hout * c.Wout;
         return (c.R0 & 3) ? 0 : hw % BM == 0 ? BM : hw == 64 ? 64 : 0;
     }
-    if (wino4_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4 && wino4_image_stats(c.Cout)) ? 64 : 0;   // (four whole 8x8 images per block: one partial per image)
+    if (wino4_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4) ? 64 : 0;   // (four whole 8x8 images per block: one partial per image)
     if (wino_geometry(c, &a, &b, &n)) return n == 1 ? 4 * wino_tiles(c) : 0;
     if (c.out_nchw || (c.Cout & 3) || (c.R0 & 3)) return 0;
     return ((int64_t)c.Hout * c.Wout) % BM == 0 ? BM : 0;
@@ -1189,9 +1157,6 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
 #ifdef DLPM_PHASE_TIMING
         const_cast<ConvLaunch &>(c).phase = phase_buffer();
 #endif
-#ifdef DLPM_IGEMM_ABLATIONS
-        { const char *e = getenv("DLPM_ABL"); if (e) const_cast<ConvLaunch &>(c).abl = atoi(e); }
-#endif
         return launch_conv_split(c, st);
     }
     {
@@ -1214,26 +1179,12 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
         }
     }
     ProfScope ps(pname, 2.0 * M * c.Cout * K, bytes, st);
-#ifdef DLPM_IGEMM_ABLATIONS   // developer builds only (DLPM_BUILD_DEFS): timing ablations, results are WRONG when set
-    static int abl = -1;
-    if (abl < 0) { const char *e = getenv("DLPM_ABL"); abl = e ? atoi(e) : 0; }
-    if (abl) const_cast<ConvLaunch &>(c).abl = abl;
-#endif
 #ifdef DLPM_PHASE_TIMING
     const_cast<ConvLaunch &>(c).phase = phase_buffer();
 #endif
-    if (gemm_ws_ok(c, &th, &nimg)) {
-        int r;
-        if (c.Cout > 64) r = launch_gemm_ws<128, 2, 2, 2, 2>(c, th, nimg, mt * ceil_div(c.Cout, 128), st);
-        else if (c.Cout > 32) r = launch_gemm_ws<64, 2, 2, 2, 1>(c, th, nimg, mt * ceil_div(c.Cout, 64), st);
-        else r = launch_gemm_ws<32, 4, 1, 1, 1>(c, th, nimg, mt * ceil_div(c.Cout, 32), st);
-        if (r != DLPM_OK) return r;
-        DLPM_LAUNCH_CHECK();
-        return DLPM_OK;
-    }
     if (halo_ok(c, &th, &nimg)) {
         int r;
-        if (c.w_frag && !ws_disabled() && !c.abl && (c.C0 + c.C1) % KC == 0) {
+        if (c.w_frag && !ws_disabled() && (c.C0 + c.C1) % KC == 0) {
             if (c.Cout > 64) r = launch_halo_ws<128, 2, 2, 2, 2>(c, th, nimg, mt * ceil_div(c.Cout, 128), st);
             else if (c.Cout > 32) r = launch_halo_ws<64, 2, 2, 2, 1>(c, th, nimg, mt * ceil_div(c.Cout, 64), st);
             else r = launch_halo_ws<32, 4, 1, 1, 1>(c, th, nimg, mt * ceil_div(c.Cout, 32), st);
@@ -1252,7 +1203,7 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
     static int nofast = -1;
     if (nofast < 0) { const char *e = getenv("DLPM_NO_FAST_IGEMM"); nofast = (e && e[0] == '1') ? 1 : 0; }
     const int bn = c.Cout > 64 ? 128 : c.Cout > 32 ? 64 : 32;
-    const bool full = !nofast && !c.abl && M % BM == 0 && c.Cout % bn == 0 && !c.out_nchw && (c.R0 & 3) == 0;
+    const bool full = !nofast && M % BM == 0 && c.Cout % bn == 0 && !c.out_nchw && (c.R0 & 3) == 0;
     const bool g1 = full && c.ks == 1 && c.stride == 1 && !c.ups && !c.in_nchw && c.C0 % KC == 0 && (c.C0 + c.C1) % KC == 0;
     const int mode = g1 ? 2 : full ? 1 : 0;
     const unsigned grid = (unsigned)(mt * ceil_div(c.Cout, bn));
@@ -1270,15 +1221,15 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
     return DLPM_OK;
 }
 
-int64_t frag_weight_floats(int Cout, int Cin, int taps) {
+int64_t frag_weight_floats(int Cout, int Cin) {
     // + 2 groups of padding at the end: the 2-ahead prefetch of the last groups reads past the data
-    return ((int64_t)((Cout + 31) / 32) * (Cin / 32) * taps * 4 + 2) * 256;
+    return ((int64_t)((Cout + 31) / 32) * (Cin / 32) * 9 * 4 + 2) * 256;
 }
 
-int relayout_weight_frag(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st, int taps) {
-    const int64_t n = (int64_t)((Cout + 31) / 32) * (Cin / 32) * taps * 4 * 256;
+int relayout_weight_frag(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st) {
+    const int64_t n = (int64_t)((Cout + 31) / 32) * (Cin / 32) * 9 * 4 * 256;
     DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, 2 * 256 * sizeof(float), st));
-    k_relayout_weight_frag<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, taps);
+    k_relayout_weight_frag<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

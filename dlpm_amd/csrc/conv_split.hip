@@ -23,16 +23,6 @@
 #include "conv.h"
 #include "igemm_epilogue.h"
 
-#ifndef SPLIT_ABL   // developer builds only (DLPM_BUILD_DEFS): 1 no re-load after stage 0, 2 no split arithmetic, 4 no MFMAs
-#define SPLIT_ABL 0   // (results are wrong when set)
-#endif
-
-#ifdef DLPM_IGEMM_ABLATIONS   // developer builds only: DLPM_ABL bits at run time (results are wrong when set): 1 no output stores,
-#define SABL(b) (p.abl & (b))  // 2 no activation re-loads, 4 no weight re-loads, 8 no MFMAs, 16 no activation staging, 32 no weight staging, 64 no B fragment reads
-#else
-#define SABL(b) 0
-#endif
-
 #ifndef SPLIT_WGS
 #define SPLIT_WGS 2   // workgroups per CU the register budget is set for
 #endif
@@ -138,7 +128,6 @@ __device__ __forceinline__ void split_store_from_registers(const ConvLaunch &p, 
                     s1 += dd;
                     s2 = fmaf(dd, dd, s2);
                 }
-                if (SABL(1) && v == v) continue;
                 if (!MASKED || row <= rlim) op[(int64_t)row * p.Cout] = v;
             }
         if (STATS) {
@@ -162,16 +151,13 @@ __device__ __forceinline__ void split_store_from_registers(const ConvLaunch &p, 
 // PFLOP/s, 80 % of the bf16 pipe; on random data 1.45) -- the bf16 MFMAs at this rate with toggling operands pull the clock
 // down.  Which is why every structural variant measured here landed within +-5 % of this one (all under profiles/r02/gemm_*):
 // two 8-wave groups in one workgroup one barrier phase apart (ping-pong), 256-pixel tiles with two LDS stages and one
-// barrier per stage, 4 waves at three workgroups per CU, two register stages at 128 VGPRs.
-// NW = 16 (round 3, measured and NOT the default -- launch_conv_split): ONE workgroup of 2 x 8 waves per CU computes 128 pixels x 256
-// channels -- the activation stage (loads, GroupNorm affine, SiLU, the three-plane split, LDS writes) is shared by twice the MFMAs,
-// half as many prologues / epilogues per layer; LDS 24 KB of A + 48 KB of B per stage.  Same per-output accumulation order as the
-// other shapes: same bits.
+// barrier per stage, 4 waves at three workgroups per CU, two register stages at 128 VGPRs, and 256-channel tiles on 16 waves
+// (8-40 % slower per launch, profiles/r03/gemm_bf16x3_256wide_tiles.txt).
 template <int NW, int DIST, int TAPS>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split(ConvLaunch p, int nsamp, int xcd_map) {
-    constexpr int NT = NW * 64, RN = NW == 4 ? 2 : 1, WN = NW == 16 ? 8 : 4 / RN;   // threads, MFMA column tiles per wave, waves across N
-    constexpr int NB = NW == 16 ? 2 : 1, BNW = NB * 128;                              // 128-channel weight tiles per stage, tile width
-    constexpr int RSTEP = NT / 8, NV = 128 / RSTEP, NWV = NB * SCHUNKS / NT;   // staging: rows per pass, passes, weight chunks per thread
+    static_assert(NW == 4 || NW == 8, "4- and 8-wave shapes");
+    constexpr int NT = NW * 64, RN = NW == 4 ? 2 : 1, WN = 4 / RN;   // threads, MFMA column tiles per wave, waves across N
+    constexpr int RSTEP = NT / 8, NV = 128 / RSTEP, NWV = SCHUNKS / NT;   // staging: rows per pass, passes, weight chunks per thread
     // [A stage 24 KB][B stage 24 KB] (the statistics epilogue's row image afterwards) [GroupNorm coefficients of the tile's samples]
     extern __shared__ __align__(16) unsigned char smem[];
     DLPM_PHASE_DECL;
@@ -186,7 +172,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
     const int l31 = lane & 31, kh = lane >> 5;
     const int wm = wave / WN, wn = wave % WN;
     const int Cin = p.C0 + p.C1;
-    const int ntile_n = p.Cout / BNW;
+    const int ntile_n = p.Cout / 128;
     // Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8), each with its own L2.  The ntile_n channel tiles of one
     // pixel tile read the same activations: they go to ONE XCD, back to back (xcd_map: pixel tiles % 8 == 0).
     int mt_i, nt;
@@ -199,7 +185,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
         nt = blockIdx.x % ntile_n;
     }
     const int64_t m0 = (int64_t)mt_i * BM;
-    const int n0 = nt * BNW;
+    const int n0 = nt * 128;
     const int HWo = p.Hout * p.Wout;
 
     // A staging: 8 consecutive lanes read one pixel's 32 channels (a whole 128-byte line), a wave instruction 8 pixels;
@@ -226,10 +212,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
         }
     }
     const int nkc = Cin / SKC;
-    // weight image [tap][Cout / 128][Cin / 32][SCHUNKS]: a 256-wide tile stages two consecutive 128-channel tiles, the second one
-    // nkc * SCHUNKS chunks behind the first (thread -> chunk v * NT + tid of the 2 * SCHUNKS; NT = 1024 < SCHUNKS: a thread's chunks
-    // v = 0, 1 lie in the first tile or straddle, computed per chunk below)
-    const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(p.w_split) + (int64_t)nt * NB * nkc * SCHUNKS + (NB == 1 ? tid : 0);
+    // weight image [tap][Cout / 128][Cin / 32][SCHUNKS]
+    const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(p.w_split) + (int64_t)nt * nkc * SCHUNKS + tid;
     const bool has_coef = p.coefA != nullptr;
 
     // stage s = (channel chunk kc, tap); `ok` collects which of this thread's rows read inside the image (zero padding)
@@ -239,37 +223,27 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
         const bool first = c0 < p.C0;             // uniform: C0 % 32 == 0
         const float *src = first ? a0 + c0 : a1 + c0;
         const int rs = first ? p.C0 : p.C1;
-        if (!(SABL(2) && s >= 2)) {
-            if (TAPS == 1) {
+        if (TAPS == 1) {
 #pragma unroll
-                for (int v = 0; v < NV; v++) xa[v] = *reinterpret_cast<const float4 *>(src + rcl[v] * rs);
-            } else {
-                const int ky = tap / 3, kx = tap - 3 * ky;
-                ok = 0;
+            for (int v = 0; v < NV; v++) xa[v] = *reinterpret_cast<const float4 *>(src + rcl[v] * rs);
+        } else {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            ok = 0;
 #pragma unroll
-                for (int v = 0; v < NV; v++) {
-                    const int iy = iy0[v] + ky, ix = ix0[v] + kx;
-                    if ((unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win) ok |= 1 << v;
-                    const int pix = rcl[v] + min(max(iy, 0), p.Hin - 1) * p.Win + min(max(ix, 0), p.Win - 1);
-                    xa[v] = *reinterpret_cast<const float4 *>(src + (int64_t)pix * rs);   // unconditional: a load in a branch drains the queue
-                }
+            for (int v = 0; v < NV; v++) {
+                const int iy = iy0[v] + ky, ix = ix0[v] + kx;
+                if ((unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win) ok |= 1 << v;
+                const int pix = rcl[v] + min(max(iy, 0), p.Hin - 1) * p.Win + min(max(ix, 0), p.Win - 1);
+                xa[v] = *reinterpret_cast<const float4 *>(src + (int64_t)pix * rs);   // unconditional: a load in a branch drains the queue
             }
         }
-        if (!(SABL(4) && s >= 2)) {
-            const u32x4 *ws = wsrc + ((int64_t)tap * (p.Cout >> 7) * nkc + kc) * SCHUNKS;
+        const u32x4 *ws = wsrc + ((int64_t)tap * (p.Cout >> 7) * nkc + kc) * SCHUNKS;
 #pragma unroll
-            for (int v = 0; v < NWV; v++) {
-                if (NB == 1) wb[v] = ws[v * NT];
-                else {
-                    const int c = v * NT + tid, half = c >= SCHUNKS ? 1 : 0;     // chunk of the 2 x SCHUNKS stage image
-                    wb[v] = ws[(int64_t)half * nkc * SCHUNKS + (c - half * SCHUNKS)];
-                }
-            }
-        }
+        for (int v = 0; v < NWV; v++) wb[v] = ws[v * NT];
     };
     uint32_t *As = reinterpret_cast<uint32_t *>(smem);
     u32x4 *Bs = reinterpret_cast<u32x4 *>(smem + SOPER);
-    const float *cf = reinterpret_cast<const float *>(smem + (1 + NB) * SOPER);
+    const float *cf = reinterpret_cast<const float *>(smem + 2 * SOPER);
     int cfo[NV];                                  // this thread's rows' coefficient rows in the LDS table
 #pragma unroll
     for (int v = 0; v < NV; v++) cfo[v] = (nsamp > 1 ? min(rb + RSTEP * v, mrem - 1) / HWo : 0) * Cin + 4 * q;   // rows beyond M: the last valid sample's (written) coefficients
@@ -278,7 +252,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
         const int c0 = (TAPS == 1 ? s : s / TAPS) * SKC;
 #pragma unroll
         for (int v = 0; v < NV; v++) {
-            if (SABL(16) && s >= 2) break;
             float4 x = xa[v];
             if (has_coef) {
                 const float4 ca = *reinterpret_cast<const float4 *>(cf + cfo[v] + c0);
@@ -296,22 +269,16 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
             }
             if (TAPS > 1 && !(ok >> v & 1)) x = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding of the ACTIVATED tensor
             uint32_t P[3][2];
-            if (SPLIT_ABL & 2) {
-                for (int pl = 0; pl < 3; pl++) { P[pl][0] = __float_as_uint(x.x + x.y); P[pl][1] = __float_as_uint(x.z + x.w); }
-            } else {
-                split2(x.x, x.y, P[0][0], P[1][0], P[2][0]);
-                split2(x.z, x.w, P[0][1], P[1][1], P[2][1]);
-            }
+            split2(x.x, x.y, P[0][0], P[1][0], P[2][0]);
+            split2(x.z, x.w, P[0][1], P[1][1], P[2][1]);
 #pragma unroll
             for (int pl = 0; pl < 3; pl++) {
                 As[pl * (SPLANE / 4) + wofs + v * (RSTEP * 4)] = P[pl][0];
                 As[pl * (SPLANE / 4) + wofs + v * (RSTEP * 4) + 1024] = P[pl][1];
             }
         }
-        if (!(SABL(32) && s >= 2)) {
 #pragma unroll
-            for (int v = 0; v < NWV; v++) Bs[v * NT + tid] = wb[v];
-        }
+        for (int v = 0; v < NWV; v++) Bs[v * NT + tid] = wb[v];
     };
 
     floatx16 acc[2][RN];
@@ -323,14 +290,12 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
 
     const bf16x8 *af = reinterpret_cast<const bf16x8 *>(smem) + kh * 128 + wm * 64;
-    const bf16x8 *bf = reinterpret_cast<const bf16x8 *>(smem + SOPER + (NW == 16 ? (wn >> 2) * SOPER : 0)) + kh * 128 +
-                       (NW == 16 ? (wn & 3) * 32 : wn * (RN * 32)) + l31;
+    const bf16x8 *bf = reinterpret_cast<const bf16x8 *>(smem + SOPER) + kh * 128 + wn * (RN * 32) + l31;
     const int ax0 = l31 ^ (kh * 4), ax1 = ax0;   // swizzled row of this lane
     auto mfma_step = [&]() {
-        if (SABL(8)) return;
-        if (!(SPLIT_ABL & 16)) __builtin_amdgcn_s_setprio(1);   // MFMA-issuing waves first: +4-8 % on the long launches (profiles/r02/gemm_bf16x3_priority.txt)
+        __builtin_amdgcn_s_setprio(1);   // MFMA-issuing waves first: +4-8 % on the long launches (profiles/r02/gemm_bf16x3_priority.txt)
 #pragma unroll
-        for (int ks = 0; ks < ((SPLIT_ABL & 4) ? 0 : 2); ks++) {
+        for (int ks = 0; ks < 2; ks++) {
             bf16x8 A[2][3], B[RN][3];
             const int ax = ks ? ax1 : ax0;
 #pragma unroll
@@ -338,7 +303,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
 #pragma unroll
                 for (int i = 0; i < 2; i++) A[i][pl] = af[pl * (SPLANE / 16) + ks * 256 + i * 32 + ax];
 #pragma unroll
-                for (int j = 0; j < RN; j++) B[j][pl] = SABL(64) ? A[j][pl] : bf[pl * (SPLANE / 16) + ks * 256 + j * 32];
+                for (int j = 0; j < RN; j++) B[j][pl] = bf[pl * (SPLANE / 16) + ks * 256 + j * 32];
             }
             // smallest terms first within a (tile, k-step)
 #pragma unroll
@@ -378,7 +343,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
     load_step(xa0, wb0, ok0, 0);
     if (DIST == 2 && nsteps > 1) load_step(xa1, wb1, ok1, 1);
     if (has_coef) {
-        f32x4 *dst = reinterpret_cast<f32x4 *>(smem + (1 + NB) * SOPER);
+        f32x4 *dst = reinterpret_cast<f32x4 *>(smem + 2 * SOPER);
 #pragma unroll
         for (int r = 0; r < CR; r++) {
             const int i = tid + r * NT;
@@ -399,7 +364,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
             SPLIT_LP(0);   // developer counters 4..7: stage (incl. the wait for its loads) / barrier / MFMAs / barrier
             __syncthreads();
             SPLIT_LP(1);
-            if (s + 2 < nsteps && !(SPLIT_ABL & 1)) load_step(xa0, wb0, ok0, s + 2);
+            if (s + 2 < nsteps) load_step(xa0, wb0, ok0, s + 2);
             mfma_step();
             SPLIT_LP(2);
             __syncthreads();   // the stage is dead: the next store_step may overwrite it
@@ -409,7 +374,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
                 SPLIT_LP(0);
                 __syncthreads();
                 SPLIT_LP(1);
-                if (s + 3 < nsteps && !(SPLIT_ABL & 1)) load_step(xa1, wb1, ok1, s + 3);
+                if (s + 3 < nsteps) load_step(xa1, wb1, ok1, s + 3);
                 mfma_step();
                 SPLIT_LP(2);
                 __syncthreads();
@@ -418,11 +383,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? SPLIT_WGS : 1) k_conv_split
         }
     } else {
         for (int s = 0; s < nsteps; s++) {
-            if (!(SPLIT_ABL & 8) || s == 0) store_step(xa0, wb0, ok0, s);   // SPLIT_ABL 8: stage 0 only
+            store_step(xa0, wb0, ok0, s);
             SPLIT_LP(0);
             __syncthreads();
             SPLIT_LP(1);
-            if (s + 1 < nsteps && !(SPLIT_ABL & 1)) load_step(xa0, wb0, ok0, s + 1);   // in flight under the MFMAs below
+            if (s + 1 < nsteps) load_step(xa0, wb0, ok0, s + 1);   // in flight under the MFMAs below
             mfma_step();
             SPLIT_LP(2);
             __syncthreads();
@@ -734,19 +699,11 @@ int launch_conv_split(const ConvLaunch &c, hipStream_t st) {
     static_assert(2 * SOPER >= 64 * 132 * 4, "epilogue image must fit the stage buffers");
     const int HW = c.Hout * c.Wout;
     const int nsamp = HW >= BM ? 1 : BM / HW;     // samples a 128-pixel tile spans
-    // DLPM_SPLIT_NW16=1 (A/B runs; same bits either way): 256-wide channel tiles, 16 waves, ONE workgroup per CU, wherever Cout is a
-    // multiple of 256 -- the activation stage shared by twice the MFMAs.  Measured 8-40 % SLOWER per launch on every shape and +0.5 ms
-    // on the whole step (profiles/r03/gemm_bf16x3_256wide_tiles.txt, bench_cifar_alternating_256wide.txt): what two co-resident
-    // workgroups hide of each other's barriers, prologues and epilogues is worth more than the staging they repeat.  Off by default.
-    static int nw16 = -1;
-    if (nw16 < 0) { const char *e = getenv("DLPM_SPLIT_NW16"); nw16 = e ? atoi(e) : 0; }
     const bool row_stats = c.stats_out && HW % BM == 0;      // per 128-pixel tile, through the 4-wave shape's row epilogue
-    const bool wide = nw16 && c.Cout % 256 == 0 && !row_stats;
-    const int bnw = wide ? 256 : 128;
-    const int lds = (wide ? 3 : 2) * SOPER + (c.coefA ? nsamp * (c.C0 + c.C1) * 8 : 0);
+    const int lds = 2 * SOPER + (c.coefA ? nsamp * (c.C0 + c.C1) * 8 : 0);
     const int64_t mt = ceil_div(M, BM);
-    const unsigned grid = (unsigned)(mt * (c.Cout / bnw));
-    const int xcd_map = (c.Cout > bnw && mt % 8 == 0) ? 1 : 0;
+    const unsigned grid = (unsigned)(mt * (c.Cout / 128));
+    const int xcd_map = (c.Cout > 128 && mt % 8 == 0) ? 1 : 0;
     if (c.stats_out && !row_stats && HW != 64) {   // one partial per in-image 128-pixel tile, or per whole 8x8 image
         set_error("launch_conv_split: fused statistics need whole 128-pixel tiles inside one image, or 8x8 images (HW %d)", HW);
         return DLPM_ERR_UNSUPPORTED;
@@ -765,7 +722,7 @@ int launch_conv_split(const ConvLaunch &c, hipStream_t st) {
     // (the pipelined kernel's LDS limit is 80 KB = 48 KB of stages + the fused GroupNorm coefficients, nsamp x Cin x 8 bytes; launches
     //  beyond it -- Cin > 4096 with coefficients -- stay on k_conv_split<8, 1, 1>, whose 104-KB limit takes Cin up to 7168: ADVICE r05)
     const int lds_p = 48 * 1024 + (c.coefA ? nsamp * (c.C0 + c.C1) * 8 : 0);
-    if (pipe && c.ks == 1 && !row_stats && !wide && lds_p <= 80 * 1024) {
+    if (pipe && c.ks == 1 && !row_stats && lds_p <= 80 * 1024) {
         const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv_split_pipe), 80 * 1024);
         if (r != DLPM_OK) return r;
         k_conv_split_pipe<<<grid, 512, lds_p, st>>>(c, nsamp, xcd_map);
@@ -774,11 +731,9 @@ int launch_conv_split(const ConvLaunch &c, hipStream_t st) {
     }
     if (c.ks == 1) {
         if (row_stats) DLPM_SPLIT_LAUNCH(4, 2, 1);
-        else if (wide) DLPM_SPLIT_LAUNCH(16, 1, 1);
         else DLPM_SPLIT_LAUNCH(8, 1, 1);
     } else {
         if (row_stats) DLPM_SPLIT_LAUNCH(4, 2, 9);
-        else if (wide) DLPM_SPLIT_LAUNCH(16, 1, 9);
         else DLPM_SPLIT_LAUNCH(8, 1, 9);
     }
 #undef DLPM_SPLIT_LAUNCH

@@ -65,7 +65,7 @@ int conv_ksplit_for(const ConvLaunch &c) {
         nchunks = (c.C0 + c.C1) / 8;
     } else if (wino_geometry(c, &a, &b, &n)) {
         grid = wino_grid_at(c, c.dispatch_B);
-        nchunks = (c.C0 + c.C1) / wino_chunk_channels(c);
+        nchunks = (c.C0 + c.C1) / 8;
     } else {
         return 1;
     }

@@ -30,6 +30,7 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int WN = 64;        // output channels a layer must be a multiple of
 constexpr int WKC = 16;       // input channels a layer must be a multiple of
+constexpr int KC = 8;         // input channels per phase of k_conv3x3_wino_q (16 measured 2 % slower)
 constexpr int RAW_MAXPIX = 576;   // halo pixels per phase of a 64-tile block (half of it for 32 tiles)
 constexpr int WGRP = 32;      // weight fragment groups (256 floats) per 16 input channels and 32 output channels
 
@@ -52,12 +53,9 @@ constexpr int QRING = 8;      // weight prefetch ring of the 8-wave kernel (grou
 // is added to MFMA time on this chip -- at the price of streaming every weight fragment for one MFMA tile only.
 // NW = waves per workgroup: 8 (one workgroup per CU, 256-KB accumulator block) or 4 (MT = 32 only: 32 tiles x 64
 // channels, 128-KB block, TWO workgroups per CU, so that one's prologue / epilogue / barriers overlap the other's MFMAs).
-// KC = input channels per phase: 8, or 16 (MT = 32, NW = 8 only: the smaller V / raw tiles leave room for it): half as many
-// barriers and phase start-ups per MFMA.
-template <bool UPS, int MT, int NW = 8, int ABL = 0, int KC = 8>   // ABL (DLPM_WINO_ABLATIONS builds): 1 no S, 2 no X, 4 no raw loads, 8 no barrier, 16 no weight loads, 32 no MFMA
+template <bool UPS, int MT, int NW = 8>
 __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(ConvLaunch p, int bh, int bw, int nimg) {
     static_assert(NW == 8 || (NW == 4 && MT == 32), "wave layout");
-    static_assert(KC == 8 || (KC == 16 && MT == 32 && NW == 8), "chunk");
     constexpr int NT = NW * 64;                      // threads
     constexpr int NQ = NW == 8 ? 4096 / MT : 64;     // output channels per workgroup
     constexpr int RAWPIX = MT == 64 ? RAW_MAXPIX : RAW_MAXPIX / 2;
@@ -65,7 +63,6 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(Con
     constexpr int QNIT = (RAWPIX * NQD + NT - 1) / NT; // staging items per thread
     constexpr int PVLD = KC + 4, PRLD = KC + 4;      // padded V / raw rows: conflict-free ds_read_b128 over consecutive tiles
     constexpr int CFS = 16 * 2 * KC;                 // floats per coefficient slot: [16 images][2][KC]
-    constexpr int NJQ = KC / 8;                      // float4 fragments per position and lane
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float *V = wsm;                                  // [2][16][MT][PVLD]
     float *raw = wsm + 2 * 16 * MT * PVLD;           // [2][RAWPIX][PRLD]
@@ -209,7 +206,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(Con
 
     // ---- weight stream of this wave: Wf[nb][ph][chunk][8 positions][lane][4]
     const float4 *__restrict__ wbase = reinterpret_cast<const float4 *>(p.w_wino) + lane;
-    int64_t woff = ((int64_t)(((n0 >> 5) + wn) * 2 + ph) * (Cin / KC) + kb) * 8 * NJQ * 64;
+    int64_t woff = ((int64_t)(((n0 >> 5) + wn) * 2 + ph) * (Cin / KC) + kb) * 8 * 64;
     constexpr int AHEAD = QRING - 1;
     float4 bq[QRING];
     const float *asrc = V + (ph * 8) * MT * PVLD + (wm * 32 + l31) * PVLD + kh * (KC / 2);
@@ -266,8 +263,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(Con
         // second wave does hide is latency: LDS, global loads, barriers.  Running the two waves of a SIMD in opposite
         // order measured 4 % slower.)
 #pragma unroll
-        for (int g = 0; g < 8 * NJQ; g++) {
-            const int q = g / NJQ, jq = g % NJQ;
+        for (int q = 0; q < 8; q++) {
             // the side work is spread over the phase (one piece behind each of the first positions): bunched in the
             // middle of the phase it measured 2.5 % slower (both waves of a SIMD reach it together and the matrix pipe idles)
             // placement sweep (DLPM_BUILD_DEFS="WQ_S0=.. WQ_X=.."): staging from an odd position on is 3-6 % faster than
@@ -278,25 +274,21 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(Con
 #ifndef WQ_X
 #define WQ_X 6
 #endif
-            if (!(ABL & 1) && g % NJQ == 0 && g / NJQ >= WQ_S0 && g / NJQ < WQ_S0 + QNIT)
-                store_raw_item(cur, g / NJQ - WQ_S0);                   // S(chunk+2): raw[cur] was read by X(chunk), a barrier ago
-            if (g == (WQ_S0 + QNIT) * NJQ && !(ABL & 4)) load_raw(min(chunk + 3, last));   // G(chunk+3)
-            if (g == WQ_X * NJQ && !(ABL & 2)) transform(nxt);          // X(chunk+1): raw[nxt] -> V[nxt]
-            if (!(ABL & 16)) bq[(g + AHEAD) % QRING] = wbase[woff + AHEAD * 64];
+            if (q >= WQ_S0 && q < WQ_S0 + QNIT) store_raw_item(cur, q - WQ_S0);   // S(chunk+2): raw[cur] was read by X(chunk), a barrier ago
+            if (q == WQ_S0 + QNIT) load_raw(min(chunk + 3, last));                 // G(chunk+3)
+            if (q == WQ_X) transform(nxt);                                          // X(chunk+1): raw[nxt] -> V[nxt]
+            bq[(q + AHEAD) % QRING] = wbase[woff + AHEAD * 64];
             woff += 64;
-            const float4 af = *reinterpret_cast<const float4 *>(ab + q * MT * PVLD + jq * 4);
-            const float4 b = bq[g % QRING];
-            if (!(ABL & 32)) {
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, b.x, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, b.y, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, b.z, acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, b.w, acc[q], 0, 0, 0);
-            }
+            const float4 af = *reinterpret_cast<const float4 *>(ab + q * MT * PVLD);
+            const float4 b = bq[q % QRING];
+            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, b.x, acc[q], 0, 0, 0);
+            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, b.y, acc[q], 0, 0, 0);
+            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, b.z, acc[q], 0, 0, 0);
+            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, b.w, acc[q], 0, 0, 0);
         }
         store_coef(nxt);
-        if (!(ABL & 8)) __syncthreads();
+        __syncthreads();
     }
-    if (ABL & 8) __syncthreads();
     DLPM_PHASE(p, 9);
 
     // ---- epilogue addressing + residual prefetch (8 rows per thread)
@@ -417,24 +409,21 @@ __global__ void __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) k_conv3x3_wino_q(Con
 
 // OIHW (3x3) -> U = G g G^T in k_conv3x3_wino_q's fragment order  Wf[nb][ph][chunk8][pos8][lane][4]:
 // lane = h*32 + n holds U_pos[cin = chunk*8 + h*4 + e][cout = nb*32 + n], pos = ph*8 + pos8.
-__global__ void k_relayout_weight_wino_q(const float *oihw, float *dst, int Cout, int Cin, int kc) {
-    // kc = 8: Wf[nb][ph][chunk][pos8][lane][4], cin = chunk*8 + h*4 + e
-    // kc = 16: Wf[nb][ph][chunk][pos8][jq][lane][4], cin = chunk*16 + h*8 + jq*4 + e
-    const int nbk = Cout / 32, nch = Cin / kc, njq = kc / 8;
-    const int64_t total = (int64_t)nbk * 2 * nch * 8 * njq * 64 * 4;
+__global__ void k_relayout_weight_wino_q(const float *oihw, float *dst, int Cout, int Cin) {
+    const int nbk = Cout / 32, nch = Cin / KC;
+    const int64_t total = (int64_t)nbk * 2 * nch * 8 * 64 * 4;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int e = (int)(i & 3);
     const int lane = (int)((i >> 2) & 63);
     int64_t r = i >> 8;
-    const int jq = (int)(r % njq); r /= njq;
     const int pos8 = (int)(r & 7); r >>= 3;
     const int chunk = (int)(r % nch); r /= nch;
     const int ph = (int)(r & 1);
     const int nb = (int)(r >> 1);
     const int pos = ph * 8 + pos8;
     const int h = lane >> 5, nn = lane & 31;
-    const int cin = chunk * kc + h * (kc / 2) + jq * 4 + e, cout = nb * 32 + nn;
+    const int cin = chunk * KC + h * 4 + e, cout = nb * 32 + nn;
     const float *g = oihw + ((int64_t)cout * Cin + cin) * 9;
     const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
     const int a = pos >> 2, b = pos & 3;
@@ -456,18 +445,6 @@ static bool wino_disabled() {
 }
 
 int wino_waves(const ConvLaunch &c);
-// input channels per phase of the 8-wave kernel for a layer with Cout output channels: 8; DLPM_WINO_KC=16 selects 16 for
-// the 32-tile x 128-channel shape (half the barriers per MFMA -- measured 2 % SLOWER: 61.3 vs 60.1 ms/step).  It fixes the
-// Winograd-domain weight layout, so it depends on Cout only
-static int wino_kc_for(int Cout) {
-    static int pref = -1, nw = -1, mtp = -1;
-    if (pref < 0) {
-        const char *e = getenv("DLPM_WINO_KC"); pref = e ? atoi(e) : 8;
-        const char *f = getenv("DLPM_WINO_NW"); nw = f ? atoi(f) : 8;
-        const char *g = getenv("DLPM_WINO_MT"); mtp = g ? atoi(g) : 32;
-    }
-    return (pref == 16 && nw != 4 && mtp == 32 && Cout % 128 == 0) ? 16 : 8;
-}
 // Small launches of 64-channel-multiple layers (the MNIST-width nets): when a 64-tile block would hold SEVERAL whole
 // images (8x8 / 4x4-pixel tensors) and the grid of 64-tile x 64-channel blocks would leave most CUs empty, the 4-wave
 // 32-tile x 64-channel shape is used instead: twice the workgroups, two per CU.  Per (tile, channel) the arithmetic is the
@@ -484,21 +461,15 @@ static bool wino_small_launch(const ConvLaunch &c) {
 
 // tiles per workgroup: 32 (x 128 output channels) for the 8-wave kernel when Cout allows it, else 64 (x 64 channels)
 int wino_tiles(const ConvLaunch &c) {
-    static int pref = -1;
-    if (pref < 0) { const char *e = getenv("DLPM_WINO_MT"); pref = e ? atoi(e) : 32; }
     if (wino_waves(c) == 4) return 32;
-    return (pref == 32 && c.Cout % 128 == 0) ? 32 : 64;
+    return c.Cout % 128 == 0 ? 32 : 64;
 }
 
-// waves per workgroup of the 8-wave kernel family: DLPM_WINO_NW=4 selects the two-workgroups-per-CU shape (32 x 64 blocks)
-int wino_waves(const ConvLaunch &c) {
-    static int pref = -1;
-    if (pref < 0) { const char *e = getenv("DLPM_WINO_NW"); pref = e ? atoi(e) : 8; }
-    return (pref == 4 || wino_small_launch(c)) ? 4 : 8;
-}
+// waves per workgroup of the 8-wave kernel family: 4 (two workgroups per CU, 32 x 64 blocks) for small launches
+int wino_waves(const ConvLaunch &c) { return wino_small_launch(c) ? 4 : 8; }
 
 bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
-    if (wino_disabled() || c.gen == DLPM_CONV_IGEMM || !c.w_wino || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw || c.abl) return false;
+    if (wino_disabled() || c.gen == DLPM_CONV_IGEMM || !c.w_wino || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
     if ((c.Hout & 1) || (c.Wout & 1) || c.Cout % WN != 0 || (c.C0 + c.C1) % WKC != 0 || c.C0 % WKC != 0) return false;
     if ((c.R0 & 3) != 0) return false;
     if (c.ups && ((c.Hout & 3) || (c.Wout & 3))) return false;
@@ -535,40 +506,22 @@ int launch_conv_wino(const ConvLaunch &c, hipStream_t st) {
     using KFn = void (*)(ConvLaunch, int, int, int);
     const int mt = wino_tiles(c);
     const int nw = wino_waves(c);
-    const int kc = wino_kc_for(c.Cout);
     KFn fn;
     if (mt == 32 && nw == 4) fn = c.ups ? &k_conv3x3_wino_q<true, 32, 4> : &k_conv3x3_wino_q<false, 32, 4>;
-    else if (mt == 32 && kc == 16) fn = c.ups ? &k_conv3x3_wino_q<true, 32, 8, 0, 16> : &k_conv3x3_wino_q<false, 32, 8, 0, 16>;
     else if (mt == 32) fn = c.ups ? &k_conv3x3_wino_q<true, 32> : &k_conv3x3_wino_q<false, 32>;
     else fn = c.ups ? &k_conv3x3_wino_q<true, 64> : &k_conv3x3_wino_q<false, 64>;
-#ifdef DLPM_WINO_ABLATIONS
-    static int abl = -1;   // timing-only ablations (results are wrong when set)
-    if (abl < 0) { const char *e = getenv("DLPM_WABL"); abl = e ? atoi(e) : 0; }
-    if (!c.ups && mt == 32 && nw == 8 && kc == 8) {
-        switch (abl) {
-            case 1: fn = &k_conv3x3_wino_q<false, 32, 8, 1>; break;
-            case 2: fn = &k_conv3x3_wino_q<false, 32, 8, 2>; break;
-            case 3: fn = &k_conv3x3_wino_q<false, 32, 8, 3>; break;
-            case 8: fn = &k_conv3x3_wino_q<false, 32, 8, 8>; break;
-            case 16: fn = &k_conv3x3_wino_q<false, 32, 8, 16>; break;
-            case 31: fn = &k_conv3x3_wino_q<false, 32, 8, 31>; break;
-            case 32: fn = &k_conv3x3_wino_q<false, 32, 8, 32>; break;
-            default: break;
-        }
-    }
-#endif
     {
         int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 160 * 1024);
         if (r != DLPM_OK) return r;
     }
     const int nq = nw == 8 ? 4096 / mt : 64;
-    size_t shmem = (size_t)(2 * 16 * mt * (kc + 4) + 2 * (mt == 64 ? RAW_MAXPIX : RAW_MAXPIX / 2) * (kc + 4) + 2 * 16 * 2 * kc) * sizeof(float);
+    size_t shmem = (size_t)(2 * 16 * mt * (KC + 4) + 2 * (mt == 64 ? RAW_MAXPIX : RAW_MAXPIX / 2) * (KC + 4) + 2 * 16 * 2 * KC) * sizeof(float);
     const size_t epi = (size_t)((nw / 2) * 4 * 16 * 64 + 4 * mt * (nq + 4)) * sizeof(float);   // exchange + row image
     if (shmem < epi) shmem = epi;
     const int64_t tiles = (int64_t)c.B * (c.Hout / 2) * (c.Wout / 2);
     const int64_t mblocks = nimg == 1 ? tiles / mt : ceil_div(c.B, nimg);
     const int ks = c.ksplit > 1 ? c.ksplit : 1;
-    if (ks > 1 && (c.bias || c.res0 || c.stats_out || ((c.C0 + c.C1) / kc) % ks != 0)) {
+    if (ks > 1 && (c.bias || c.res0 || c.stats_out || ((c.C0 + c.C1) / KC) % ks != 0)) {
         set_error("launch_conv_wino: a split-K launch carries no bias / residual / statistics and divides its chunks evenly");
         return DLPM_ERR_ARG;
     }
@@ -587,8 +540,6 @@ int64_t wino_grid_at(const ConvLaunch &c, int64_t B) {
     return mblocks * (c.Cout / nq);
 }
 
-int wino_chunk_channels(const ConvLaunch &c) { return wino_kc_for(c.Cout); }
-
 int64_t wino_weight_floats(int Cout, int Cin) {
     // + AHEAD groups of padding: the prefetch ring reads past the last group
     return ((int64_t)(Cout / 32) * (Cin / WKC) * WGRP + 8) * 256;   // 8 >= every kernel's ring depth - 1
@@ -597,7 +548,7 @@ int64_t wino_weight_floats(int Cout, int Cin) {
 int relayout_weight_wino(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st) {
     const int64_t n = (int64_t)(Cout / 32) * (Cin / WKC) * WGRP * 256;
     DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, (size_t)8 * 256 * sizeof(float), st));
-    k_relayout_weight_wino_q<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, wino_kc_for(Cout));
+    k_relayout_weight_wino_q<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

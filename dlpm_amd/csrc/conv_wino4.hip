@@ -82,24 +82,6 @@ constexpr int F4_PAD = 8;         // float4 fragments of zero padding behind the
 #define F4_S0 6    // position pair behind which the staging stores start (round 4, QN = 2: 6 is 0.8-1.2 % faster than 4, 5, 7..10 -- four alternating
                    // repetitions, profiles/r04/conv_layers_sidework_placement_qn2.txt; same bits)
 #endif
-#ifndef F4_EPI_T
-#define F4_EPI_T 0  // 1: accumulators transposed (lane = tile, 4 consecutive channels): 16-byte epilogue accesses, 32 instead of 128 memory
-                    // instructions per lane -- bit-identical outputs, measured 0.3-0.7 % SLOWER over the eight layer shapes
-                    // (profiles/r03/conv_layers_transposed_epilogue.txt: the same 512 cache-line accesses per wave either way);
-                    // 0 (the build): lane = channel, 4 tiles
-#endif
-#ifndef F4N_ABL
-#define F4N_ABL 0   // developer builds (DLPM_BUILD_DEFS), narrow shapes' epilogue, timing only (results are wrong): 1 no stores, 2 no residual loads, 4 no statistics
-#endif
-#ifndef F4_RES_AHEAD
-#define F4_RES_AHEAD 0   // 1: the 8-wave shape, too, requests all four tiles' residual values before the first output transform (the narrow
-                         // shapes always do): 64 more live registers in the epilogue, where the weight ring / A fragments / staging items are dead
-#endif
-#ifndef F4_SKIP_TAIL
-#define F4_SKIP_TAIL 0   // 1: skip the look-ahead staging / transform of the last phases (they feed chunks that do not exist): 2 of 16 phases'
-                         // side work on the K = 128 layers -- measured 1.3-2.5 % SLOWER (the two uniform branches cost the phase its schedule:
-                         // 256 VGPRs; profiles/r03/conv_layers_skip_tail_phases.txt, +0.45 ms on the whole step in alternating runs)
-#endif
 #ifndef F4_X
 #define F4_X 13    // position pair behind which waves 0..2 run the input transform (placement sweep, DLPM_BUILD_DEFS="F4_S0=..
                    // F4_X=..": X = 13 is 3-8 % faster than 3, 9, 11, 12, 14..17 for every S0; S0 = 3, 5, 7 are within 0.5 %)
@@ -127,50 +109,19 @@ __device__ __forceinline__ float2 f2fma(float a, float2 x, float2 y) { return ma
 __device__ __forceinline__ float2 f2add(float2 x, float2 y) { return make_float2(x.x + y.x, x.y + y.y); }
 __device__ __forceinline__ float2 f2sub(float2 x, float2 y) { return make_float2(x.x - y.x, x.y - y.y); }
 
-// ABL (DLPM_WINO_ABLATIONS builds, DLPM_WABL): timing-only ablations, results are wrong: 1 no staging stores, 2 no transform,
-// 4 no raw loads, 8 no barrier, 16 no weight loads, 32 no MFMA, 64 no A-fragment reads
 // QN: staging items per thread (2 for halo patches of <= 512 pixels -- every block shape but 16 whole 4x4 images; round 4: the third
 // item's geometry registers and its dead branch per phase pushed the main instantiation into a scratch reload inside the loop)
-// SPEC (round 4, VERDICT r03 next #4b): 1 / 2 = the 32x32 128 -> 128 ResBlock convolution without / with a residual -- 7 launches and
-// 7.2 of the 30.7 ms this kernel takes per CIFAR step, its worst shape (16 phases: prologue + epilogue are 19 % of a workgroup's life).
-// Channel counts (row pitches, the phase count, the single input / residual source) and the presence of the fused GroupNorm +
-// SiLU / bias / residual become compile-time constants, so the generic address arithmetic of the staging and the epilogue folds
-// away.  (The image and block geometry stay run-time values: as constants they let hipcc hoist per-lane addresses out of the
-// phase loop -- 8 to 12 spilled registers, with reloads inside the loop.)
-// VS = 1 (round 4; measured neutral, off -- see wino4_vsplit): waves = 2 POSITION HALVES (transform rows 0-2 / 3-5) x 4 channel quarters of 32 instead of 8
-// channel eighths for all 36 positions: a wave still owns 36 accumulator tiles (18 positions x 2 channel tiles) and streams the same
-// weight bytes, but reads only ITS half of V -- every V fragment is read by 4 waves instead of 8 (the held-clock ablations put 12 % of
-// the clock on that LDS traffic).  Y = A^T M A splits by rows of A^T: each wave of a pair turns its 18 positions into 16 partial outputs
-// per (tile, channel), hands the partials of the channel tile its PARTNER finalises over through LDS (one barrier pair, 128 KB: the
-// loop's buffers are dead by then) and runs the unchanged register epilogue on the other.
-// PERS = 1 (round 6, the 8-wave shape): PERSISTENT workgroups -- the grid is one workgroup per CU and each walks the tiles wgid, wgid + gridDim.x,
-// ... of the n-tile-major order (all workgroups in flight still stream the same slab of weights); the tile body is unchanged.  What it
-// saves is the turnover between the 16 workgroups a CU runs per launch of the CIFAR net (teardown, dispatch, LDS allocation, kernel-argument
-// loads: ~4 us per round by the launch time against the sum of the workgroups' lives, profiles/r06/persistent_wino4/).
-template <bool UPS, int ABL = 0, int QN = F4_QNIT, int SPEC = 0, int VS = 0, int NW = 8, int PERS = 0>
+// NW: MFMA waves (8: the 128-channel n-tile; 4 / 2: the narrow shapes with their helper waves, above).
+// (Variants that were measured and lost -- transposed accumulators, skipped tail phases, wave split by position halves, channel-specialised
+// and persistent instantiations, timing ablations -- are recorded in DESIGN.md section 3.1 and profiles/, and were removed.)
+template <bool UPS, int QN = F4_QNIT, int NW = 8>
 __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, NW == 2 ? 2 : 1) k_conv3x3_wino4(ConvLaunch p_in, int bh_in, int bw_in, int nimg_in) {
-    static_assert(PERS == 0 || NW == 8, "persistent workgroups: the 8-wave shape");
     constexpr bool HELP = NW != 8;                                        // MFMA waves 0 .. NW-1 + helper waves NW .. NW+NH-1
     constexpr int NH = NW == 8 ? 0 : NW == 4 ? 3 : 2;
     constexpr int F4_NT = (NW + NH) * 64, F4_NQ = NW * 16;                // threads, channels (shadow the main shape's constants)
-    // Transposed accumulators (lane = tile, 4 consecutive channels: 16-byte epilogue accesses, 32 instead of 128 memory instructions per
-    // lane): F4_EPI_T above.
-    constexpr bool EPI_T = F4_EPI_T != 0;   // (measured on the narrow shapes too, with the residual requested ahead: 64 float4 of residual + Y beside the
-                                            //  accumulators spill 48-63 registers and the epilogue gets LONGER, 28 -> 35 k cycles: profiles/r05/)
     constexpr int F4_RAWBUF = NW == 8 ? dlpm::F4_RAWBUF : F4_RAWBUF_N;
-    static_assert(NW == 8 || (VS == 0 && SPEC == 0), "wave-split and specialised forms exist for the 128-channel shape only");
     ConvLaunch p = p_in;
-    int bh = bh_in, bw = bw_in, nimg = nimg_in;
-    if (SPEC) {
-        p.C0 = 128; p.C1 = 0; p.Cout = 128; p.R0 = 128; p.act_silu = 1;
-        p.src1 = nullptr; p.res1 = nullptr;
-        if (SPEC == 1) p.res0 = nullptr;
-        nimg = 1;
-        __builtin_assume(p.coefA != nullptr);
-        __builtin_assume(p.coefB != nullptr);
-        __builtin_assume(p.bias != nullptr);
-        if (SPEC == 2) __builtin_assume(p.res0 != nullptr);
-    }
+    const int bh = bh_in, bw = bw_in, nimg = nimg_in;
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float *V = wsm;                               // [2][18][4][16][4]
     float *raw = wsm + 2 * F4_VBUF;               // [2][F4_RAWPIX][F4_PRLD] (+ skew)
@@ -183,28 +134,21 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
 #ifdef DLPM_PHASE_TIMING
     long long _wait = 0;      // cycles this wave spends at the phase barrier (developer builds: slots 16 + wave)
 #endif
-    unsigned wgid = blockIdx.x;
-    const unsigned ngrid = PERS ? (unsigned)p.pers_total : gridDim.x;
-    do {      // (one trip unless PERS)
-    int tid_ = threadIdx.x;
-    // (persistent form: the thread index is opaque per tile -- otherwise every lane-dependent constant of the body is hoisted out of the
-    //  tile loop and lives in scratch memory across the K loop: 79 spilled registers)
-    if (PERS) asm volatile("" : "+v"(tid_));
-    const int tid = tid_, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool mfma_wave = !HELP || wave < NW;                 // wave-uniform
     const int li = lane & 15, lk = lane >> 4;
     const int W = p.Wout, H = p.Hout, TW = W >> 2, TH = H >> 2;
     const int Ws = UPS ? (W >> 1) : W, Hs = UPS ? (H >> 1) : H;
     const int Cin = p.C0 + p.C1;
     int nch = Cin / F4_KC, kb = 0;
-    unsigned bid = wgid, nblk = ngrid;      // (unsigned, like the grid built-ins: the prologue's divisions stay what they were)
+    unsigned bid = blockIdx.x, nblk = gridDim.x;
     if constexpr (HELP) {
         // split-K (round 6, narrow shapes only: the 8-wave instantiations compile without it): grid copy ks walks chunks [kb, kb + nch) and
         // writes its partial outputs behind those of the copies before it (the launch carries no bias / residual / statistics)
         if (p.ksplit > 1) {
-            nblk = ngrid / p.ksplit;
-            const int ks = (int)(wgid / nblk);
-            bid = wgid - (unsigned)ks * nblk;
+            nblk = gridDim.x / p.ksplit;
+            const int ks = (int)(blockIdx.x / nblk);
+            bid = blockIdx.x - (unsigned)ks * nblk;
             nch /= p.ksplit;
             kb = ks * nch;
             p.out += (int64_t)ks * p.B * H * W * p.Cout;
@@ -424,58 +368,24 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
         load_coef(min(chunk + 3, last));
         float4 aq[F4_AAHEAD + 1];
 #pragma unroll
-        for (int a = 0; a < F4_AAHEAD; a++)
-            if (!VS) aq[a] = (ABL & 64) ? make_float4(1.f, 2.f, 1.f, 2.f) : *reinterpret_cast<const float4 *>(ab + a * (4 * F4_TILES * 4));
-        if (ABL & 64) aq[F4_AAHEAD] = make_float4(1.f, 2.f, 1.f, 2.f);
+        for (int a = 0; a < F4_AAHEAD; a++) aq[a] = *reinterpret_cast<const float4 *>(ab + a * (4 * F4_TILES * 4));
         if (HELP && !mfma_wave) {
             // helper wave: its share of S(chunk+2) raw stores and G(chunk+3) global loads, X(chunk+1) its row pair(s) of the transform
 #pragma unroll
             for (int it = 0; it < QN; it++) store_raw_item(cur, it);
             load_raw_into(xr, min(chunk + 3, last));
             transform(nxt);
-        } else if (VS) {
-            // slot s = (position pair pp = s / 2 of this wave's nine, channel tile nt = s % 2): 18 slots, one weight fragment and four
-            // MFMAs each, side work keyed on the slot exactly as on the position pair of the VS = 0 loop
-            const float *abh = ab + (wave >> 2) * 9 * (4 * F4_TILES * 4);
-            aq[0] = *reinterpret_cast<const float4 *>(abh);
-#pragma unroll
-            for (int sl = 0; sl < 18; sl++) {
-                const int pp = sl >> 1, nt = sl & 1;
-                if (sl >= F4_S0 && sl < F4_S0 + QN) store_raw_item(cur, sl - F4_S0);
-                if (sl == F4_S0 + QN) load_raw_into(xr, min(chunk + 3, last));
-                if (sl == F4_X) transform(nxt);
-                bq[(sl + AHEAD) % F4_RING] = wp[AHEAD * 64 + lane];
-                wp += 64;
-                if (nt == 0 && pp + 1 < 9) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(abh + (pp + 1) * (4 * F4_TILES * 4));
-                const float4 aa = aq[pp & 1];
-                const float2 a0 = make_float2(aa.x, aa.y), a1 = make_float2(aa.z, aa.w);
-                const float4 b = bq[sl % F4_RING];
-                if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
-                acc[4 * pp + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, acc[4 * pp + nt], 0, 0, 0);
-                acc[4 * pp + 2 + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.z, acc[4 * pp + 2 + nt], 0, 0, 0);
-                acc[4 * pp + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, acc[4 * pp + nt], 0, 0, 0);
-                acc[4 * pp + 2 + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.w, acc[4 * pp + 2 + nt], 0, 0, 0);
-                if (F4_PRIO) __builtin_amdgcn_s_setprio(1);
-            }
         } else {
 #pragma unroll
         for (int pp = 0; pp < 18; pp++) {
-#if F4_SKIP_TAIL
-            // the pipeline's look-ahead work of the LAST phases feeds chunks that do not exist: S(chunk+2) in the last two phases and
-            // X(chunk+1) in the last one are skipped (one-sided wave-uniform branches; the loads stay unconditional)
-            if (!(ABL & 1) && pp >= F4_S0 && pp < F4_S0 + QN && chunk + 2 < nch) store_raw_item(cur, pp - F4_S0);
-            if (!(ABL & 4) && pp == F4_S0 + QN) load_raw_into(xr, min(chunk + 3, last));
-            if (!(ABL & 2) && pp == F4_X && chunk + 1 < nch) transform(nxt);
-#else
-            if (!(ABL & 1) && pp >= F4_S0 && pp < F4_S0 + QN) store_raw_item(cur, pp - F4_S0);   // S(chunk+2): raw[cur] was read by X(chunk), a barrier ago
-            if (!(ABL & 4) && pp == F4_S0 + QN) load_raw_into(xr, min(chunk + 3, last));        // G(chunk+3)
-            if (!HELP && !(ABL & 2) && pp == F4_X) transform(nxt);                                    // X(chunk+1): raw[nxt] -> V[nxt] (narrow shapes: the helper waves')
-#endif
-            if (!(ABL & 16)) bq[(pp + AHEAD) % F4_RING] = wp[AHEAD * 64 + lane];
+            if (pp >= F4_S0 && pp < F4_S0 + QN) store_raw_item(cur, pp - F4_S0);   // S(chunk+2): raw[cur] was read by X(chunk), a barrier ago
+            if (pp == F4_S0 + QN) load_raw_into(xr, min(chunk + 3, last));        // G(chunk+3)
+            if (!HELP && pp == F4_X) transform(nxt);                              // X(chunk+1): raw[nxt] -> V[nxt] (narrow shapes: the helper waves')
+            bq[(pp + AHEAD) % F4_RING] = wp[AHEAD * 64 + lane];
             wp += 64;
             // A fragments are read F4_AAHEAD position pairs ahead (left to the compiler each ds_read sat directly in
             // front of its MFMAs with an s_waitcnt lgkmcnt(0) between them)
-            if (!(ABL & 64) && pp + F4_AAHEAD < 18)
+            if (pp + F4_AAHEAD < 18)
                 aq[(pp + F4_AAHEAD) % (F4_AAHEAD + 1)] = *reinterpret_cast<const float4 *>(ab + (pp + F4_AAHEAD) * (4 * F4_TILES * 4));
             const float4 aa = aq[pp % (F4_AAHEAD + 1)];
             const float2 a0 = make_float2(aa.x, aa.y), a1 = make_float2(aa.z, aa.w);
@@ -484,24 +394,10 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
             // MFMAs at 0 -- when both waves of a SIMD are ready, the one with side work goes first and the other's MFMAs
             // fill the pipe behind it.  Measured 45.6 -> 43.9 ms/step (the opposite assignment: 44.4)
             if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
-            if (!(ABL & 32)) {
-            if constexpr (EPI_T) {
-            // operands swapped: D rows = the wave's 16 output channels, D columns = the 16 tiles, i.e. a lane (li = tile, lk)
-            // ends up with FOUR CONSECUTIVE CHANNELS (4 lk + r) of one tile -- same products, same order, transposed registers
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, a0.x, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.z, a1.x, acc[2 * pp + 1], 0, 0, 0);
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.y, a0.y, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.w, a1.y, acc[2 * pp + 1], 0, 0, 0);
-            } else {
             acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, acc[2 * pp], 0, 0, 0);
             acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.z, acc[2 * pp + 1], 0, 0, 0);
             acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, acc[2 * pp], 0, 0, 0);
             acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.w, acc[2 * pp + 1], 0, 0, 0);
-            }
-            } else {
-                acc[2 * pp][0] += a0.x * b.x + a0.y * b.y;   // keep the operands alive
-                acc[2 * pp + 1][0] += a1.x * b.z + a1.y * b.w;
-            }
             if (F4_PRIO) __builtin_amdgcn_s_setprio(1);
         }
         }
@@ -509,12 +405,11 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
 #ifdef DLPM_PHASE_TIMING
         const long long _w0 = clock64();
 #endif
-        if (!(ABL & 8)) __syncthreads();
+        __syncthreads();
 #ifdef DLPM_PHASE_TIMING
         _wait += clock64() - _w0;
 #endif
     }
-    if (ABL & 8) __syncthreads();
     if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
     DLPM_PHASE(p, 9);
     if (HELP && !mfma_wave) return;   // (no barrier behind the loop: the epilogue runs out of the MFMA waves' registers)
@@ -522,270 +417,118 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
     if (p.phase && lane == 0) atomicAdd(p.phase + 16 + wave, (unsigned long long)_wait);
 #endif
 
-    if constexpr (EPI_T) {
-        // ---- epilogue from registers: no LDS, no barrier.  With the MFMA operands swapped a lane (li = tile, lk) holds
-        // M_pos[tile li][channels 16 wave + 4 lk .. + 3] in acc[pos][0..3]: the output transform runs once per channel, and
-        // bias / residual / stores move FOUR consecutive channels of a pixel per instruction (16 bytes per lane, the four lk
-        // lanes of a tile = one 64-byte segment): 16 loads + 16 stores per lane where the lane = channel layout of round 2
-        // issued 64 + 64 four-byte ones (the epilogue is bound by the number of memory instructions the CU's one
-        // texture-address unit takes from 8 waves, not by bytes).  Fused GroupNorm statistics: per-lane shifted sums over
-        // the tile's 16 pixels, then the 16 tiles merged by four butterfly steps in a fixed order.
-        const int64_t pix0 = ((int64_t)img0 * H + 4 * ty0) * W + 4 * tx0;      // wave-uniform
-        const int ch = n0 + 16 * wave + 4 * lk;
-        float4 bias_v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.bias) bias_v = *reinterpret_cast<const float4 *>(p.bias + ch);
-        const bool has_res = p.res0 != nullptr;
-        const bool res_first = __builtin_amdgcn_readfirstlane(n0 + 16 * wave) < p.R0;   // R0 % 16 == 0 (wino4_geometry)
-        const float *res_u = has_res ? (res_first ? p.res0 : p.res1 - p.R0) : nullptr;
-        const int res_ld = res_first ? p.R0 : p.Cout - p.R0;
-        const int lbw = 31 - __builtin_clz(bw), lbhw = 31 - __builtin_clz(bh * bw);      // block shapes are powers of two
-        const int timg = li >> lbhw, ty = (li & (bh * bw - 1)) >> lbw, tx = li & (bw - 1);
+    // ---- epilogue from registers: no LDS, no barrier.  A lane holds 64 outputs of ONE channel (4 tiles x 16 pixels:
+    // M_pos[tile 4 lk + r][channel 16 wave + li] in acc[pos][r]), so the output transform, bias, residual, the fused
+    // GroupNorm statistics (per-lane shifted sums, then the four 16-lane groups merged in a fixed order) and the stores
+    // all happen where the values are; a 16-lane group writes 64 contiguous bytes of an NHWC row.  (The round-1
+    // epilogue staged the block through a 135-KB LDS row image for whole-row stores: 3 % slower once the loop's own LDS
+    // traffic had been cut, profiles/r02/conv_layers_register_epilogue*.txt.)
+    const int64_t pix0 = ((int64_t)img0 * H + 4 * ty0) * W + 4 * tx0;      // wave-uniform
+    const int ch = n0 + 16 * wave + li;
+    const float bias_v = p.bias ? p.bias[ch] : 0.f;
+    const bool has_res = p.res0 != nullptr;
+    const bool res_first = __builtin_amdgcn_readfirstlane(n0 + 16 * wave) < p.R0;   // R0 % 16 == 0 (wino4_geometry)
+    const float *res_u = has_res ? (res_first ? p.res0 : p.res1 - p.R0) : nullptr;
+    const int res_ld = res_first ? p.R0 : p.Cout - p.R0;
+    const int lbw = 31 - __builtin_clz(bw), lbhw = 31 - __builtin_clz(bh * bw);      // block shapes are powers of two
+    float *__restrict__ out_blk = p.out + pix0 * p.Cout;
+    const float *__restrict__ res_blk = has_res ? res_u + pix0 * res_ld : nullptr;
+    // statistics: one partial per 256-pixel block inside an image (nimg == 1), or -- four whole 8x8 images per block, four tiles
+    // each -- one per IMAGE: a lane's 64 outputs (tiles 4 lk .. 4 lk + 3) are then exactly image lk's pixels of its channel
+    const bool img_stats = p.stats_out != nullptr && nimg == 4 && bh * bw == 4;
+    const bool do_stats = (p.stats_out != nullptr && nimg == 1) || img_stats;
+    float K = 0.f, s1 = 0.f, s2 = 0.f;
+    float rs_all[HELP ? 4 : 1][16] = {};   // (read unconditionally below, used only under has_res)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int tile = 4 * lk + r;
+        const int timg = tile >> lbhw, ty = (tile & (bh * bw - 1)) >> lbw, tx = tile & (bw - 1);
         const int tpix = (timg * H + 4 * ty) * W + 4 * tx;
         const bool ok = img0 + timg < p.B;
-        float *__restrict__ out_t = p.out + (pix0 + tpix) * p.Cout + ch;
-        const float *__restrict__ res_t = has_res ? res_u + (pix0 + tpix) * res_ld + ch : nullptr;
-        const bool do_stats = p.stats_out != nullptr && nimg == 1;
-        float Y[4][16];   // [channel][pixel 4 i + j]
+        float rs[16];
+        // addresses = wave-uniform base (block origin + pixel (i, j) of the tile) + a 32-bit per-lane byte offset
+        const uint32_t bo_o = (uint32_t)(tpix * p.Cout + ch) * 4u, bo_r = (uint32_t)(tpix * res_ld + ch) * 4u;
+        if (HELP) {
+            // narrow shapes (one or two waves per SIMD, nothing else hides a wait): ALL four tiles' residual values are requested
+            // before the first output transform -- the registers of the weight ring and the A fragments are free by now
+            if (r == 0 && has_res) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float Z[4][6];
+                for (int rr = 0; rr < 4; rr++) {
+                    const int t2 = 4 * lk + rr;
+                    const int tp2 = ((t2 >> lbhw) * H + 4 * ((t2 & (bh * bw - 1)) >> lbw)) * W + 4 * (t2 & (bw - 1));
+                    const uint32_t b2 = (uint32_t)(tp2 * res_ld + ch) * 4u;
+                    const bool ok2 = img0 + (t2 >> lbhw) < p.B;
 #pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-                const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-                const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                Z[0][b] = m0 + s12 + s34;
-                Z[1][b] = fmaf(PB, d34, PA * d12);
-                Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-                Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
+                    for (int k = 0; k < 16; k++)
+                        rs_all[rr][k] = ok2 ? *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + ((k >> 2) * W + (k & 3)) * res_ld) + b2) : 0.f;
+                }
             }
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-                Y[r][i * 4 + 0] = Z[i][0] + s12 + s34;
-                Y[r][i * 4 + 1] = fmaf(PB, d34, PA * d12);
-                Y[r][i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-                Y[r][i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-            }
+            for (int k = 0; k < 16; k++) rs[k] = rs_all[r][k];
+        } else if (has_res && ok) {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    rs[i * 4 + j] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + (i * W + j) * res_ld) + bo_r);
         }
-        float4 K = make_float4(0.f, 0.f, 0.f, 0.f), s1 = K, s2 = K;
-        if (ok) {
+        float Yt[16];
+        float Z[4][6];
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                float4 rs[4];
-                if (has_res) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) rs[j] = *reinterpret_cast<const float4 *>(res_t + (i * W + j) * res_ld);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float4 v = make_float4(Y[0][i * 4 + j] + bias_v.x, Y[1][i * 4 + j] + bias_v.y, Y[2][i * 4 + j] + bias_v.z,
-                                           Y[3][i * 4 + j] + bias_v.w);
-                    if (has_res) { v.x += rs[j].x; v.y += rs[j].y; v.z += rs[j].z; v.w += rs[j].w; }
-                    if (do_stats) {
-                        if (i == 0 && j == 0) K = v;
-                        float d;
-                        d = v.x - K.x; s1.x += d; s2.x = fmaf(d, d, s2.x);
-                        d = v.y - K.y; s1.y += d; s2.y = fmaf(d, d, s2.y);
-                        d = v.z - K.z; s1.z += d; s2.z = fmaf(d, d, s2.z);
-                        d = v.w - K.w; s1.w += d; s2.w = fmaf(d, d, s2.w);
-                    }
-                    *reinterpret_cast<float4 *>(out_t + (i * W + j) * p.Cout) = v;
-                }
-            }
+        for (int b = 0; b < 6; b++) {
+            const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
+            const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
+            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
+            Z[0][b] = m0 + s12 + s34;
+            Z[1][b] = fmaf(PB, d34, PA * d12);
+            Z[2][b] = fmaf(PB2, s34, PA2 * s12);
+            Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
         }
-        if (do_stats) {
-            float mean[4] = {K.x + s1.x * (1.f / 16.f), K.y + s1.y * (1.f / 16.f), K.z + s1.z * (1.f / 16.f), K.w + s1.w * (1.f / 16.f)};
-            float M2[4] = {fmaxf(s2.x - s1.x * s1.x * (1.f / 16.f), 0.f), fmaxf(s2.y - s1.y * s1.y * (1.f / 16.f), 0.f),
-                           fmaxf(s2.z - s1.z * s1.z * (1.f / 16.f), 0.f), fmaxf(s2.w - s1.w * s1.w * (1.f / 16.f), 0.f)};
-            float na = 16.f;
 #pragma unroll
-            for (int sft = 1; sft <= 8; sft <<= 1) {      // the 16 tiles (lane bits 0..3), lower lane first
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const float om = __shfl_xor(mean[c], sft), oM2 = __shfl_xor(M2[c], sft);
-                    const float lo_m = (lane & sft) ? om : mean[c], hi_m = (lane & sft) ? mean[c] : om;
-                    const float lo_M = (lane & sft) ? oM2 : M2[c], hi_M = (lane & sft) ? M2[c] : oM2;
-                    const float dd = hi_m - lo_m;
-                    mean[c] = lo_m + dd * 0.5f;
-                    M2[c] = lo_M + hi_M + dd * dd * (na * 0.5f);
-                }
-                na *= 2.f;
-            }
-            if (li == 0) {
-                float2 *so = p.stats_out + ((int64_t)img0 * ((H * W) / 256) + blk_in_img) * p.Cout + ch;
-#pragma unroll
-                for (int c = 0; c < 4; c++) so[c] = make_float2(mean[c], M2[c]);
-            }
+        for (int i = 0; i < 4; i++) {
+            const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
+            Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
+            Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
+            Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
+            Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
         }
-    } else {
-        // ---- epilogue from registers: no LDS, no barrier.  A lane holds 64 outputs of ONE channel (4 tiles x 16 pixels:
-        // M_pos[tile 4 lk + r][channel 16 wave + li] in acc[pos][r]), so the output transform, bias, residual, the fused
-        // GroupNorm statistics (per-lane shifted sums, then the four 16-lane groups merged in a fixed order) and the stores
-        // all happen where the values are; a 16-lane group writes 64 contiguous bytes of an NHWC row.  (The round-1
-        // epilogue staged the block through a 135-KB LDS row image for whole-row stores: 3 % slower once the loop's own LDS
-        // traffic had been cut, profiles/r02/conv_layers_register_epilogue*.txt.)
-        const int64_t pix0 = ((int64_t)img0 * H + 4 * ty0) * W + 4 * tx0;      // wave-uniform
-        // VS: wave (q = wave & 3, ph = wave >> 2) finalises channel tile ph of its quarter: channels 32 q + 16 ph ..
-        const int vph = wave >> 2, cw = VS ? 32 * (wave & 3) + 16 * vph : 16 * wave;
-        const int ch = n0 + cw + li;
-        const float bias_v = p.bias ? p.bias[ch] : 0.f;
-        const bool has_res = p.res0 != nullptr;
-        const bool res_first = __builtin_amdgcn_readfirstlane(n0 + cw) < p.R0;   // R0 % 16 == 0 (wino4_geometry)
-        // VS: the 16 partial outputs of tile r and channel tile nt from this wave's three transform rows (ph = 0: the points 0, +a, -a;
-        // ph = 1: +b, -b, inf), then the partner's channel tile goes to LDS: xb[writer wave][r][k][lane]
-        float *xb = wsm;
-        // (nt arrives as a compile-time constant: a run-time index into acc[] would move the accumulators to scratch memory)
-        auto partial = [&](int r, auto nt_c, float (&y)[16]) {
-            constexpr int nt = decltype(nt_c)::value;
-            float Z[4][6];
+        if (!ok) continue;
 #pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const float ma = acc[(0 * 6 + b) * 2 + nt][r], mb = acc[(1 * 6 + b) * 2 + nt][r], mc = acc[(2 * 6 + b) * 2 + nt][r];
-                if (vph == 0) {
-                    const float sm = mb + mc, df = mb - mc;
-                    Z[0][b] = ma + sm; Z[1][b] = PA * df; Z[2][b] = PA2 * sm; Z[3][b] = PA3 * df;
-                } else {
-                    const float sm = ma + mb, df = ma - mb;
-                    Z[0][b] = sm; Z[1][b] = PB * df; Z[2][b] = PB2 * sm; Z[3][b] = fmaf(PB3, df, mc);
+        for (int i = 0; i < 4; i++) {
+            const float *y = Yt + 4 * i;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float v = y[j] + bias_v;
+                if (has_res) v += rs[i * 4 + j];
+                if (do_stats) {
+                    if (r == 0 && i == 0 && j == 0) K = v;
+                    const float dd = v - K;
+                    s1 += dd;
+                    s2 = fmaf(dd, dd, s2);
                 }
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(out_blk + (i * W + j) * p.Cout) + bo_o) = v;
             }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-                y[i * 4 + 0] = Z[i][0] + s12 + s34;
-                y[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-                y[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-                y[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-            }
-        };
-        if (VS) {
-            // (the loop's last phase barrier is behind every wave: V / raw are dead, the exchange buffer may overwrite them)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float yo[16];
-                if (vph == 0) partial(r, std::integral_constant<int, 1>(), yo);
-                else partial(r, std::integral_constant<int, 0>(), yo);
-#pragma unroll
-                for (int k = 0; k < 16; k++) xb[((wave * 4 + r) * 16 + k) * 64 + lane] = yo[k];
-            }
-            __syncthreads();
-        }
-        const float *res_u = has_res ? (res_first ? p.res0 : p.res1 - p.R0) : nullptr;
-        const int res_ld = res_first ? p.R0 : p.Cout - p.R0;
-        const int lbw = 31 - __builtin_clz(bw), lbhw = 31 - __builtin_clz(bh * bw);      // block shapes are powers of two
-        float *__restrict__ out_blk = p.out + pix0 * p.Cout;
-        const float *__restrict__ res_blk = has_res ? res_u + pix0 * res_ld : nullptr;
-        // statistics: one partial per 256-pixel block inside an image (nimg == 1), or -- four whole 8x8 images per block, four tiles
-        // each -- one per IMAGE: a lane's 64 outputs (tiles 4 lk .. 4 lk + 3) are then exactly image lk's pixels of its channel
-        const bool img_stats = p.stats_out != nullptr && nimg == 4 && bh * bw == 4;
-        const bool do_stats = ((p.stats_out != nullptr && nimg == 1) || img_stats) && !(HELP && (F4N_ABL & 4));
-        float K = 0.f, s1 = 0.f, s2 = 0.f;
-        constexpr bool RES_AHEAD = HELP || F4_RES_AHEAD != 0;
-        float rs_all[RES_AHEAD ? 4 : 1][16] = {};   // (read unconditionally below, used only under has_res)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int tile = 4 * lk + r;
-            const int timg = tile >> lbhw, ty = (tile & (bh * bw - 1)) >> lbw, tx = tile & (bw - 1);
-            const int tpix = (timg * H + 4 * ty) * W + 4 * tx;
-            const bool ok = img0 + timg < p.B;
-            float rs[16];
-            // addresses = wave-uniform base (block origin + pixel (i, j) of the tile) + a 32-bit per-lane byte offset
-            const uint32_t bo_o = (uint32_t)(tpix * p.Cout + ch) * 4u, bo_r = (uint32_t)(tpix * res_ld + ch) * 4u;
-            if (RES_AHEAD) {
-                // narrow shapes (one or two waves per SIMD, nothing else hides a wait): ALL four tiles' residual values are requested
-                // before the first output transform -- the registers of the weight ring and the A fragments are free by now
-                if (r == 0 && has_res && !(HELP && (F4N_ABL & 2))) {
-#pragma unroll
-                    for (int rr = 0; rr < 4; rr++) {
-                        const int t2 = 4 * lk + rr;
-                        const int tp2 = ((t2 >> lbhw) * H + 4 * ((t2 & (bh * bw - 1)) >> lbw)) * W + 4 * (t2 & (bw - 1));
-                        const uint32_t b2 = (uint32_t)(tp2 * res_ld + ch) * 4u;
-                        const bool ok2 = img0 + (t2 >> lbhw) < p.B;
-#pragma unroll
-                        for (int k = 0; k < 16; k++)
-                            rs_all[rr][k] = ok2 ? *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + ((k >> 2) * W + (k & 3)) * res_ld) + b2) : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 16; k++) rs[k] = rs_all[r][k];
-            } else if (has_res && ok) {
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        rs[i * 4 + j] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + (i * W + j) * res_ld) + bo_r);
-            }
-            float Yt[16];
-            if (VS) {
-                if (vph == 0) partial(r, std::integral_constant<int, 0>(), Yt);
-                else partial(r, std::integral_constant<int, 1>(), Yt);
-#pragma unroll
-                for (int k = 0; k < 16; k++) Yt[k] += xb[(((wave ^ 4) * 4 + r) * 16 + k) * 64 + lane];
-            } else {
-                float Z[4][6];
-#pragma unroll
-                for (int b = 0; b < 6; b++) {
-                    const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-                    const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-                    const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                    Z[0][b] = m0 + s12 + s34;
-                    Z[1][b] = fmaf(PB, d34, PA * d12);
-                    Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-                    Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-                    Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
-                    Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-                    Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-                    Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-                }
-            }
-            if (!ok) continue;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const float *y = Yt + 4 * i;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float v = y[j] + bias_v;
-                    if (has_res) v += rs[i * 4 + j];
-                    if (do_stats) {
-                        if (r == 0 && i == 0 && j == 0) K = v;
-                        const float dd = v - K;
-                        s1 += dd;
-                        s2 = fmaf(dd, dd, s2);
-                    }
-                    if (HELP && (F4N_ABL & 1)) { if (v == 123.456f) *reinterpret_cast<float *>(reinterpret_cast<char *>(out_blk) + bo_o) = v; continue; }
-                    *reinterpret_cast<float *>(reinterpret_cast<char *>(out_blk + (i * W + j) * p.Cout) + bo_o) = v;
-                }
-            }
-        }
-        if (img_stats) {
-            if (img0 + lk < p.B)
-                p.stats_out[(int64_t)(img0 + lk) * p.Cout + ch] = make_float2(K + s1 * (1.f / 64.f), fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f));
-        } else if (do_stats) {
-            float mean = K + s1 * (1.f / 64.f), M2 = fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f), na = 64.f;
-#pragma unroll
-            for (int sft = 16; sft <= 32; sft <<= 1) {
-                const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
-                const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
-                const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
-                const float dd = hi_m - lo_m;
-                mean = lo_m + dd * 0.5f;
-                M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
-                na *= 2.f;
-            }
-            if (lk == 0) p.stats_out[((int64_t)img0 * ((H * W) / 256) + blk_in_img) * p.Cout + ch] = make_float2(mean, M2);
         }
     }
-    } while (PERS && (wgid += gridDim.x) < ngrid);
+    if (img_stats) {
+        if (img0 + lk < p.B)
+            p.stats_out[(int64_t)(img0 + lk) * p.Cout + ch] = make_float2(K + s1 * (1.f / 64.f), fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f));
+    } else if (do_stats) {
+        float mean = K + s1 * (1.f / 64.f), M2 = fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f), na = 64.f;
+#pragma unroll
+        for (int sft = 16; sft <= 32; sft <<= 1) {
+            const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
+            const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
+            const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
+            const float dd = hi_m - lo_m;
+            mean = lo_m + dd * 0.5f;
+            M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
+            na *= 2.f;
+        }
+        if (lk == 0) p.stats_out[((int64_t)img0 * ((H * W) / 256) + blk_in_img) * p.Cout + ch] = make_float2(mean, M2);
+    }
     DLPM_PHASE(p, 10);
     DLPM_PHASE_FLUSH(p, 8);
-#ifdef DLPM_PHASE_TIMING
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#endif
 #ifdef DLPM_PHASE_DEFER
     if (p.phase && lane == 0) atomicAdd(p.phase + 16 + wave, (unsigned long long)_wait);
 #endif
@@ -1784,10 +1527,8 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
 // OIHW (3x3) -> U = G g G^T (6x6 per filter) in the kernel's fragment order Wf[ntile][wave][phase][18][lane][4]:
 // lane = lk*16 + li holds, for position pair pp and e = 0..3, U_pos[cin = phase*8 + 2 lk + (e & 1)][cout = ntile*128 + wave*16 + li]
 // with pos = 2 pp + (e >> 1).  Computed in double, rounded once.
-// vs = 1 (the VS kernel): Wf[ntile][wave = 4 ph + q][phase][slot = 2 pp + nt][lane][4]: lane holds, for e = 0..3,
-// U_pos[cin = phase*8 + 2 lk + (e & 1)][cout = ntile*128 + 32 q + 16 nt + li] with pos = 18 ph + 2 pp + (e >> 1)
 // nw = waves per workgroup (8 / 4 / 2 for 128- / 64- / 32-channel n-tiles): Wf[ntile][wave < nw][phase][18][lane][4]
-__global__ void k_relayout_weight_wino4(const float *oihw, float *dst, int Cout, int Cin, int vs, int nw) {
+__global__ void k_relayout_weight_wino4(const float *oihw, float *dst, int Cout, int Cin, int nw) {
     const int nch = Cin / F4_KC;
     const int64_t total = (int64_t)Cout * Cin * 36;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1800,9 +1541,9 @@ __global__ void k_relayout_weight_wino4(const float *oihw, float *dst, int Cout,
     const int wave = (int)(r % nw);
     const int nt = (int)(r / nw);
     const int lk = lane >> 4, li = lane & 15;
-    const int pos = vs ? 18 * (wave >> 2) + 2 * (pp >> 1) + (e >> 1) : 2 * pp + (e >> 1);
+    const int pos = 2 * pp + (e >> 1);
     const int cin = chunk * F4_KC + 2 * lk + (e & 1);
-    const int cout = vs ? nt * F4_NQ + 32 * (wave & 3) + 16 * (pp & 1) + li : nt * (16 * nw) + wave * 16 + li;
+    const int cout = nt * (16 * nw) + wave * 16 + li;
     const float *g = oihw + ((int64_t)cout * Cin + cin) * 9;
     const double a = F4_PA, b = F4_PB, a2 = a * a, b2 = b * b;
     const double n0 = a2 * b2, na = 2. * a2 * (a2 - b2), nb = 2. * b2 * (b2 - a2);    // prod_{l != j} (p_j - p_l) for p_j = 0, +-a, +-b
@@ -1827,19 +1568,6 @@ int f4_mode() {   // DLPM_WINO_F4=0: keep every 3x3 layer on the F(2x2,3x3) kern
 }  // namespace
 
 bool wino4_enabled() { return f4_mode() != 0; }
-// DLPM_WINO_VS=1: waves = 2 position halves x 4 channel quarters (every V fragment read by 4 waves instead of 8).  Built in round 4
-// because the held-clock ablations blamed 12 % of the clock on the V reads; with REAL operands halving that LDS traffic is worth
-// nothing: 12.25 / 12.31 / 12.29 ms against 12.20 / 12.25 / 12.27 over the eight layer shapes in three alternating pairs (long-K layers
-// -0.4 %, K = 128 layers +3 %: the LDS hand-over of the split output transform), profiles/r04/conv_layers_vsplit.txt -- what the
-// ablation had measured was the MFMA's own data activity (it replaces the A fragments by constants), not the LDS.  Off; same
-// results to rounding (the output transform sums two partial transforms).  Read once per process: the weight fragment order built
-// at finalize and the instantiation launched must agree.
-bool wino4_vsplit() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WINO_VS"); v = e ? atoi(e) : 0; }
-    return v != 0;
-}
-bool wino4_image_stats(int cout) { (void)cout; return F4_EPI_T == 0; }
 
 // DLPM_WINO4_NARROW=0 (A/B runs): the 64- / 32-channel n-tile shapes off -- those layers take F(2x2) / the implicit GEMM as in rounds 1-4
 static bool narrow_enabled() {
@@ -1851,7 +1579,7 @@ static bool narrow_enabled() {
 // geometry of a launch on n-tiles of nq channels (the narrow shapes' raw buffer holds halo patches of <= 400 pixels)
 static bool wino4_geometry_nq(const ConvLaunch &c, int nq, int *bh, int *bw, int *nimg) {
     if (nq != F4_NQ && !narrow_enabled()) return false;
-    if (!c.w_wino4 || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw || c.abl) return false;
+    if (!c.w_wino4 || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
     if ((c.Hout & 3) || (c.Wout & 3) || c.Cout % 32 != 0 || (c.C0 + c.C1) % F4_KC != 0 || c.C0 % F4_KC != 0) return false;
     const int rawpix = nq == F4_NQ ? F4_RAWPIX : F4_RAWPIX_N;
     if ((c.R0 & 15) != 0) return false;   // a wave's 16 output channels stay on one side of a residual concat
@@ -1963,8 +1691,8 @@ static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int
         return DLPM_OK;
     }
     if (nq != F4_NQ) {   // narrow layers: 4 MFMA + 3 helper waves (448 threads: 2 staging items cover 400 halo pixels), or 2 + 2 (256 threads: 4 items)
-        KFn fn = nq == 64 ? (c.ups ? &k_conv3x3_wino4<true, 0, 2, 0, 0, 4> : &k_conv3x3_wino4<false, 0, 2, 0, 0, 4>)
-                          : (c.ups ? &k_conv3x3_wino4<true, 0, 4, 0, 0, 2> : &k_conv3x3_wino4<false, 0, 4, 0, 0, 2>);
+        KFn fn = nq == 64 ? (c.ups ? &k_conv3x3_wino4<true, 2, 4> : &k_conv3x3_wino4<false, 2, 4>)
+                          : (c.ups ? &k_conv3x3_wino4<true, 4, 2> : &k_conv3x3_wino4<false, 4, 2>);
         const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 160 * 1024);
         if (r != DLPM_OK) return r;
         const size_t lds = (size_t)(2 * F4_VBUF + 2 * F4_RAWBUF_N + 2 * F4_CFS) * sizeof(float);
@@ -1983,62 +1711,11 @@ static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int
     }
     const int RHp = c.ups ? 2 * bh + 2 : 4 * bh + 2, RWp = c.ups ? 2 * bw + 2 : 4 * bw + 2;
     const bool small = nimg * RHp * RWp <= F4_NT;      // two staging items per thread cover the patch
-    KFn fn = c.ups ? (small ? &k_conv3x3_wino4<true, 0, 2> : &k_conv3x3_wino4<true>) : (small ? &k_conv3x3_wino4<false, 0, 2> : &k_conv3x3_wino4<false>);
-    if (wino4_vsplit()) fn = c.ups ? (small ? &k_conv3x3_wino4<true, 0, 2, 0, 1> : &k_conv3x3_wino4<true, 0, F4_QNIT, 0, 1>)
-                                   : (small ? &k_conv3x3_wino4<false, 0, 2, 0, 1> : &k_conv3x3_wino4<false, 0, F4_QNIT, 0, 1>);
-    static int spec_on = -1;    // DLPM_WINO_SPEC=1: the channel-specialised instantiations (same bits; measured NEUTRAL, 1.0764-1.0823 vs 1.0786-1.0850 ms
-                                // on the H32 128 -> 128 layer in three alternating runs, profiles/r04/conv_layers_specialised_h32_c128.txt: off)
-    if (spec_on < 0) { const char *e = getenv("DLPM_WINO_SPEC"); spec_on = e ? atoi(e) : 0; }
-    if (spec_on && !wino4_vsplit() && !c.ups && c.Hout == 32 && c.Wout == 32 && c.C0 == 128 && c.C1 == 0 && c.Cout == 128 && c.coefA && c.coefB && c.bias &&
-        c.act_silu && bh == 4 && bw == 4 && nimg == 1 && !c.res1 && (!c.res0 || c.R0 == 128))
-        fn = c.res0 ? &k_conv3x3_wino4<false, 0, 2, 2> : &k_conv3x3_wino4<false, 0, 2, 1>;
-
-#ifdef DLPM_WINO_ABLATIONS
-    static int abl = -1;
-    if (abl < 0) { const char *e = getenv("DLPM_WABL"); abl = e ? atoi(e) : 0; }
-    if (!c.ups && small) {       // (the measured shapes: halo patches of <= 512 pixels, the QN = 2 instantiation)
-        switch (abl) {
-            case 1: fn = &k_conv3x3_wino4<false, 1, 2>; break;
-            case 2: fn = &k_conv3x3_wino4<false, 2, 2>; break;
-            case 3: fn = &k_conv3x3_wino4<false, 3, 2>; break;
-            case 7: fn = &k_conv3x3_wino4<false, 7, 2>; break;
-            case 8: fn = &k_conv3x3_wino4<false, 8, 2>; break;
-            case 16: fn = &k_conv3x3_wino4<false, 16, 2>; break;
-            case 32: fn = &k_conv3x3_wino4<false, 32, 2>; break;
-            case 64: fn = &k_conv3x3_wino4<false, 64, 2>; break;
-            case 80: fn = &k_conv3x3_wino4<false, 80, 2>; break;
-            case 87: fn = &k_conv3x3_wino4<false, 87, 2>; break;
-            default: break;
-        }
-    }
-#endif
-    {
-        int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 160 * 1024);
-        if (r != DLPM_OK) return r;
-    }
-    size_t loop_b = (size_t)(2 * F4_VBUF + 2 * F4_RAWBUF + 2 * F4_CFS) * sizeof(float);
-    if (wino4_vsplit() && loop_b < (size_t)8 * 4 * 16 * 64 * sizeof(float)) loop_b = (size_t)8 * 4 * 16 * 64 * sizeof(float);   // the epilogue's exchange buffer
-    const int64_t total = mblocks * (c.Cout / F4_NQ);
-    // DLPM_WINO4_PERSIST=1 (round 6 experiment): one workgroup per CU walking total / CUs tiles (launches of more than two rounds, plain shapes only)
-    static int pers = -1, ncu = 0;
-    if (pers < 0) {
-        const char *e = getenv("DLPM_WINO4_PERSIST"); pers = e ? atoi(e) : 0;
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount;
-    }
-    if (pers && ncu > 0 && total > 2 * ncu && !wino4_vsplit() && fn == (c.ups ? (small ? (KFn)&k_conv3x3_wino4<true, 0, 2> : (KFn)&k_conv3x3_wino4<true>)
-                                                                            : (small ? (KFn)&k_conv3x3_wino4<false, 0, 2> : (KFn)&k_conv3x3_wino4<false>))) {
-        KFn pf = c.ups ? (small ? &k_conv3x3_wino4<true, 0, 2, 0, 0, 8, 1> : &k_conv3x3_wino4<true, 0, F4_QNIT, 0, 0, 8, 1>)
-                       : (small ? &k_conv3x3_wino4<false, 0, 2, 0, 0, 8, 1> : &k_conv3x3_wino4<false, 0, F4_QNIT, 0, 0, 8, 1>);
-        const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(pf), 160 * 1024);
-        if (r != DLPM_OK) return r;
-        ConvLaunch cp = c;
-        cp.pers_total = (int)total;
-        pf<<<(unsigned)ncu, F4_NT, loop_b, st>>>(cp, bh, bw, nimg);
-        DLPM_LAUNCH_CHECK();
-        return DLPM_OK;
-    }
-    fn<<<(unsigned)total, F4_NT, loop_b, st>>>(c, bh, bw, nimg);
+    KFn fn = c.ups ? (small ? &k_conv3x3_wino4<true, 2> : &k_conv3x3_wino4<true>) : (small ? &k_conv3x3_wino4<false, 2> : &k_conv3x3_wino4<false>);
+    const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 160 * 1024);
+    if (r != DLPM_OK) return r;
+    const size_t lds = (size_t)(2 * F4_VBUF + 2 * F4_RAWBUF + 2 * F4_CFS) * sizeof(float);
+    fn<<<(unsigned)(mblocks * (c.Cout / F4_NQ)), F4_NT, lds, st>>>(c, bh, bw, nimg);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }
@@ -2093,7 +1770,7 @@ int relayout_weight_wino4(const float *oihw_dev, float *dst_dev, int Cout, int C
     const int64_t n = (int64_t)Cout * Cin * 36;
     DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, (size_t)F4_PAD * 256 * sizeof(float), st));
     const int nq = nq_in > 0 ? nq_in : f4_nq_of(Cout);
-    k_relayout_weight_wino4<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, (nq == F4_NQ && wino4_vsplit()) ? 1 : 0, nq / 16);
+    k_relayout_weight_wino4<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, nq / 16);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

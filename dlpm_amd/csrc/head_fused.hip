@@ -45,9 +45,6 @@ constexpr int HF_NT = 256;        // 4 waves, two workgroups per CU
 constexpr int HF_NW = HF_NT / 64;
 constexpr int HF_MAXCH = 4;       // Cin <= 128 (registers: two tiles of input per wave)
 constexpr float HF_LOG2E = 1.44269504088896340736f;
-#ifndef HF_ABLATE          // timing-only developer builds (wrong results): 1 no MFMAs, 2 no SiLU / split arithmetic, 4 no gather, 8 no reloads
-#define HF_ABLATE 0
-#endif
 
 // fp32 pair -> the packed bf16 pairs of its three planes (conv_split.hip's split, exact: 8 + 8 + 8 significand bits)
 __device__ __forceinline__ void hf_split2(float lo, float hi, uint32_t &p0, uint32_t &p1, uint32_t &p2) {
@@ -154,10 +151,8 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
     };
     float4 xb[2][NL];
     auto load2 = [&](const float *src, int s, int m) __attribute__((always_inline)) {       // the two loads of K-step m
-        if (!(HF_ABLATE & 8)) {
-            xb[s][2 * m] = *reinterpret_cast<const float4 *>(src + 16 * m);
-            xb[s][2 * m + 1] = *reinterpret_cast<const float4 *>(src + 16 * m + 8);
-        }
+        xb[s][2 * m] = *reinterpret_cast<const float4 *>(src + 16 * m);
+        xb[s][2 * m + 1] = *reinterpret_cast<const float4 *>(src + 16 * m + 8);
     };
     // stage(s, m, slot): GroupNorm affine + SiLU of the lane's eight values of K-step m -> its A operand: three bf16 planes, or the
     // eight fp32 values
@@ -170,20 +165,11 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
             const float4 xr = xb[s][2 * m + h];
             const float4 cA = *reinterpret_cast<const float4 *>(cfs + 16 * m + 8 * h + 4 * kh);
             const float4 cB = *reinterpret_cast<const float4 *>(cfs + C + 16 * m + 8 * h + 4 * kh);
-            f32x2 v01, v23;
-            if (HF_ABLATE & 2) { v01 = f32x2{xr.x, xr.y} + f32x2{cA.x, cA.y}; v23 = f32x2{xr.z, xr.w} + f32x2{cB.z, cB.w}; }
-            else {
-                v01 = hf_act2(f32x2{xr.x, xr.y}, f32x2{cA.x, cA.y}, f32x2{cB.x, cB.y});
-                v23 = hf_act2(f32x2{xr.z, xr.w}, f32x2{cA.z, cA.w}, f32x2{cB.z, cB.w});
-            }
+            const f32x2 v01 = hf_act2(f32x2{xr.x, xr.y}, f32x2{cA.x, cA.y}, f32x2{cB.x, cB.y});
+            const f32x2 v23 = hf_act2(f32x2{xr.z, xr.w}, f32x2{cA.z, cA.w}, f32x2{cB.z, cB.w});
             if constexpr (BF) {
-                if (HF_ABLATE & 2) {
-                    q[0][2 * h] = q[1][2 * h] = q[2][2 * h] = __float_as_uint(v01.x) ^ __float_as_uint(v01.y);
-                    q[0][2 * h + 1] = q[1][2 * h + 1] = q[2][2 * h + 1] = __float_as_uint(v23.x) ^ __float_as_uint(v23.y);
-                } else {
-                    hf_split2(v01.x, v01.y, q[0][2 * h], q[1][2 * h], q[2][2 * h]);
-                    hf_split2(v23.x, v23.y, q[0][2 * h + 1], q[1][2 * h + 1], q[2][2 * h + 1]);
-                }
+                hf_split2(v01.x, v01.y, q[0][2 * h], q[1][2 * h], q[2][2 * h]);
+                hf_split2(v23.x, v23.y, q[0][2 * h + 1], q[1][2 * h + 1], q[2][2 * h + 1]);
             } else {   // fp32 form: planes 0 / 1 carry the eight values themselves
                 q[h][0] = __float_as_uint(v01.x); q[h][1] = __float_as_uint(v01.y);
                 q[h][2] = __float_as_uint(v23.x); q[h][3] = __float_as_uint(v23.y);
@@ -207,7 +193,6 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
     };
     // K-step m's MFMAs
     auto mfmas = [&](floatx16 &acc, const AFrag &a, const BFrag &bfr, int m) __attribute__((always_inline)) {
-        if (HF_ABLATE & 1) { asm volatile("" :: "v"(a.pl[0]), "v"(a.pl[1]), "v"(a.pl[2])); return; }
         if constexpr (BF) {
             const bf16x8 A0 = __builtin_bit_cast(bf16x8, a.pl[0]), A1 = __builtin_bit_cast(bf16x8, a.pl[1]), A2 = __builtin_bit_cast(bf16x8, a.pl[2]);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, bfr.pl[0], acc, 0, 0, 0);      // small terms first (conv_split.hip's order)
@@ -353,7 +338,7 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
         float *hr = hist ? hist + ((int64_t)(u.T - tt) * u.B + b) * D : nullptr;
         const HfItem it = hf_item(tid, g_lo, g_hi - g_lo, nq);
         const int co = it.co, y = it.y, q = it.q;
-        const bool item = co < COUT && !(HF_ABLATE & 4);
+        const bool item = co < COUT;
         const int64_t e0 = (int64_t)co * HW + (int64_t)y * W + 4 * q;
         if (item) {
             if (!p.bias) bv = 0.f;   // a launch without bias (valid for dlpm_conv2d_f32): the dummy load above read W'[0]
@@ -517,9 +502,7 @@ int launch_conv_head_fused(const ConvLaunch &c, const HeadUpdate *hu, hipStream_
         DLPM_HIP(hipGetDevice(&dev));
         DLPM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    static int wgs = 0;                                                  // (DLPM_HEAD_WGS=1: one workgroup per CU -- A/B runs)
-    if (!wgs) { const char *e = getenv("DLPM_HEAD_WGS"); wgs = (e && e[0] == '1') ? 1 : 2; }
-    const unsigned grid = (unsigned)(c.B < wgs * ncu ? c.B : wgs * ncu);   // persistent: two workgroups per CU walk the images
+    const unsigned grid = (unsigned)(c.B < 2 * ncu ? c.B : 2 * ncu);   // persistent: two workgroups per CU walk the images
 #define DLPM_HF1(CO, NCH, BFV)                                                                            \
     do {                                                                                                  \
         int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_head_fused<CO, NCH, BFV>), 160 * 1024); \

@@ -311,12 +311,6 @@ void build_arch(dlpm_unet *u) {
     u->head = u->conv("out.2.", c.out_channels, mc, 3);
 }
 
-bool ws_gemm_enabled() {   // DLPM_WS1X1=1: route the UNet's 1x1 convolutions through the weight-streaming kernel (experiment)
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WS1X1"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
-
 int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
     ConvLaunch probe;
     probe.C0 = C0; probe.C1 = c.cin - C0; probe.Cout = c.cout; probe.ks = c.ks;
@@ -332,12 +326,7 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary) {  // boundary: 0 no
         }
         if (c.cout % 128 == 0 && c.cin % 32 == 0 && boundary == 0) {
             DLPM_HIP(hipMalloc(&c.w_split, (size_t)split_weight_floats(c.cout, c.cin, 1) * sizeof(float)));
-            int r = relayout_weight_split(src, c.w_split, c.cout, c.cin, 1, nullptr);
-            if (r != DLPM_OK) return r;
-        }
-        if (ws_gemm_enabled() && c.cin % 32 == 0 && boundary == 0) {   // fragment order for the weight-streaming GEMM (TAPS = 1)
-            DLPM_HIP(hipMalloc(&c.w_frag, (size_t)frag_weight_floats(c.cout, c.cin, 1) * sizeof(float)));
-            return relayout_weight_frag(src, c.w_frag, c.cout, c.cin, nullptr, 1);
+            return relayout_weight_split(src, c.w_split, c.cout, c.cin, 1, nullptr);
         }
         return DLPM_OK;
     }
@@ -399,7 +388,6 @@ void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
     L.w_taps = c.w_taps;
     L.w_hfused = c.w_hfused;
     L.w_split = c.w_split;
-    L.ws_gemm = (c.ks == 1 && c.w_frag) ? 1 : 0;
     L.ks = c.ks;
     L.Cout = c.cout;
 }
@@ -416,7 +404,6 @@ int run_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch L, hipStream_t st, c
     L.w_taps = c.w_taps;
     L.w_hfused = c.w_hfused;
     L.w_split = c.w_split;
-    L.ws_gemm = (c.ks == 1 && c.w_frag) ? 1 : 0;
     L.ks = c.ks;
     L.Cout = c.cout;
     if (head_fused_ok(L)) return launch_conv_head_fused(L, hu, st);
@@ -1325,16 +1312,13 @@ extern "C" int dlpm_conv2d_f32(const dlpm_conv_args *a, float *scratch_dev, dlpm
         set_error("dlpm_conv2d_f32: NCHW boundary layouts do not combine with a concat input");
         return DLPM_ERR_UNSUPPORTED;
     }
+    if (a->force_direct & 4) {
+        set_error("dlpm_conv2d_f32: force_direct bit 2 (value 4) asked for 1x1 convolutions on the weight-streaming kernel, which was removed");
+        return DLPM_ERR_UNSUPPORTED;
+    }
     hipStream_t st = as_stream(stream);
     TRY(relayout_weight(a->weight, scratch_dev, a->Cout, a->C0 + a->C1, a->ksize, ig, st));
     L.w = scratch_dev;
-    if (ig && a->ksize == 1 && (a->C0 + a->C1) % 32 == 0 && (a->force_direct & 4) &&
-        a->scratch_floats >= (int64_t)a->Cout * (a->C0 + a->C1) + frag_weight_floats(a->Cout, a->C0 + a->C1, 1)) {
-        float *wf = scratch_dev + (int64_t)a->Cout * (a->C0 + a->C1);
-        TRY(relayout_weight_frag(a->weight, wf, a->Cout, a->C0 + a->C1, st, 1));
-        L.w_frag = wf;
-        L.ws_gemm = 1;
-    }
     L.gemm = DLPM_GEMM_F32;
     const int taps = a->ksize * a->ksize;
     if (ig && (a->force_direct & 16) && a->Cout % 128 == 0 && (a->C0 + a->C1) % 32 == 0 &&

@@ -427,7 +427,8 @@ typedef struct dlpm_conv_args {
     int32_t Cout;
     int32_t in_nchw, out_nchw;  /* boundary layouts (direct kernel only) */
     int32_t force_direct;       /* bit 0: use the direct (non-MFMA) kernel regardless of shape; bit 1: no Winograd;
-                                   bit 2: 1x1 through the weight-streaming kernel; bit 3: 3x3 through the
+                                   bit 2: unused (its 1x1 weight-streaming kernel was removed; set, the call fails with
+                                   DLPM_ERR_UNSUPPORTED); bit 3: 3x3 through the
                                    Winograd F(4x4,3x3) kernel where the shape qualifies (needs scratch for it);
                                    bit 4: 1x1, or 3x3 as an implicit GEMM, through the bf16-split kernel where the shape
                                    qualifies (scratch: + 1.5x weight); bit 5: the head (Cout <= 3) as a 1x1 GEMM onto its tap

@@ -146,9 +146,9 @@ def test_conv(case):
         print('%s: winograd/auto err %.2e, implicit-GEMM err %.2e, tol %.2e' % (
             name, (got - want).abs().max().item(), (got_h - want).abs().max().item(), conv_tol(w, Cin)))
     if 'igemm' in name and ks == 1:
-        # force_direct bit 2: the same 1x1 shape through the weight-streaming kernel (TAPS = 1; opt-in, see gemm_ws_ok)
-        got_l = run_conv(x0, w, bias, x1, stride, ups, coef, silu, res, force_direct=4)
-        assert (got_l - want).abs().max().item() < conv_tol(w, Cin), name + ' (weight-streaming GEMM)'
+        # force_direct bit 2 asked for the weight-streaming 1x1 kernel, which was measured slower and removed: an error, not a fall-back
+        with pytest.raises(_lib.DlpmError, match=r'dlpm status -3\]'):   # DLPM_ERR_UNSUPPORTED
+            run_conv(x0, w, bias, x1, stride, ups, coef, silu, res, force_direct=4)
     if 'igemm' in name:  # same shape through the direct kernel: the two kernels agree with each other
         got_d = run_conv(x0, w, bias, x1, stride, ups, coef, silu, res, force_direct=True)
         assert (got_d - want).abs().max().item() < conv_tol(w, Cin), name + ' (direct)'
