@@ -16,6 +16,8 @@ ABI_VERSION = 6   # must equal dlpm_abi_version(): struct layouts below mirror i
 UPD_DLIM, UPD_CLIP, UPD_ADVANCE, SMP_NO_FUSED_MLP, UPD_ELEMENTWISE, SMP_LIM = 1, 2, 4, 8, 16, 32
 MEAN_TYPES = {'EPSILON': 0, 'START_X': 1, 'Z': 2, 'PREVIOUS_X': 3}   # dlpm_mean_type
 PRED_TO_XSTART, PRED_CLIP, PRED_TO_EPS, PRED_ELEMENTWISE = 1, 2, 4, 16
+LOSS_RESCALE_T, LOSS_ELEMENTWISE = 1, 16    # dlpm_loss_flags
+AT_T_Q_SAMPLE, AT_T_PREDICT_EPS, AT_T_PREDICT_XSTART = 0, 1, 2    # dlpm_at_t_mode
 CONV_AUTO, CONV_F4, CONV_F2, CONV_IGEMM = 0, 1, 2, 3
 GEMM_AUTO, GEMM_F32, GEMM_BF16X3 = 0, 1, 2
 
@@ -40,6 +42,13 @@ class LimUpdateArgs(C.Structure):
     _fields_ = [('x_dev', vp), ('eps_dev', vp), ('z_dev', vp), ('t_dev', vp), ('tmp_dev', vp), ('cx_dev', vp),
                 ('cs_dev', vp), ('cn_dev', vp), ('A_dev', vp), ('B', i64), ('D', i64), ('T', i32), ('flags', i32),
                 ('clamp_eps', f32), ('seed', u64), ('sample_offset', i64), ('key_dev', vp), ('hist_pp', vp)]
+
+
+class LossArgs(C.Structure):
+    _fields_ = [('x0_dev', vp), ('t_dev', vp), ('a_dev', vp), ('z_dev', vp), ('bg_dev', vp), ('bs_dev', vp), ('in_scale_dev', vp),
+                ('x_in_dev', vp), ('eps_dev', vp), ('x_t_dev', vp), ('tvec_out_dev', vp), ('t_out_dev', vp), ('a_out_dev', vp),
+                ('B', i64), ('D', i64), ('T', i32), ('outer', i32), ('inner', i32), ('flags', i32), ('alpha', f64),
+                ('clamp_a', f64), ('seed', u64), ('sample_offset', i64)]
 
 
 class UNetConfig(C.Structure):
@@ -98,6 +107,10 @@ SIGNATURES = {
     'dlpm_lim_tables_f32': (C.c_int, [f64, i32, i32, vp, vp, vp, vp, vp]),
     'dlpm_lim_update_f32': (C.c_int, [C.POINTER(LimUpdateArgs), vp]),
     'dlpm_fill_table_t_f32': (C.c_int, [vp, vp, vp, i32, i64, vp]),
+    'dlpm_loss_elements_f32': (C.c_int, [C.POINTER(LossArgs), vp]),
+    'dlpm_loss_terms_f32': (C.c_int, [vp, vp, vp, i64, i32, i64, i32, i64, i64, vp]),
+    'dlpm_loss_reduce_f32': (C.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp]),
+    'dlpm_at_t_f32': (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp]),
     'dlpm_images_to_rgb8': (C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
     'dlpm_png_bound': (i64, [i32, i32]),
     'dlpm_png_encode_rgb8': (C.c_int, [vp, i32, i32, i32, vp, i64, C.POINTER(i64)]),

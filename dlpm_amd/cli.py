@@ -7,6 +7,9 @@ plus the checkpoint to evaluate, resolved like eval.py does (eval.py:21, bem/uti
   --name N [--models_dir models] [--epoch E]  ->  models/N/<dataset>/model_<exphash>[_<E>].pt
 or given directly with --checkpoint FILE; --ema_eval [--ema_index I] evaluates an EMA shadow.
 Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-193).
+  --eval_loss DATA.npy [--lploss P] [--median OUTER INNER]: instead of generating, the held-out denoising loss of the checkpoint on
+  the float32 samples of DATA.npy (already in the net's range), EvaluationManager.evaluate_loss; --lploss / --median as the
+  reference's training flags.  The figure does not depend on --batch_size.
 """
 import argparse
 import os
@@ -77,6 +80,12 @@ def main(argv=None):
     ap.add_argument('--class_labels', default=None, metavar='cycle|K',
                     help='labels of a class-conditional net (model.class_cond): cycle = sample i gets i %% num_classes, an integer k = '
                          'every sample gets k.  With --gen_data_path they are written to labels.npy next to the images')
+    ap.add_argument('--eval_loss', default=None, metavar='DATA.npy',
+                    help='held-out denoising loss (the reference\'s training objective, forward only) on the float32 [N, C, H, W] / '
+                         '[N, 1, F] samples of this file; prints `loss <value> over <N> samples`')
+    ap.add_argument('--lploss', type=float, default=None, help='with --eval_loss: 2 (L2, default), 1 (smooth L1), -1 (squared L2)')
+    ap.add_argument('--median', type=int, nargs=2, default=None, metavar=('OUTER', 'INNER'),
+                    help='with --eval_loss: median-of-means estimator with these Monte-Carlo counts')
     a = ap.parse_args(argv)
 
     p = dlpm_amd.load_config(a.config)
@@ -127,6 +136,20 @@ def main(argv=None):
             raise SystemExit('--gemm applies to the UNet score networks')
         model.set_gemm_policy(a.gemm)
     method = dlpm_amd.init_method_by_parameter(p, rng=a.rng, seed=seed or 0)
+    if a.eval_loss:
+        data = np.load(a.eval_loss)
+        tr = dict((p.get('training') or {}).get(m) or {})      # a reference-schema YAML carries the loss settings of its training run
+        kw = {k: tr[k] for k in ('lploss', 'loss_monte_carlo', 'monte_carlo_outer', 'monte_carlo_inner', 'clamp_a', 'clamp_eps')
+              if k in tr}
+        if a.lploss is not None:
+            kw['lploss'] = a.lploss
+        if a.median is not None:
+            kw.update(loss_monte_carlo='median', monte_carlo_outer=a.median[0], monte_carlo_inner=a.median[1])
+        labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), len(data))
+        ev = dlpm_amd.EvaluationManager(method, None, None, verbose=False)
+        loss = ev.evaluate_loss({'default': model}, data, p['eval']['batch_size'], class_labels=labels, **kw)
+        print('loss %.9g over %d samples' % (loss, len(data)))
+        return loss
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])

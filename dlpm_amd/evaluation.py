@@ -10,7 +10,9 @@ dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so
 chunks beyond `eval.batch_size` without changing a pixel.
 
 The metrics half (FID / PRDC / Wasserstein / MMD) needs third-party packages and Inception weights that are not
-available offline and is out of scope: `evals` keeps the reference's keys but nothing is appended to them.
+available offline and is out of scope: `evals` keeps the reference's keys but nothing is appended to them -- except
+`losses`, which `evaluate_loss` fills with the one quality figure that needs nothing but the net and data: the
+reference's own objective (GenerativeLevyProcess.training_losses), forward only, on held-out samples.
 """
 import copy
 import ctypes as C
@@ -149,6 +151,67 @@ class EvaluationManager:
             e[k] = old[k] if keep_evals else []
         e['grad_norm'] = old['grad_norm'] if keep_evals else np.array([], dtype=np.float32)
         self.evals = e
+
+    def evaluate_loss(self, models, data, batch_size, per_timestep=False, class_labels=None, **loss_kwargs):
+        """Held-out denoising loss of `models['default']` on `data`: the Proposition-9 loss of the reference
+        (training_losses_dlpm, GenerativeLevyProcess.py:612-677) without gradients, as a Python float appended to
+        `evals['losses']` (the key the reference fills from training).
+
+        `data`: float32 [N, C, H, W] / [N, 1, F] tensor or array already in the net's range, or an iterable of such batches
+        (an (x, label) pair counts as x); it is cut into chunks of `batch_size`.  `loss_kwargs`: lploss, loss_monte_carlo,
+        monte_carlo_outer, monte_carlo_inner, clamp_a, clamp_eps as training_losses_dlpm.  `class_labels` [N]: labels of a
+        class-conditional net, sliced with the chunks.
+
+        The whole pass is one dataset_stream(): sample i draws the same (t, a, z) whatever the chunking, its terms go to the
+        slot of an [outer * inner * N] device buffer that ONE call on all N samples would put them in, and the estimator runs
+        once at the end -- so with rng='philox' the figure is bit-identical for every batch_size.  (rng='reference' continues the
+        host streams chunk by chunk, as successive reference calls would.)  One non-finite check for the whole pass.
+        `per_timestep=True` returns (loss, t[N] int32, terms[outer * inner * N]) on the host."""
+        method = self.method
+        if method.LIM:
+            raise NotImplementedError('evaluate_loss covers the DLPM loss; training_losses_lim is outside this build')
+        model = models['default']
+        if not torch.is_tensor(data) and not isinstance(data, np.ndarray):
+            data = [torch.as_tensor(b[0] if isinstance(b, (tuple, list)) else b) for b in data]
+            data = torch.cat(data) if data else torch.empty(0)
+        data = torch.as_tensor(data)
+        N = int(data.shape[0])
+        assert N > 0, 'evaluate_loss: no data'
+        assert data.dtype == torch.float32, 'evaluate_loss takes float32 data in the net\'s range, got %s' % data.dtype
+        kw = dict(loss_type='EPS_LOSS', lploss=2.0, loss_monte_carlo='mean', monte_carlo_outer=1, monte_carlo_inner=1,
+                  model_kwargs=None, clamp_a=None, clamp_eps=None)
+        assert set(loss_kwargs) <= set(kw), 'unknown loss arguments {}'.format(sorted(set(loss_kwargs) - set(kw)))
+        kw.update(loss_kwargs)
+        outer, inner = int(kw['monte_carlo_outer']), int(kw['monte_carlo_inner'])
+        mk = dict(kw['model_kwargs'] or {})
+        if class_labels is not None:
+            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        dev = torch.device(method.device)
+        batch_size = max(1, int(batch_size))
+        terms = t_all = None
+        with method.dataset_stream():
+            for first in range(0, N, batch_size):
+                x = data[first:first + batch_size].to(dev)
+                if class_labels is not None:
+                    mk['y'] = class_labels[first:first + x.shape[0]]
+                lploss, mkc = method._loss_check_args(model, x, kw['loss_type'], kw['lploss'], kw['loss_monte_carlo'], outer, inner, mk)
+                if terms is None:
+                    method.dlpm.gen_a.setParams(clamp_a=kw['clamp_a'])
+                    method.dlpm.gen_eps.setParams(clamp_eps=kw['clamp_eps'])
+                    if hasattr(model, 'eval'):
+                        model.eval()
+                    terms = torch.empty(outer * inner * N, dtype=torch.float32, device=dev)
+                    t_all = torch.empty(N, dtype=torch.int32, device=dev)
+                with torch.inference_mode():
+                    method._loss_terms(model, x, lploss, outer, inner, mkc, kw['clamp_a'], None, out=terms, out_stride=N,
+                                       out_offset=first, t_out=t_all[first:first + x.shape[0]])
+            with torch.inference_mode():
+                loss = float(method._loss_reduce(terms, N, outer, inner, kw['loss_monte_carlo'], check_finite=True))
+        self.evals['losses'] = np.append(self.evals['losses'], np.float32(loss))
+        if per_timestep:
+            return loss, t_all.cpu(), terms.cpu()
+        return loss
 
     def generate_default(self, models, nsamples, **kwargs):
         self.gen_manager.generate(models, nsamples, **kwargs)

@@ -10,6 +10,10 @@ dlpm/methods/GenerativeLevyProcess.py:48-90,512-569 (what `GenerationManager.gen
   * any other callable `model(x, t)` on the GPU                -> the same noise / table / update
     kernels, with the model called from Python between them.
 
+`training_losses(...)` is the forward half of the reference's objective as a held-out evaluation metric (no
+backward pass): forward noising at a per-sample timestep, the net, the loss terms and the mean / median-of-means
+estimator, three kernels of libdlpm_amd around one forward.
+
 Two RNG modes:
   rng='philox'     device Philox4x32-10 keyed by (seed, GLOBAL sample index, step, element): the
                    samples do not depend on how a batch is sharded over GPUs (default);
@@ -40,6 +44,16 @@ class ModelVarType:
     FIXED = 'FIXED'
 
 
+class LossType:
+    """dlpm/methods/dlpm.py:34-42; only EPS_LOSS is implemented there and here."""
+    LP_LOSS = 'LP_LOSS'
+    MEAN_LOSS = 'MEAN_LOSS'
+    EPS_LOSS = 'EPS_LOSS'
+    LAMBDA_LOSS = 'LAMBDA_LOSS'
+    VAR_KL = 'VAR_KL'
+    VAR_LP_SUM = 'VAR_LP_SUM'
+
+
 class ReferenceStreams:
     """Stream N (numpy global RandomState, consumed by scipy's levy_stable.rvs) and stream P (torch's
     default CPU generator), as libdlpm_amd MT19937 states."""
@@ -49,6 +63,9 @@ class ReferenceStreams:
         L = _lib.lib()
         _lib.check(L.dlpm_mt19937_seed(C.byref(self.N), np_seed & 0xFFFFFFFF))
         _lib.check(L.dlpm_mt19937_seed(C.byref(self.P), torch_seed & 0xFFFFFFFF))
+        # torch's own CPU generator under the same seed: the draws of training_losses (`randint`, `randn_like`), which
+        # equal the default generator's after torch.manual_seed(torch_seed) bit for bit
+        self.G = torch.Generator().manual_seed(torch_seed & 0xFFFFFFFF)
 
     @classmethod
     def from_global_numpy(cls, torch_seed):
@@ -554,8 +571,193 @@ class GenerativeLevyProcess:
             self.calls += 1
         return out
 
-    def training_losses(self, *a, **k):
-        raise NotImplementedError('training is outside the sampling hot path this build covers (SURVEY.md 2b)')
+    # -------------------------------------------------------------------------------- BEM: held-out loss
+    def q_sample(self, x_start, t, eps=None):
+        """GenerativeLevyProcess.q_sample (:105-116): (x_t, eps) from q(x_t | x_0)."""
+        return self.dlpm.sample_x_t_from_xstart(x_start, t, eps)
+
+    def _input_scale_dev(self):
+        """_input_scale() on the device, uploaded once per schedule (the loss kernels index it per sample)."""
+        isc = self._input_scale()
+        if isc is None:
+            return None
+        key = self.dlpm.host_schedule[3].data_ptr()
+        if getattr(self, '_isc_dev', None) is None or self._isc_dev[0] != key:
+            self._isc_dev = (key, isc.to(self.device))
+        return self._isc_dev[1]
+
+    def _loss_host_draws(self, shape, outer, inner, clamp_a):
+        """rng='reference': (t, a, z) on the host in the reference's order (GenerativeLevyProcess.py:634,650,652) -- `randint(1, T,
+        [B])` and `randn` on a private torch.Generator seeded like the torch stream (ReferenceStreams.G: torch's own generator, so t
+        and z equal the reference's bit for bit), `outer * B` (non-isotropic: `outer * B * D`) skewed-Levy draws on the restated
+        numpy stream."""
+        st = self._streams()
+        B, D = shape[0], int(np.prod(shape[1:]))
+        t = torch.randint(1, self.reverse_steps, size=[B], generator=st.G)
+        a = st.skewed_levy(self.alpha, outer * B * (1 if self.isotropic else D), clamp_a)
+        z = torch.randn([outer * inner * B] + list(shape[1:]), generator=st.G)
+        return {'t': t, 'a': a, 'z': z}
+
+    def _loss_terms(self, model, x_start, lploss, outer, inner, model_kwargs, clamp_a, noise, out=None, out_stride=None,
+                    out_offset=0, t_out=None, keep=False):
+        """The launches before the estimator: k_loss_elements, the net on the extended batch, k_loss_terms.  Terms go to
+        `out[r * out_stride + out_offset + b]` (default: a fresh [outer * inner * B] buffer, the reference's layout).  Returns a dict
+        with 'losses', 't' (int32 [B]) and, with `keep`, 'x_t', 'eps_t', 'x_in', 'model_eps'.  No synchronisation, no host read."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        L, st = _lib.lib(), _lib.stream_ptr()
+        dev = x_start.device
+        shape = list(x_start.shape)
+        B, D, R = shape[0], int(np.prod(shape[1:])), outer * inner
+        T = self.reverse_steps
+        x0 = x_start.contiguous().float()
+        if noise is None and self.rng == 'reference':
+            noise = self._loss_host_draws(shape, outer, inner, clamp_a)
+        noise = dict(noise or {})
+        assert set(noise) <= {'t', 'a', 'z'}, 'noise takes the keys t, a, z; got {}'.format(sorted(noise))
+        t_in = a_in = z_in = None
+        if noise.get('t') is not None:
+            t_in = torch.as_tensor(noise['t']).to(dev, torch.int32).contiguous()
+            assert t_in.shape == (B,), 't must be [B]'
+        if noise.get('a') is not None:
+            a_in = torch.as_tensor(noise['a']).to(dev, torch.float32).reshape(outer * B, -1)
+            if self.isotropic:
+                a_in = a_in[:, 0]               # as drawn [outer * B], or the reference's expanded [outer * B, C, H, W]
+            else:
+                assert a_in.shape[1] == D, 'non-isotropic a must be [outer * B, D]'
+            a_in = a_in.contiguous()
+        if noise.get('z') is not None:
+            z_in = torch.as_tensor(noise['z']).to(dev, torch.float32).contiguous()
+            assert z_in.numel() == R * B * D, 'z must be [outer * inner * B, ...]'
+        ext = [R * B] + shape[1:]
+        x_in = torch.empty(ext, dtype=torch.float32, device=dev)
+        eps_t = torch.empty(ext, dtype=torch.float32, device=dev)
+        x_t = torch.empty(ext, dtype=torch.float32, device=dev) if keep else None
+        tvec = torch.empty(R * B, dtype=torch.float32, device=dev)
+        if t_out is None:
+            t_out = torch.empty(B, dtype=torch.int32, device=dev)
+        isc = self._input_scale_dev()
+        seed, offset = self._philox_key()
+        a = _lib.LossArgs()
+        a.x0_dev, a.t_dev, a.a_dev, a.z_dev = x0.data_ptr(), _lib.ptr(t_in), _lib.ptr(a_in), _lib.ptr(z_in)
+        a.bg_dev, a.bs_dev, a.in_scale_dev = _lib.ptr(self.dlpm.bargammas), _lib.ptr(self.dlpm.barsigmas), _lib.ptr(isc)
+        a.x_in_dev, a.eps_dev, a.x_t_dev = x_in.data_ptr(), eps_t.data_ptr(), _lib.ptr(x_t)
+        a.tvec_out_dev, a.t_out_dev, a.a_out_dev = tvec.data_ptr(), t_out.data_ptr(), None
+        a.B, a.D, a.T, a.outer, a.inner = B, D, T, outer, inner
+        a.flags = (_lib.LOSS_RESCALE_T if self.rescale_timesteps else 0) | (0 if self.isotropic else _lib.LOSS_ELEMENTWISE)
+        a.alpha, a.clamp_a = float(self.alpha), -1.0 if clamp_a is None else float(clamp_a)
+        a.seed, a.sample_offset = seed, offset
+        _lib.check(L.dlpm_loss_elements_f32(C.byref(a), st))
+
+        kw = dict(model_kwargs or {})
+        y = kw.get('y')
+        if y is not None and R > 1 and torch.is_tensor(y) and y.shape[:1] == (B,):
+            kw['y'] = y = y.to(dev).repeat(R, *([1] * (y.dim() - 1)))       # replica r of sample b carries label y[b]
+        if isinstance(model, UNetModel) and set(kw) <= {'y'}:
+            model_eps = model._forward_checked(x_in, tvec, y)
+        elif isinstance(model, MLPModel) and not kw:
+            model_eps = model(x_in, tvec)
+        else:
+            t_arg = tvec if self.rescale_timesteps else t_out.to(torch.int64).repeat(R)
+            model_eps = model(x_in, t_arg, **kw).contiguous().float()
+        assert model_eps.shape == x_in.shape, 'the model returned {}, expected {}'.format(tuple(model_eps.shape), tuple(x_in.shape))
+
+        if out is None:
+            out, out_stride = torch.empty(R * B, dtype=torch.float32, device=dev), B
+        _lib.check(L.dlpm_loss_terms_f32(model_eps.data_ptr(), eps_t.data_ptr(), out.data_ptr(), B, R, D, int(lploss), out_stride,
+                                         out_offset, st))
+        if self._dataset is not None:
+            self._dataset['next'] += B
+        else:
+            self.calls += 1
+        res = {'losses': out, 't': t_out}
+        if keep:
+            res.update(x_t=x_t, eps_t=eps_t, x_in=x_in, model_eps=model_eps)
+        return res
+
+    def _loss_reduce(self, terms, N, outer, inner, loss_monte_carlo, check_finite, median_index=None):
+        """k_loss_reduce on terms[outer * inner * N] -> 0-dim fp32 loss on the device; `check_finite` reads the 4-byte flag."""
+        res = torch.empty(1, dtype=torch.float32, device=terms.device)
+        flag = torch.empty(1, dtype=torch.int32, device=terms.device)
+        _lib.check(_lib.lib().dlpm_loss_reduce_f32(terms.data_ptr(), N, outer, inner, int(loss_monte_carlo == 'median'),
+                                                   res.data_ptr(), flag.data_ptr(), _lib.ptr(median_index), _lib.stream_ptr()))
+        if check_finite:
+            assert int(flag) == 0, 'Nan in losses'                         # GenerativeLevyProcess.py:667
+        return res[0]
+
+    def _loss_check_args(self, model, x_start, loss_type, lploss, loss_monte_carlo, outer, inner, model_kwargs):
+        """Every argument check of training_losses_dlpm, before any device work.  Returns (lploss as int, model_kwargs)."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        assert self.model_mean_type == ModelMeanType.EPSILON, 'only epsilon model output is supported for the moment'
+        assert loss_type == LossType.EPS_LOSS, 'only epsilon loss is supported for the moment'
+        if lploss not in (2, 1, -1):
+            # the reference's general-p branch (torch.linalg.norm over three dims) raises on image tensors and is not reproduced
+            raise ValueError('lploss must be 2, 1 or -1 (L2, smooth-L1, squared L2), got {}'.format(lploss))
+        assert loss_monte_carlo in ('mean', 'median'), "loss_monte_carlo must be 'mean' or 'median'"
+        outer, inner = int(outer), int(inner)
+        assert outer >= 1 and inner >= 1, 'monte_carlo_outer and monte_carlo_inner must be >= 1'
+        if loss_monte_carlo == 'median' and outer > 64:
+            raise ValueError('median of means takes monte_carlo_outer <= 64, got {}'.format(outer))
+        model_kwargs = dict(model_kwargs or {})
+        if set(model_kwargs) == {'model_kwargs'}:          # the nested form a reference caller has to write (:608)
+            model_kwargs = dict(model_kwargs['model_kwargs'] or {})
+        assert torch.is_tensor(x_start) and x_start.dim() >= 2 and x_start.shape[0] >= 1, 'x_start must be a [B, ...] tensor'
+        if isinstance(model, UNetModel):
+            y = model_kwargs.get('y')
+            if set(model_kwargs) <= {'y'}:
+                model._check_labels(x_start.shape[0], y)    # the reference's checks, once, on the [B] labels
+        elif isinstance(model, MLPModel):
+            assert x_start.dim() == 3 and tuple(x_start.shape[1:]) == (1, model.nfeatures), x_start.shape
+        if not x_start.is_cuda:
+            raise _lib.DlpmError('training_losses runs on the MI355X only (x_start is on {}); there is no CPU fallback'.format(
+                x_start.device))
+        return int(lploss), model_kwargs
+
+    def training_losses_dlpm(self, model, x_start, loss_type='EPS_LOSS', lploss=2.0, loss_monte_carlo='mean', monte_carlo_outer=1,
+                             monte_carlo_inner=1, model_kwargs=None, clamp_a=None, clamp_eps=None, noise=None, check_finite=True,
+                             return_terms=False):
+        """Forward-only, under torch.inference_mode(): the result carries no autograd graph -- this is the Proposition-9 loss
+        (GenerativeLevyProcess.training_losses_dlpm, :612-677) as an evaluation metric, not a training step.
+
+        Three kernels of libdlpm_amd around one forward of the net on the `outer * inner * B` extended batch; nothing is
+        synchronised and no host value is read unless `check_finite` (one 4-byte flag, the reference's `Nan in losses`
+        assertion).  `loss_type` defaults to 'EPS_LOSS' (the reference's own default 'EPSILON' fails its own assertion).
+        `noise={'t': [B], 'a': [outer*B] (non-isotropic [outer*B, D]), 'z': [outer*inner*B, ...]}` injects any of the draws;
+        what is not injected comes from the device Philox stream (rng='philox': key as sample(), so dataset_stream() and
+        sample_offset mean the same here) or, with rng='reference', all three from the reference's CPU streams
+        (_loss_host_draws).  The index quirk of the reference is kept: replica r reads a[(r mod outer) * B + b], while the
+        median estimator reads the terms as [outer, inner, B].  Returns the 0-dim fp32 loss on the device (with
+        `return_terms`: (loss, terms[outer*inner*B], t[B]))."""
+        lploss, model_kwargs = self._loss_check_args(model, x_start, loss_type, lploss, loss_monte_carlo, monte_carlo_outer,
+                                                     monte_carlo_inner, model_kwargs)
+        outer, inner = int(monte_carlo_outer), int(monte_carlo_inner)
+        self.dlpm.gen_a.setParams(clamp_a=clamp_a)          # stateful, as in the reference (:629-630)
+        self.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
+        if hasattr(model, 'eval'):
+            model.eval()
+        with torch.inference_mode():
+            r = self._loss_terms(model, x_start, lploss, outer, inner, model_kwargs, clamp_a, noise)
+            loss = self._loss_reduce(r['losses'], x_start.shape[0], outer, inner, loss_monte_carlo, check_finite)
+        return (loss, r['losses'], r['t']) if return_terms else loss
+
+    def training_losses(self, models, x_start, model_kwargs=None, **kwargs):
+        """Forward-only, under torch.inference_mode(): the result carries no autograd graph.  GenerativeLevyProcess.training_losses
+        (:581-609) as a held-out metric: {'loss': 0-dim fp32 tensor on the device, 'losses': the per-extended-sample terms
+        [outer * inner * B] (this build's addition), 't': the timesteps [B]}.  `model_kwargs={'y': labels}` reaches a
+        class-conditional net with the labels following their sample into every replica; the nested form
+        {'model_kwargs': {'y': labels}} (the only one the reference's own splat lets through) is accepted too.  Other keywords
+        as training_losses_dlpm."""
+        if self.LIM:
+            raise NotImplementedError('training_losses_lim (LIM\'s own loss and nets) is outside this build; LIM=False evaluates '
+                                      'the DLPM loss')
+        model = models['default']
+        mk = dict(model_kwargs or {})
+        if set(mk) == {'model_kwargs'}:
+            mk = dict(mk['model_kwargs'] or {})
+        assert 'model_kwargs' not in kwargs and 'return_terms' not in kwargs
+        loss, losses, t = self.training_losses_dlpm(model, x_start, model_kwargs=mk, return_terms=True, **kwargs)
+        return {'loss': loss, 'losses': losses, 't': t}
 
 
 def _native_kwargs(model, model_kwargs):

@@ -6,7 +6,13 @@ schedule vectors, `rescale_diffusion`, and the stateful clamp parameters of the 
 Sigma recursion, x_{t-1} update) lives in libdlpm_amd and keeps [T,B] scalars instead of the
 reference's [T,B,C,H,W] tensors (non-isotropic noise, `isotropic=False`, is the one case that really
 needs a value per element: [T,B,D] tables).
+
+The helpers of the training half the reference exposes (`sample_x_t_from_xstart`, `predict_eps`, `predict_xstart`,
+`get_one_rv_loss_elements`, dlpm.py:191-217,384-401) are thin calls into libdlpm_amd at a per-sample timestep; they take
+tensors on the GPU.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -100,3 +106,73 @@ class DLPM:
         # as in the reference (dlpm.py:182-183) the regenerated schedule is ALWAYS scale_preserving, whatever
         # self.scale says: a scale_exploding process sampled with reverse_steps != its own switches schedule
         self._set_schedule(diffusion_steps)
+
+    # -------------------------------------------------------------------------------- per-sample-t helpers (GPU)
+    def _t_dev(self, x, t):
+        """get_t_to_batch_size (dlpm.py:165-168) as int32 [B] on x's device."""
+        if not x.is_cuda:
+            raise _lib.DlpmError('the DLPM helpers run on the MI355X only (the tensor is on %s); there is no CPU fallback' % x.device)
+        if isinstance(t, int):
+            return torch.full([x.shape[0]], t, dtype=torch.int32, device=x.device)
+        t = torch.as_tensor(t).to(x.device, torch.int32).contiguous()
+        assert t.shape == (x.shape[0],), 't must be an int or [B]'
+        return t
+
+    def _at_t(self, mode, u, v, t):
+        assert u.shape == v.shape
+        t = self._t_dev(u, t)
+        u, v = u.contiguous().float(), v.to(u.device).contiguous().float()
+        out = torch.empty_like(u)
+        B = u.shape[0]
+        _lib.check(_lib.lib().dlpm_at_t_f32(mode, u.data_ptr(), v.data_ptr(), t.data_ptr(), _lib.ptr(self.bargammas),
+                                            _lib.ptr(self.barsigmas), out.data_ptr(), B, u.numel() // B, self.diffusion_steps,
+                                            _lib.stream_ptr()))
+        return out
+
+    def predict_xstart(self, x_t, t, eps):
+        """(x_t - eps bs[t]) / bg[t]  (dlpm.py:191-196)."""
+        return self._at_t(_lib.AT_T_PREDICT_XSTART, x_t, eps, t)
+
+    def predict_eps(self, x_t, t, xstart):
+        """(x_t - xstart bg[t]) / bs[t]  (dlpm.py:198-202)."""
+        return self._at_t(_lib.AT_T_PREDICT_EPS, x_t, xstart, t)
+
+    def sample_x_t_from_xstart(self, xstart, t, eps=None, seed=0, sample_offset=0):
+        """(x_t, eps) with x_t = bg[t] xstart + bs[t] eps (dlpm.py:211-217).  eps=None draws gen_eps's noise -- clamp(sqrt(a) z) with
+        an unclamped skewed-Levy a per sample (per element when non-isotropic) -- from the device Philox stream (seed, sample_offset)."""
+        if eps is None:
+            self._t_dev(xstart, 0)
+            B = xstart.shape[0]
+            eps = torch.empty(xstart.shape, dtype=torch.float32, device=xstart.device)
+            ce = self.gen_eps.kwargs.get('clamp_eps')
+            fn = _lib.lib().dlpm_init_state_philox_f32 if self.isotropic else _lib.lib().dlpm_init_state_elem_philox_f32
+            _lib.check(fn(eps.data_ptr(), B, eps.numel() // B, float(self.alpha), -1.0 if ce is None else float(ce), 1.0, seed,
+                          sample_offset, _lib.stream_ptr()))
+        return self._at_t(_lib.AT_T_Q_SAMPLE, xstart, eps, t), eps
+
+    def get_one_rv_loss_elements(self, t, x_0, a_t=None, z_t=None, seed=0, sample_offset=0):
+        """(x_t, eps_t) of Proposition 9 (dlpm.py:395-401): x_t = bg[t] x_0 + sqrt(a_t bs[t]^2) z_t, eps_t = predict_eps(x_t, t, x_0).
+        a_t: [B] or the reference's expanded [B, ...] (non-isotropic: one value per element); a_t / z_t left None are drawn by
+        the kernel from the Philox stream (seed, sample_offset), a_t with gen_a's current clamp_a."""
+        t = self._t_dev(x_0, t)
+        x0 = x_0.contiguous().float()
+        B = x0.shape[0]
+        D = x0.numel() // B
+        x_t, eps_t, x_in = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        if a_t is not None:
+            a_t = torch.as_tensor(a_t).to(x0.device, torch.float32).reshape(B, -1)
+            a_t = (a_t[:, 0] if self.isotropic else a_t).contiguous()
+            assert self.isotropic or a_t.shape[1] == D
+        if z_t is not None:
+            z_t = z_t.to(x0.device, torch.float32).contiguous()
+            assert z_t.shape == x0.shape
+        ca = self.gen_a.kwargs.get('clamp_a')
+        a = _lib.LossArgs()
+        a.x0_dev, a.t_dev, a.a_dev, a.z_dev = x0.data_ptr(), t.data_ptr(), _lib.ptr(a_t), _lib.ptr(z_t)
+        a.bg_dev, a.bs_dev = _lib.ptr(self.bargammas), _lib.ptr(self.barsigmas)
+        a.x_in_dev, a.eps_dev, a.x_t_dev = x_in.data_ptr(), eps_t.data_ptr(), x_t.data_ptr()
+        a.B, a.D, a.T, a.outer, a.inner = B, D, self.diffusion_steps, 1, 1
+        a.flags = 0 if self.isotropic else _lib.LOSS_ELEMENTWISE
+        a.alpha, a.clamp_a, a.seed, a.sample_offset = float(self.alpha), -1.0 if ca is None else float(ca), seed, sample_offset
+        _lib.check(_lib.lib().dlpm_loss_elements_f32(C.byref(a), _lib.stream_ptr()))
+        return x_t, eps_t

@@ -241,6 +241,11 @@ class UNetModel(nn.Module):
     def forward(self, x, timesteps, y=None):
         """eps = model(x[B,C,H,W] fp32 on the GPU, t[B] floats[, y[B] class labels]) -- GenerativeLevyProcess.py:180."""
         y = self._check_labels(x.shape[0], y)
+        return self._forward_checked(x, timesteps, y)
+
+    def _forward_checked(self, x, timesteps, y):
+        """forward() after its label checks (which read the labels back): what a caller that has checked y[B] once runs on the
+        labels repeated per replica (training_losses), and what a captured graph can hold."""
         if not x.is_cuda:
             raise _lib.DlpmError('dlpm_amd.UNetModel.forward runs on the MI355X only (x is on %s); '
                                  'there is no CPU fallback' % x.device)

@@ -260,6 +260,76 @@ int dlpm_fill_table_t_f32(float *tvec_dev, const int32_t *t_dev, const float *ts
                           dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Held-out denoising loss: the forward half of the Proposition-9 objective as an evaluation metric (no backward pass).
+ * Reference: GenerativeLevyProcess.training_losses_dlpm (dlpm/methods/GenerativeLevyProcess.py:612-677),
+ * DLPM.get_one_rv_loss_elements (dlpm/methods/dlpm.py:384-401), compute_loss_terms (GenerativeLevyProcess.py:19-31).
+ * An "extended sample" is j = r * B + b, replica r in [0, outer * inner) of sample b: the reference materialises
+ * x_start.repeat / t.repeat / A.repeat (:645-651); here x0 and t are read by index b.
+ * ------------------------------------------------------------------------------------------ */
+enum dlpm_loss_flags {
+    DLPM_LOSS_RESCALE_T = 1,   /* tvec_out = float(t) * (1/T) (rescale_timesteps, :92-96) instead of float(t)          */
+    DLPM_LOSS_ELEMENTWISE = 16 /* non-isotropic noise: one a per element, a_dev is [outer*B, D] (same bit as the update's) */
+};
+
+typedef struct dlpm_loss_args {
+    const float *x0_dev;      /* [B,D] x_start                                                                      */
+    const int32_t *t_dev;     /* [B] injected timesteps in [1, T-1], or NULL = Philox, uniform on [1, T-1] (:634)   */
+    const float *a_dev;       /* injected a as DRAWN: [outer*B] (or [outer*B, D] elementwise), or NULL = Philox CMS */
+    const float *z_dev;       /* [outer*inner*B, D] injected N(0,1), or NULL = in-kernel Philox                     */
+    const float *bg_dev, *bs_dev;   /* schedule, [T]                                                                */
+    const float *in_scale_dev;      /* [T] 1/(1 + barsigma_t) when input_scaling applies (:658-661), else NULL      */
+    float *x_in_dev;          /* [outer*inner*B, D] what the net reads: x_t (times in_scale[t])                     */
+    float *eps_dev;           /* [outer*inner*B, D] eps_t = predict_eps(x_t, t, x0)                                 */
+    float *x_t_dev;           /* [outer*inner*B, D] x_t itself, or NULL                                             */
+    float *tvec_out_dev;      /* [outer*inner*B] the timesteps the net is fed, or NULL                              */
+    int32_t *t_out_dev;       /* [B] the timesteps used, or NULL                                                    */
+    float *a_out_dev;         /* the a used, laid out as a_dev, or NULL                                             */
+    int64_t B, D;
+    int32_t T;
+    int32_t outer, inner;     /* monte_carlo_outer, monte_carlo_inner                                               */
+    int32_t flags;            /* dlpm_loss_flags                                                                    */
+    double alpha;
+    double clamp_a;           /* < 0: none; applied to Philox draws as gen_skewed_levy does (injected a is used as given) */
+    uint64_t seed;            /* Philox key                                                                         */
+    int64_t sample_offset;    /* global index of sample 0 of this call                                              */
+} dlpm_loss_args;
+
+/* For every extended sample j = r*B + b, with t = t[b] and a = a[j mod (outer*B)] -- the reference draws A for outer*B
+ * samples and repeats it `inner` times (:650-651), so replica r reads the a of replica r mod outer:
+ *   x_t  = bg_t x0_b + sqrt(a bs_t^2) z_j                  dlpm.py:388-393,242-248
+ *   eps  = (x_t - x0_b bg_t) / bs_t                        dlpm.py:198-202 (predict_eps; differs from sqrt(a) z in the last bits)
+ *   x_in = x_t * in_scale[t]   or x_t                      GenerativeLevyProcess.py:658-661
+ * in the reference's fp32 operation order, one correctly rounded operation each.  Philox draws are keyed by (seed, global
+ * sample index, element, replica): a sample's loss does not depend on how a dataset is cut into calls.
+ * HBM-bound: 12 B/element with Philox draws, +4 with x_t, +4 with injected z, +4 with injected elementwise a. */
+int dlpm_loss_elements_f32(const dlpm_loss_args *args, dlpm_stream_t stream);
+
+/* compute_loss_terms (GenerativeLevyProcess.py:19-31) over [replicas*B, D]: with d = model_eps - eps_t, lploss 2 ->
+ * sqrt(mean d^2), 1 -> mean smooth-L1 (beta = 1), -1 -> mean d^2; other values are refused.  The term of extended sample
+ * (r, b) is stored at terms_dev[r*out_stride + out_offset + b]: out_stride = B, out_offset = 0 gives the reference's
+ * layout; a chunk of a dataset of N samples starting at sample n0 passes (N, n0) and fills the buffer ONE call on all
+ * N samples would fill.  Fixed summation order (fp64 accumulators): the bits do not depend on B.  8 B/element. */
+int dlpm_loss_terms_f32(const float *model_eps_dev, const float *eps_t_dev, float *terms_dev, int64_t B, int32_t replicas,
+                        int64_t D, int32_t lploss, int64_t out_stride, int64_t out_offset, dlpm_stream_t stream);
+
+/* The estimator (GenerativeLevyProcess.py:667-677) over terms_dev[outer*inner*N], one launch: median == 0 -> the mean of
+ * all terms; else the terms viewed as [outer, inner, N] -> mean over inner -> LOWER median over outer (torch.median) ->
+ * mean over N.  flag_dev[0] = 1 if any term or the result is not finite (the reference asserts `not isnan`, :667).
+ * median_index_dev (nullable, [N]): which of the outer means was taken.  monte_carlo_outer <= 64 for the median. */
+int dlpm_loss_reduce_f32(const float *terms_dev, int64_t N, int32_t outer, int32_t inner, int32_t median, float *loss_dev,
+                         int32_t *flag_dev, int32_t *median_index_dev, dlpm_stream_t stream);
+
+enum dlpm_at_t_mode {
+    DLPM_AT_T_Q_SAMPLE = 0,        /* out = bg_t u + bs_t v        u = x_0, v = eps     sample_x_t_from_xstart, dlpm.py:211-217 */
+    DLPM_AT_T_PREDICT_EPS = 1,     /* out = (u - v bg_t) / bs_t    u = x_t, v = x_0     predict_eps, dlpm.py:198-202            */
+    DLPM_AT_T_PREDICT_XSTART = 2   /* out = (u - v bs_t) / bg_t    u = x_t, v = eps     predict_xstart, dlpm.py:191-196         */
+};
+/* The three affine maps between x_0, x_t and eps at a PER-SAMPLE timestep t_dev[B] (the sampler's dlpm_predict_f32 takes one
+ * t for the whole batch): what q_sample and the helpers of the training half call.  Reference rounding order.  12 B/element. */
+int dlpm_at_t_f32(int32_t mode, const float *u_dev, const float *v_dev, const int32_t *t_dev, const float *bg_dev,
+                  const float *bs_dev, float *out_dev, int64_t B, int64_t D, int32_t T, dlpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generated-image dump: what EvaluationManager does with each chunk of samples,
  * bem/evaluate/EvaluationManager.py:174-196 -- `tvu.save_image(samples[i], f"{i+total}.png")` per sample.
  * ------------------------------------------------------------------------------------------ */

@@ -22,6 +22,7 @@ Fixture families:
   F14 16x16 / 32x32 blocks  AttentionBlock at T = 256, ResBlocks of the MNIST-sized net's fine levels   dlpm/models/unet.py:105-250
   F15 any geometry      QKVAttention at any T / head dim, the 28x28 MNIST UNet (forward, bounded T=1000 sample)   dlpm/models/unet.py
   F16 class-conditional  UNetModel(num_classes=10) forwards, p_sample_loop / ddim_sample_loop with model_kwargs={'y': y}   unet.py:341-342, 463-481
+  F17 held-out loss      training_losses / training_losses_dlpm with every draw recorded   GenerativeLevyProcess.py:581-677, dlpm.py:384-401
   F12 mean types         p_mean_variance: START_X / Z / PREVIOUS_X, denoised_fn, model_kwargs   GenerativeLevyProcess.py:154-219
   F11 image quantisation PIL's float -> 8-bit path (torchvision absent)  bem/evaluate/EvaluationManager.py:188-190
   F9 checkpoints         TrainingManager.save/load, EMAHelper,    bem/TrainingManager.py:240-285, bem/utils_ema.py,
@@ -1013,6 +1014,134 @@ def f16_conditional():
         raise AssertionError('f16: no DLIM setting of F16_DLIM gives an informative, checkable trajectory')
 
 
+# (case, net, B, T, alpha, method kwargs, loss kwargs)
+F17_CASES = [
+    ('mlp_l2', 'mlp', 64, 100, 1.7, {}, dict(lploss=2.0)),
+    ('mlp_l1', 'mlp', 64, 100, 1.7, {}, dict(lploss=1.0)),
+    ('mlp_sq', 'mlp', 64, 100, 1.7, {}, dict(lploss=-1)),
+    ('mlp_median', 'mlp', 64, 100, 1.7, {}, dict(loss_monte_carlo='median', monte_carlo_outer=5, monte_carlo_inner=3)),
+    ('tiny_l2', 'tiny', 8, 100, 1.7, {}, dict(lploss=2.0)),
+    ('tiny_l1', 'tiny', 8, 100, 1.7, {}, dict(lploss=1.0)),
+    ('tiny_sq', 'tiny', 8, 100, 1.7, {}, dict(lploss=-1)),
+    ('tiny_median', 'tiny', 8, 100, 1.7, {}, dict(loss_monte_carlo='median', monte_carlo_outer=3, monte_carlo_inner=2)),
+    ('tiny_median_even', 'tiny', 8, 100, 1.7, {}, dict(loss_monte_carlo='median', monte_carlo_outer=4, monte_carlo_inner=1)),
+    ('tiny_clamp', 'tiny', 8, 100, 1.7, {}, dict(clamp_a=5)),
+    ('tiny_noniso', 'tiny', 4, 50, 1.7, dict(isotropic=False), {}),
+    ('tiny_exploding', 'tiny', 8, 50, 1.7, dict(scale='scale_exploding', input_scaling=True), {}),
+    ('mnist_l2', 'mnist', 4, 1000, 1.8, {}, {}),
+    ('cond_l2', 'cond', 4, 100, 1.7, {}, {}),
+]
+F17_SEED = 13     # three of the first eight a draws under this numpy seed exceed 5: tiny_clamp's clamp_a bites
+
+
+def f17_loss():
+    """The reference's own training_losses (forward only) with every draw and every intermediate recorded: gen_a.generate (A as drawn),
+    torch.randint (t), torch.randn_like (z), Sigma' and Sigma' ** (1/2) as sample_x_t_from_xstart_given_Sigma sees them, get_one_rv_loss_elements (x_t, eps_t), the model call (x_in, model_eps),
+    compute_loss_terms (the per-extended-sample terms) and the returned loss.  np.random.seed / torch.manual_seed(F17_SEED) right before
+    the call.  Nets: the toy MLP of f6, the `tiny` / `mnist` UNets of f6 and the conditional `mnist` net of f16
+    (rebuilt from their seeds, pinned by digest).  x_start = 0.5 * N(0, 1) from a generator of its own."""
+    import dlpm.methods.GenerativeLevyProcess as ref_glp
+    F6 = {'tiny': (3, 32, [1, 2], [2], 4, 1, 16), 'mnist': (1, 32, [1, 2, 2, 2], [2, 4], 4, 2, 32)}
+
+    class Rec(torch.nn.Module):
+        def __init__(self, net):
+            super().__init__()
+            self.net = net
+
+        def forward(self, x, t, **kw):
+            self.x_in, self.t_in = x.clone(), t.clone()
+            self.out = self.net(x, t, **kw)
+            return self.out
+
+    for name, kind, B, T, alpha, mkw, lkw in F17_CASES:
+        extra, y = {}, None
+        if kind == 'mlp':
+            p = yaml.safe_load(open(os.path.join(REF, 'dlpm/configs/2d_data.yml')))
+            p['device'] = 'cpu'
+            torch.manual_seed(1)
+            net = ref_mlp.MLPModel(p).eval()          # default init under manual_seed(1), as f6_mlp_forward (which pins the weights)
+            shape = [B, 1, 2]
+        elif kind == 'cond':
+            in_ch, mc, mult, attn, heads, res = F16_NETS['mnist']
+            torch.manual_seed(1234)
+            net = make_unet(in_ch, mc, mult, attn, heads, res, num_classes=F16_K).eval()
+            rerandomize(net, 4321)
+            shape = [B, in_ch, 32, 32]
+            y = torch.tensor(F16_Y[:B], dtype=torch.int64)
+            extra = dict(y=y)
+        else:
+            in_ch, mc, mult, attn, heads, res, hw = F6[kind]
+            torch.manual_seed(1234)
+            net = make_unet(in_ch, mc, mult, attn, heads, res).eval()
+            rerandomize(net, 4321)
+            shape = [B, in_ch, hw, hw]
+        extra['digest'] = np.frombuffer(bytes.fromhex(weight_digest(net)), dtype=np.uint8)
+        x_start = 0.5 * torch.randn(shape, generator=torch.Generator().manual_seed(170))
+        meth = GenerativeLevyProcess(alpha=alpha, device='cpu', reverse_steps=T, rescale_timesteps=True, **mkw)
+        rec = Rec(net)
+        got = {}
+        o_gen, o_ri, o_rl, o_el, o_terms = (meth.dlpm.gen_a.generate, torch.randint, torch.randn_like,
+                                           meth.dlpm.get_one_rv_loss_elements, ref_glp.compute_loss_terms)
+
+        def gen(*a, **k):
+            got['A'] = o_gen(*a, **k).clone()
+            return got['A']
+
+        def randint(*a, **k):
+            got['t'] = o_ri(*a, **k).clone()
+            return got['t']
+
+        def randn_like(*a, **k):
+            got['z'] = o_rl(*a, **k).clone()
+            return got['z']
+
+        def elements(*a, **k):
+            got['x_t'], got['eps_t'] = (v.clone() for v in o_el(*a, **k))
+            return got['x_t'], got['eps_t']
+
+        def terms(*a, **k):
+            got['losses'] = o_terms(*a, **k).clone()
+            return got['losses']
+        o_given = meth.dlpm.sample_x_t_from_xstart_given_Sigma
+
+        def given(xstart, t, Sigma_t, z_t=None):
+            # the one operation of the chain that is not correctly rounded on every CPU build of torch: Sigma ** (1/2) (dlpm.py:247)
+            got['sigma'], got['sqrt_sigma'] = Sigma_t.clone(), Sigma_t ** (1 / 2)
+            return o_given(xstart, t, Sigma_t, z_t=z_t)
+        meth.dlpm.sample_x_t_from_xstart_given_Sigma = given
+        meth.dlpm.gen_a.generate, torch.randint, torch.randn_like = gen, randint, randn_like
+        meth.dlpm.get_one_rv_loss_elements, ref_glp.compute_loss_terms = elements, terms
+        try:
+            np.random.seed(F17_SEED)
+            torch.manual_seed(F17_SEED)
+            if kind == 'cond':        # the reference's training_losses cannot pass model_kwargs on (:608): the direct call
+                loss = meth.training_losses_dlpm(rec, x_start, loss_type='EPS_LOSS', model_kwargs={'y': y}, **lkw)
+            else:
+                loss = meth.training_losses({'default': rec}, x_start, loss_type='EPS_LOSS', **lkw)['loss']
+        finally:
+            meth.dlpm.gen_a.generate, torch.randint, torch.randn_like = o_gen, o_ri, o_rl
+            meth.dlpm.get_one_rv_loss_elements, ref_glp.compute_loss_terms = o_el, o_terms
+        outer, inner = lkw.get('monte_carlo_outer', 1), lkw.get('monte_carlo_inner', 1)
+        A = got['A']
+        assert A.shape[0] == outer * B
+        A = A.reshape(outer * B, -1)
+        if mkw.get('isotropic', True):
+            assert bool((A == A[:, :1]).all())
+            A = A[:, 0]
+        assert got['losses'].shape == (outer * inner * B,) and got['z'].shape[0] == outer * inner * B
+        sig, sq = (got[k].reshape(outer * inner * B, -1) for k in ('sigma', 'sqrt_sigma'))
+        if mkw.get('isotropic', True):
+            sig, sq = sig[:, 0], sq[:, 0]
+        extra.update(sigma=sig, sqrt_sigma=sq)
+        save('f17_loss_' + name, x_start=x_start, t=got['t'].to(torch.int32), A=A, z=got['z'], x_t=got['x_t'], eps_t=got['eps_t'],
+             x_in=rec.x_in, t_in=rec.t_in, model_eps=rec.out, losses=got['losses'], loss=loss, seed=np.array(F17_SEED),
+             meta=np.array([B, T, alpha, outer, inner, float(lkw.get('lploss', 2.0)), -1 if lkw.get('clamp_a') is None else lkw['clamp_a'],
+                            float(lkw.get('loss_monte_carlo', 'mean') == 'median'), float(mkw.get('isotropic', True)),
+                            float(mkw.get('scale', '') == 'scale_exploding')]),
+             **extra)
+        print('   %-18s loss %.6f' % (name, float(loss)))
+
+
 def f8_generation_manager():
     class FakeMethod:
         device = 'cpu'
@@ -1202,9 +1331,9 @@ def f10_lim():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16']
+    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16', 'f17']
     table = dict(f12=f12_mean_types, f11=f11_image_quantise, f10=f10_lim, f1=f1_schedule, f2=f2_noise, f3=f3_tables, f4=f4_single_step, f5=f5_trajectories, f5u=f5_unet_trajectory, f5w=f5_wide_unet_trajectory, f5k=f5_unet_trajectories_T1000, f5b=f5_bounded_unet_trajectories, f5c=f5_cifar_teacher_forced,
-                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f8=f8_generation_manager, f9=f9_checkpoints)
+                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f17=f17_loss, f8=f8_generation_manager, f9=f9_checkpoints)
     with torch.no_grad():
         for w in which:
             table[w]()
