@@ -7,8 +7,8 @@
 //     Y = A^T [ (G g G^T) .* (B^T d B) ] A        d: 6x6 input tile, g: 3x3 filter, Y: 4x4 output tile
 //
 // with Toom-Cook transform matrices for the interpolation points {0, +-a, +-b, inf}, (a, b) = (11/16, 3/2) (F4_PA, F4_PB below;
-// Lavin & Gray's matrices are a = 1, b = 2): rows of B^T above transform(), rows of A^T in the epilogue, G in
-// k_relayout_weight_wino4.
+// Lavin & Gray's matrices are a = 1, b = 2): rows of B^T in f4_bt_end / f4_bt_part / f4_bt_plus / f4_bt_minus, rows of A^T in f4_at,
+// G in k_relayout_weight_wino4 -- one definition each, in the section of shared building blocks that all four kernels of this file call.
 // The price is numerical: the products are accumulated over the input channels IN the Winograd domain, where the partial sums
 // are larger than the result they cancel to, and the point set fixes by how much.  tools/err_wino4_points.py (round 4,
 // profiles/r04/err_wino4_points.txt) emulates the kernel's arithmetic for the whole symmetric family -- every member costs
@@ -108,6 +108,187 @@ constexpr float PS2 = (float)(F4_PA * F4_PA + F4_PB * F4_PB), PP2 = (float)(F4_P
 __device__ __forceinline__ float2 f2fma(float a, float2 x, float2 y) { return make_float2(fmaf(a, x.x, y.x), fmaf(a, x.y, y.y)); }
 __device__ __forceinline__ float2 f2add(float2 x, float2 y) { return make_float2(x.x + y.x, x.y + y.y); }
 __device__ __forceinline__ float2 f2sub(float2 x, float2 y) { return make_float2(x.x - y.x, x.y - y.y); }
+
+// =====================================================================================================================================
+// The building blocks of all four kernels of this file.  Each piece of arithmetic that decides a result bit is written ONCE here; the kernels
+// pass layout constants only (V stride, patch pitch, sample count) and keep what is theirs: work split, schedule, barriers, LDS carve-up,
+// residual prefetch, register fences.  Everything is forced inline and takes its register arrays by reference.  The unrolled loops over
+// the weight ring and the position pairs stay in the kernels, around loop-free steps: written as loops inside a shared function the same
+// statements came out with other spills and other ds_read2 pairings (tools/isa_report.py, profiles/wino4_shared/).
+
+// ---- rows of B^T over one line of six samples x0..x5 (a column of d, or a row of T = B^T d).  Rows 0 and 5 are one expression on
+// (x0, x2, x4) / (x1, x3, x5); rows 1 | 2 and 3 | 4 are one expression on the points a and b (ROW = 1 / 3): an even part e from (x2, x4)
+// and an odd part o from (x1, x3), row ROW = e + p o, row ROW + 1 = e - p o
+__device__ __forceinline__ float2 f4_bt_end(float2 x0, float2 x2, float2 x4) { return f2fma(PP2, x0, f2fma(-PS2, x2, x4)); }
+template <int ROW> __device__ __forceinline__ float2 f4_bt_part(float2 xa, float2 xb) { return f2fma(ROW == 1 ? -PB2 : -PA2, xa, xb); }
+template <int ROW> __device__ __forceinline__ float2 f4_bt_plus(float2 o, float2 e) { return f2fma(ROW == 1 ? PA : PB, o, e); }
+template <int ROW> __device__ __forceinline__ float2 f4_bt_minus(float2 o, float2 e) { return f2fma(ROW == 1 ? -PA : -PB, o, e); }
+// d(i, c): sample row i, column c (two channels) of a lane's 6x6 patch in the raw buffer: rw pixels per patch row, PRLD floats per pixel;
+// UPS: nearest-x2 upsampling folded into the addressing (source row (i + 1) >> 1 of the 4x4 source patch); skew: rows 4 and 5 of the
+// patch lie in the next skew group of the raw image (4 floats late)
+template <bool UPS, int PRLD>
+struct F4Patch {
+    const float *rb;
+    int rw;
+    bool skew;
+    __device__ __forceinline__ float2 operator()(int i, int c) const {
+        const int ri = UPS ? (i + 1) >> 1 : i, ci = UPS ? (c + 1) >> 1 : c;
+        return *reinterpret_cast<const float2 *>(rb + (ri * rw + ci) * PRLD + ((skew && i >= 4) ? 4 : 0));
+    }
+};
+// column c of T = B^T d: the row pair ROW | ROW + 1 (ROW = 1, 3), or one of the outer rows (ROW = 0, 5)
+template <int ROW, class D>
+__device__ __forceinline__ void f4_bt_mid(const D &d, int c, float2 &tp, float2 &tm) {
+    const float2 e = f4_bt_part<ROW>(d(2, c), d(4, c)), o = f4_bt_part<ROW>(d(1, c), d(3, c));
+    tp = f4_bt_plus<ROW>(o, e);
+    tm = f4_bt_minus<ROW>(o, e);
+}
+template <int ROW, class D>
+__device__ __forceinline__ float2 f4_bt_outer(const D &d, int c) {
+    constexpr int o = ROW == 0 ? 0 : 1;
+    return f4_bt_end(d(o, c), d(o + 2, c), d(o + 4, c));
+}
+// V row = T B: positions (a, 0..5) of transform row a = position pairs 3 a .. 3 a + 2, one float4 {pos 2 pp: 2 channels, pos 2 pp + 1:
+// 2 channels} each, vpp floats apart; vr = the lane's slot of position pair 3 a
+__device__ __forceinline__ void f4_v_row_out(const float2 (&T)[6], float *vr, int vpp) {
+    const float2 e1 = f4_bt_part<1>(T[2], T[4]), o1 = f4_bt_part<1>(T[1], T[3]);
+    const float2 e2 = f4_bt_part<3>(T[2], T[4]), o2 = f4_bt_part<3>(T[1], T[3]);
+    const float2 v0 = f4_bt_end(T[0], T[2], T[4]), v1 = f4_bt_plus<1>(o1, e1), v2 = f4_bt_minus<1>(o1, e1);
+    const float2 v3 = f4_bt_plus<3>(o2, e2), v4 = f4_bt_minus<3>(o2, e2), v5 = f4_bt_end(T[1], T[3], T[5]);
+    *reinterpret_cast<float4 *>(vr + 0 * vpp) = make_float4(v0.x, v0.y, v1.x, v1.y);
+    *reinterpret_cast<float4 *>(vr + 1 * vpp) = make_float4(v2.x, v2.y, v3.x, v3.y);
+    *reinterpret_cast<float4 *>(vr + 2 * vpp) = make_float4(v4.x, v4.y, v5.x, v5.y);
+}
+// the three row groups a wave can take: rp = 0: rows 0 | 5, 1: rows 1 | 2, 2: rows 3 | 4 (k_conv3x3_wino4's split)
+template <class D>
+__device__ __forceinline__ void f4_transform_rp(int rp, const D &d, float *vb, int vpp) {
+    float2 Ta[6], Tb[6];
+    int a0, a1;
+    if (rp == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            Ta[c] = f4_bt_outer<0>(d, c);
+            Tb[c] = f4_bt_outer<5>(d, c);
+        }
+        a0 = 0; a1 = 5;
+    } else if (rp == 1) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) f4_bt_mid<1>(d, c, Ta[c], Tb[c]);
+        a0 = 1; a1 = 2;
+    } else {
+#pragma unroll
+        for (int c = 0; c < 6; c++) f4_bt_mid<3>(d, c, Ta[c], Tb[c]);
+        a0 = 3; a1 = 4;
+    }
+    f4_v_row_out(Ta, vb + a0 * 3 * vpp, vpp);
+    f4_v_row_out(Tb, vb + a1 * 3 * vpp, vpp);
+}
+// the two halves of the whole-image kernels: th = 0: rows {1, 2} + {0}, th = 1: rows {3, 4} + {5}
+template <class D>
+__device__ __forceinline__ void f4_transform_half(int th, const D &d, float *vb, int vpp) {
+    float2 Ta[6], Tb[6];
+    if (th == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; c++) f4_bt_mid<1>(d, c, Ta[c], Tb[c]);
+        f4_v_row_out(Ta, vb + 1 * 3 * vpp, vpp);
+        f4_v_row_out(Tb, vb + 2 * 3 * vpp, vpp);
+#pragma unroll
+        for (int c = 0; c < 6; c++) Ta[c] = f4_bt_outer<0>(d, c);
+        f4_v_row_out(Ta, vb + 0 * 3 * vpp, vpp);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 6; c++) f4_bt_mid<3>(d, c, Ta[c], Tb[c]);
+        f4_v_row_out(Ta, vb + 3 * 3 * vpp, vpp);
+        f4_v_row_out(Tb, vb + 4 * 3 * vpp, vpp);
+#pragma unroll
+        for (int c = 0; c < 6; c++) Tb[c] = f4_bt_outer<5>(d, c);
+        f4_v_row_out(Tb, vb + 5 * 3 * vpp, vpp);
+    }
+}
+
+// ---- one line of A^T m, and Y = A^T M A of tile r of a lane (M_pos in acc[pos][r]): 36 -> 16 values
+__device__ __forceinline__ void f4_at(float m0, float m1, float m2, float m3, float m4, float m5, float &y0, float &y1, float &y2, float &y3) {
+    const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
+    y0 = m0 + s12 + s34;
+    y1 = fmaf(PB, d34, PA * d12);
+    y2 = fmaf(PB2, s34, PA2 * s12);
+    y3 = fmaf(PB3, d34, PA3 * d12) + m5;
+}
+__device__ __forceinline__ void f4_out_tile(const floatx4 (&acc)[36], int r, float (&Yt)[16]) {
+    float Z[4][6];
+#pragma unroll
+    for (int b = 0; b < 6; b++)
+        f4_at(acc[0 * 6 + b][r], acc[1 * 6 + b][r], acc[2 * 6 + b][r], acc[3 * 6 + b][r], acc[4 * 6 + b][r], acc[5 * 6 + b][r], Z[0][b], Z[1][b],
+              Z[2][b], Z[3][b]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) f4_at(Z[i][0], Z[i][1], Z[i][2], Z[i][3], Z[i][4], Z[i][5], Yt[i * 4 + 0], Yt[i * 4 + 1], Yt[i * 4 + 2], Yt[i * 4 + 3]);
+}
+
+// ---- GroupNorm statistics of the epilogues: a lane's shifted sums over its N outputs of one channel (s1 = sum (v - K), s2 = sum (v - K)^2)
+// -> (mean, M2), then the four 16-lane groups of the wave merged in a fixed order (two Chan steps): every lane ends up with the 4 N values'
+template <int N>
+__device__ __forceinline__ void f4_stats_lane(float K, float s1, float s2, float &mean, float &M2) {
+    mean = K + s1 * (1.f / N);
+    M2 = fmaxf(s2 - s1 * s1 * (1.f / N), 0.f);
+}
+template <int N>
+__device__ __forceinline__ void f4_stats_merge(float K, float s1, float s2, int lane, float &mean, float &M2) {
+    f4_stats_lane<N>(K, s1, s2, mean, M2);
+    float na = (float)N;
+#pragma unroll
+    for (int sft = 16; sft <= 32; sft <<= 1) {
+        const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
+        const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
+        const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
+        const float dd = hi_m - lo_m;
+        mean = lo_m + dd * 0.5f;
+        M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
+        na *= 2.f;
+    }
+}
+
+// ---- the four MFMAs of a position pair (aa: A fragment {pos 2 pp: 2 channels, pos 2 pp + 1: 2 channels}, b: weight fragment {2 positions x
+// 2 k-steps}), and position pair pp of an 8-channel phase as the whole-image kernels run it: weight ring refilled F4_RING - 1 fragments
+// ahead (the kernel has put the first ones in flight), A fragment of the next pair read ahead (vpp floats further), the pair's MFMAs
+__device__ __forceinline__ void f4_mfma4(float4 aa, float4 b, floatx4 &acc0, floatx4 &acc1) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.x, b.x, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.z, b.z, acc1, 0, 0, 0);
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.y, b.y, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.w, b.w, acc1, 0, 0, 0);
+}
+__device__ __forceinline__ void f4_mfma_pair(int pp, const float *asrc, int vpp, const float4 *wp, int lane, float4 (&aq)[2], float4 (&bq)[F4_RING],
+                                             floatx4 (&acc)[36]) {
+    constexpr int AHEAD = F4_RING - 1;
+    if (pp == 0) aq[0] = *reinterpret_cast<const float4 *>(asrc);
+    if (pp + AHEAD < 18) bq[(pp + AHEAD) % F4_RING] = wp[(pp + AHEAD) * 64 + lane];
+    if (pp + 1 < 18) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(asrc + (pp + 1) * vpp);
+    f4_mfma4(aq[pp & 1], bq[pp % F4_RING], acc[2 * pp], acc[2 * pp + 1]);
+}
+
+// ---- staging: the activation of a staged channel quad, silu(x A + B), as its two steps (a launch may carry either alone), and the
+// item word of the whole-image kernels: LDS float offset (bits 0..13) | source pixel inside the image (bits 14..23) | padding (bit 24) |
+// no item (bit 25)
+__device__ __forceinline__ float4 f4_affine4(float4 x, float4 ca, float4 cb) {
+    return make_float4(fmaf(x.x, ca.x, cb.x), fmaf(x.y, ca.y, cb.y), fmaf(x.z, ca.z, cb.z), fmaf(x.w, ca.w, cb.w));
+}
+__device__ __forceinline__ float4 f4_silu4(float4 x) { return make_float4(silu_f(x.x), silu_f(x.y), silu_f(x.z), silu_f(x.w)); }
+__device__ __forceinline__ float4 f4_affine_silu4(float4 x, float4 ca, float4 cb) { return f4_silu4(f4_affine4(x, ca, cb)); }
+// halo pixel pix of a W x W image's (W + 2)-wide patch, prld floats per staged pixel, the item's channels ch .. ch + 3 of the chunk;
+// patch row ry starts 4 (ry >> 2) floats late (bank spread of the transform's reads)
+template <int W, int PRLD>
+__device__ __forceinline__ int f4_item_pack(int pix, int ch) {
+    constexpr int RW = W + 2;
+    const int ry = pix / RW, rx = pix - ry * RW;
+    const int iy = ry - 1, ix = rx - 1;
+    const bool pad = iy < 0 || iy >= W || ix < 0 || ix >= W;
+    const int lo = pix * PRLD + ch + 4 * (ry >> 2);
+    return pix >= RW * RW ? (1 << 25) : (lo | (pad ? (1 << 24) : ((iy * W + ix) << 14)));
+}
+__device__ __forceinline__ int f4_item_lds(int iv) { return iv & 16383; }
+__device__ __forceinline__ int f4_item_src(int iv) { return (iv >> 14) & 1023; }      // (padding / no item: pixel 0)
+__device__ __forceinline__ bool f4_item_pad(int iv) { return iv & (1 << 24); }        // zero padding applies AFTER the activation
+__device__ __forceinline__ bool f4_item_none(int iv) { return iv & (1 << 25); }
+// =====================================================================================================================================
 
 // QN: staging items per thread (2 for halo patches of <= 512 pixels -- every block shape but 16 whole 4x4 images; round 4: the third
 // item's geometry registers and its dead branch per phase pushed the main instantiation into a scratch reload inside the loop)
@@ -220,17 +401,9 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
         if (has_coef) {
             const float4 ca = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16));
             const float4 cb = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16) + F4_KC);
-            x.x = fmaf(x.x, ca.x, cb.x);
-            x.y = fmaf(x.y, ca.y, cb.y);
-            x.z = fmaf(x.z, ca.z, cb.z);
-            x.w = fmaf(x.w, ca.w, cb.w);
+            x = f4_affine4(x, ca, cb);
         }
-        if (p.act_silu) {
-            x.x = silu_f(x.x);
-            x.y = silu_f(x.y);
-            x.z = silu_f(x.z);
-            x.w = silu_f(x.w);
-        }
+        if (p.act_silu) x = f4_silu4(x);
         if (off[it] < 0) x = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding applies AFTER the activation
         *reinterpret_cast<float4 *>(rb + (lo[it] & 0xffff)) = x;
     };
@@ -250,53 +423,7 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
         vofs = (pair * F4_TILES + tile) * 4;
     }
     auto transform_rp = [&](int slot, int rp) {
-        const float *rb = raw + slot * F4_RAWBUF + rbase;
-        float *vb = V + slot * F4_VBUF + vofs;
-        // d(i, c): sample row i, column c of this tile's 6x6 patch (upsampled: source row (i + 1) >> 1 of the 4x4 source patch);
-        // rows 4 and 5 of the patch lie in the next skew group
-        auto d = [&](int i, int c) {
-            const int ri = UPS ? (i + 1) >> 1 : i, ci = UPS ? (c + 1) >> 1 : c;
-            return *reinterpret_cast<const float2 *>(rb + (ri * RW + ci) * F4_PRLD + ((skewed && i >= 4) ? 4 : 0));
-        };
-        float2 Ta[6], Tb[6];
-        int a0, a1;
-        if (rp == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                Ta[c] = f2fma(PP2, d(0, c), f2fma(-PS2, d(2, c), d(4, c)));
-                Tb[c] = f2fma(PP2, d(1, c), f2fma(-PS2, d(3, c), d(5, c)));
-            }
-            a0 = 0; a1 = 5;
-        } else if (rp == 1) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PB2, d(2, c), d(4, c)), o = f2fma(-PB2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PA, o, e);
-                Tb[c] = f2fma(-PA, o, e);
-            }
-            a0 = 1; a1 = 2;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PA2, d(2, c), d(4, c)), o = f2fma(-PA2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PB, o, e);
-                Tb[c] = f2fma(-PB, o, e);
-            }
-            a0 = 3; a1 = 4;
-        }
-        // positions (a, 0..5) of row a = position pairs 3 a .. 3 a + 2: one float4 {pos 2 pp: 2 channels, pos 2 pp + 1: 2 channels} each
-        auto row_out = [&](const float2 (&T)[6], int a) {
-            float *vr = vb + a * 3 * (4 * F4_TILES * 4);
-            const float2 e1 = f2fma(-PB2, T[2], T[4]), o1 = f2fma(-PB2, T[1], T[3]);
-            const float2 e2 = f2fma(-PA2, T[2], T[4]), o2 = f2fma(-PA2, T[1], T[3]);
-            const float2 v0 = f2fma(PP2, T[0], f2fma(-PS2, T[2], T[4])), v1 = f2fma(PA, o1, e1), v2 = f2fma(-PA, o1, e1);
-            const float2 v3 = f2fma(PB, o2, e2), v4 = f2fma(-PB, o2, e2), v5 = f2fma(PP2, T[1], f2fma(-PS2, T[3], T[5]));
-            *reinterpret_cast<float4 *>(vr + 0 * (4 * F4_TILES * 4)) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            *reinterpret_cast<float4 *>(vr + 1 * (4 * F4_TILES * 4)) = make_float4(v2.x, v2.y, v3.x, v3.y);
-            *reinterpret_cast<float4 *>(vr + 2 * (4 * F4_TILES * 4)) = make_float4(v4.x, v4.y, v5.x, v5.y);
-        };
-        row_out(Ta, a0);
-        row_out(Tb, a1);
+        f4_transform_rp(rp, F4Patch<UPS, F4_PRLD>{raw + slot * F4_RAWBUF + rbase, RW, skewed}, V + slot * F4_VBUF + vofs, 4 * F4_TILES * 4);
     };
     auto transform = [&](int slot) {
         if (HELP) {
@@ -343,7 +470,7 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
     }
     if (mfma_wave) {
 #pragma unroll
-        for (int a = 0; a < AHEAD; a++) bq[a] = wp[a * 64 + lane];
+        for (int a = 0; a < F4_RING - 1; a++) bq[a] = wp[a * 64 + lane];
     }
     store_coef(0);
     cfr = cfr1;
@@ -387,17 +514,11 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
             // front of its MFMAs with an s_waitcnt lgkmcnt(0) between them)
             if (pp + F4_AAHEAD < 18)
                 aq[(pp + F4_AAHEAD) % (F4_AAHEAD + 1)] = *reinterpret_cast<const float4 *>(ab + (pp + F4_AAHEAD) * (4 * F4_TILES * 4));
-            const float4 aa = aq[pp % (F4_AAHEAD + 1)];
-            const float2 a0 = make_float2(aa.x, aa.y), a1 = make_float2(aa.z, aa.w);
-            const float4 b = bq[pp % F4_RING];
             // wave priority: everything that is not an MFMA (operand fetch, staging, transform) issues at priority 1, the
             // MFMAs at 0 -- when both waves of a SIMD are ready, the one with side work goes first and the other's MFMAs
             // fill the pipe behind it.  Measured 45.6 -> 43.9 ms/step (the opposite assignment: 44.4)
             if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b.x, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b.z, acc[2 * pp + 1], 0, 0, 0);
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b.y, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b.w, acc[2 * pp + 1], 0, 0, 0);
+            f4_mfma4(aq[pp % (F4_AAHEAD + 1)], bq[pp % F4_RING], acc[2 * pp], acc[2 * pp + 1]);
             if (F4_PRIO) __builtin_amdgcn_s_setprio(1);
         }
         }
@@ -473,25 +594,7 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
                     rs[i * 4 + j] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + (i * W + j) * res_ld) + bo_r);
         }
         float Yt[16];
-        float Z[4][6];
-#pragma unroll
-        for (int b = 0; b < 6; b++) {
-            const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-            const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            Z[0][b] = m0 + s12 + s34;
-            Z[1][b] = fmaf(PB, d34, PA * d12);
-            Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-            Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-            Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
-            Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-            Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-            Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-        }
+        f4_out_tile(acc, r, Yt);
         if (!ok) continue;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -511,20 +614,14 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
         }
     }
     if (img_stats) {
-        if (img0 + lk < p.B)
-            p.stats_out[(int64_t)(img0 + lk) * p.Cout + ch] = make_float2(K + s1 * (1.f / 64.f), fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f));
-    } else if (do_stats) {
-        float mean = K + s1 * (1.f / 64.f), M2 = fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f), na = 64.f;
-#pragma unroll
-        for (int sft = 16; sft <= 32; sft <<= 1) {
-            const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
-            const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
-            const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
-            const float dd = hi_m - lo_m;
-            mean = lo_m + dd * 0.5f;
-            M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
-            na *= 2.f;
+        if (img0 + lk < p.B) {
+            float mean, M2;
+            f4_stats_lane<64>(K, s1, s2, mean, M2);
+            p.stats_out[(int64_t)(img0 + lk) * p.Cout + ch] = make_float2(mean, M2);
         }
+    } else if (do_stats) {
+        float mean, M2;
+        f4_stats_merge<64>(K, s1, s2, lane, mean, M2);
         if (lk == 0) p.stats_out[((int64_t)img0 * ((H * W) / 256) + blk_in_img) * p.Cout + ch] = make_float2(mean, M2);
     }
     DLPM_PHASE(p, 10);
@@ -555,8 +652,10 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
 //     barrier;  MFMAs(c) with the global loads of chunk c+1 in flight, then activate + store raw(c+1);  barrier.  V and raw are single
 //     buffers (73.7 + 55.7 KB); the barriers order LDS only, so the read-ahead stays in flight across them;
 //   * the halo is the image's own border: 1156 staged pixels per 1024 outputs (the 16-tile blocks stage 1296), every element activated once;
-//   * SAME arithmetic per output as the 2 + 2-wave shape -- same staged values, same transform expressions, same k order per accumulator,
-//     same register epilogue and the same four 256-pixel statistics partials per image -- so the results are bit-identical to it
+//   * SAME arithmetic per output as the 2 + 2-wave shape: the staged values (f4_affine4, f4_silu4), the transform (f4_transform_half: the
+//     rows f4_transform_rp takes, from the same f4_bt_* / f4_v_row_out), the MFMAs (f4_mfma4) in the same k order per accumulator, the output
+//     transform (f4_out_tile) and the four 256-pixel statistics partials per image (f4_stats_merge<64>) are the functions that kernel calls,
+//     the rest of the register epilogue is written as there -- so the results are bit-identical to it
 //     (tests/test_gpu_kernels.py::test_conv_winograd_f4_whole_image_is_bit_identical) and the weights are its fragment stream
 //     Wf[ntile][wave < 2][phase][18][lane][4], here read by the four M-block waves of a channel half.
 constexpr int FI_TILES = 64, FI_RW = 34, FI_NPIX = FI_RW * FI_RW, FI_NT = 512;
@@ -591,18 +690,11 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
     const bool has_coef = p.coefA != nullptr;
 
     // ---- raw staging: item = (halo pixel, channel quad of the chunk), 5 per thread
-    // One register per item: LDS float offset (bits 0..13) | source pixel inside the image (bits 14..23) | padding (bit 24) | no item (bit 25)
+    // One register per item (f4_item_pack)
     const int squad = tid & 1;
     int itm[FI_QN];
 #pragma unroll
-    for (int it = 0; it < FI_QN; it++) {
-        const int pix = it * (FI_NT / 2) + (tid >> 1);
-        const int ry = pix / FI_RW, rx = pix - ry * FI_RW;
-        const int iy = ry - 1, ix = rx - 1;
-        const bool pad = iy < 0 || iy >= H || ix < 0 || ix >= W;
-        const int lo = pix * F4_PRLD + squad * 4 + 4 * (ry >> 2);      // patch row ry starts 4 (ry >> 2) floats late (bank spread of the transform's reads)
-        itm[it] = pix >= FI_NPIX ? (1 << 25) : (lo | (pad ? (1 << 24) : ((iy * W + ix) << 14)));
-    }
+    for (int it = 0; it < FI_QN; it++) itm[it] = f4_item_pack<W, F4_PRLD>(it * (FI_NT / 2) + (tid >> 1), squad * 4);
     float4 xr[FI_QN];
     auto load_raw = [&](int chunk) {
         const int c = chunk * F4_KC + squad * 4;
@@ -610,7 +702,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
         const int ld = first ? p.C0 : p.C1;
         const float *sb = (first ? p.src0 + c : p.src1 + (c - p.C0)) + (int64_t)img * (H * W) * ld;
 #pragma unroll
-        for (int it = 0; it < FI_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + ((itm[it] >> 14) & 1023) * ld);   // (padding / no item: pixel 0)
+        for (int it = 0; it < FI_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + f4_item_src(itm[it]) * ld);
     };
     auto store_raw = [&](int chunk) {
         const int c = chunk * F4_KC + squad * 4;
@@ -623,22 +715,12 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
         for (int it = 0; it < FI_QN; it++) {
             int iv = itm[it];
             asm volatile("" : "+v"(iv));     // (opaque: hoisted out of the chunk loop, the five LDS addresses and padding masks cost registers the loop does not have)
-            if (iv & (1 << 25)) continue;
+            if (f4_item_none(iv)) continue;
             float4 x = xr[it];
-            if (has_coef) {
-                x.x = fmaf(x.x, ca.x, cb.x);
-                x.y = fmaf(x.y, ca.y, cb.y);
-                x.z = fmaf(x.z, ca.z, cb.z);
-                x.w = fmaf(x.w, ca.w, cb.w);
-            }
-            if (p.act_silu) {
-                x.x = silu_f(x.x);
-                x.y = silu_f(x.y);
-                x.z = silu_f(x.z);
-                x.w = silu_f(x.w);
-            }
-            if (iv & (1 << 24)) x = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding applies AFTER the activation
-            *reinterpret_cast<float4 *>(raw + (iv & 16383)) = x;
+            if (has_coef) x = f4_affine4(x, ca, cb);
+            if (p.act_silu) x = f4_silu4(x);
+            if (f4_item_pad(iv)) x = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(raw + f4_item_lds(iv)) = x;
         }
     };
 
@@ -652,53 +734,10 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
         vofs = (pair * FI_TILES + 16 * tg + tile) * 4;
     }
     const int th = wave >> 2;
-    auto transform = [&]() {
-        const float *rb = raw + rbase;
-        float *vb = V + vofs;
-        auto d = [&](int i, int c) {      // sample row i, column c of this tile's 6x6 patch; rows 4 and 5 lie in the next skew group
-            return *reinterpret_cast<const float2 *>(rb + (i * FI_RW + c) * F4_PRLD + (i >= 4 ? 4 : 0));
-        };
-        auto row_out = [&](const float2 (&T)[6], int a) {
-            float *vr = vb + a * 3 * FI_VPP;
-            const float2 e1 = f2fma(-PB2, T[2], T[4]), o1 = f2fma(-PB2, T[1], T[3]);
-            const float2 e2 = f2fma(-PA2, T[2], T[4]), o2 = f2fma(-PA2, T[1], T[3]);
-            const float2 v0 = f2fma(PP2, T[0], f2fma(-PS2, T[2], T[4])), v1 = f2fma(PA, o1, e1), v2 = f2fma(-PA, o1, e1);
-            const float2 v3 = f2fma(PB, o2, e2), v4 = f2fma(-PB, o2, e2), v5 = f2fma(PP2, T[1], f2fma(-PS2, T[3], T[5]));
-            *reinterpret_cast<float4 *>(vr + 0 * FI_VPP) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            *reinterpret_cast<float4 *>(vr + 1 * FI_VPP) = make_float4(v2.x, v2.y, v3.x, v3.y);
-            *reinterpret_cast<float4 *>(vr + 2 * FI_VPP) = make_float4(v4.x, v4.y, v5.x, v5.y);
-        };
-        float2 Ta[6], Tb[6];
-        if (th == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PB2, d(2, c), d(4, c)), o = f2fma(-PB2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PA, o, e);
-                Tb[c] = f2fma(-PA, o, e);
-            }
-            row_out(Ta, 1);
-            row_out(Tb, 2);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Ta[c] = f2fma(PP2, d(0, c), f2fma(-PS2, d(2, c), d(4, c)));
-            row_out(Ta, 0);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PA2, d(2, c), d(4, c)), o = f2fma(-PA2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PB, o, e);
-                Tb[c] = f2fma(-PB, o, e);
-            }
-            row_out(Ta, 3);
-            row_out(Tb, 4);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Tb[c] = f2fma(PP2, d(1, c), f2fma(-PS2, d(3, c), d(5, c)));
-            row_out(Tb, 5);
-        }
-    };
+    auto transform = [&]() { f4_transform_half(th, F4Patch<false, F4_PRLD>{raw + rbase, FI_RW, true}, V + vofs, FI_VPP); };
 
     // ---- weight stream of this wave's channel half (the 2 + 2-wave shape's Wf[ntile 0][wave nw][phase][18][lane][4]) and its A fragments
     const float4 *__restrict__ wp = reinterpret_cast<const float4 *>(p.w_wino4) + (int64_t)nw * nch * 18 * 64;
-    constexpr int AHEAD = F4_RING - 1;
     float4 bq[F4_RING];
     const float *asrc = V + (lk * FI_TILES + 16 * mb + li) * 4;
     floatx4 acc[36];
@@ -723,29 +762,19 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
         // (the weight ring is refilled per chunk, BEHIND the transform: kept across it, its 20 registers beside the 36 accumulators
         //  and the transform's patch rows were scratch memory; the fragments are L2-resident and land during the barrier)
 #pragma unroll
-        for (int a = 0; a < AHEAD; a++) bq[a] = wp[a * 64 + lane];
+        for (int a = 0; a < F4_RING - 1; a++) bq[a] = wp[a * 64 + lane];
         load_raw(min(chunk + 1, last));                // in flight across the barrier and the MFMAs
         F4_LDS_BARRIER();                              // V complete, raw free
         float4 aq[2];
-        aq[0] = *reinterpret_cast<const float4 *>(asrc);
 #pragma unroll
-        for (int pp = 0; pp < 18; pp++) {
-            if (pp + AHEAD < 18) bq[(pp + AHEAD) % F4_RING] = wp[(pp + AHEAD) * 64 + lane];
-            if (pp + 1 < 18) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(asrc + (pp + 1) * FI_VPP);
-            const float4 aa = aq[pp & 1];
-            const float4 b = bq[pp % F4_RING];
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.x, b.x, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.z, b.z, acc[2 * pp + 1], 0, 0, 0);
-            acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.y, b.y, acc[2 * pp], 0, 0, 0);
-            acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.w, b.w, acc[2 * pp + 1], 0, 0, 0);
-        }
+        for (int pp = 0; pp < 18; pp++) f4_mfma_pair(pp, asrc, FI_VPP, wp, lane, aq, bq, acc);
         wp += 18 * 64;
         if (chunk < last) store_raw(chunk + 1);
         F4_LDS_BARRIER();                              // raw(chunk + 1) complete, V free
     }
     DLPM_PHASE(p, 9);
 
-    // ---- epilogue from registers (the 2 + 2-wave shape's: lane = channel, 4 tiles x 16 pixels; all four tiles' residual values are
+    // ---- epilogue from registers (the 2 + 2-wave shape's, f4_out_tile and f4_stats_merge: lane = channel, 4 tiles x 16 pixels; all four tiles' residual values are
     // requested before the first output transform; statistics = one partial per 256-pixel quadrant)
     {
         const int ty0 = 4 * (mb >> 1), tx0 = 4 * (mb & 1);
@@ -778,25 +807,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
             const int tpix = (4 * (tile >> 2)) * W + 4 * (tile & 3);
             const uint32_t bo_o = (uint32_t)(tpix * p.Cout + ch) * 4u;
             float Yt[16];
-            float Z[4][6];
-#pragma unroll
-            for (int b = 0; b < 6; b++) {
-                const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-                const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-                const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                Z[0][b] = m0 + s12 + s34;
-                Z[1][b] = fmaf(PB, d34, PA * d12);
-                Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-                Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-                Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
-                Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-                Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-                Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-            }
+            f4_out_tile(acc, r, Yt);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
 #pragma unroll
@@ -814,17 +825,8 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
             }
         }
         if (do_stats) {
-            float mean = K + s1 * (1.f / 64.f), M2 = fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f), na = 64.f;
-#pragma unroll
-            for (int sft = 16; sft <= 32; sft <<= 1) {
-                const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
-                const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
-                const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
-                const float dd = hi_m - lo_m;
-                mean = lo_m + dd * 0.5f;
-                M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
-                na *= 2.f;
-            }
+            float mean, M2;
+            f4_stats_merge<64>(K, s1, s2, lane, mean, M2);
             if (lk == 0) p.stats_out[((int64_t)img * 4 + mb) * p.Cout + ch] = make_float2(mean, M2);
         }
     }
@@ -848,8 +850,9 @@ __global__ void __launch_bounds__(FI_NT, 1) k_conv3x3_wino4_img(ConvLaunch p) {
 // registers and writes them ONCE, activated, to a scratch image that the second pass stages like any input (no coefficients, no SiLU
 // there: a plain copy with zero padding).  That image is 128 KB per workgroup and is read back by the CU that wrote it: an L2 round
 // trip.  GroupNorm-1's coefficients come from the producers' statistics inside the prologue (same function) when they exist.
-// Every value is computed by the expressions of the separate launches (conv -> k_gn_coeffs_stats -> conv), so the block's output
-// and its statistics partials are bit-identical to that path (tests/test_gpu_kernels.py::test_resblock_whole_image_*).
+// Every value is computed by the functions of the separate launches (conv: the shared building blocks above, as k_conv3x3_wino4_img calls
+// them; k_gn_coeffs_stats: gn_stats.h), so the block's output and its statistics partials are bit-identical to that path
+// (tests/test_gpu_kernels.py::test_resblock_whole_image_*).
 __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p) {
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float *V = wsm;                      // [18 position pairs][4 channel pairs][64 tiles][2 pos x 2 ch]
@@ -868,14 +871,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
 
     const int squad = tid & 1;
 #pragma unroll
-    for (int it = 0; it < FI_QN; it++) {
-        const int pix = it * (FI_NT / 2) + (tid >> 1);
-        const int ry = pix / FI_RW, rx = pix - ry * FI_RW;
-        const int iy = ry - 1, ix = rx - 1;
-        const bool pad = iy < 0 || iy >= H || ix < 0 || ix >= W;
-        const int lo = pix * F4_PRLD + squad * 4 + 4 * (ry >> 2);
-        itmL[it * FI_NT + tid] = pix >= FI_NPIX ? (1 << 25) : (lo | (pad ? (1 << 24) : ((iy * W + ix) << 14)));   // (read back by this thread only)
-    }
+    for (int it = 0; it < FI_QN; it++) itmL[it * FI_NT + tid] = f4_item_pack<W, F4_PRLD>(it * (FI_NT / 2) + (tid >> 1), squad * 4);   // (read back by this thread only)
     // ---- the source of the pass in flight (pass 1: x0 | x1 with GroupNorm-1 + SiLU; pass 2: the activated scratch image, plain)
     const float *s0 = p.x0, *s1 = p.x1;
     int c0 = p.C0, c1 = p.C1;
@@ -886,7 +882,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
         const int ld = first ? c0 : c1;
         const float *sb = (first ? s0 + c : s1 + (c - c0)) + (int64_t)img * (H * W) * ld;
 #pragma unroll
-        for (int it = 0; it < FI_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + ((itmL[it * FI_NT + tid] >> 14) & 1023) * ld);
+        for (int it = 0; it < FI_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + f4_item_src(itmL[it * FI_NT + tid]) * ld);
     };
     auto store_raw = [&](int chunk, auto act_c) {
         constexpr bool ACT = decltype(act_c)::value;      // pass 1: x A + B, SiLU; pass 2: plain copy
@@ -899,16 +895,11 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
 #pragma unroll
         for (int it = 0; it < FI_QN; it++) {
             const int iv = itmL[it * FI_NT + tid];
-            if (iv & (1 << 25)) continue;
+            if (f4_item_none(iv)) continue;
             float4 x = xr[it];
-            if (ACT) {
-                x.x = silu_f(fmaf(x.x, ca.x, cb.x));
-                x.y = silu_f(fmaf(x.y, ca.y, cb.y));
-                x.z = silu_f(fmaf(x.z, ca.z, cb.z));
-                x.w = silu_f(fmaf(x.w, ca.w, cb.w));
-            }
-            if (iv & (1 << 24)) x = make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4 *>(raw + (iv & 16383)) = x;
+            if (ACT) x = f4_affine_silu4(x, ca, cb);
+            if (f4_item_pad(iv)) x = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(raw + f4_item_lds(iv)) = x;
         }
     };
     int rbase, vofs;
@@ -919,50 +910,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
         vofs = (pair * FI_TILES + 16 * tg + tile) * 4;
     }
     const int th = wave >> 2;
-    auto transform = [&]() {
-        const float *rb = raw + rbase;
-        float *vb = V + vofs;
-        auto d = [&](int i, int c) {
-            return *reinterpret_cast<const float2 *>(rb + (i * FI_RW + c) * F4_PRLD + (i >= 4 ? 4 : 0));
-        };
-        auto row_out = [&](const float2 (&T)[6], int a) {
-            float *vr = vb + a * 3 * FI_VPP;
-            const float2 e1 = f2fma(-PB2, T[2], T[4]), o1 = f2fma(-PB2, T[1], T[3]);
-            const float2 e2 = f2fma(-PA2, T[2], T[4]), o2 = f2fma(-PA2, T[1], T[3]);
-            const float2 v0 = f2fma(PP2, T[0], f2fma(-PS2, T[2], T[4])), v1 = f2fma(PA, o1, e1), v2 = f2fma(-PA, o1, e1);
-            const float2 v3 = f2fma(PB, o2, e2), v4 = f2fma(-PB, o2, e2), v5 = f2fma(PP2, T[1], f2fma(-PS2, T[3], T[5]));
-            *reinterpret_cast<float4 *>(vr + 0 * FI_VPP) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            *reinterpret_cast<float4 *>(vr + 1 * FI_VPP) = make_float4(v2.x, v2.y, v3.x, v3.y);
-            *reinterpret_cast<float4 *>(vr + 2 * FI_VPP) = make_float4(v4.x, v4.y, v5.x, v5.y);
-        };
-        float2 Ta[6], Tb[6];
-        if (th == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PB2, d(2, c), d(4, c)), o = f2fma(-PB2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PA, o, e);
-                Tb[c] = f2fma(-PA, o, e);
-            }
-            row_out(Ta, 1);
-            row_out(Tb, 2);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Ta[c] = f2fma(PP2, d(0, c), f2fma(-PS2, d(2, c), d(4, c)));
-            row_out(Ta, 0);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PA2, d(2, c), d(4, c)), o = f2fma(-PA2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PB, o, e);
-                Tb[c] = f2fma(-PB, o, e);
-            }
-            row_out(Ta, 3);
-            row_out(Tb, 4);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Tb[c] = f2fma(PP2, d(1, c), f2fma(-PS2, d(3, c), d(5, c)));
-            row_out(Tb, 5);
-        }
-    };
-    constexpr int AHEAD = F4_RING - 1;
+    auto transform = [&]() { f4_transform_half(th, F4Patch<false, F4_PRLD>{raw + rbase, FI_RW, true}, V + vofs, FI_VPP); };
     const float *asrc = V + (lk * FI_TILES + 16 * mb + li) * 4;
     floatx4 acc[36];
     // one convolution: chunk 0 is in xr on entry (load_raw(0) issued by the caller); acc is zeroed here
@@ -980,63 +928,15 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
         for (int chunk = 0; chunk < nch; chunk++) {
             transform();
 #pragma unroll
-            for (int a = 0; a < AHEAD; a++) bq[a] = wp[a * 64 + lane];
+            for (int a = 0; a < F4_RING - 1; a++) bq[a] = wp[a * 64 + lane];
             load_raw(min(chunk + 1, last));
             F4_LDS_BARRIER();
             float4 aq[2];
-            aq[0] = *reinterpret_cast<const float4 *>(asrc);
 #pragma unroll
-            for (int pp = 0; pp < 18; pp++) {
-                if (pp + AHEAD < 18) bq[(pp + AHEAD) % F4_RING] = wp[(pp + AHEAD) * 64 + lane];
-                if (pp + 1 < 18) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(asrc + (pp + 1) * FI_VPP);
-                const float4 aa = aq[pp & 1];
-                const float4 b = bq[pp % F4_RING];
-                acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.x, b.x, acc[2 * pp], 0, 0, 0);
-                acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.z, b.z, acc[2 * pp + 1], 0, 0, 0);
-                acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.y, b.y, acc[2 * pp], 0, 0, 0);
-                acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.w, b.w, acc[2 * pp + 1], 0, 0, 0);
-            }
+            for (int pp = 0; pp < 18; pp++) f4_mfma_pair(pp, asrc, FI_VPP, wp, lane, aq, bq, acc);
             wp += 18 * 64;
             if (chunk < last) store_raw(chunk + 1, act_c);
             F4_LDS_BARRIER();
-        }
-    };
-    // Y = A^T M A of tile r of this lane (the 2 + 2-wave shape's expressions)
-    auto out_tile = [&](int r, float (&Yt)[16]) {
-        float Z[4][6];
-#pragma unroll
-        for (int b = 0; b < 6; b++) {
-            const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-            const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            Z[0][b] = m0 + s12 + s34;
-            Z[1][b] = fmaf(PB, d34, PA * d12);
-            Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-            Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-            Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
-            Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-            Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-            Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-        }
-    };
-    // the quadrant's statistics partial from the per-lane shifted sums (the convolution kernels' epilogue): lanes lk == 0 hold it
-    auto quadrant_stats = [&](float K, float s1, float s2, float &mean, float &M2) {
-        mean = K + s1 * (1.f / 64.f);
-        M2 = fmaxf(s2 - s1 * s1 * (1.f / 64.f), 0.f);
-        float na = 64.f;
-#pragma unroll
-        for (int sft = 16; sft <= 32; sft <<= 1) {
-            const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
-            const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
-            const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
-            const float dd = hi_m - lo_m;
-            mean = lo_m + dd * 0.5f;
-            M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
-            na *= 2.f;
         }
     };
     const int ty0 = 4 * (mb >> 1), tx0 = 4 * (mb & 1);
@@ -1069,7 +969,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             float Yt[16];
-            out_tile(r, Yt);
+            f4_out_tile(acc, r, Yt);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const float v = Yt[k] + bias_v;
@@ -1081,7 +981,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
             }
         }
         float mean, M2;
-        quadrant_stats(K, s1, s2, mean, M2);
+        f4_stats_merge<64>(K, s1, s2, lane, mean, M2);      // the quadrant's partial: lanes lk == 0 hold it
         if (lk == 0) part[mb * CO + chv] = make_float2(mean, M2);
         F4_LDS_BARRIER();
         gn_coeffs_from_stats_image(part, nullptr, CO, 0, 4, 1, H * W, 32, p.gn2_w, p.gn2_b, p.emb + (int64_t)img * p.emb_stride + p.emb_off, gsh, Cf,
@@ -1131,7 +1031,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
             const int tpix = (4 * (tile >> 2)) * W + 4 * (tile & 3);
             if (r + 1 < 4) load_res(r + 1, rs[(r + 1) & 1]);
             float Yt[16];
-            out_tile(r, Yt);
+            f4_out_tile(acc, r, Yt);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 float v = Yt[k] + bias_v;
@@ -1147,7 +1047,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
         }
         if (do_stats) {
             float mean, M2;
-            quadrant_stats(K, s1, s2, mean, M2);
+            f4_stats_merge<64>(K, s1, s2, lane, mean, M2);      // the quadrant's partial: lanes lk == 0 hold it
             if (lkv == 0) p.stats_out[((int64_t)img * 4 + mb) * CO + chv] = make_float2(mean, M2);
         }
     }
@@ -1166,7 +1066,8 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img(ResImgLaunch p)
 // partner the two tiles the partner finalises and keeps the other two, so the output transform, the GroupNorm statistics and the
 // epilogue run on all eight waves.  Per chunk: waves 0..3 transform (two row groups x two channel-pair groups), barrier, every wave
 // its 72 MFMAs with the next chunk's loads in flight, staging, barrier.  The intermediate h never leaves the CU: activated, it goes
-// to an LDS image [256][68] from which pass 2 stages its chunks (LDS -> LDS, zero padding applied there).  The sums of the two K halves
+// to an LDS image [256][68] from which pass 2 stages its chunks (LDS -> LDS, zero padding applied there).  Staging, transform, MFMAs,
+// output transform and statistics merge (f4_stats_merge<32>: a lane holds 32 outputs) are the shared building blocks.  The sums of the two K halves
 // are added once per output, so this kernel rounds differently from the 4 + 3-wave launches it replaces (5e-6 of the reference's
 // ResBlock, tests/golden/f14_blocks16.npz; bits independent of the batch: an image is a workgroup).
 constexpr int F6_TILES = 16, F6_RW = 18, F6_NPIX = F6_RW * F6_RW, F6_KC = 16, F6_PRLD = F6_KC + 4;
@@ -1199,12 +1100,8 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
     // staging item e = it * 512 + tid: (halo pixel e >> 2, channel quad e & 3 of the 16-channel chunk)
 #pragma unroll
     for (int it = 0; it < F6_QN; it++) {
-        const int e = it * FI_NT + tid, pix = e >> 2, quad = e & 3;
-        const int ry = pix / F6_RW, rx = pix - ry * F6_RW;
-        const int iy = ry - 1, ix = rx - 1;
-        const bool pad = iy < 0 || iy >= H || ix < 0 || ix >= W;
-        const int lo = pix * F6_PRLD + quad * 4 + 4 * (ry >> 2);
-        itmL[it * FI_NT + tid] = pix >= F6_NPIX ? (1 << 25) : (lo | (pad ? (1 << 24) : ((iy * W + ix) << 14)));
+        const int e = it * FI_NT + tid;
+        itmL[it * FI_NT + tid] = f4_item_pack<W, F6_PRLD>(e >> 2, (e & 3) * 4);
     }
     const int quad = tid & 3;
     const float *s0 = p.x0, *s1 = p.x1;
@@ -1216,7 +1113,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
         const int ld = first ? c0 : c1;
         const float *sb = (first ? s0 + c : s1 + (c - c0)) + (int64_t)img * (H * W) * ld;
 #pragma unroll
-        for (int it = 0; it < F6_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + ((itmL[it * FI_NT + tid] >> 14) & 255) * ld);
+        for (int it = 0; it < F6_QN; it++) xr[it] = *reinterpret_cast<const float4 *>(sb + f4_item_src(itmL[it * FI_NT + tid]) * ld);
     };
     auto store_raw = [&](int chunk, auto first_pass) __attribute__((always_inline)) {
         constexpr bool P1 = decltype(first_pass)::value;   // pass 1: x A + B, SiLU from registers; pass 2: copy from the LDS image
@@ -1229,19 +1126,12 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
 #pragma unroll
         for (int it = 0; it < F6_QN; it++) {
             const int iv = itmL[it * FI_NT + tid];
-            if (iv & (1 << 25)) continue;
+            if (f4_item_none(iv)) continue;
             float4 x;
-            if (P1) {
-                x = xr[it];
-                x.x = silu_f(fmaf(x.x, ca.x, cb.x));
-                x.y = silu_f(fmaf(x.y, ca.y, cb.y));
-                x.z = silu_f(fmaf(x.z, ca.z, cb.z));
-                x.w = silu_f(fmaf(x.w, ca.w, cb.w));
-            } else {
-                x = *reinterpret_cast<const float4 *>(hL + ((iv >> 14) & 255) * F6_HLD + c);
-            }
-            if (iv & (1 << 24)) x = make_float4(0.f, 0.f, 0.f, 0.f);
-            *reinterpret_cast<float4 *>(raw + (iv & 16383)) = x;
+            if (P1) x = f4_affine_silu4(xr[it], ca, cb);
+            else x = *reinterpret_cast<const float4 *>(hL + f4_item_src(iv) * F6_HLD + c);
+            if (f4_item_pad(iv)) x = make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(raw + f4_item_lds(iv)) = x;
         }
     };
     // input transform: wave w < 4 = (row group th = w & 1, channel-pair group cp = w >> 1); lane = (pair of the group, tile)
@@ -1253,50 +1143,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
         vofs = (pair * F6_TILES + tile) * 4;
     }
     const int th = wave & 1;
-    auto transform = [&]() __attribute__((always_inline)) {
-        const float *rb = raw + rbase;
-        float *vb = V + vofs;
-        auto d = [&](int i, int c) {
-            return *reinterpret_cast<const float2 *>(rb + (i * F6_RW + c) * F6_PRLD + (i >= 4 ? 4 : 0));
-        };
-        auto row_out = [&](const float2 (&T)[6], int a) {
-            float *vr = vb + a * 3 * F6_VPP;
-            const float2 e1 = f2fma(-PB2, T[2], T[4]), o1 = f2fma(-PB2, T[1], T[3]);
-            const float2 e2 = f2fma(-PA2, T[2], T[4]), o2 = f2fma(-PA2, T[1], T[3]);
-            const float2 v0 = f2fma(PP2, T[0], f2fma(-PS2, T[2], T[4])), v1 = f2fma(PA, o1, e1), v2 = f2fma(-PA, o1, e1);
-            const float2 v3 = f2fma(PB, o2, e2), v4 = f2fma(-PB, o2, e2), v5 = f2fma(PP2, T[1], f2fma(-PS2, T[3], T[5]));
-            *reinterpret_cast<float4 *>(vr + 0 * F6_VPP) = make_float4(v0.x, v0.y, v1.x, v1.y);
-            *reinterpret_cast<float4 *>(vr + 1 * F6_VPP) = make_float4(v2.x, v2.y, v3.x, v3.y);
-            *reinterpret_cast<float4 *>(vr + 2 * F6_VPP) = make_float4(v4.x, v4.y, v5.x, v5.y);
-        };
-        float2 Ta[6], Tb[6];
-        if (th == 0) {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PB2, d(2, c), d(4, c)), o = f2fma(-PB2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PA, o, e);
-                Tb[c] = f2fma(-PA, o, e);
-            }
-            row_out(Ta, 1);
-            row_out(Tb, 2);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Ta[c] = f2fma(PP2, d(0, c), f2fma(-PS2, d(2, c), d(4, c)));
-            row_out(Ta, 0);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                const float2 e = f2fma(-PA2, d(2, c), d(4, c)), o = f2fma(-PA2, d(1, c), d(3, c));
-                Ta[c] = f2fma(PB, o, e);
-                Tb[c] = f2fma(-PB, o, e);
-            }
-            row_out(Ta, 3);
-            row_out(Tb, 4);
-#pragma unroll
-            for (int c = 0; c < 6; c++) Tb[c] = f2fma(PP2, d(1, c), f2fma(-PS2, d(3, c), d(5, c)));
-            row_out(Tb, 5);
-        }
-    };
-    constexpr int AHEAD = F4_RING - 1;
+    auto transform = [&]() __attribute__((always_inline)) { f4_transform_half(th, F4Patch<false, F6_PRLD>{raw + rbase, F6_RW, true}, V + vofs, F6_VPP); };
     const float *asrc = V + ((4 * kh + lk) * F6_TILES + li) * 4;     // this K half's channel pairs of the chunk
     floatx4 acc[36];
     // one convolution over nch16 chunks of 16 channels; pass 1 has chunk 0 in xr on entry
@@ -1316,22 +1163,12 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
         for (int chunk = 0; chunk < nch16; chunk++) {
             if (wave < 4) transform();
 #pragma unroll
-            for (int a = 0; a < AHEAD; a++) bq[a] = wp[a * 64 + lane];
+            for (int a = 0; a < F4_RING - 1; a++) bq[a] = wp[a * 64 + lane];
             if (P1) load_raw(min(chunk + 1, last));
             F4_LDS_BARRIER();
             float4 aq[2];
-            aq[0] = *reinterpret_cast<const float4 *>(asrc);
 #pragma unroll
-            for (int pp = 0; pp < 18; pp++) {
-                if (pp + AHEAD < 18) bq[(pp + AHEAD) % F4_RING] = wp[(pp + AHEAD) * 64 + lane];
-                if (pp + 1 < 18) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(asrc + (pp + 1) * F6_VPP);
-                const float4 aa = aq[pp & 1];
-                const float4 b = bq[pp % F4_RING];
-                acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.x, b.x, acc[2 * pp], 0, 0, 0);
-                acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.z, b.z, acc[2 * pp + 1], 0, 0, 0);
-                acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.y, b.y, acc[2 * pp], 0, 0, 0);
-                acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aa.w, b.w, acc[2 * pp + 1], 0, 0, 0);
-            }
+            for (int pp = 0; pp < 18; pp++) f4_mfma_pair(pp, asrc, F6_VPP, wp, lane, aq, bq, acc);
             wp += 2 * 18 * 64;
             if (chunk < last) store_raw(chunk + 1, first_pass);
             F4_LDS_BARRIER();
@@ -1360,44 +1197,6 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
                 asm volatile("" ::: "memory");
             }
             F4_LDS_BARRIER();
-        }
-    };
-    auto out_tile = [&](auto r_c, float (&Yt)[16]) __attribute__((always_inline)) {
-        constexpr int r = decltype(r_c)::value;
-        float Z[4][6];
-#pragma unroll
-        for (int b = 0; b < 6; b++) {
-            const float m0 = acc[0 * 6 + b][r], m1 = acc[1 * 6 + b][r], m2 = acc[2 * 6 + b][r];
-            const float m3 = acc[3 * 6 + b][r], m4 = acc[4 * 6 + b][r], m5 = acc[5 * 6 + b][r];
-            const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-            Z[0][b] = m0 + s12 + s34;
-            Z[1][b] = fmaf(PB, d34, PA * d12);
-            Z[2][b] = fmaf(PB2, s34, PA2 * s12);
-            Z[3][b] = fmaf(PB3, d34, PA3 * d12) + m5;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float s12 = Z[i][1] + Z[i][2], d12 = Z[i][1] - Z[i][2], s34 = Z[i][3] + Z[i][4], d34 = Z[i][3] - Z[i][4];
-            Yt[i * 4 + 0] = Z[i][0] + s12 + s34;
-            Yt[i * 4 + 1] = fmaf(PB, d34, PA * d12);
-            Yt[i * 4 + 2] = fmaf(PB2, s34, PA2 * s12);
-            Yt[i * 4 + 3] = fmaf(PB3, d34, PA3 * d12) + Z[i][5];
-        }
-    };
-    // (mean, M2) of this wave's 128 pixels of its channel from the per-lane shifted sums over 32 values; every lane ends up with it
-    auto half_stats = [&](float K, float s1, float s2, float &mean, float &M2) __attribute__((always_inline)) {
-        mean = K + s1 * (1.f / 32.f);
-        M2 = fmaxf(s2 - s1 * s1 * (1.f / 32.f), 0.f);
-        float na = 32.f;
-#pragma unroll
-        for (int sft = 16; sft <= 32; sft <<= 1) {
-            const float om = __shfl_xor(mean, sft), oM2 = __shfl_xor(M2, sft);
-            const float lo_m = (lane & sft) ? om : mean, hi_m = (lane & sft) ? mean : om;
-            const float lo_M = (lane & sft) ? oM2 : M2, hi_M = (lane & sft) ? M2 : oM2;
-            const float dd = hi_m - lo_m;
-            mean = lo_m + dd * 0.5f;
-            M2 = lo_M + hi_M + dd * dd * (na * 0.5f);
-            na *= 2.f;
         }
     };
 
@@ -1429,7 +1228,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
         float K = 0.f, s1 = 0.f, s2 = 0.f;
         {
             float Yt[16];
-            out_tile(std::integral_constant<int, RA>(), Yt);
+            f4_out_tile(acc, RA, Yt);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const float v = Yt[k] + bias_v;
@@ -1439,7 +1238,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
                 s2 = fmaf(dd, dd, s2);
                 hv[0][k] = v;
             }
-            out_tile(std::integral_constant<int, RA + 1>(), Yt);
+            f4_out_tile(acc, RA + 1, Yt);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const float v = Yt[k] + bias_v;
@@ -1450,7 +1249,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
             }
         }
         float mean, M2;
-        half_stats(K, s1, s2, mean, M2);
+        f4_stats_merge<32>(K, s1, s2, lane, mean, M2);      // this wave's 128 pixels of its channel; every lane ends up with it
         if (lkv == 0) part[kh * CO + chv] = make_float2(mean, M2);
         F4_LDS_BARRIER();
         gn_coeffs_from_stats_image(part, nullptr, CO, 0, 2, 1, H * W, 32, p.gn2_w, p.gn2_b, p.emb + (int64_t)img * p.emb_stride + p.emb_off, gsh, Cf,
@@ -1490,7 +1289,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
 #pragma unroll
             for (int k = 0; k < 16; k++) rs[k] = res_blk[(tpix + (k >> 2) * W + (k & 3)) * CO + chv];
             float Yt[16];
-            out_tile(r_c, Yt);
+            f4_out_tile(acc, decltype(r_c)::value, Yt);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const float v = (Yt[k] + bias_v) + rs[k];
@@ -1505,7 +1304,7 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
         one(std::integral_constant<int, RA + 1>(), 1);
         if (do_stats) {     // per-image statistics: the two halves' 128-pixel partials merged in a fixed order (Chan's update)
             float mean, M2;
-            half_stats(K, s1, s2, mean, M2);
+            f4_stats_merge<32>(K, s1, s2, lane, mean, M2);      // this wave's 128 pixels of its channel; every lane ends up with it
             if (lkv == 0) part[kh * CO + chv] = make_float2(mean, M2);
             F4_LDS_BARRIER();
             if (kh == 0 && lkv == 0) {
