@@ -111,6 +111,8 @@ SIGNATURES = {
     'dlpm_loss_terms_f32': (C.c_int, [vp, vp, vp, i64, i32, i64, i32, i64, i64, vp]),
     'dlpm_loss_reduce_f32': (C.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp]),
     'dlpm_at_t_f32': (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp]),
+    'dlpm_mmd_workspace_bytes': (i64, [i64, i64, i64]),
+    'dlpm_mmd_f32': (C.c_int, [vp, i64, vp, i64, i64, f64, i32, f64, vp, i64, vp, vp]),
     'dlpm_images_to_rgb8': (C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
     'dlpm_png_bound': (i64, [i32, i32]),
     'dlpm_png_encode_rgb8': (C.c_int, [vp, i32, i32, i32, vp, i64, C.POINTER(i64)]),

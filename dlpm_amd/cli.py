@@ -10,6 +10,9 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_loss DATA.npy [--lploss P] [--median OUTER INNER]: instead of generating, the held-out denoising loss of the checkpoint on
   the float32 samples of DATA.npy (already in the net's range), EvaluationManager.evaluate_loss; --lploss / --median as the
   reference's training flags.  The figure does not depend on --batch_size.
+  --eval_mmd REAL.npy --generate N: generate N samples and print the reference's multi-bandwidth Gaussian MMD between them and the
+  first N float32 samples of REAL.npy (EvaluationManager.evaluate_mmd; images in [0, 1], 2-D points as they are).  May be combined
+  with --out, not with --gen_data_path.  With --rng philox the figure does not depend on --batch_size.
 """
 import argparse
 import os
@@ -86,7 +89,14 @@ def main(argv=None):
     ap.add_argument('--lploss', type=float, default=None, help='with --eval_loss: 2 (L2, default), 1 (smooth L1), -1 (squared L2)')
     ap.add_argument('--median', type=int, nargs=2, default=None, metavar=('OUTER', 'INNER'),
                     help='with --eval_loss: median-of-means estimator with these Monte-Carlo counts')
+    ap.add_argument('--eval_mmd', default=None, metavar='REAL.npy',
+                    help='with --generate N: MMD (the reference\'s MMD_loss, 5 Gaussian kernels) between the N generated samples and the '
+                         'first N float32 samples of this file; prints `mmd <value> over <N> generated vs <N> real samples`')
     a = ap.parse_args(argv)
+    if a.eval_mmd and a.gen_data_path:
+        raise SystemExit('--eval_mmd cannot be combined with --gen_data_path')
+    if a.eval_mmd and a.generate is None:
+        raise SystemExit('--eval_mmd needs --generate N')
 
     p = dlpm_amd.load_config(a.config)
     p['device'] = 'cuda'
@@ -153,6 +163,15 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
+    if a.eval_mmd:
+        N = p['eval']['data_to_generate']
+        real = np.load(a.eval_mmd)
+        ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
+        value, samples = ev.evaluate_mmd({'default': model}, real, N, p['eval']['batch_size'], class_labels=labels, return_samples=True)
+        if a.out:
+            np.save(a.out, samples.cpu().numpy())
+        print('mmd %.9g over %d generated vs %d real samples' % (value, N, N))
+        return value
     if a.gen_data_path:
         assert is_image, '--gen_data_path dumps images; 2-D data has no image form'
         ev = dlpm_amd.EvaluationManager(method, gm, None, is_image=True, gen_data_path=a.gen_data_path,

@@ -36,6 +36,24 @@ inline hipStream_t as_stream(dlpm_stream_t s) { return reinterpret_cast<hipStrea
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+#ifdef __HIPCC__   // device code: host.cpp and png.cpp are also built by a plain C++ compiler (tests/test_host_sanitizers.py)
+// fixed-order sum of one fp64 partial per thread of a THREADS-wide workgroup (sh: THREADS doubles of LDS): the same tree whatever
+// the grid or the batch (loss.hip, mmd.hip)
+template <int THREADS>
+__device__ inline double block_sum(double v, double *sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double out = sh[0];
+    __syncthreads();
+    return out;
+}
+#endif
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute: set it once per (device, kernel), under a lock
 // (a process may drive several GPUs, and two host threads may launch a kernel for the first time together).
 int ensure_dynamic_lds(const void *kernel, int bytes);

@@ -152,21 +152,6 @@ __global__ void __launch_bounds__(256) k_loss_elements(dlpm_loss_args p) {
     }
 }
 
-// fixed-order sum of one fp64 partial per thread: the same tree whatever the grid or the batch
-template <int THREADS>
-__device__ inline double block_sum(double v, double *sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = THREADS / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double out = sh[0];
-    __syncthreads();
-    return out;
-}
-
 __device__ inline float loss_value(float m, float e, int lploss) {
     const float d = __fsub_rn(m, e);
     if (lploss == 1) {                       // smooth-L1, beta = 1

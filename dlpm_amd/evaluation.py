@@ -9,10 +9,11 @@ are the reference's (`<gen_data_path>/<i>.png`, i counting over all chunks).  Wi
 dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so `device_batch` may enlarge the
 chunks beyond `eval.batch_size` without changing a pixel.
 
-The metrics half (FID / PRDC / Wasserstein / MMD) needs third-party packages and Inception weights that are not
+The metrics half (FID / PRDC / Wasserstein / PRD precision and recall) needs third-party packages and Inception weights that are not
 available offline and is out of scope: `evals` keeps the reference's keys but nothing is appended to them -- except
 `losses`, which `evaluate_loss` fills with the one quality figure that needs nothing but the net and data: the
-reference's own objective (GenerativeLevyProcess.training_losses), forward only, on held-out samples.
+reference's own objective (GenerativeLevyProcess.training_losses), forward only, on held-out samples; and `mmd`, which
+`evaluate_mmd` fills with the reference's multi-bandwidth Gaussian MMD (dlpm_amd/metrics.py) between generated and real samples.
 """
 import copy
 import ctypes as C
@@ -212,6 +213,48 @@ class EvaluationManager:
         if per_timestep:
             return loss, t_all.cpu(), terms.cpu()
         return loss
+
+    def evaluate_mmd(self, models, real_data, data_to_generate, batch_size, class_labels=None, kernel_mul=2.0, kernel_num=5,
+                     fix_sigma=None, return_samples=False, **kwargs):
+        """Multi-bandwidth Gaussian MMD (the reference's MMD_loss, EvaluationManager.py:153) between `data_to_generate` generated
+        samples and `real_data[:data_to_generate]`, as a Python float appended to `evals['mmd']`.
+
+        `real_data`: float32 [N, ...] tensor or array with N >= data_to_generate, in the range GenerationManager leaves its samples in
+        ([0, 1] for images, the raw coordinates for 2-D data).  The samples are generated in chunks of `batch_size` like
+        `_evaluate_model` -- inside one dataset_stream(), on the device, without declaring a batch -- and every chunk is written after
+        GenerationManager's post-processing into one [N, D] device buffer; the metric is ONE dlpm_mmd_f32 call on that buffer.  With
+        rng='philox' the figure therefore does not depend on `batch_size`.  `class_labels` and `kwargs` as `_evaluate_model`.
+        `return_samples=True` returns (mmd, the generated samples in their own shape, on the device)."""
+        from . import metrics
+        N = int(data_to_generate)
+        assert N > 0, 'evaluate_mmd: data_to_generate must be positive'
+        real = torch.as_tensor(real_data)
+        assert real.dtype == torch.float32, 'evaluate_mmd takes float32 real_data, got %s' % real.dtype
+        assert real.shape[0] >= N, 'evaluate_mmd: %d real samples for %d generated' % (real.shape[0], N)
+        if class_labels is not None:
+            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        batch_size = max(1, int(batch_size))
+        stream = getattr(self.method, 'dataset_stream', None)
+        gen, total = None, 0
+        with (stream() if stream is not None else _null()):
+            while total < N:
+                n = min(batch_size, N - total)
+                if class_labels is not None:
+                    kwargs['model_kwargs'] = {'y': class_labels[total:total + n]}
+                x = self.gen_manager.generate(models, n, to_host=False, declare_batch=False, **kwargs)
+                if gen is None:
+                    shape = tuple(x.shape[1:])
+                    gen = torch.empty((N, x[0].numel()), dtype=torch.float32, device=x.device)
+                gen[total:total + n] = x.reshape(n, -1)
+                total += n
+        real = real[:N].reshape(N, -1)
+        assert real.shape[1] == gen.shape[1], 'evaluate_mmd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
+        value = metrics.mmd(gen, real.to(gen.device), kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
+        self.evals['mmd'].append(value)
+        if return_samples:
+            return value, gen.reshape((N,) + shape)
+        return value
 
     def generate_default(self, models, nsamples, **kwargs):
         self.gen_manager.generate(models, nsamples, **kwargs)

@@ -330,6 +330,27 @@ int dlpm_at_t_f32(int32_t mode, const float *u_dev, const float *v_dev, const in
                   const float *bs_dev, float *out_dev, int64_t B, int64_t D, int32_t T, dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-quality metric: the multi-bandwidth Gaussian MMD of the reference's MMD_loss(kernel_mul, kernel_num)(source, target)
+ * (bem/evaluate/mmd_loss.py:5-37, called at EvaluationManager.py:153) between x [n1, D] and y [n2, D], fp32 rows on the device.
+ * With p = [x; y], n = n1 + n2:  L2[i,j] = |p_i - p_j|^2,  bandwidth = sum L2 / (n^2 - n) (or fix_sigma),
+ * K[i,j] = sum_{k < kernel_num} exp(-L2[i,j] / (bandwidth / kernel_mul^(kernel_num / 2) * kernel_mul^k)), diagonal included,
+ * mmd = sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2) -- the reference's mean(XX + YY - XY - YX) when n1 == n2 (the only case it
+ * runs).  No n x n array is stored: the pairs are walked in tiles, D <= 16 by the reference's own (a - b)^2 sum on the VALU, larger D
+ * as tiles of the centred Gram matrix on the fp32 MFMA (the choice depends on D alone).  Every workgroup writes fp64 partial sums to
+ * the workspace and one workgroup adds them in a fixed order: the same inputs give the same bits.  The bandwidth is produced and
+ * consumed on the device; the call is one enqueue sequence without a host synchronisation (it can be captured in a hipGraph).
+ * All points equal: bandwidth 0 and a NaN result, as the reference.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of workspace a call on these shapes needs; a negative dlpm_status for n1 < 1, n2 < 1, D < 1 or shapes out of range. */
+int64_t dlpm_mmd_workspace_bytes(int64_t n1, int64_t n2, int64_t D);
+
+/* out_dev[0] = mmd, [1] = bandwidth before the division by kernel_mul^(kernel_num / 2), [2..4] = sum XX, sum YY, sum XY.
+ * fix_sigma <= 0: the bandwidth comes from the data.  DLPM_ERR_ARG for n1 < 1, n2 < 1, D < 1, kernel_num outside 1..16,
+ * kernel_mul <= 0 or a null pointer; DLPM_ERR_NOMEM for a short workspace (which must be 16-byte aligned) -- before any launch. */
+int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, double kernel_mul, int32_t kernel_num,
+                 double fix_sigma, void *workspace_dev, int64_t workspace_bytes, double *out_dev, dlpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generated-image dump: what EvaluationManager does with each chunk of samples,
  * bem/evaluate/EvaluationManager.py:174-196 -- `tvu.save_image(samples[i], f"{i+total}.png")` per sample.
  * ------------------------------------------------------------------------------------------ */

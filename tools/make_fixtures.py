@@ -23,6 +23,7 @@ Fixture families:
   F15 any geometry      QKVAttention at any T / head dim, the 28x28 MNIST UNet (forward, bounded T=1000 sample)   dlpm/models/unet.py
   F16 class-conditional  UNetModel(num_classes=10) forwards, p_sample_loop / ddim_sample_loop with model_kwargs={'y': y}   unet.py:341-342, 463-481
   F17 held-out loss      training_losses / training_losses_dlpm with every draw recorded   GenerativeLevyProcess.py:581-677, dlpm.py:384-401
+  F18 MMD                MMD_loss(kernel_mul, kernel_num)(source, target) on fp32 and on fp64 inputs, with the bandwidth   bem/evaluate/mmd_loss.py:5-37
   F12 mean types         p_mean_variance: START_X / Z / PREVIOUS_X, denoised_fn, model_kwargs   GenerativeLevyProcess.py:154-219
   F11 image quantisation PIL's float -> 8-bit path (torchvision absent)  bem/evaluate/EvaluationManager.py:188-190
   F9 checkpoints         TrainingManager.save/load, EMAHelper,    bem/TrainingManager.py:240-285, bem/utils_ema.py,
@@ -1142,6 +1143,72 @@ def f17_loss():
         print('   %-18s loss %.6f' % (name, float(loss)))
 
 
+# (name, n1 = n2, D, shift of the second set's mean, distribution, kernel_num, kernel_mul, fix_sigma)
+F18_CASES = [
+    ('toy64', 64, 2, 0.5, 'normal', 5, 2.0, None),            # a single tile
+    ('toy257', 257, 2, 0.3, 'normal', 5, 2.0, None),          # one row past a tile edge both ways; the quadrant split inside a tile
+    ('toy257_same', 257, 2, 0.0, 'normal', 5, 2.0, None),     # cancellation of XX + YY - 2 XY
+    ('toy1000', 1000, 2, 0.2, 'normal', 5, 2.0, None),        # many tiles and partial sums
+    ('d3', 100, 3, 0.5, 'normal', 5, 2.0, None),              # odd D
+    ('d16', 96, 16, 0.3, 'normal', 5, 2.0, None),             # the last D of the direct form
+    ('d17', 96, 17, 0.3, 'normal', 5, 2.0, None),             # the first D of the Gram form
+    ('g147', 130, 147, 0.2, 'normal', 5, 2.0, None),          # Gram form, ragged K step and ragged rows
+    ('g192', 200, 192, 0.2, 'normal', 5, 2.0, None),          # Gram form over several tiles
+    ('g3072_img', 32, 3072, 0.0, 'pixels', 5, 2.0, None),     # uncentred [0, 1] data at the image workload's D
+    ('params_k3', 100, 2, 0.5, 'normal', 3, 3.0, None),       # the bandwidth ladder
+    ('params_sigma', 100, 2, 0.5, 'normal', 5, 2.0, 0.7),     # the fixed-bandwidth branch
+]
+F18_SEED = 18
+
+
+def f18_mmd():
+    """The reference's MMD_loss, loaded by file path, on seeded inputs: its result on the fp32 inputs (`ref32`) and on the same inputs
+    converted to fp64 (`ref64`, the yardstick of the tests), and the bandwidth of both runs before the division by
+    kernel_mul ** (kernel_num // 2).  The class does not return the bandwidth; its numerator is the one `torch.sum(...)` call inside
+    gaussian_kernel, recorded here while the class runs."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('ref_mmd_loss', os.path.join(REF, 'bem', 'evaluate', 'mmd_loss.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+
+    def run(x, y, num, mul, sigma):
+        loss = mod.MMD_loss(kernel_mul=mul, kernel_num=num)
+        loss.fix_sigma = sigma
+        seen, real_sum = [], torch.sum
+
+        def recording_sum(*a, **k):
+            seen.append(real_sum(*a, **k))
+            return seen[-1]
+        torch.sum = recording_sum
+        try:
+            out = loss(x, y)
+        finally:
+            torch.sum = real_sum
+        n = x.shape[0] + y.shape[0]
+        if sigma:
+            assert not seen
+            bw = torch.tensor(sigma, dtype=x.dtype)
+        else:
+            assert len(seen) == 1
+            bw = seen[0] / (n ** 2 - n)
+        assert out.dtype == x.dtype and bw.dtype == x.dtype
+        return out, bw
+
+    for i, (name, n, D, shift, dist, num, mul, sigma) in enumerate(F18_CASES):
+        g = torch.Generator().manual_seed(F18_SEED * 100 + i)
+        if dist == 'pixels':
+            x = torch.rand(n, D, generator=g)
+            y = torch.rand(n, D, generator=g) ** 1.25
+        else:
+            x = torch.randn(n, D, generator=g)
+            y = torch.randn(n, D, generator=g) + shift
+        r32, b32 = run(x, y, num, mul, sigma)
+        r64, b64 = run(x.double(), y.double(), num, mul, sigma)
+        save('f18_mmd_' + name, x=x, y=y, ref32=r32, ref64=r64, bandwidth32=b32, bandwidth64=b64, kernel_num=np.array(num),
+             kernel_mul=np.array(mul), fix_sigma=np.array(0.0 if sigma is None else sigma))
+        print('    %-14s ref32 %.9g  ref32 - ref64 %.3g  bandwidth %.9g' % (name, float(r32), float(r32) - float(r64), float(b64)))
+
+
 def f8_generation_manager():
     class FakeMethod:
         device = 'cpu'
@@ -1331,9 +1398,9 @@ def f10_lim():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16', 'f17']
+    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16', 'f17', 'f18']
     table = dict(f12=f12_mean_types, f11=f11_image_quantise, f10=f10_lim, f1=f1_schedule, f2=f2_noise, f3=f3_tables, f4=f4_single_step, f5=f5_trajectories, f5u=f5_unet_trajectory, f5w=f5_wide_unet_trajectory, f5k=f5_unet_trajectories_T1000, f5b=f5_bounded_unet_trajectories, f5c=f5_cifar_teacher_forced,
-                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f17=f17_loss, f8=f8_generation_manager, f9=f9_checkpoints)
+                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f17=f17_loss, f18=f18_mmd, f8=f8_generation_manager, f9=f9_checkpoints)
     with torch.no_grad():
         for w in which:
             table[w]()
