@@ -150,6 +150,7 @@ SIGNATURES = {
     'dlpm_mlp_sample_steps_f32': (C.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, i32, u64, i64, vp, vp]),
     'dlpm_mlp_destroy': (None, [vp]),
     'dlpm_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), vp, vp]),
+    'dlpm_conv2d_stats_f32': (C.c_int, [C.POINTER(ConvArgs), vp, vp, C.POINTER(i32), vp]),
     'dlpm_groupnorm_coeffs_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, i64, vp, vp, vp]),
     'dlpm_attention_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     'dlpm_attention_general_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),

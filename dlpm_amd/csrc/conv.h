@@ -18,6 +18,8 @@ struct ConvLaunch {
     const float *w_wino4 = nullptr;// optional, 3x3 s1 only: F(4x4,3x3) Winograd-domain weights (conv_wino4.hip); preferred over w_wino
     const float *w_wino4_n64 = nullptr, *w_wino4_n32 = nullptr;   // optional, Cout % 128 == 0 only: the same weights in the fragment order of 64- / 32-channel
                                    // n-tiles (round 6: at a small DECLARED batch the narrow shapes give 2-4x as many workgroups; same bits)
+    const float *w_wino4sp = nullptr; // optional, ups launches with Cout % 128 == 0 only: the four parity classes' F(4x4,2x2) weights
+                                   // (conv_wino4.hip: k_conv3x3_wino4sp); taken where wino4sp_preferred says so
     const void *w_split = nullptr; // optional: the weights as three bf16 planes in stage-tile order (conv_split.hip); a 3x3 launch
                                    // that carries it is a stride-2 downsampling convolution, or a test forcing the path
     const float *w_small = nullptr;// optional, 3x3 with Cout <= 4 (the head): [tap][Cin][4] for k_conv3x3_head
@@ -45,7 +47,8 @@ struct ConvLaunch {
     // Optional fused GroupNorm statistics of the OUTPUT: per (image, pixel tile, channel) the
     // pair (mean, centred sum of squares) over the tile's pixels, written by the MFMA kernels'
     // epilogue when the tile lies inside one image.  [B][HW/tile][Cout] float2 with tile =
-    // conv_stats_pixels(launch): 128 for the implicit-GEMM kernels, 256 for the Winograd kernel.
+    // conv_stats_pixels(launch): 128 for the implicit-GEMM kernels, 256 for the Winograd kernel
+    // (the sub-pixel kernel: one partial per block AND parity class, [B][HW/256][Cout] in (block, class) order, or [B][4 classes][Cout]).
     float2 *stats_out = nullptr;
 #ifdef DLPM_PHASE_TIMING
     unsigned long long *phase = nullptr;
@@ -100,6 +103,14 @@ bool wino4_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg);   // geo
 int launch_conv_wino4(const ConvLaunch &c, hipStream_t st);
 int64_t wino4_weight_floats(int Cout, int Cin);
 int relayout_weight_wino4(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st, int nq = 0);   // nq: n-tile width (0: the layer's own)
+// the nearest-x2 Upsample convolutions as four parity-class F(4x4,2x2) convolutions on the low-res image (conv_wino4.hip: k_conv3x3_wino4sp)
+bool wino4sp_enabled();                // DLPM_WINO4_SUBPIX
+bool wino4sp_layer_ok(int Cout, int Cin, int Hlo, int Wlo);               // worth building the weights for
+bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg);
+bool wino4sp_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg); // geometry + dispatch policy (generations AUTO / F4, 128-channel n-tile)
+int launch_conv_wino4sp(const ConvLaunch &c, hipStream_t st);
+int64_t wino4sp_weight_floats(int Cout, int Cin);
+int relayout_weight_wino4sp(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 // A WHOLE ResBlock with 32 output channels on 32x32 images in one launch (round 6, conv_wino4.hip: k_resblock_wino4_img): GroupNorm-1
 // coefficients from the producers' statistics (or given), conv1 as F(4x4,3x3), GroupNorm-2 with scale-shift inside the workgroup (an image
 // is one workgroup), conv2 over the activated intermediate (which makes one trip through L2, never a second launch), skip, output

@@ -1127,6 +1127,7 @@ int conv_stats_pixels(const ConvLaunch &c) {
         const int64_t hw = (int64_t)c.Hout * c.Wout;
         return (c.R0 & 3) ? 0 : hw % BM == 0 ? BM : hw == 64 ? 64 : 0;
     }
+    if (wino4sp_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4) ? 64 : 0;   // per (block | image, parity class)
     if (wino4_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4) ? 64 : 0;   // (four whole 8x8 images per block: one partial per image)
     if (wino_geometry(c, &a, &b, &n)) return n == 1 ? 4 * wino_tiles(c) : 0;
     if (c.out_nchw || (c.Cout & 3) || (c.R0 & 3)) return 0;
@@ -1161,6 +1162,14 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
     }
     {
         int wb, ww, wi;
+        if (wino4sp_preferred(c, &wb, &ww, &wi)) {   // a class of its own: it executes 100 multiplies per 64 outputs, conv3x3_wino4 144
+            if (prof_enabled() && prof_detail())
+                snprintf(pname, sizeof(pname), "conv3x3_wino4sp:H%d:Cin%d+%d:Cout%d:u%d:coef%d", c.Hout, c.C0, c.C1, c.Cout, c.ups, c.coefA ? 1 : 0);
+            else
+                snprintf(pname, sizeof(pname), "conv3x3_wino4sp");
+            ProfScope psw(pname, 2.0 * M * c.Cout * K, bytes, st);   // ALGORITHMIC flops (direct-conv count)
+            return launch_conv_wino4sp(c, st);
+        }
         if (wino4_preferred(c, &wb, &ww, &wi)) {
             if (prof_enabled() && prof_detail())
                 snprintf(pname, sizeof(pname), "conv3x3_wino4:H%d:Cin%d+%d:Cout%d:u%d:coef%d", c.Hout, c.C0, c.C1, c.Cout, c.ups, c.coefA ? 1 : 0);

@@ -288,6 +288,49 @@ __device__ __forceinline__ int f4_item_lds(int iv) { return iv & 16383; }
 __device__ __forceinline__ int f4_item_src(int iv) { return (iv >> 14) & 1023; }      // (padding / no item: pixel 0)
 __device__ __forceinline__ bool f4_item_pad(int iv) { return iv & (1 << 24); }        // zero padding applies AFTER the activation
 __device__ __forceinline__ bool f4_item_none(int iv) { return iv & (1 << 25); }
+
+// ---- F(4x4,2x2) on the five finite points {0, +-a, +-b} (the parity classes of an upsampling convolution, k_conv3x3_wino4sp): B^T is
+// rows 0..4 of the 6x6 matrix over five samples x0..x4, A^T is f4_at without the inf column (m5 = 0).  Position (ra, rb) = 5 ra + rb sits in
+// half (pos & 1) of position pair pos >> 1 of the A-fragment layout: one float2 per position
+__device__ __forceinline__ void fs_v_row_out(const float2 (&T)[5], int ra, float *vb, int vpp) {
+    const float2 e1 = f4_bt_part<1>(T[2], T[4]), o1 = f4_bt_part<1>(T[1], T[3]);
+    const float2 e2 = f4_bt_part<3>(T[2], T[4]), o2 = f4_bt_part<3>(T[1], T[3]);
+    const float2 v[5] = {f4_bt_end(T[0], T[2], T[4]), f4_bt_plus<1>(o1, e1), f4_bt_minus<1>(o1, e1), f4_bt_plus<3>(o2, e2), f4_bt_minus<3>(o2, e2)};
+#pragma unroll
+    for (int rb = 0; rb < 5; rb++) {
+        const int pos = 5 * ra + rb;
+        *reinterpret_cast<float2 *>(vb + (pos >> 1) * vpp + (pos & 1) * 2) = v[rb];
+    }
+}
+// the three row groups a wave can take: rp = 0: row 0, 1: rows 1 | 2, 2: rows 3 | 4
+template <class D>
+__device__ __forceinline__ void fs_transform_rp(int rp, const D &d, float *vb, int vpp) {
+    float2 Ta[5], Tb[5];
+    if (rp == 0) {
+#pragma unroll
+        for (int c = 0; c < 5; c++) Ta[c] = f4_bt_outer<0>(d, c);
+        fs_v_row_out(Ta, 0, vb, vpp);
+    } else if (rp == 1) {
+#pragma unroll
+        for (int c = 0; c < 5; c++) f4_bt_mid<1>(d, c, Ta[c], Tb[c]);
+        fs_v_row_out(Ta, 1, vb, vpp);
+        fs_v_row_out(Tb, 2, vb, vpp);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 5; c++) f4_bt_mid<3>(d, c, Ta[c], Tb[c]);
+        fs_v_row_out(Ta, 3, vb, vpp);
+        fs_v_row_out(Tb, 4, vb, vpp);
+    }
+}
+// Y = A^T M A of tile r of a lane (M_pos in acc[pos][r]): 25 -> 16 values
+__device__ __forceinline__ void fs_out_tile(const floatx4 (&acc)[25], int r, float (&Yt)[16]) {
+    float Z[4][5];
+#pragma unroll
+    for (int b = 0; b < 5; b++)
+        f4_at(acc[0 * 5 + b][r], acc[1 * 5 + b][r], acc[2 * 5 + b][r], acc[3 * 5 + b][r], acc[4 * 5 + b][r], 0.f, Z[0][b], Z[1][b], Z[2][b], Z[3][b]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) f4_at(Z[i][0], Z[i][1], Z[i][2], Z[i][3], Z[i][4], 0.f, Yt[i * 4 + 0], Yt[i * 4 + 1], Yt[i * 4 + 2], Yt[i * 4 + 3]);
+}
 // =====================================================================================================================================
 
 // QN: staging items per thread (2 for halo patches of <= 512 pixels -- every block shape but 16 whole 4x4 images; round 4: the third
@@ -629,6 +672,291 @@ __global__ void __launch_bounds__((NW + (NW == 8 ? 0 : NW == 4 ? 3 : 2)) * 64, N
 #ifdef DLPM_PHASE_DEFER
     if (p.phase && lane == 0) atomicAdd(p.phase + 16 + wave, (unsigned long long)_wait);
 #endif
+#ifdef DLPM_PHASE_TIMING
+    if (p.phase && tid == 0) {
+        atomicAdd(p.phase + 11, 1ull);
+        atomicAdd(p.phase + 12, (unsigned long long)(clock64() - _c0));
+        atomicAdd(p.phase + 13, (unsigned long long)(wall_clock64() - _r0));
+    }
+#endif
+}
+
+// =====================================================================================================================================
+// The SUB-PIXEL form of the nearest-x2 Upsample convolutions (unet.py:64-75): upsampling followed by a 3x3 convolution is four independent
+// 2x2 convolutions on the LOW-RESOLUTION image, one per output parity class (a, b):
+//     out[2i+a, 2j+b] = sum_{u,v in {0,1}} e_ab[u,v] x[i-1+a+u, j-1+b+v]        rows: a = 0: (g0, g1+g2), a = 1: (g0+g1, g2); columns likewise
+// and each class runs as Winograd F(4x4,2x2) on the five finite points {0, +-a, +-b}: 25 products per 4x4 low-res output tile, 100 per 8x8
+// block of output pixels (1.5625 per output) where the UPS instantiation above spends 4 x 36 (2.25) -- 0.69x the MFMAs and the weight
+// stream.  One workgroup = 16 low-res tiles x 128 output channels x ONE class, 8 MFMA waves of 16 channels, the k_conv3x3_wino4<.., 8>
+// schedule: raw halo patch of (4 bh + 1) x (4 bw + 1) source pixels per image, offset by (a, b); V in the same A-fragment order, 12 full
+// position pairs + position 24 alone; waves 0..2 transform (row 0 | rows 1, 2 | rows 3, 4 of B^T).
+// The 25th position is a single-position TAIL step (two MFMAs behind the twelve pairs of a phase) rather than a 13th pair with a zero half:
+// 12 pairs keep the six-deep weight ring's slots static across phases (13 is coprime to every ring depth: the slot of a fragment would rotate
+// from phase to phase, i.e. six copies of the loop body or register moves), and the tail's fragment -- one float2 per lane and phase, stored as
+// the 13th float4 of the phase with a zero half -- is requested one phase ahead.  50 MFMAs per phase and wave instead of 72.
+// Epilogue from registers as above; output pixel (2 (4 ty + i) + a, 2 (4 tx + j) + b).  Statistics partials are per (block, class) of 256 outputs,
+// or -- four whole low-res 8x8 images per block -- per (image, class) of 64: equal counts, merged by k_gn_coeffs_stats in index order.
+// Blocks of sixteen one-tile images (4x4 low-res) are not taken: that layer stays on the UPS instantiation.
+constexpr int FS_PP = 12;                            // position pairs per phase that go through the weight ring (positions 0..23)
+constexpr int FS_FRAGS = 13;                         // weight fragments (float4) per lane and phase: 12 pairs + {position 24: 2 k-steps, 0, 0}
+constexpr int FS_VPP = 4 * F4_TILES * 4;             // floats per position pair of V: [4 channel pairs][16 tiles][4]
+constexpr int FS_VBUF = FS_FRAGS * FS_VPP;
+constexpr int FS_RAWPIX = 352;                       // halo pixels per phase: 17x17, 2 x 17x9, 4 x 9x9, ... <= 4 x 17x5 = 340
+constexpr int FS_RAWBUF = FS_RAWPIX * F4_PRLD + 16;
+constexpr int FS_PAD = 16;                           // float4 fragments of zero padding behind the weights (read-ahead of the last phase: 5 + the tail's)
+constexpr int FS_S0 = 4, FS_X = 9;                   // side-work placement inside the 12 pairs (F4_S0 / F4_X of the 18-pair loop, scaled; builds with
+                                                     // (S0, X) = (4, 7), (2, 10), (6, 11) measured within +-0.5 %: profiles/wino4_subpixel/variants.txt)
+static_assert(FS_PP % F4_RING == 0, "a fragment's ring slot must not depend on the phase");
+
+__global__ void __launch_bounds__(F4_NT, 1) k_conv3x3_wino4sp(ConvLaunch p_in, int bh_in, int bw_in, int nimg_in) {
+    constexpr int QN = 2;
+    ConvLaunch p = p_in;
+    const int bh = bh_in, bw = bw_in, nimg = nimg_in;
+    extern __shared__ __attribute__((aligned(16))) float wsm[];
+    float *V = wsm;                               // [2][13][4][16][4]
+    float *raw = wsm + 2 * FS_VBUF;               // [2][FS_RAWPIX][F4_PRLD] (+ skew)
+    float *Cf = raw + 2 * FS_RAWBUF;              // [2][16][2][8]
+
+    DLPM_PHASE_DECL;
+#ifdef DLPM_PHASE_TIMING
+    const long long _c0 = clock64(), _r0 = wall_clock64();
+#endif
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int W = p.Wout, H = p.Hout, Ws = p.Win, Hs = p.Hin, TW = Ws >> 2, TH = Hs >> 2;   // tiles of the LOW-RES image
+    const int Cin = p.C0 + p.C1;
+    const int nch = Cin / F4_KC;
+    // grid: class fastest, then M, n-tile slowest.  Workgroups b and b + 8 share an XCD and its L2, so an XCD sees ONE class: the workgroups
+    // in flight on it stream one (class, n-tile) slab of the weights, and the four classes of an M-block -- which stage the same input
+    // pixels -- run at the same time.  Measured against (class, n-tile)-major with M fastest, the rule of k_conv3x3_wino4: 1 % faster on the
+    // 16x16 -> 32x32 layer in every alternating run, equal on 8x8 -> 16x16 (profiles/wino4_subpixel/variants.txt)
+    const unsigned bid = blockIdx.x;
+    const int ntn = p.Cout / F4_NQ;
+    const int nmb = (gridDim.x >> 2) / ntn;
+    const int cls = bid & 3, mb = (bid >> 2) % nmb, nt = (bid >> 2) / nmb;
+    const int ca = cls >> 1, cb = cls & 1, n0 = nt * F4_NQ;
+    int img0, ty0, tx0, blk_in_img = 0;
+    const int bpr = TW / bw, bpi = (TH / bh) * bpr;
+    if (nimg == 1) {
+        img0 = mb / bpi;
+        blk_in_img = mb - img0 * bpi;
+        ty0 = (blk_in_img / bpr) * bh;
+        tx0 = (blk_in_img % bpr) * bw;
+    } else {
+        img0 = mb * nimg;
+        ty0 = tx0 = 0;
+    }
+    // halo patch of the class in source pixels: low-res rows 4 ty0 - 1 + a .. 4 (ty0 + bh) - 1 + a
+    const int RH = 4 * bh + 1, RW = 4 * bw + 1;
+    const int oy = 4 * ty0 - 1 + ca, ox = 4 * tx0 - 1 + cb;
+    const int rpi = RH * RW, npix = nimg * rpi;
+
+    // ---- raw staging: item = (pixel, channel quad of the phase), two per thread, the second in reverse thread order (k_conv3x3_wino4)
+    const int squad = tid & 1;
+    auto pix_of = [&](int it) { return it == 1 ? (F4_NT / 2) + ((F4_NT - 1 - tid) >> 1) : (tid >> 1); };
+    const bool skewed = nimg == 1 && bh <= 4;   // patch row ry starts 4 (ry >> 2) floats late (17 rows: inside the 16 floats of slack)
+    int off[QN], lo[QN];   // lo: LDS float offset of the item (bits 0..15) | its image's coefficient offset (bits 16..)
+#pragma unroll
+    for (int it = 0; it < QN; it++) {
+        const int pix = pix_of(it);
+        const int img = min(pix / rpi, nimg - 1), r = pix - img * rpi;
+        const int ry = r / RW, rx = r - ry * RW;
+        const int iy = oy + ry, ix = ox + rx;
+        const bool pad = iy < 0 || iy >= Hs || ix < 0 || ix >= Ws || (img0 + img) >= p.B;
+        off[it] = pix >= npix ? -2 : (pad ? -1 : (((img0 + img) * Hs + iy) * Ws + ix));
+        lo[it] = (pix * F4_PRLD + squad * 4 + (skewed ? 4 * (ry >> 2) : 0)) | ((img * 2 * F4_KC + squad * 4) << 16);
+    }
+    const bool has_coef = p.coefA != nullptr;
+    const int cf_img = tid >> 2, cf_isb = (tid >> 1) & 1;
+    const bool cf_mine = has_coef && tid < nimg * 4;
+    const float *cf_base = has_coef ? ((cf_isb ? p.coefB : p.coefA) + (int64_t)min(img0 + cf_img, p.B - 1) * Cin + squad * 4) : nullptr;
+    float4 xr[QN], cfr = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto load_raw_into = [&](float4 (&dst)[QN], int chunk) {
+        const int c = chunk * F4_KC + squad * 4;
+        const bool first = c < p.C0;
+        const float *sb = first ? p.src0 + c : p.src1 + (c - p.C0);
+        const int ld = first ? p.C0 : p.C1;
+#pragma unroll
+        for (int it = 0; it < QN; it++) dst[it] = *reinterpret_cast<const float4 *>(sb + (int64_t)max(off[it], 0) * ld);
+    };
+    auto load_coef = [&](int chunk) {
+        if (cf_mine) cfr = *reinterpret_cast<const float4 *>(cf_base + chunk * F4_KC);
+    };
+    auto store_coef = [&](int slot) {
+        if (cf_mine) *reinterpret_cast<float4 *>(Cf + slot * F4_CFS + cf_img * 2 * F4_KC + cf_isb * F4_KC + squad * 4) = cfr;
+    };
+    auto store_raw_item = [&](int slot, int it) {
+        if (off[it] == -2) return;
+        float *rb = raw + slot * FS_RAWBUF;
+        float4 x = xr[it];
+        if (has_coef) {
+            const float4 ca4 = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16));
+            const float4 cb4 = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16) + F4_KC);
+            x = f4_affine4(x, ca4, cb4);
+        }
+        if (p.act_silu) x = f4_silu4(x);
+        if (off[it] < 0) x = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding applies AFTER the activation
+        *reinterpret_cast<float4 *>(rb + (lo[it] & 0xffff)) = x;
+    };
+    auto store_raw = [&](int slot) {
+#pragma unroll
+        for (int it = 0; it < QN; it++) store_raw_item(slot, it);
+    };
+
+    // ---- input transform V = B^T d B (5x5): waves 0..2 take row 0, rows (1, 2), rows (3, 4) of B^T; lane = (channel pair, tile)
+    int rbase, vofs;
+    {
+        const int tile = lane & 15, pair = lane >> 4;
+        const int timg = tile / (bh * bw), r = tile - timg * (bh * bw);
+        const int ty = r / bw, tx = r - ty * bw;
+        rbase = (timg * rpi + 4 * ty * RW + 4 * tx) * F4_PRLD + pair * 2 + (skewed ? 4 * ty : 0);
+        vofs = (pair * F4_TILES + tile) * 4;
+    }
+    auto transform = [&](int slot) {
+        if (wave < 3) fs_transform_rp(wave, F4Patch<false, F4_PRLD>{raw + slot * FS_RAWBUF + rbase, RW, skewed}, V + slot * FS_VBUF + vofs, FS_VPP);
+    };
+
+    // ---- weight stream of this wave: Wf[class][ntile][wave][phase][13][lane][4], contiguous per wave
+    const float4 *__restrict__ wp = reinterpret_cast<const float4 *>(p.w_wino4sp) +
+                                    ((int64_t)((cls * ntn + nt) * 8 + __builtin_amdgcn_readfirstlane(wave)) * nch) * FS_FRAGS * 64;
+    constexpr int AHEAD = F4_RING - 1;
+    float4 bq[F4_RING];
+    float2 bt;                                   // the tail position's fragment of the current phase
+    const float *asrc = V + lane * 4;
+
+    floatx4 acc[25];
+#pragma unroll
+    for (int q = 0; q < 25; q++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[q][r] = 0.f;
+
+    // ---- prologue: S(0), S(1), X(0), G(2) and the coefficient slots (k_conv3x3_wino4)
+    const int last = nch - 1;
+    float4 xr1[QN], cfr1 = make_float4(0.f, 0.f, 0.f, 0.f), cfr2 = cfr1;
+    load_raw_into(xr, 0);
+    load_raw_into(xr1, min(1, last));
+    load_coef(0);
+    if (cf_mine) {
+        cfr1 = *reinterpret_cast<const float4 *>(cf_base + min(1, last) * F4_KC);
+        cfr2 = *reinterpret_cast<const float4 *>(cf_base + min(2, last) * F4_KC);
+    }
+#pragma unroll
+    for (int a = 0; a < AHEAD; a++) bq[a] = wp[a * 64 + lane];
+    bt = *reinterpret_cast<const float2 *>(wp + FS_PP * 64 + lane);
+    store_coef(0);
+    cfr = cfr1;
+    store_coef(1);
+    __syncthreads();
+    store_raw(0);
+#pragma unroll
+    for (int it = 0; it < QN; it++) xr[it] = xr1[it];
+    store_raw(1);
+    load_raw_into(xr, min(2, last));
+    __syncthreads();
+    transform(0);
+    cfr = cfr2;
+    store_coef(0);
+    __syncthreads();
+    DLPM_PHASE(p, 8);
+
+#pragma unroll 1
+    for (int chunk = 0; chunk < nch; chunk++) {
+        const int cur = chunk & 1, nxt = cur ^ 1;
+        const float *ab = asrc + cur * FS_VBUF;
+        load_coef(min(chunk + 3, last));
+        float4 aq[2];
+        float2 at;
+        aq[0] = *reinterpret_cast<const float4 *>(ab);
+        const float2 btn = *reinterpret_cast<const float2 *>(wp + (FS_FRAGS + FS_PP) * 64 + lane);   // the NEXT phase's tail fragment
+#pragma unroll
+        for (int pp = 0; pp < FS_PP; pp++) {
+            if (pp >= FS_S0 && pp < FS_S0 + QN) store_raw_item(cur, pp - FS_S0);   // S(chunk+2): raw[cur] was read by X(chunk), a barrier ago
+            if (pp == FS_S0 + QN) load_raw_into(xr, min(chunk + 3, last));        // G(chunk+3)
+            if (pp == FS_X) transform(nxt);                                       // X(chunk+1): raw[nxt] -> V[nxt]
+            {
+                const int f = pp + AHEAD;                                         // pairs 12.. are the next phase's 0.., behind the tail slot
+                bq[f % F4_RING] = wp[(f < FS_PP ? f : f + 1) * 64 + lane];
+            }
+            if (pp + 1 < FS_PP) aq[(pp + 1) & 1] = *reinterpret_cast<const float4 *>(ab + (pp + 1) * FS_VPP);
+            else at = *reinterpret_cast<const float2 *>(ab + FS_PP * FS_VPP);
+            if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
+            f4_mfma4(aq[pp & 1], bq[pp % F4_RING], acc[2 * pp], acc[2 * pp + 1]);
+            if (pp == FS_PP - 1) {   // position 24: the k order of f4_mfma4's first accumulator
+                acc[24] = __builtin_amdgcn_mfma_f32_16x16x4f32(at.x, bt.x, acc[24], 0, 0, 0);
+                acc[24] = __builtin_amdgcn_mfma_f32_16x16x4f32(at.y, bt.y, acc[24], 0, 0, 0);
+            }
+            if (F4_PRIO) __builtin_amdgcn_s_setprio(1);
+        }
+        bt = btn;
+        wp += FS_FRAGS * 64;
+        store_coef(nxt);
+        __syncthreads();
+    }
+    if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
+    DLPM_PHASE(p, 9);
+
+    // ---- epilogue from registers (k_conv3x3_wino4): a lane holds 64 outputs of ONE channel and ONE class, 4 tiles x 16 pixels two apart
+    const int64_t pix0 = ((int64_t)img0 * H + 8 * ty0 + ca) * W + 8 * tx0 + cb;      // wave-uniform
+    const int ch = n0 + 16 * wave + li;
+    const float bias_v = p.bias ? p.bias[ch] : 0.f;
+    const bool has_res = p.res0 != nullptr;
+    const bool res_first = __builtin_amdgcn_readfirstlane(n0 + 16 * wave) < p.R0;   // R0 % 16 == 0 (wino4sp_geometry)
+    const float *res_u = has_res ? (res_first ? p.res0 : p.res1 - p.R0) : nullptr;
+    const int res_ld = res_first ? p.R0 : p.Cout - p.R0;
+    const int lbw = 31 - __builtin_clz(bw), lbhw = 31 - __builtin_clz(bh * bw);      // block shapes are powers of two
+    float *__restrict__ out_blk = p.out + pix0 * p.Cout;
+    const float *__restrict__ res_blk = has_res ? res_u + pix0 * res_ld : nullptr;
+    const bool img_stats = p.stats_out != nullptr && nimg == 4 && bh * bw == 4;
+    const bool do_stats = (p.stats_out != nullptr && nimg == 1) || img_stats;
+    float K = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int tile = 4 * lk + r;
+        const int timg = tile >> lbhw, ty = (tile & (bh * bw - 1)) >> lbw, tx = tile & (bw - 1);
+        const int tpix = (timg * H + 8 * ty) * W + 8 * tx;
+        const bool ok = img0 + timg < p.B;
+        float rs[16];
+        const uint32_t bo_o = (uint32_t)(tpix * p.Cout + ch) * 4u, bo_r = (uint32_t)(tpix * res_ld + ch) * 4u;
+        if (has_res && ok) {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    rs[i * 4 + j] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + (2 * i * W + 2 * j) * res_ld) + bo_r);
+        }
+        float Yt[16];
+        fs_out_tile(acc, r, Yt);
+        if (!ok) continue;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float *y = Yt + 4 * i;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float v = y[j] + bias_v;
+                if (has_res) v += rs[i * 4 + j];
+                if (do_stats) {
+                    if (r == 0 && i == 0 && j == 0) K = v;
+                    const float dd = v - K;
+                    s1 += dd;
+                    s2 = fmaf(dd, dd, s2);
+                }
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(out_blk + (2 * i * W + 2 * j) * p.Cout) + bo_o) = v;
+            }
+        }
+    }
+    if (img_stats) {      // [image][class][channel]: 64 outputs each
+        if (img0 + lk < p.B) {
+            float mean, M2;
+            f4_stats_lane<64>(K, s1, s2, mean, M2);
+            p.stats_out[((int64_t)(img0 + lk) * 4 + cls) * p.Cout + ch] = make_float2(mean, M2);
+        }
+    } else if (do_stats) {   // [image][block inside the image][class][channel]: 256 outputs each, H W / 256 partials per image
+        float mean, M2;
+        f4_stats_merge<64>(K, s1, s2, lane, mean, M2);
+        if (lk == 0) p.stats_out[(((int64_t)img0 * bpi + blk_in_img) * 4 + cls) * p.Cout + ch] = make_float2(mean, M2);
+    }
+    DLPM_PHASE(p, 10);
+    DLPM_PHASE_FLUSH(p, 8);
 #ifdef DLPM_PHASE_TIMING
     if (p.phase && tid == 0) {
         atomicAdd(p.phase + 11, 1ull);
@@ -1358,6 +1686,41 @@ __global__ void k_relayout_weight_wino4(const float *oihw, float *dst, int Cout,
     dst[i] = (float)u;
 }
 
+// OIHW (3x3) -> the four parity classes' effective 2x2 filters e_ab (taps summed: rows a = 0: (g0, g1 + g2), a = 1: (g0 + g1, g2); columns
+// likewise with b), U = G e G^T (5x5 per filter, G[j][k] = p_j^k / prod_{l != j} (p_j - p_l) on {0, +-a, +-b}) in k_conv3x3_wino4sp's fragment
+// order Wf[class 2 a + b][ntile][wave][phase][13][lane][4]: position 2 pp + (e >> 1), position 25 = 0.  All in double, rounded once.
+__global__ void k_relayout_weight_wino4sp(const float *oihw, float *dst, int Cout, int Cin) {
+    const int nch = Cin / F4_KC;
+    const int64_t total = (int64_t)4 * Cout * Cin * 26;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int e = (int)(i & 3);
+    const int lane = (int)((i >> 2) & 63);
+    int64_t r = i >> 8;
+    const int pp = (int)(r % FS_FRAGS); r /= FS_FRAGS;
+    const int chunk = (int)(r % nch); r /= nch;
+    const int wave = (int)(r % 8); r /= 8;
+    const int ntn = Cout / F4_NQ;
+    const int nt = (int)(r % ntn);
+    const int cls = (int)(r / ntn), ca = cls >> 1, cb = cls & 1;
+    const int lk = lane >> 4, li = lane & 15;
+    const int pos = 2 * pp + (e >> 1);
+    if (pos >= 25) { dst[i] = 0.f; return; }
+    const int cin = chunk * F4_KC + 2 * lk + (e & 1);
+    const int cout = nt * F4_NQ + wave * 16 + li;
+    const float *g = oihw + ((int64_t)cout * Cin + cin) * 9;
+    double ef[2][2] = {{0., 0.}, {0., 0.}};
+    for (int ii = 0; ii < 3; ii++)
+        for (int jj = 0; jj < 3; jj++) ef[ca ? (ii == 2) : (ii != 0)][cb ? (jj == 2) : (jj != 0)] += (double)g[ii * 3 + jj];
+    const double a = F4_PA, b = F4_PB, a2 = a * a, b2 = b * b;
+    const double n0 = a2 * b2, na = 2. * a2 * (a2 - b2), nb = 2. * b2 * (b2 - a2);
+    const double G[5][2] = {{1. / n0, 0.}, {1. / na, a / na}, {1. / na, -a / na}, {1. / nb, b / nb}, {1. / nb, -b / nb}};
+    const int ra = pos / 5, rb = pos % 5;
+    double u = 0.;
+    for (int ii = 0; ii < 2; ii++) u += G[ra][ii] * (ef[ii][0] * G[rb][0] + ef[ii][1] * G[rb][1]);
+    dst[i] = (float)u;
+}
+
 int f4_mode() {   // DLPM_WINO_F4=0: keep every 3x3 layer on the F(2x2,3x3) kernel (default: F(4x4) where the shape qualifies)
     static int v = -1;
     if (v < 0) { const char *e = getenv("DLPM_WINO_F4"); v = e ? atoi(e) : 1; }
@@ -1570,6 +1933,82 @@ int relayout_weight_wino4(const float *oihw_dev, float *dst_dev, int Cout, int C
     DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, (size_t)F4_PAD * 256 * sizeof(float), st));
     const int nq = nq_in > 0 ? nq_in : f4_nq_of(Cout);
     k_relayout_weight_wino4<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, nq / 16);
+    DLPM_LAUNCH_CHECK();
+    return DLPM_OK;
+}
+
+// ---- the sub-pixel form of the Upsample convolutions (k_conv3x3_wino4sp)
+// DLPM_WINO4_SUBPIX=0 (A/B runs): those layers on the UPS instantiation of k_conv3x3_wino4 as before; their sub-pixel weights are not built
+bool wino4sp_enabled() {
+    static int v = -1;
+    if (v < 0) { const char *e = getenv("DLPM_WINO4_SUBPIX"); v = e ? atoi(e) : 1; }
+    return v != 0 && wino4_enabled();
+}
+
+// block shape of a layer with Cout output channels on low-res images of Hlo x Wlo pixels (the rule of wino4_geometry_nq on the low-res tiles)
+static bool wino4sp_block(int Cout, int Cin, int Hlo, int Wlo, int *bh, int *bw, int *nimg) {
+    if (Cout % F4_NQ != 0 || Cin % F4_KC != 0 || Hlo <= 0 || Wlo <= 0 || (Hlo & 3) || (Wlo & 3)) return false;
+    const int TH = Hlo / 4, TW = Wlo / 4;
+    int h, w, n;
+    if (TH * TW >= F4_TILES) {
+        w = TW < 4 ? TW : 4;
+        if (F4_TILES % w != 0) return false;
+        h = F4_TILES / w;
+        if (TW % w != 0 || TH % h != 0) return false;
+        n = 1;
+    } else {
+        if (F4_TILES % (TH * TW) != 0) return false;
+        h = TH; w = TW; n = F4_TILES / (TH * TW);
+    }
+    if (n > 4) return false;       // sixteen one-tile images (4x4 low-res): stays on the UPS instantiation
+    if (n * (4 * h + 1) * (4 * w + 1) > FS_RAWPIX) return false;
+    *bh = h; *bw = w; *nimg = n;
+    return true;
+}
+bool wino4sp_layer_ok(int Cout, int Cin, int Hlo, int Wlo) {
+    int h, w, n;
+    return wino4sp_enabled() && wino4sp_block(Cout, Cin, Hlo, Wlo, &h, &w, &n);
+}
+
+bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+    if (!c.ups || !c.w_wino4sp || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
+    if (c.Hout != 2 * c.Hin || c.Wout != 2 * c.Win || c.C0 % F4_KC != 0 || (c.R0 & 15) != 0 || c.ksplit > 1) return false;
+    return wino4sp_block(c.Cout, c.C0 + c.C1, c.Hin, c.Win, bh, bw, nimg);
+}
+
+// dispatch: a launch that the F(4x4) policy takes (wino4_preferred: generations AUTO and F4) on the 128-channel n-tile, and that carries the
+// sub-pixel weights -- a function of the layer and the declared policy only
+bool wino4sp_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+    int a, b, n;
+    if (!c.ups || !c.w_wino4sp || !wino4sp_enabled() || !wino4_preferred(c, &a, &b, &n) || wino4_nq_for(c) != F4_NQ) return false;
+    return wino4sp_geometry(c, bh, bw, nimg);
+}
+
+int launch_conv_wino4sp(const ConvLaunch &c, hipStream_t st) {
+    int bh, bw, nimg;
+    if (!wino4sp_geometry(c, &bh, &bw, &nimg)) {
+        set_error("launch_conv_wino4sp: unsupported shape");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+#ifdef DLPM_PHASE_TIMING
+    const_cast<ConvLaunch &>(c).phase = phase_buffer();
+#endif
+    const int64_t tiles = (int64_t)c.B * (c.Hin / 4) * (c.Win / 4);
+    const int64_t mblocks = nimg == 1 ? tiles / F4_TILES : ceil_div(c.B, nimg);
+    const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_wino4sp), 160 * 1024);
+    if (r != DLPM_OK) return r;
+    const size_t lds = (size_t)(2 * FS_VBUF + 2 * FS_RAWBUF + 2 * F4_CFS) * sizeof(float);
+    k_conv3x3_wino4sp<<<(unsigned)(mblocks * (c.Cout / F4_NQ) * 4), F4_NT, lds, st>>>(c, bh, bw, nimg);
+    DLPM_LAUNCH_CHECK();
+    return DLPM_OK;
+}
+
+int64_t wino4sp_weight_floats(int Cout, int Cin) { return (int64_t)4 * Cout * Cin * 26 + FS_PAD * 256; }
+
+int relayout_weight_wino4sp(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st) {
+    const int64_t n = (int64_t)4 * Cout * Cin * 26;
+    DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, (size_t)FS_PAD * 256 * sizeof(float), st));
+    k_relayout_weight_wino4sp<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

@@ -46,6 +46,7 @@ struct ConvW {            // one convolution's weights
     float *w_wino4 = nullptr;// 3x3 only: F(4x4,3x3) Winograd-domain weights (conv_wino4.hip), when DLPM_WINO_F4 is on
     float *w_wino4_n64 = nullptr, *w_wino4_n32 = nullptr;   // cout % 128 == 0, built while a SMALL dispatch batch is declared: the same weights in the
                              // fragment order of 64- / 32-channel n-tiles (narrow_wino4_copies)
+    float *w_wino4sp = nullptr; // Upsample convolutions with cout % 128 == 0: the parity classes' F(4x4,2x2) weights (conv_wino4.hip: k_conv3x3_wino4sp)
     float *w_small = nullptr;// 3x3 with cout <= 4 (head): [tap][cin][4]
     float *w_taps = nullptr; // 3x3 with cout <= 3 (head): [9 cout -> 32][cin], the head as a 1x1 GEMM + gather (conv_direct.hip)
     void *w_split = nullptr; // 1x1 with cout % 128 == 0, cin % 32 == 0: three bf16 planes in stage-tile order (conv_split.hip)
@@ -133,7 +134,7 @@ void plan_stats(const dlpm_unet *u, Bump &ws, Tensor4 &t, const ConvW &c, int B,
     t.stats_px = 0;
     if (off || (!c.use_igemm && !stem)) return;
     ConvLaunch L;
-    L.w_wino = c.w_wino; L.w_wino4 = c.w_wino4; L.w_wino4_n64 = c.w_wino4_n64; L.w_wino4_n32 = c.w_wino4_n32; L.w_split = c.w_split; L.ks = c.ks; L.stride = stride; L.ups = ups; L.Hout = t.H; L.Wout = t.W; L.Cout = c.cout;
+    L.w_wino = c.w_wino; L.w_wino4 = c.w_wino4; L.w_wino4_n64 = c.w_wino4_n64; L.w_wino4_n32 = c.w_wino4_n32; L.w_wino4sp = c.w_wino4sp; L.w_split = c.w_split; L.ks = c.ks; L.stride = stride; L.ups = ups; L.Hout = t.H; L.Wout = t.W; L.Cout = c.cout;
     L.Hin = ups ? t.H / 2 : t.H * stride; L.Win = ups ? t.W / 2 : t.W * stride;
     L.C0 = C0; L.C1 = c.cin - C0; L.B = B;
     L.in_nchw = stem ? 1 : 0;
@@ -311,7 +312,8 @@ void build_arch(dlpm_unet *u) {
     u->head = u->conv("out.2.", c.out_channels, mc, 3);
 }
 
-int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
+// ups_lo: low-res image size of an Upsample convolution (0: not one)
+int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
     ConvLaunch probe;
     probe.C0 = C0; probe.C1 = c.cin - C0; probe.Cout = c.cout; probe.ks = c.ks;
     probe.in_nchw = boundary == 1; probe.out_nchw = boundary == 2;
@@ -365,6 +367,11 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary) {  // boundary: 0 no
             DLPM_HIP(hipMalloc(&c.w_wino4, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)));
             r = relayout_weight_wino4(src, c.w_wino4, c.cout, c.cin, nullptr);
             if (r != DLPM_OK) return r;
+            if (ups_lo > 0 && wino4sp_layer_ok(c.cout, c.cin, ups_lo, ups_lo)) {   // sub-pixel copy of an Upsample convolution (104 floats per filter)
+                DLPM_HIP(hipMalloc(&c.w_wino4sp, (size_t)wino4sp_weight_floats(c.cout, c.cin) * sizeof(float)));
+                r = relayout_weight_wino4sp(src, c.w_wino4sp, c.cout, c.cin, nullptr);
+                if (r != DLPM_OK) return r;
+            }
         }
     }
     if (small_weight_ok(c.cout, c.cin, c.ks) && boundary == 0) {
@@ -384,6 +391,7 @@ void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
     L.w_wino4 = c.w_wino4;
     L.w_wino4_n64 = c.w_wino4_n64;
     L.w_wino4_n32 = c.w_wino4_n32;
+    L.w_wino4sp = c.w_wino4sp;
     L.w_small = c.w_small;
     L.w_taps = c.w_taps;
     L.w_hfused = c.w_hfused;
@@ -400,6 +408,7 @@ int run_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch L, hipStream_t st, c
     L.w_wino4 = c.w_wino4;
     L.w_wino4_n64 = c.w_wino4_n64;
     L.w_wino4_n32 = c.w_wino4_n32;
+    L.w_wino4sp = c.w_wino4sp;
     L.w_small = c.w_small;
     L.w_taps = c.w_taps;
     L.w_hfused = c.w_hfused;
@@ -909,6 +918,8 @@ static void free_conv(ConvW &c) {
     if (c.w_wino4_n64) (void)hipFree(c.w_wino4_n64);
     if (c.w_wino4_n32) (void)hipFree(c.w_wino4_n32);
     c.w_wino4_n64 = c.w_wino4_n32 = nullptr;
+    if (c.w_wino4sp) (void)hipFree(c.w_wino4sp);
+    c.w_wino4sp = nullptr;
     if (c.w_small) (void)hipFree(c.w_small);
     c.w_small = nullptr;
     if (c.w_taps) (void)hipFree(c.w_taps);
@@ -984,12 +995,15 @@ extern "C" int dlpm_unet_finalize(dlpm_unet *u) {
         }
     for_each_conv(u, free_conv);
     // per-conv weight layouts; C0 matters only for the concat inputs of the output blocks
+    int res = u->cfg.image_size;     // image size at the layer being prepared (as run_seq walks it)
     auto prep_seq = [&](std::vector<Layer> &s, int C0_first) -> int {
         for (size_t i = 0; i < s.size(); i++) {
             Layer &L = s[i];
             const bool cat = (i == 0 && L.kind == L_RES && C0_first > 0);
             const int C0 = cat ? C0_first : L.c1.cin;
-            TRY(prep_conv(u, L.c1, L.kind == L_STEM ? L.c1.cin : C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0));
+            TRY(prep_conv(u, L.c1, L.kind == L_STEM ? L.c1.cin : C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0));
+            if (L.kind == L_DOWN) res = (res - 1) / 2 + 1;
+            if (L.kind == L_UP) res *= 2;
             if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0));
             if (L.kind == L_RES && L.has_skip) TRY(prep_conv(u, L.skip, cat ? C0_first : L.skip.cin, 0));
         }
@@ -1295,7 +1309,16 @@ extern "C" void dlpm_unet_destroy(dlpm_unet *u) {
 // ---------------------------------------------------------------------------------------------
 // building-block entry points (parity tests call each kernel through the C ABI)
 // ---------------------------------------------------------------------------------------------
+static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream);
 extern "C" int dlpm_conv2d_f32(const dlpm_conv_args *a, float *scratch_dev, dlpm_stream_t stream) {
+    return conv2d_entry(a, scratch_dev, nullptr, nullptr, stream);
+}
+extern "C" int dlpm_conv2d_stats_f32(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(stats_out && stats_px, "dlpm_conv2d_stats_f32: null argument");
+    return conv2d_entry(a, scratch_dev, stats_out, stats_px, stream);
+}
+// stats_out: the launch also emits the GroupNorm statistics partials of its output (Winograd F(4x4) kernels only: force_direct bits 8 / 256)
+static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(a && a->src0 && a->weight && a->out && scratch_dev, "dlpm_conv2d_f32: null argument");
     DLPM_CHECK_ARG(a->ksize == 1 || a->ksize == 3, "dlpm_conv2d_f32: ksize must be 1 or 3");
     DLPM_CHECK_ARG(a->stride == 1 || a->stride == 2, "dlpm_conv2d_f32: stride must be 1 or 2");
@@ -1328,36 +1351,64 @@ extern "C" int dlpm_conv2d_f32(const dlpm_conv_args *a, float *scratch_dev, dlpm
         L.w_split = wsp;
         L.gemm = DLPM_GEMM_BF16X3;
     }
-    if (ig && a->ksize == 3 && !L.w_split && (a->C0 + a->C1) % 32 == 0 &&   // (the split copy sits where these would go)
-        a->scratch_floats >= (int64_t)a->Cout * (a->C0 + a->C1) * 9 + frag_weight_floats(a->Cout, a->C0 + a->C1)) {
-        float *wf = scratch_dev + (int64_t)a->Cout * (a->C0 + a->C1) * 9;
-        TRY(relayout_weight_frag(a->weight, wf, a->Cout, a->C0 + a->C1, st));
+    const int Cin_ = a->C0 + a->C1;
+    int64_t used = (int64_t)a->Cout * Cin_ * taps;
+    const bool wino_shape = a->ksize == 3 && !L.w_split && !(a->force_direct & 2) && a->stride == 1 && !a->in_nchw && !a->out_nchw;
+    if (ig && a->ksize == 3 && !L.w_split && Cin_ % 32 == 0 &&   // (the split copy sits where these would go)
+        a->scratch_floats >= used + frag_weight_floats(a->Cout, Cin_)) {
+        float *wf = scratch_dev + used;
+        TRY(relayout_weight_frag(a->weight, wf, a->Cout, Cin_, st));
         L.w_frag = wf;
-        int64_t used = (int64_t)a->Cout * (a->C0 + a->C1) * 9 + frag_weight_floats(a->Cout, a->C0 + a->C1);
-        const bool wino_shape = !(a->force_direct & 2) && a->stride == 1 && !a->in_nchw && !a->out_nchw;
-        if (wino_shape && a->Cout % 64 == 0 && a->scratch_floats >= used + wino_weight_floats(a->Cout, a->C0 + a->C1)) {
+        used += frag_weight_floats(a->Cout, Cin_);
+        if (wino_shape && a->Cout % 64 == 0 && a->scratch_floats >= used + wino_weight_floats(a->Cout, Cin_)) {
             float *ww = scratch_dev + used;
-            TRY(relayout_weight_wino(a->weight, ww, a->Cout, a->C0 + a->C1, st));
+            TRY(relayout_weight_wino(a->weight, ww, a->Cout, Cin_, st));
             L.w_wino = ww;
-            used += wino_weight_floats(a->Cout, a->C0 + a->C1);
-        }
-        // bit 8: the F(4x4,3x3) kernel where the shape qualifies (128-, 64- or 32-channel n-tiles; its weights go behind the F(2x2) copy)
-        if (wino_shape && (a->force_direct & 8) && a->Cout % 32 == 0 && (a->C0 + a->C1) % 8 == 0 &&
-            a->scratch_floats >= used + wino4_weight_floats(a->Cout, a->C0 + a->C1)) {
-            float *w4 = scratch_dev + used;
-            TRY(relayout_weight_wino4(a->weight, w4, a->Cout, a->C0 + a->C1, st));
-            L.w_wino4 = w4;
-            // bit 8 ASKS for the F(4x4) kernel: a geometry it rejects (e.g. 16 one-tile 4x4 images on a 64- / 32-channel n-tile: 576 halo
-            // pixels > F4_RAWPIX_N) is an error, not a silent drop to the implicit GEMM -- tests that compare "the F(4x4) kernel" with the
-            // default path must not pass for the wrong reason
-            int bh_, bw_, ni_;
-            if (!wino4_geometry(L, &bh_, &bw_, &ni_)) {
-                set_error("dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry");
-                return DLPM_ERR_UNSUPPORTED;
-            }
-            L.w_wino = nullptr;   // no F(2x2) alternative: the launch takes the F(4x4) kernel
+            used += wino_weight_floats(a->Cout, Cin_);
         }
     }
+    // bit 8: the F(4x4,3x3) kernel where the shape qualifies (128-, 64- or 32-channel n-tiles; its weights go behind the F(2x2) copy).  The
+    // kernel takes input channels in multiples of 8, also where the implicit GEMM (multiples of 32) does not
+    if (wino_shape && (a->force_direct & (8 | 256)) && a->Cout % 32 == 0 && Cin_ % 8 == 0 &&
+        a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
+        float *w4 = scratch_dev + used;
+        TRY(relayout_weight_wino4(a->weight, w4, a->Cout, Cin_, st));
+        L.w_wino4 = w4;
+        // bit 8 ASKS for the F(4x4) kernel: a geometry it rejects (e.g. 16 one-tile 4x4 images on a 64- / 32-channel n-tile: 576 halo
+        // pixels > F4_RAWPIX_N) is an error, not a silent drop to the implicit GEMM -- tests that compare "the F(4x4) kernel" with the
+        // default path must not pass for the wrong reason
+        int bh_, bw_, ni_;
+        if (!wino4_geometry(L, &bh_, &bw_, &ni_)) {
+            set_error("dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry");
+            return DLPM_ERR_UNSUPPORTED;
+        }
+        L.w_wino = nullptr;   // no F(2x2) alternative: the launch takes the F(4x4) kernel
+        used += wino4_weight_floats(a->Cout, Cin_);
+    }
+    // bit 256: an upsampling convolution through the sub-pixel kernel (four parity-class F(4x4,2x2) convolutions on the low-res image); its
+    // weights go behind the F(4x4,3x3) copy.  Like bit 8 it ASKS: a geometry or scratch size the kernel cannot take is an error
+    if (a->force_direct & 256) {
+        int bh_, bw_, ni_;
+        if (L.w_wino4 && a->Cout % 128 == 0 && a->scratch_floats >= used + wino4sp_weight_floats(a->Cout, Cin_)) {
+            L.w_wino4sp = scratch_dev + used;
+            if (wino4sp_preferred(L, &bh_, &bw_, &ni_)) TRY(relayout_weight_wino4sp(a->weight, scratch_dev + used, a->Cout, Cin_, st));
+            else L.w_wino4sp = nullptr;
+        }
+        if (!L.w_wino4sp) {
+            set_error("dlpm_conv2d_f32: force_direct bit 256 asks for the sub-pixel upsampling kernel, which does not take this geometry / scratch size");
+            return DLPM_ERR_UNSUPPORTED;
+        }
+    }
+    if (stats_out) {
+        const int px = L.w_wino4 ? conv_stats_pixels(L) : 0;
+        if (px <= 0) {
+            set_error("dlpm_conv2d_stats_f32: this launch emits no statistics (Winograd F(4x4) kernels on whole blocks or whole 8x8 images only)");
+            return DLPM_ERR_UNSUPPORTED;
+        }
+        L.stats_out = reinterpret_cast<float2 *>(stats_out);
+        *stats_px = px;
+    }
+    if (L.w_wino4 && !ig) return L.w_wino4sp ? launch_conv_wino4sp(L, st) : launch_conv_wino4(L, st);   // (input channels a multiple of 8 but not of 32)
     if ((a->force_direct & 64) && a->ksize == 3 && a->Cout <= 3 && a->C0 % 32 == 0 && a->C1 == 0) {
         // bit 64: the one-pass head kernel (head_fused.hip; in the UNet it also carries the sampler's update): W' fragments in scratch
         L.w_hfused = scratch_dev;

@@ -519,13 +519,18 @@ typedef struct dlpm_conv_args {
     int32_t in_nchw, out_nchw;  /* boundary layouts (direct kernel only) */
     int32_t force_direct;       /* bit 0: use the direct (non-MFMA) kernel regardless of shape; bit 1: no Winograd;
                                    bit 2: unused (its 1x1 weight-streaming kernel was removed; set, the call fails with
-                                   DLPM_ERR_UNSUPPORTED); bit 3: 3x3 through the
-                                   Winograd F(4x4,3x3) kernel where the shape qualifies (needs scratch for it);
+                                   DLPM_ERR_UNSUPPORTED); bit 3 (value 8): 3x3 through the
+                                   Winograd F(4x4,3x3) kernel where the shape qualifies (needs scratch for it; input channels in
+                                   multiples of 8 -- where they are no multiple of 32, which the implicit GEMM needs, the kernel
+                                   is launched directly);
                                    bit 4: 1x1, or 3x3 as an implicit GEMM, through the bf16-split kernel where the shape
                                    qualifies (scratch: + 1.5x weight); bit 5: the head (Cout <= 3) as a 1x1 GEMM onto its tap
                                    channels + gather; bit 6: the head as the one-pass kernel (tap channels stay in LDS; scratch >= 80 Cin
                                    floats), on the bf16 matrix pipe with the exact three-plane split; bit 7: with bit 6, on the
-                                   fp32 MFMA */
+                                   fp32 MFMA; bit 8 (value 256): an upsampling 3x3 (Cout % 128 == 0, low-res size a multiple of 4 and
+                                   not 4x4 itself) as four parity-class Winograd F(4x4,2x2) convolutions on the low-res image
+                                   (scratch: + 36 + 104 floats per filter behind the other copies); a geometry or scratch size it
+                                   cannot take fails with DLPM_ERR_UNSUPPORTED */
     int64_t scratch_floats;     /* size of scratch_dev in floats; room for a second, fragment-ordered copy of a
                                    3x3 weight (+1 KB per 32 output channels) enables the weight-streaming kernel */
 } dlpm_conv_args;
@@ -535,6 +540,12 @@ typedef struct dlpm_conv_args {
  * scratch buffer (scratch_dev, >= 2*weight bytes) -- test/bring-up entry point; the UNet handle
  * pre-transforms its weights once.  Replaces F.conv2d / conv1d / linear: unet.py:64,96,143,157,168,213,215. */
 int dlpm_conv2d_f32(const dlpm_conv_args *args, float *scratch_dev, dlpm_stream_t stream);
+/* Test / bring-up entry point like dlpm_conv2d_f32 (the UNet plan wires the statistics itself): the same launch, also emitting the fused
+ * GroupNorm statistics of its output as the plan consumes them (force_direct bit 3 (value 8) or bit 8 (value 256): the Winograd F(4x4)
+ * kernels; anything else: DLPM_ERR_UNSUPPORTED).  stats_out: [B][Hout*Wout / *stats_px][Cout][2] floats, (mean, centred sum of
+ * squares) of *stats_px output pixels each (256, or 64 = per image and, with bit 8 (value 256), parity class); room for
+ * B * Hout*Wout/64 * Cout * 2 floats is always enough.  k_gn_coeffs_stats merges an image's partials in index order. */
+int dlpm_conv2d_stats_f32(const dlpm_conv_args *args, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream);
 
 /* GroupNorm statistics -> per-(sample, channel) affine coefficients, optionally folding the
  * ResBlock scale/shift: y = GN(x)*(1+scale)+shift == x*A + B.  x is NHWC (virtual concat).

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Single-layer timing of the 3x3 stride-1 convolution kernels at the CIFAR step's launch shapes (developer tool).
 
-    python tools/bench_conv.py [--gen f4|auto|f2|igemm] [--reps N] [--check]
+    python tools/bench_conv.py [--gen f4|sp|auto|f2|igemm] [--reps N] [--only I] [--pairs N]
+
+--gen sp: the Upsample shapes through the sub-pixel kernel (force_direct 8 | 256), everything else as f4.  --pairs N: the Upsample
+shapes only, N times (f4, sp) alternating in one process -- the per-layer A/B table of the sub-pixel kernel.
 
 Prints ms per launch (HIP events around `reps` back-to-back launches, weights pre-transformed once through a throw-away
 dlpm_conv2d_f32 call is NOT possible -- that entry point re-lays the weights out on every call, so the relayout kernels are
@@ -29,6 +32,8 @@ SHAPES = [
     ('H16->32 256->256 ups', 1024, 256, 0, 16, 256, 1, False, False),
     ('H16 128->256 gn', 1024, 128, 0, 16, 256, 0, True, False),
 ]
+# the three Upsample convolutions of the CIFAR net (--pairs; index 6 above is the first)
+UPS_SHAPES = [SHAPES[6], ('H8->16 256->256 ups', 1024, 256, 0, 8, 256, 1, False, False), ('H4->8 256->256 ups', 1024, 256, 0, 4, 256, 1, False, False)]
 
 
 def run(name, B, C0, C1, H, Cout, ups, coef, res, gen, reps, zeros=False):
@@ -63,7 +68,7 @@ def run(name, B, C0, C1, H, Cout, ups, coef, res, gen, reps, zeros=False):
         keep.append(r)
         a.res0, a.R0 = r.data_ptr(), Cout
     a.out, a.Cout = out.data_ptr(), Cout
-    a.force_direct = {'auto': 0, 'f4': 8, 'f2': 0, 'igemm': 2}[gen]
+    a.force_direct = {'auto': 0, 'f4': 8, 'f2': 0, 'igemm': 2, 'sp': (8 | 256) if ups and H > 4 else 8}[gen]
     scratch = torch.empty(90 * w.numel() + 64 * 1024 * (1 + Cout // 32), device=DEV)
     a.scratch_floats = scratch.numel()
     st = _lib.stream_ptr()
@@ -82,7 +87,7 @@ def run(name, B, C0, C1, H, Cout, ups, coef, res, gen, reps, zeros=False):
             ms, fl, cls = float(t) / int(n), float(f) / int(n), nm
     dig = hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:12]
     print('%-24s %-14s %8.4f ms  %7.1f alg TFLOP/s  mfma-util %5.3f  out %s' % (
-        name, cls, ms, fl / ms / 1e9, (fl / ms / 1e9) * (0.25 if 'wino4' in cls else 16 / 36 if 'wino' in cls else 1) / 157.3, dig), flush=True)
+        name, cls, ms, fl / ms / 1e9, (fl / ms / 1e9) * (100 / 576 if 'wino4sp' in cls else 0.25 if 'wino4' in cls else 16 / 36 if 'wino' in cls else 1) / 157.3, dig), flush=True)
     return ms
 
 
@@ -90,8 +95,16 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--gen', default='f4')
 ap.add_argument('--reps', type=int, default=10)
 ap.add_argument('--only', type=int, default=-1)
+ap.add_argument('--pairs', type=int, default=0)
 ap.add_argument('--zeros', action='store_true', help='all-zero operands: the same instruction stream at the clock the chip holds without data toggling (DVFS check)')
 args = ap.parse_args()
+if args.pairs:
+    for k in range(args.pairs):
+        for s in UPS_SHAPES:
+            for gen in ('f4', 'sp'):
+                print('pair %d %-3s' % (k, gen), end=' ')
+                run(*s, gen=gen, reps=args.reps)
+    sys.exit(0)
 tot = 0.0
 for i, s in enumerate(SHAPES):
     if args.only >= 0 and i != args.only:
