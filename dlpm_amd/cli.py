@@ -13,6 +13,9 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_mmd REAL.npy --generate N: generate N samples and print the reference's multi-bandwidth Gaussian MMD between them and the
   first N float32 samples of REAL.npy (EvaluationManager.evaluate_mmd; images in [0, 1], 2-D points as they are).  May be combined
   with --out, not with --gen_data_path.  With --rng philox the figure does not depend on --batch_size.
+  --eval_prd REAL.npy --generate N [--prd_seed S]: generate N samples and print the reference's PRD figures between the first N float32
+  samples of REAL.npy and them (EvaluationManager.evaluate_prd: precision = max F_8, recall = max F_1/8 of the PRD curve, and their
+  F_1; 100 clusters above 2500 samples, else 20).  Together with --eval_mmd the samples are generated once and both are printed.
 """
 import argparse
 import os
@@ -92,11 +95,17 @@ def main(argv=None):
     ap.add_argument('--eval_mmd', default=None, metavar='REAL.npy',
                     help='with --generate N: MMD (the reference\'s MMD_loss, 5 Gaussian kernels) between the N generated samples and the '
                          'first N float32 samples of this file; prints `mmd <value> over <N> generated vs <N> real samples`')
+    ap.add_argument('--eval_prd', default=None, metavar='REAL.npy',
+                    help='with --generate N: PRD precision / recall (the reference\'s compute_precision_recall_curve + compute_f_beta) '
+                         'between the first N float32 samples of this file and the N generated samples; prints `prd precision <p> '
+                         'recall <r> f_1_pr <f> over <N> generated vs <N> real samples`')
+    ap.add_argument('--prd_seed', type=int, default=0, help='with --eval_prd: seed of the k-means++ draws')
     a = ap.parse_args(argv)
-    if a.eval_mmd and a.gen_data_path:
-        raise SystemExit('--eval_mmd cannot be combined with --gen_data_path')
-    if a.eval_mmd and a.generate is None:
-        raise SystemExit('--eval_mmd needs --generate N')
+    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd)):
+        if value and a.gen_data_path:
+            raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
+        if value and a.generate is None:
+            raise SystemExit('%s needs --generate N' % flag)
 
     p = dlpm_amd.load_config(a.config)
     p['device'] = 'cuda'
@@ -163,14 +172,28 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
-    if a.eval_mmd:
+    if a.eval_mmd or a.eval_prd:
         N = p['eval']['data_to_generate']
-        real = np.load(a.eval_mmd)
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
-        value, samples = ev.evaluate_mmd({'default': model}, real, N, p['eval']['batch_size'], class_labels=labels, return_samples=True)
+        value = samples = None
+        if a.eval_mmd:
+            real = np.load(a.eval_mmd)
+            value, samples = ev.evaluate_mmd({'default': model}, real, N, p['eval']['batch_size'], class_labels=labels, return_samples=True)
+            print('mmd %.9g over %d generated vs %d real samples' % (value, N, N))
+        if a.eval_prd:
+            if a.eval_prd != a.eval_mmd:
+                real = np.load(a.eval_prd)
+            if samples is None:                     # no --eval_mmd: generate here, the same way
+                samples, shape = ev._generate_flat({'default': model}, N, p['eval']['batch_size'], labels, {})
+                samples = samples.reshape((N,) + shape)
+            res = ev.evaluate_prd({'default': model}, real, N, p['eval']['batch_size'], seed=a.prd_seed, samples=samples)
+            print('prd precision %.9g recall %.9g f_1_pr %.9g over %d generated vs %d real samples' % (
+                res['precision'], res['recall'], res['f_1_pr'], N, N))
+            if value is not None:
+                res = dict(res, mmd=value)
+            value = res
         if a.out:
             np.save(a.out, samples.cpu().numpy())
-        print('mmd %.9g over %d generated vs %d real samples' % (value, N, N))
         return value
     if a.gen_data_path:
         assert is_image, '--gen_data_path dumps images; 2-D data has no image form'

@@ -9,11 +9,11 @@ are the reference's (`<gen_data_path>/<i>.png`, i counting over all chunks).  Wi
 dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so `device_batch` may enlarge the
 chunks beyond `eval.batch_size` without changing a pixel.
 
-The metrics half (FID / PRDC / Wasserstein / PRD precision and recall) needs third-party packages and Inception weights that are not
-available offline and is out of scope: `evals` keeps the reference's keys but nothing is appended to them -- except
-`losses`, which `evaluate_loss` fills with the one quality figure that needs nothing but the net and data: the
-reference's own objective (GenerativeLevyProcess.training_losses), forward only, on held-out samples; and `mmd`, which
-`evaluate_mmd` fills with the reference's multi-bandwidth Gaussian MMD (dlpm_amd/metrics.py) between generated and real samples.
+Of the metrics half, FID / PRDC need Inception weights and Wasserstein needs pyemd; they are out of scope and `evals` keeps the
+reference's keys for them with nothing appended.  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
+(GenerativeLevyProcess.training_losses), forward only, on held-out samples; `mmd`, which `evaluate_mmd` fills with the reference's
+multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
+the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device (dlpm_amd/metrics.py).
 """
 import copy
 import ctypes as C
@@ -234,6 +234,19 @@ class EvaluationManager:
         if class_labels is not None:
             class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
             assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
+        real = real[:N].reshape(N, -1)
+        assert real.shape[1] == gen.shape[1], 'evaluate_mmd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
+        value = metrics.mmd(gen, real.to(gen.device), kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
+        self.evals['mmd'].append(value)
+        if return_samples:
+            return value, gen.reshape((N,) + shape)
+        return value
+
+    def _generate_flat(self, models, N, batch_size, class_labels, kwargs):
+        """N samples in chunks of `batch_size`, like `_evaluate_model`: inside one dataset_stream(), on the device, without declaring a
+        batch, every chunk written after GenerationManager's post-processing into one [N, D] device buffer.  Returns (buffer, the
+        shape of one sample).  `class_labels`: None or an int64 host tensor of at least N labels."""
         batch_size = max(1, int(batch_size))
         stream = getattr(self.method, 'dataset_stream', None)
         gen, total = None, 0
@@ -248,13 +261,47 @@ class EvaluationManager:
                     gen = torch.empty((N, x[0].numel()), dtype=torch.float32, device=x.device)
                 gen[total:total + n] = x.reshape(n, -1)
                 total += n
+        return gen, shape
+
+    def evaluate_prd(self, models, real_data, data_to_generate, batch_size, class_labels=None, num_angles=201, num_clusters=None,
+                     seed=0, samples=None, **kwargs):
+        """PRD precision / recall (the reference's compute_precision_recall_curve + compute_f_beta, EvaluationManager.py:157-168)
+        between `real_data[:data_to_generate]` and `data_to_generate` generated samples: appends the max F_8 to `evals['precision']`,
+        the max F_1/8 to `evals['recall']` and 2 p r / (p + r) (0 when both vanish, :218-221) to `evals['f_1_pr']`, and returns them as
+        {'precision', 'recall', 'f_1_pr'}.  As in the reference the REAL data is the curve's `eval_data`.
+
+        The samples are generated as `evaluate_mmd` generates them (same chunk loop, so the same samples for the same method state),
+        or taken from `samples=` (e.g. `evaluate_mmd(..., return_samples=True)[1]`) without generating again.  `num_clusters=None`
+        is the reference's rule: 100 above 2500 samples, else 20.  `seed` seeds the k-means++ draws.  `density`, `coverage` and
+        `fid` are not touched."""
+        from . import metrics
+        N = int(data_to_generate)
+        assert N > 0, 'evaluate_prd: data_to_generate must be positive'
+        real = torch.as_tensor(real_data)
+        assert real.dtype == torch.float32, 'evaluate_prd takes float32 real_data, got %s' % real.dtype
+        assert real.shape[0] >= N, 'evaluate_prd: %d real samples for %d generated' % (real.shape[0], N)
+        if num_clusters is None:
+            num_clusters = 100 if N > 2500 else 20
+        if samples is not None:
+            gen = torch.as_tensor(samples)
+            assert gen.dtype == torch.float32, 'evaluate_prd takes float32 samples, got %s' % gen.dtype
+            assert gen.shape[0] == N, 'evaluate_prd: %d samples given for data_to_generate = %d' % (gen.shape[0], N)
+            gen = gen.reshape(N, -1)
+        else:
+            if class_labels is not None:
+                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+            gen, _ = self._generate_flat(models, N, batch_size, class_labels, kwargs)
         real = real[:N].reshape(N, -1)
-        assert real.shape[1] == gen.shape[1], 'evaluate_mmd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
-        value = metrics.mmd(gen, real.to(gen.device), kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
-        self.evals['mmd'].append(value)
-        if return_samples:
-            return value, gen.reshape((N,) + shape)
-        return value
+        assert real.shape[1] == gen.shape[1], 'evaluate_prd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
+        if gen.is_cuda:
+            real = real.to(gen.device)
+        _, _, parts = metrics.prd(real, gen, num_clusters=num_clusters, num_angles=num_angles, seed=seed, return_parts=True)
+        p, r = parts['f_beta']
+        res = {'precision': p, 'recall': r, 'f_1_pr': (2 * p * r) / (p + r) if p + r > 0 else 0.}
+        for k, v in res.items():
+            self.evals[k].append(v)
+        return res
 
     def generate_default(self, models, nsamples, **kwargs):
         self.gen_manager.generate(models, nsamples, **kwargs)

@@ -1,13 +1,18 @@
-"""Sample-quality metrics on the device.  One is built: the multi-bandwidth Gaussian MMD of the reference
-(bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153).
+"""Sample-quality metrics on the device.  Two are built: the multi-bandwidth Gaussian MMD of the reference
+(bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153) and its PRD
+precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168).
 
     mmd(source, target) -> float                      dlpm_mmd_f32: tiled pairwise reduction, no n x n array
     MMD_loss(kernel_mul, kernel_num)(source, target)  drop-in for the reference's class: a 0-dim fp32 tensor
+    kmeans(points, K) -> centres, labels, ...         dlpm_kmeans_f32: all run x init instances in one grid
+    prd(eval_data, ref_data) -> precision, recall     dlpm_prd_f32: clustering, histograms, curve and F pair in one enqueue sequence
+    compute_prd_from_embedding, compute_precision_recall_curve, prd_to_max_f_beta_pair, compute_f_beta
+                                                      drop-ins under the reference's names and signatures
 
 Inputs are float32 tensors or arrays [N, ...] (rows are flattened), on the host or the GPU; host inputs are copied once.
 Unequal counts are allowed (the reference's broadcast raises on them): sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2).
-`wass`, the PRD precision / recall and FID / PRDC need packages and weights that are not available and are not built; neither are
-the reference's unused get_MMD / MMDStatistic / MMD helpers."""
+`wass` needs pyemd, FID / PRDC need Inception weights; they are not built; neither are the reference's unused get_MMD / MMDStatistic /
+MMD helpers."""
 import numpy as np
 import torch
 
@@ -79,3 +84,191 @@ class MMD_loss(torch.nn.Module):
     def forward(self, source, target):
         out = mmd_device(source, target, self.kernel_mul, self.kernel_num, self.fix_sigma)[0].to(torch.float32)
         return out if torch.as_tensor(source).is_cuda else out.cpu()
+
+
+# ---------------------------------------------------------------------------------------------- PRD precision / recall
+MAX_CLUSTERS = 256
+MAX_WIDTH = 4096
+KMEANS_TOL = 1e-4          # sklearn's default: rounds stop at a centre shift <= tol * mean per-feature variance
+PRD_EPSILON = 1e-10        # compute_prd's default angle offset
+
+
+def _prd_points(a, name):
+    t = torch.as_tensor(a)
+    assert t.dtype == torch.float32, 'prd takes float32 %s, got %s' % (name, t.dtype)
+    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], 'prd: %s needs at least one point, got shape %s' % (
+        name, tuple(t.shape))
+    return t.reshape(t.shape[0], -1)
+
+
+def _prd_check(eval_data, ref_data, num_clusters, num_runs, n_init, max_iter):
+    x, y = _prd_points(eval_data, 'eval_data'), _prd_points(ref_data, 'ref_data')
+    assert x.shape[1] == y.shape[1], 'prd: eval_data rows hold %d values, ref_data rows %d' % (x.shape[1], y.shape[1])
+    assert x.shape[1] <= MAX_WIDTH, 'prd: rows of at most %d values, got %d' % (MAX_WIDTH, x.shape[1])
+    n = x.shape[0] + y.shape[0]
+    assert int(num_clusters) == num_clusters and 1 <= num_clusters <= min(MAX_CLUSTERS, n), (
+        'prd: num_clusters must be in [1, min(%d, number of points = %d)], got %r' % (MAX_CLUSTERS, n, num_clusters))
+    for v, name in ((num_runs, 'num_runs'), (n_init, 'n_init'), (max_iter, 'max_iter')):
+        assert int(v) == v and v >= 1, 'prd: %s must be a positive integer, got %r' % (name, v)
+    assert num_runs * n_init <= 65535, 'prd: num_runs * n_init must be at most 65535'
+    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    return x.to(dev).contiguous(), y.to(dev).contiguous(), dev
+
+
+def _curve_check(num_angles, epsilon, beta):
+    if not (int(num_angles) == num_angles and 3 <= num_angles <= 1e6):          # prd_score.py:78-81 raises ValueError on these
+        raise ValueError('num_angles must be in [3, 1e6] but is %s.' % (num_angles,))
+    if not 0 < epsilon < 0.1:
+        raise ValueError('epsilon must be in (0, 0.1] but is %s.' % str(epsilon))
+    if beta <= 0:
+        raise ValueError('Given parameter beta %s must be positive.' % str(beta))
+
+
+def _workspace(L, n1, n2, D, K, R, n_init, dev):
+    nbytes = L.dlpm_prd_workspace_bytes(n1, n2, D, K, R, n_init)
+    if nbytes < 0:
+        _lib.check(int(nbytes))
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def _kmeans_device(x, y, dev, K, runs, n_init, max_iter, seed, tol, first_run):
+    L = _lib.lib()
+    n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    with torch.cuda.device(dev):
+        ws, nbytes = _workspace(L, n1, n2, D, K, runs, n_init, dev)
+        centres = torch.empty((runs, K, D), dtype=torch.float64, device=dev)
+        labels = torch.empty((runs, n1 + n2), dtype=torch.uint8, device=dev)
+        counts = torch.empty((runs, 2, K), dtype=torch.int32, device=dev)
+        inertia = torch.empty(runs, dtype=torch.float64, device=dev)
+        iters = torch.empty(runs, dtype=torch.int32, device=dev)
+        conv = torch.empty(runs, dtype=torch.int32, device=dev)
+        _lib.check(L.dlpm_kmeans_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, K, runs, n_init, max_iter, float(tol), int(seed), first_run,
+                                     ws.data_ptr(), nbytes, centres.data_ptr(), labels.data_ptr(), counts.data_ptr(), inertia.data_ptr(),
+                                     iters.data_ptr(), conv.data_ptr(), _lib.stream_ptr()))
+    return centres, labels, counts, inertia, iters, conv
+
+
+def kmeans(points, K, n_init=10, max_iter=100, seed=0, runs=1, tol=KMEANS_TOL, first_run=0):
+    """Full-batch k-means of float32 `points` [n >= 2, ...]: `runs` independent clusterings, each the best of `n_init` k-means++
+    seedings (lowest inertia, lowest index on ties), all runs x inits advancing together on the device.  Returns numpy arrays
+    (centres [runs, K, D] float64, labels [runs, n] uint8, inertia [runs] float64, iterations [runs], converged [runs] bool).
+    Rounds stop at a centre shift <= tol * mean per-feature variance (sklearn's rule); `converged` is set where a round left
+    every centre unchanged, i.e. every centre IS the mean of the points labelled with it (always reached with tol=0 and enough
+    rounds).  Run r draws from (seed, first_run + r): it is the same whether computed alone or beside others."""
+    pts = _prd_points(points, 'points')
+    assert pts.shape[0] >= 2, 'kmeans: needs at least two points, got %d' % pts.shape[0]
+    assert tol >= 0, 'kmeans: tol must not be negative, got %r' % (tol,)
+    assert int(first_run) == first_run and first_run >= 0, 'kmeans: first_run must be a non-negative integer, got %r' % (first_run,)
+    h = pts.shape[0] // 2
+    x, y, dev = _prd_check(pts[:h], pts[h:], K, runs, n_init, max_iter)
+    centres, labels, counts, inertia, iters, conv = _kmeans_device(x, y, dev, int(K), int(runs), int(n_init), int(max_iter), seed, tol,
+                                                                   int(first_run))
+    return (centres.cpu().numpy(), labels.cpu().numpy(), inertia.cpu().numpy(), iters.cpu().numpy(), conv.cpu().numpy().astype(bool))
+
+
+def _prd_run(eval_data, ref_data, num_clusters, num_angles, num_runs, n_init, max_iter, seed, centers, beta, epsilon, parts):
+    _curve_check(num_angles, epsilon, beta)
+    K, A = num_clusters, int(num_angles)
+    if centers is not None:
+        c = torch.as_tensor(centers)
+        assert c.dtype == torch.float64 and c.dim() == 3, 'prd: centers must be float64 [runs, clusters, D], got %s %s' % (
+            c.dtype, tuple(c.shape))
+        num_runs, K, n_init = int(c.shape[0]), int(c.shape[1]), 1
+    x, y, dev = _prd_check(eval_data, ref_data, K, num_runs, n_init, max_iter)
+    K, R = int(K), int(num_runs)
+    n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        ws, nbytes = _workspace(L, n1, n2, D, K, R, int(n_init), dev)
+        out = torch.empty(2 * A + 3, dtype=torch.float64, device=dev)
+        extra = None
+        if centers is not None:
+            assert c.shape[2] == D, 'prd: centers hold %d values per row, the points %d' % (c.shape[2], D)
+            c = c.to(dev).contiguous()
+            labels = torch.empty((R, n1 + n2), dtype=torch.uint8, device=dev)
+            counts = torch.empty((R, 2, K), dtype=torch.int32, device=dev)
+            inertia = torch.empty(R, dtype=torch.float64, device=dev)
+            _lib.check(L.dlpm_prd_histograms_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, K, R, c.data_ptr(), ws.data_ptr(), nbytes,
+                                                 labels.data_ptr(), counts.data_ptr(), inertia.data_ptr(), _lib.stream_ptr()))
+            _lib.check(L.dlpm_prd_curve_f64(counts.data_ptr(), n1, n2, K, R, A, float(epsilon), float(beta), ws.data_ptr(), nbytes,
+                                            out.data_ptr(), _lib.stream_ptr()))
+            extra = (c, labels, counts)
+        else:
+            if parts:
+                extra = (torch.empty((R, K, D), dtype=torch.float64, device=dev), torch.empty((R, n1 + n2), dtype=torch.uint8, device=dev),
+                         torch.empty((R, 2, K), dtype=torch.int32, device=dev))
+            ptrs = [t.data_ptr() for t in extra] if extra else [None, None, None]
+            _lib.check(L.dlpm_prd_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, K, R, int(n_init), int(max_iter), KMEANS_TOL, int(seed), A,
+                                      float(epsilon), float(beta), ws.data_ptr(), nbytes, ptrs[0], ptrs[1], ptrs[2], out.data_ptr(),
+                                      _lib.stream_ptr()))
+    return out, extra
+
+
+def prd_device(eval_data, ref_data, num_clusters=20, num_angles=1001, num_runs=10, n_init=10, max_iter=100, seed=0, centers=None,
+               beta=8, epsilon=PRD_EPSILON):
+    """The call itself, without a host synchronisation: a float64 [2 * num_angles + 3] tensor on the GPU holding precision[A],
+    recall[A], max F_beta, max F_1/beta and the largest precision / recall of any run before clipping.  Enqueued on the current
+    stream; it can be captured in a torch.cuda.graph."""
+    return _prd_run(eval_data, ref_data, num_clusters, num_angles, num_runs, n_init, max_iter, seed, centers, beta, epsilon, False)[0]
+
+
+def _raise_above_one(out):
+    if float(out[-1]) > 1.001:                                     # prd_score.py:99-101
+        raise ValueError('Detected value > 1.001, this should not happen.')
+
+
+def prd(eval_data, ref_data, num_clusters=20, num_angles=1001, num_runs=10, n_init=10, max_iter=100, seed=0, centers=None,
+        return_parts=False):
+    """PRD curve of `eval_data` against `ref_data` (prd_score.py:139-191): (precision, recall), float64 arrays [num_angles].
+    `centers` [runs, clusters, D] float64 skips the clustering (num_runs, num_clusters and n_init then come from its shape).
+    `return_parts=True` adds a dict: 'centers' [R, K, D] float64, 'labels' [R, n1 + n2] uint8 (eval points first), 'eval_bins' and
+    'ref_bins' [R, K] int32 counts, 'f_beta' = (max F_8, max F_1/8)."""
+    out, extra = _prd_run(eval_data, ref_data, num_clusters, num_angles, num_runs, n_init, max_iter, seed, centers, 8, PRD_EPSILON,
+                          return_parts)
+    o = out.cpu().numpy()
+    _raise_above_one(o)
+    A = int(num_angles)
+    if not return_parts:
+        return o[:A], o[A:2 * A]
+    counts = extra[2].cpu().numpy()
+    return o[:A], o[A:2 * A], {'centers': extra[0].cpu().numpy(), 'labels': extra[1].cpu().numpy(), 'eval_bins': counts[:, 0],
+                               'ref_bins': counts[:, 1], 'f_beta': (float(o[2 * A]), float(o[2 * A + 1]))}
+
+
+def compute_prd_from_embedding(eval_data, ref_data, num_clusters=20, num_angles=1001, num_runs=10, enforce_balance=True):
+    """prd_score.py:139-191 under its own name and signature.  ValueError on unequal counts unless enforce_balance=False; unequal
+    counts then work, each set's histogram normalised by its own count."""
+    if enforce_balance and len(eval_data) != len(ref_data):
+        raise ValueError('The number of points in eval_data %d is not equal to the number of points in ref_data %d. To disable this '
+                         'exception, set enforce_balance to False (not recommended).' % (len(eval_data), len(ref_data)))
+    return prd(eval_data, ref_data, num_clusters=num_clusters, num_angles=num_angles, num_runs=num_runs)
+
+
+def compute_precision_recall_curve(data, gen_samples, num_angles=201, num_clusters=20):
+    """prd_legacy.py:6-11 under its own name and signature, argument order included: the REAL data goes in as `eval_data` and the
+    generated samples as `ref_data` (so the reference's 'precision' figure is F_8 of that orientation).  Kept as it is, not "fixed":
+    the figures are compared with the reference's."""
+    n = len(data)
+    data, gen = torch.as_tensor(data), torch.as_tensor(gen_samples)
+    return compute_prd_from_embedding(data.reshape(n, -1), gen.reshape(n, -1), num_angles=num_angles, num_clusters=num_clusters)
+
+
+def prd_to_max_f_beta_pair(precision, recall, beta=8):
+    """prd_score.py:230-262 on the host (a few hundred values): (max F_beta, max F_1/beta) of a curve."""
+    precision, recall = np.asarray(precision, np.float64), np.asarray(recall, np.float64)
+    if not ((precision >= 0).all() and (precision <= 1).all()):
+        raise ValueError('All values in precision must be in [0, 1].')
+    if not ((recall >= 0).all() and (recall <= 1).all()):
+        raise ValueError('All values in recall must be in [0, 1].')
+    if beta <= 0:
+        raise ValueError('Given parameter beta %s must be positive.' % str(beta))
+
+    def f(b):
+        return np.max((1 + b ** 2) * (precision * recall) / ((b ** 2 * precision) + recall + 1e-10))
+    return f(beta), f(1 / beta)
+
+
+def compute_f_beta(prec, rec):
+    """prd_legacy.py:13-15."""
+    a, b = prd_to_max_f_beta_pair(prec, rec)
+    return np.array([a, b])

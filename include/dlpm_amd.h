@@ -351,6 +351,51 @@ int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2,
                  double fix_sigma, void *workspace_dev, int64_t workspace_bytes, double *out_dev, dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-quality metric: the PRD precision / recall of bem/evaluate/prd_score.py (compute_prd_from_embedding :139-191, compute_prd
+ * :48-105, _cluster_into_bins :108-136, prd_to_max_f_beta_pair :230-262; called through prd_legacy.py:6-16 at
+ * EvaluationManager.py:157-168) between eval points x [n1, D] and reference points y [n2, D], fp32 rows on the device.
+ * The union [x; y] is clustered num_runs times into num_clusters cells; run r gives the histograms eval_r[k] / n1 and ref_r[k] / n2;
+ * with slopes = tan(linspace(eps, pi/2 - eps, A)):  precision_r[a] = sum_k min(ref_r[k] slope_a, eval_r[k]),  recall_r = precision_r /
+ * slope, both clipped to [0, 1] and averaged over the runs;  F_b = (1 + b^2) p r / (b^2 p + r + 1e-10), maximised over the curve for
+ * b = beta and b = 1 / beta.  The reference clusters with sklearn's MiniBatchKMeans(n_init=10), one fit after the other; here every
+ * (run, init) pair is an instance of full-batch k-means (k-means++ seeding from Philox draws keyed by (seed, run, init, step), Lloyd
+ * rounds until the centre shift is <= tol * mean per-feature variance or max_iter rounds), and all instances advance together in one
+ * grid.  Distances, sums, centres and the curve are fp64; ties go to the lowest centre index; no floating-point atomics and fixed
+ * summation orders: the same inputs give the same bits, and run r does not depend on how many runs are computed with it.  Every call
+ * is one enqueue sequence without a host synchronisation (it can be captured in a hipGraph).
+ * Shapes: D <= 4096, num_clusters in [1, 256] and <= n1 + n2, num_runs * n_init <= 65535.  Labels are bytes.
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of workspace any of the calls below needs on these shapes; DLPM_ERR_ARG (-1) for a shape they refuse. */
+int64_t dlpm_prd_workspace_bytes(int64_t n1, int64_t n2, int64_t D, int32_t num_clusters, int32_t num_runs, int32_t n_init);
+
+/* k-means of the union, runs first_run .. first_run + num_runs - 1 of the seed; per run the init of lowest inertia (lowest index on
+ * ties): centres [R][K][D] fp64, labels [R][n1 + n2], counts [R][2][K] (eval, ref), inertia [R], Lloyd rounds used [R], and
+ * converged [R] = 1 where a round left every centre unchanged (the labels then reproduce the centres exactly). */
+int dlpm_kmeans_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, int32_t num_clusters, int32_t num_runs,
+                    int32_t n_init, int32_t max_iter, double tol, uint64_t seed, int32_t first_run, void *workspace_dev,
+                    int64_t workspace_bytes, double *centres_out_dev, uint8_t *labels_out_dev, int32_t *counts_out_dev,
+                    double *inertia_out_dev, int32_t *iters_out_dev, int32_t *converged_out_dev, dlpm_stream_t stream);
+
+/* _cluster_into_bins after the fit: labels, counts and inertia of GIVEN centres [R][K][D]. */
+int dlpm_prd_histograms_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, int32_t num_clusters,
+                            int32_t num_runs, const double *centres_dev, void *workspace_dev, int64_t workspace_bytes,
+                            uint8_t *labels_out_dev, int32_t *counts_out_dev, double *inertia_out_dev, dlpm_stream_t stream);
+
+/* counts [R][2][K] -> out_dev[0 .. A) = precision, [A .. 2A) = recall, then (max F_beta, max F_1/beta, the largest precision or recall
+ * of any run BEFORE clipping: the reference raises ValueError above 1.001).  Workspace: 24 bytes per 256 angles. */
+int dlpm_prd_curve_f64(const int32_t *counts_dev, int64_t n1, int64_t n2, int32_t num_clusters, int32_t num_runs, int32_t num_angles,
+                       double epsilon, double beta, void *workspace_dev, int64_t workspace_bytes, double *out_dev, dlpm_stream_t stream);
+
+/* The three chained on one stream; out_dev as dlpm_prd_curve_f64.  centres / labels / counts outputs may be null.
+ * All four: DLPM_ERR_ARG for a null pointer, n1 < 1, n2 < 1, D < 1, D > 4096, num_clusters outside [1, 256] or above n1 + n2,
+ * num_angles outside [3, 1e6], epsilon outside (0, 0.1), beta <= 0, num_runs / n_init / max_iter < 1; DLPM_ERR_NOMEM for a short
+ * workspace (which must be 16-byte aligned) -- before any launch. */
+int dlpm_prd_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, int32_t num_clusters, int32_t num_runs,
+                 int32_t n_init, int32_t max_iter, double tol, uint64_t seed, int32_t num_angles, double epsilon, double beta,
+                 void *workspace_dev, int64_t workspace_bytes, double *centres_out_dev, uint8_t *labels_out_dev,
+                 int32_t *counts_out_dev, double *out_dev, dlpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generated-image dump: what EvaluationManager does with each chunk of samples,
  * bem/evaluate/EvaluationManager.py:174-196 -- `tvu.save_image(samples[i], f"{i+total}.png")` per sample.
  * ------------------------------------------------------------------------------------------ */

@@ -24,6 +24,7 @@ Fixture families:
   F16 class-conditional  UNetModel(num_classes=10) forwards, p_sample_loop / ddim_sample_loop with model_kwargs={'y': y}   unet.py:341-342, 463-481
   F17 held-out loss      training_losses / training_losses_dlpm with every draw recorded   GenerativeLevyProcess.py:581-677, dlpm.py:384-401
   F18 MMD                MMD_loss(kernel_mul, kernel_num)(source, target) on fp32 and on fp64 inputs, with the bandwidth   bem/evaluate/mmd_loss.py:5-37
+  F19 PRD                compute_prd_from_embedding / compute_precision_recall_curve + compute_f_beta with every k-means fit recorded   bem/evaluate/prd_score.py:48-262, prd_legacy.py:6-15
   F12 mean types         p_mean_variance: START_X / Z / PREVIOUS_X, denoised_fn, model_kwargs   GenerativeLevyProcess.py:154-219
   F11 image quantisation PIL's float -> 8-bit path (torchvision absent)  bem/evaluate/EvaluationManager.py:188-190
   F9 checkpoints         TrainingManager.save/load, EMAHelper,    bem/TrainingManager.py:240-285, bem/utils_ema.py,
@@ -1209,6 +1210,101 @@ def f18_mmd():
         print('    %-14s ref32 %.9g  ref32 - ref64 %.3g  bandwidth %.9g' % (name, float(r32), float(r32) - float(r64), float(b64)))
 
 
+# (name, n1 = n2, D, clusters, angles, runs of the recorded call, kind, shift of the second set's mean)
+F19_CASES = [
+    ('toy500_k20', 500, 2, 20, 201, 4, 'normal', 0.5),
+    ('toy3000_k100', 3000, 2, 100, 201, 2, 'normal', 0.3),       # the > 2500 rule's cluster count
+    ('heavy2000_k20', 2000, 2, 20, 201, 4, 'student', 0.3),      # Student-t(2) clamped to +-6: duplicate points on the boundary
+    ('same400_k20', 400, 2, 20, 201, 4, 'same', 0.0),            # P = Q: values at 1
+    ('disjoint300_k20', 300, 2, 20, 201, 4, 'normal', 40.0),     # precision ~ 0: the epsilon terms
+    ('k7_n64', 64, 2, 7, 11, 3, 'normal', 0.5),                  # below one workgroup, odd cluster count
+    ('d3', 300, 3, 20, 201, 4, 'normal', 0.5),
+    ('d16', 300, 16, 20, 201, 4, 'normal', 0.3),                 # the last width of the direct form
+    ('d17', 300, 17, 20, 201, 4, 'normal', 0.3),                 # the first width of the tiled form
+    ('d48', 300, 48, 20, 201, 3, 'normal', 0.2),
+    ('d192', 300, 192, 20, 201, 2, 'normal', 0.1),
+]
+F19_SEED = 19
+F19_SPREAD_CALLS = 8
+
+
+def f19_prd():
+    """The reference's PRD code, loaded by file path, on seeded inputs, with sklearn.cluster.MiniBatchKMeans replaced by a subclass
+    that records every fit (and fixes random_state per run of the recorded call).  Stored per case: the inputs, the recorded call's
+    centres / labels / inertia / histograms per run, its curve and F pair, the smallest gap between a point's nearest and
+    second-nearest squared centre distance (fp64), and F19_SPREAD_CALLS further UNSEEDED calls of compute_precision_recall_curve +
+    compute_f_beta at its own defaults: the reference's run-to-run spread.  Asserted here: the gap is at least 1e-10 max |p|^2 and the
+    recorded labels are the fp64 argmin of sum (p - c)^2 over the recorded centres."""
+    import importlib.util
+    import time
+    import types
+    import sklearn.cluster
+    pkg = types.ModuleType('ref_prd')
+    pkg.__path__ = []
+    sys.modules['ref_prd'] = pkg
+    mods = {}
+    for name in ('prd_score', 'prd_legacy'):
+        spec = importlib.util.spec_from_file_location('ref_prd.' + name, os.path.join(REF, 'bem', 'evaluate', name + '.py'))
+        mods[name] = importlib.util.module_from_spec(spec)
+        sys.modules['ref_prd.' + name] = mods[name]
+        spec.loader.exec_module(mods[name])
+    score, legacy = mods['prd_score'], mods['prd_legacy']
+    real_cls = sklearn.cluster.MiniBatchKMeans
+
+    class Recording(real_cls):
+        seeds, fits = [], []
+
+        def fit(self, X, y=None, sample_weight=None):
+            if Recording.seeds:
+                self.random_state = Recording.seeds.pop(0)
+            out = super().fit(X, y, sample_weight)
+            Recording.fits.append((self.cluster_centers_.copy(), self.labels_.copy(), float(self.inertia_)))
+            return out
+
+    sklearn.cluster.MiniBatchKMeans = Recording
+    try:
+        for i, (name, n, D, K, A, R, kind, shift) in enumerate(F19_CASES):
+            rs = np.random.RandomState(F19_SEED * 100 + i)
+            if kind == 'student':
+                x = np.clip(rs.standard_t(2, size=(n, D)), -6, 6).astype(np.float32)
+                y = np.clip(rs.standard_t(2, size=(n, D)) + shift, -6, 6).astype(np.float32)
+            else:
+                x = rs.standard_normal((n, D)).astype(np.float32)
+                y = x.copy() if kind == 'same' else (rs.standard_normal((n, D)) + shift).astype(np.float32)
+            Recording.seeds, Recording.fits = [F19_SEED * 1000 + 10 * i + r for r in range(R)], []
+            precision, recall = score.compute_prd_from_embedding(x, y, num_clusters=K, num_angles=A, num_runs=R)
+            assert len(Recording.fits) == R and not Recording.seeds
+            centers = np.stack([f[0] for f in Recording.fits]).astype(np.float64)
+            labels = np.stack([f[1] for f in Recording.fits])
+            inertia = np.array([f[2] for f in Recording.fits])
+            p = np.concatenate([x, y]).astype(np.float64)
+            margin = np.inf
+            for r in range(R):
+                d2 = ((p[:, None, :] - centers[r][None, :, :]) ** 2).sum(2)
+                assert np.array_equal(d2.argmin(1), labels[r]), '%s run %d: recorded labels are not the fp64 argmin' % (name, r)
+                two = np.partition(d2, 1, axis=1)[:, :2]
+                margin = min(margin, float((two[:, 1] - two[:, 0]).min()))
+            assert margin >= 1e-10 * float((p ** 2).sum(1).max()), (name, margin)
+            eval_bins = np.stack([np.bincount(labels[r][:n], minlength=K) for r in range(R)])
+            ref_bins = np.stack([np.bincount(labels[r][n:], minlength=K) for r in range(R)])
+            f_pair = np.array(score.prd_to_max_f_beta_pair(precision, recall))
+            fb, secs = [], []
+            for _ in range(F19_SPREAD_CALLS):
+                t0 = time.time()
+                curve = legacy.compute_precision_recall_curve(torch.from_numpy(x), torch.from_numpy(y), num_clusters=K)
+                secs.append(time.time() - t0)
+                fb.append(legacy.compute_f_beta(*curve))
+            fb = np.stack(fb)
+            save('f19_prd_' + name, x=x, y=y, centers64=centers, labels=labels.astype(np.uint8), inertia=inertia,
+                 eval_bins=eval_bins.astype(np.int64), ref_bins=ref_bins.astype(np.int64), precision=precision, recall=recall,
+                 f_pair=f_pair, min_margin=np.array(margin), fb_calls=fb, ref_seconds=np.array(float(np.median(secs))),
+                 num_clusters=np.array(K), num_angles=np.array(A))
+            print('    %-16s f_pair %.6f %.6f  margin %.3g  fb mean %.6f %.6f  range %.3g %.3g  %.2f s/call' % (
+                name, f_pair[0], f_pair[1], margin, fb[:, 0].mean(), fb[:, 1].mean(), np.ptp(fb[:, 0]), np.ptp(fb[:, 1]), np.median(secs)))
+    finally:
+        sklearn.cluster.MiniBatchKMeans = real_cls
+
+
 def f8_generation_manager():
     class FakeMethod:
         device = 'cpu'
@@ -1398,9 +1494,9 @@ def f10_lim():
 
 
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16', 'f17', 'f18']
+    which = sys.argv[1:] or ['f11', 'f1', 'f2', 'f3', 'f4', 'f5', 'f5u', 'f5w', 'f5k', 'f5b', 'f5c', 'f6', 'f7', 'f8', 'f9', 'f10', 'f12', 'f13', 'f14', 'f15', 'f16', 'f17', 'f18', 'f19']
     table = dict(f12=f12_mean_types, f11=f11_image_quantise, f10=f10_lim, f1=f1_schedule, f2=f2_noise, f3=f3_tables, f4=f4_single_step, f5=f5_trajectories, f5u=f5_unet_trajectory, f5w=f5_wide_unet_trajectory, f5k=f5_unet_trajectories_T1000, f5b=f5_bounded_unet_trajectories, f5c=f5_cifar_teacher_forced,
-                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f17=f17_loss, f18=f18_mmd, f8=f8_generation_manager, f9=f9_checkpoints)
+                 f6=f6_models, f7=f7_layers, f13=f13_small_blocks, f14=f14_blocks16, f15=f15_geometry, f16=f16_conditional, f17=f17_loss, f18=f18_mmd, f19=f19_prd, f8=f8_generation_manager, f9=f9_checkpoints)
     with torch.no_grad():
         for w in which:
             table[w]()
