@@ -157,6 +157,7 @@ SIGNATURES = {
     'dlpm_conv2d_f32': (C.c_int, [C.POINTER(ConvArgs), vp, vp]),
     'dlpm_conv2d_stats_f32': (C.c_int, [C.POINTER(ConvArgs), vp, vp, C.POINTER(i32), vp]),
     'dlpm_groupnorm_coeffs_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, i64, vp, vp, vp]),
+    'dlpm_groupnorm_coeffs_from_stats_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, i64, vp, vp, vp]),
     'dlpm_attention_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     'dlpm_attention_general_f32': (C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     'dlpm_resblock_small_f32': (C.c_int, [C.POINTER(ResBlockArgs), vp, i64, vp]),

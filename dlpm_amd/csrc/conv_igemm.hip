@@ -877,7 +877,7 @@ __global__ void __launch_bounds__(256) k_conv_stem_regw(ConvLaunch p, int ppb) {
             d = acc.w - K.w; s1.w += d; s2.w = fmaf(d, d, s2.w);
         }
     }
-    if (do_stats) {   // per-thread (mean, M2) -> LDS [pl_n][Cout] -> threads < Cout merge the pl_n partials (Chan)
+    if (do_stats) {   // per-thread (mean, M2) -> LDS [pl_n][Cout] -> one thread per channel merges the pl_n partials (Chan)
         __shared__ float2 part[1024];
         const float fc = (float)(ppb / pl_n);
         const float mx = s1.x / fc, my = s1.y / fc, mz = s1.z / fc, mw = s1.w / fc;
@@ -886,16 +886,16 @@ __global__ void __launch_bounds__(256) k_conv_stem_regw(ConvLaunch p, int ppb) {
         part[pl * p.Cout + nq * 4 + 2] = make_float2(K.z + mz, fmaxf(s2.z - s1.z * mz, 0.f));
         part[pl * p.Cout + nq * 4 + 3] = make_float2(K.w + mw, fmaxf(s2.w - s1.w * mw, 0.f));
         __syncthreads();
-        if ((int)threadIdx.x < p.Cout) {
-            float mean = part[threadIdx.x].x, M2 = part[threadIdx.x].y, na = fc;
+        for (int c = threadIdx.x; c < p.Cout; c += 256) {   // (Cout up to 1024: more channels than threads)
+            float mean = part[c].x, M2 = part[c].y, na = fc;
             for (int g = 1; g < pl_n; g++) {
-                const float2 q = part[g * p.Cout + threadIdx.x];
+                const float2 q = part[g * p.Cout + c];
                 const float d = q.x - mean, N = na + fc;
                 mean += d * (fc / N);
                 M2 += q.y + d * d * (na * fc / N);
                 na = N;
             }
-            p.stats_out[(int64_t)blockIdx.x * p.Cout + threadIdx.x] = make_float2(mean, M2);
+            p.stats_out[(int64_t)blockIdx.x * p.Cout + c] = make_float2(mean, M2);
         }
     }
 }
@@ -967,7 +967,7 @@ __global__ void __launch_bounds__(256) k_conv_stem_lds(ConvLaunch p, int ppb) {
             d = acc.w - K.w; s1.w += d; s2.w = fmaf(d, d, s2.w);
         }
     }
-    if (do_stats) {   // per-thread (mean, M2) -> LDS [pl_n][Cout] -> threads < Cout merge the pl_n partials (Chan)
+    if (do_stats) {   // per-thread (mean, M2) -> LDS [pl_n][Cout] -> one thread per channel merges the pl_n partials (Chan)
         __syncthreads();   // the patch is dead: its LDS carries the partials
         float2 *part = reinterpret_cast<float2 *>(patch);
         const float fc = (float)(ppb / pl_n);
@@ -977,16 +977,16 @@ __global__ void __launch_bounds__(256) k_conv_stem_lds(ConvLaunch p, int ppb) {
         part[pl * p.Cout + nq * 4 + 2] = make_float2(K.z + mz, fmaxf(s2.z - s1.z * mz, 0.f));
         part[pl * p.Cout + nq * 4 + 3] = make_float2(K.w + mw, fmaxf(s2.w - s1.w * mw, 0.f));
         __syncthreads();
-        if ((int)threadIdx.x < p.Cout) {
-            float mean = part[threadIdx.x].x, M2 = part[threadIdx.x].y, na = fc;
+        for (int c = threadIdx.x; c < p.Cout; c += 256) {   // (Cout up to 1024: more channels than threads)
+            float mean = part[c].x, M2 = part[c].y, na = fc;
             for (int g = 1; g < pl_n; g++) {
-                const float2 q = part[g * p.Cout + threadIdx.x];
+                const float2 q = part[g * p.Cout + c];
                 const float d = q.x - mean, N = na + fc;
                 mean += d * (fc / N);
                 M2 += q.y + d * d * (na * fc / N);
                 na = N;
             }
-            p.stats_out[(int64_t)blockIdx.x * p.Cout + threadIdx.x] = make_float2(mean, M2);
+            p.stats_out[(int64_t)blockIdx.x * p.Cout + c] = make_float2(mean, M2);
         }
     }
 }

@@ -1317,7 +1317,8 @@ extern "C" int dlpm_conv2d_stats_f32(const dlpm_conv_args *a, float *scratch_dev
     DLPM_CHECK_ARG(stats_out && stats_px, "dlpm_conv2d_stats_f32: null argument");
     return conv2d_entry(a, scratch_dev, stats_out, stats_px, stream);
 }
-// stats_out: the launch also emits the GroupNorm statistics partials of its output (Winograd F(4x4) kernels only: force_direct bits 8 / 256)
+// stats_out: the launch also emits the GroupNorm statistics partials of its output, wherever the route the selectors pick can emit them
+// (conv_stats_pixels > 0 on the MFMA dispatch, the directly launched F(4x4) kernels and the stem kernels -- the routes plan_stats admits)
 static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(a && a->src0 && a->weight && a->out && scratch_dev, "dlpm_conv2d_f32: null argument");
     DLPM_CHECK_ARG(a->ksize == 1 || a->ksize == 3, "dlpm_conv2d_f32: ksize must be 1 or 3");
@@ -1400,9 +1401,14 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
         }
     }
     if (stats_out) {
-        const int px = L.w_wino4 ? conv_stats_pixels(L) : 0;
+        // the direct kernel (force_direct bit 0, or a shape neither the MFMA kernels nor the stem kernels take) has no statistics epilogue
+        // (the head kernels dispatched below have none either, and are never reached with px > 0: they take Cout <= 4, which igemm_supported
+        //  admits only with NCHW output, where conv_stats_pixels is 0 on every route; with !ig only the stem has px > 0, and its 1 or 3 input
+        //  channels are not the C0 % 32 == 0 of a head kernel.  A head route that one day emits statistics has to be added to this gate.)
+        const bool stem = !ig && !(a->force_direct & 1) && conv_takes_stem(L);
+        const int px = (ig || L.w_wino4 || stem) ? conv_stats_pixels(L) : 0;
         if (px <= 0) {
-            set_error("dlpm_conv2d_stats_f32: this launch emits no statistics (Winograd F(4x4) kernels on whole blocks or whole 8x8 images only)");
+            set_error("dlpm_conv2d_stats_f32: this launch emits no statistics (its kernel has no statistics epilogue, or its partials would not lie inside one image)");
             return DLPM_ERR_UNSUPPORTED;
         }
         L.stats_out = reinterpret_cast<float2 *>(stats_out);
@@ -1455,6 +1461,21 @@ extern "C" int dlpm_groupnorm_coeffs_f32(const float *src0, const float *src1, i
                    C0 + C1, groups);
     return launch_gn_coeffs(src0, src1, C0, C1, B, HW, groups, gamma, beta, ss, ss_stride, ss_offset, coefA, coefB,
                             as_stream(stream));
+}
+
+extern "C" int dlpm_groupnorm_coeffs_from_stats_f32(const float *st0, const float *st1, int32_t C0, int32_t C1, int32_t B, int32_t nt0,
+                                                    int32_t nt1, int32_t HW, int32_t groups, const float *gamma, const float *beta,
+                                                    const float *ss, int64_t ss_stride, int64_t ss_offset, float *coefA, float *coefB,
+                                                    dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(st0 && gamma && beta && coefA && coefB, "dlpm_groupnorm_coeffs_from_stats_f32: null argument");
+    DLPM_CHECK_ARG((C1 == 0) == (st1 == nullptr), "dlpm_groupnorm_coeffs_from_stats_f32: st1/C1 mismatch");
+    DLPM_CHECK_ARG(groups > 0 && (C0 + C1) % groups == 0, "dlpm_groupnorm_coeffs_from_stats_f32: %d channels not divisible by %d groups",
+                   C0 + C1, groups);
+    DLPM_CHECK_ARG(C0 > 0 && C1 >= 0 && B > 0 && HW > 0, "dlpm_groupnorm_coeffs_from_stats_f32: C0 %d, C1 %d, B %d, HW %d", C0, C1, B, HW);
+    DLPM_CHECK_ARG(nt0 > 0 && HW % nt0 == 0 && (C1 == 0 || (nt1 > 0 && HW % nt1 == 0)),
+                   "dlpm_groupnorm_coeffs_from_stats_f32: %d / %d partials do not divide %d pixels", nt0, nt1, HW);
+    return launch_gn_coeffs_from_stats(reinterpret_cast<const float2 *>(st0), reinterpret_cast<const float2 *>(st1), C0, C1, B, nt0,
+                                       C1 ? nt1 : 1, HW, groups, gamma, beta, ss, ss_stride, ss_offset, coefA, coefB, as_stream(stream));
 }
 
 extern "C" int dlpm_attention_f32(const float *qkv, float *out, int32_t B, int32_t T, int32_t C, int32_t heads,

@@ -586,10 +586,14 @@ typedef struct dlpm_conv_args {
  * pre-transforms its weights once.  Replaces F.conv2d / conv1d / linear: unet.py:64,96,143,157,168,213,215. */
 int dlpm_conv2d_f32(const dlpm_conv_args *args, float *scratch_dev, dlpm_stream_t stream);
 /* Test / bring-up entry point like dlpm_conv2d_f32 (the UNet plan wires the statistics itself): the same launch, also emitting the fused
- * GroupNorm statistics of its output as the plan consumes them (force_direct bit 3 (value 8) or bit 8 (value 256): the Winograd F(4x4)
- * kernels; anything else: DLPM_ERR_UNSUPPORTED).  stats_out: [B][Hout*Wout / *stats_px][Cout][2] floats, (mean, centred sum of
- * squares) of *stats_px output pixels each (256, or 64 = per image and, with bit 8 (value 256), parity class); room for
- * B * Hout*Wout/64 * Cout * 2 floats is always enough.  k_gn_coeffs_stats merges an image's partials in index order. */
+ * GroupNorm statistics of its output as the plan consumes them.  Every route the selectors of dlpm_conv2d_f32 reach that has a statistics
+ * epilogue serves it: the implicit-GEMM, halo and bf16-split kernels, the Winograd F(2x2) and F(4x4) kernels (sub-pixel form included) and
+ * the NCHW stem kernels; a launch whose kernel emits none (the direct kernel, NCHW output, R0 % 4 != 0, partials that would straddle
+ * images, ...) fails with DLPM_ERR_UNSUPPORTED -- the condition under which the plan reads the tensor instead.
+ * stats_out: [B][Hout*Wout / *stats_px][Cout][2] floats, (mean, centred sum of squares) of *stats_px output pixels each: 128 consecutive
+ * NHWC pixels (implicit-GEMM family), 64 = one 8x8 image, 128 / 256 pixels of one F(2x2) block, 256 of one 16x16 F(4x4) block (with bit 8
+ * (value 256): per block and parity class), 1024 consecutive pixels (stem); room for B * Hout*Wout/64 * Cout * 2 floats is always enough.
+ * k_gn_coeffs_stats merges an image's partials in index order. */
 int dlpm_conv2d_stats_f32(const dlpm_conv_args *args, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream);
 
 /* GroupNorm statistics -> per-(sample, channel) affine coefficients, optionally folding the
@@ -600,6 +604,13 @@ int dlpm_groupnorm_coeffs_f32(const float *src0, const float *src1, int32_t C0, 
                               int32_t groups, const float *gamma_dev, const float *beta_dev,
                               const float *ss_dev, int64_t ss_stride, int64_t ss_offset,
                               float *coefA_dev, float *coefB_dev, dlpm_stream_t stream);
+
+/* The same coefficients from the statistics partials the convolution epilogues emit (dlpm_conv2d_stats_f32) instead of the tensor: what
+ * the UNet plan runs wherever a GroupNorm's producers carry statistics.  st0 / st1: [B][nt0][C0][2] / [B][nt1][C1][2] floats of the two
+ * concat sources (st1 NULL with C1 == 0), nt partials of HW / nt pixels each per image (HW % nt == 0; the sources may differ in nt). */
+int dlpm_groupnorm_coeffs_from_stats_f32(const float *st0, const float *st1, int32_t C0, int32_t C1, int32_t B, int32_t nt0, int32_t nt1,
+                                         int32_t HW, int32_t groups, const float *gamma_dev, const float *beta_dev, const float *ss_dev,
+                                         int64_t ss_stride, int64_t ss_offset, float *coefA_dev, float *coefB_dev, dlpm_stream_t stream);
 
 /* QKVAttention over qkv[B,T,3C] (NHWC; channel layout head-major [head][q|k|v][C/heads] as produced
  * by the reference's reshape) -> out[B,T,C].  QK^T and PV on the fp32 MFMA, softmax in fp32.

@@ -1,0 +1,439 @@
+"""The fused GroupNorm statistics of every convolution kernel against float64: the (mean, M2) partials each epilogue writes into
+ConvLaunch::stats_out (dlpm_conv2d_stats_f32), and the chain partials -> k_gn_coeffs_stats (dlpm_groupnorm_coeffs_from_stats_f32)
+-> x * A + B against F.group_norm in float64.  The reference of every check is the fp32 OUTPUT THE KERNEL WROTE, so only the
+statistics arithmetic is on trial (the convolutions themselves are judged in test_gpu_kernels.py).
+
+Statistics-writing site -> cases that reach it (CASES below; `sel` is dlpm_conv_args::force_direct):
+  epilogue_rows (conv_igemm.hip, MODE 0 of k_conv_igemm)           m0_1x1_32to96_16, m0_1x1_concat_32_32to96_16; cancel_generic_rows
+  epilogue_rows_full (igemm_epilogue.h, MODE 2)                     g1_1x1_64to64_16_b2, g1_1x1_concat_64_32to128_16; cancel_full_rows
+  epilogue_rows_full (MODE 1)                                       m1_3x3s2_32to32_32to16_b2, m1_3x3s2_concat_32_32to32; halo_ups_32to64_8to16 under DLPM_NO_WS=1
+                                                                    (halo_ok refuses upsampling without the weight-streaming form: k_conv_igemm, full tiles)
+  k_conv3x3_halo_ws -> epilogue_rows (sel 2)                        halo_32to32_16, halo_64to128_32, halo_ups_32to64_8to16, halo_concat_32_32to32_16; cancel_halo
+  k_conv3x3_halo -> epilogue_rows (sel 2, DLPM_NO_WS=1)             the other halo_* cases and cancel_halo in the child of test_variant_behind_switch[DLPM_NO_WS=1]
+  k_conv_split<4, ..> -> epilogue_rows_full (sel 16)                split_1x1_128to128_16, split_3x3s2_128to128_32to16, split_1x1_concat_64_64to128_16
+  k_conv_split_pipe, per 8x8 image from registers (sel 16)          split_1x1_128to128_8_b3, split_1x1_concat_64_64to128_8; cancel_split_8x8
+  k_conv_split<8, 1, 1>, the same (sel 16, DLPM_SPLIT_PIPE=0)       those cases in the child of test_variant_behind_switch[DLPM_SPLIT_PIPE=0]
+  k_conv3x3_wino_q (F(2x2), conv_wino.hip)                          f2_64to64_16, f2_64to64_32, f2_32to128_16, f2_concat_32_32to64_16; cancel_f2
+  k_conv3x3_wino4, 128-channel n-tile, per 16x16 block (sel 8)      f4_32to128_16, f4_32to128_32, f4_ups_32to128_8to16, f4_concat_16_16to128_16; cancel_f4_block
+  k_conv3x3_wino4, 128-channel n-tile, per 8x8 image (sel 8)        f4_32to128_8_b5; cancel_f4_image
+  k_conv3x3_wino4, 64- / 32-channel n-tiles (sel 8)                 f4n_32to64_16, f4n_32to32_16, f4n_32to96_16, f4n_32to64_8_b5, f4n_concat_32_32to64_16;
+                                                                    f4n_32to32_32 in the child of test_variant_behind_switch[DLPM_WINO4_IMG=0]
+  k_conv3x3_wino4_img (whole 32x32 image, sel 8)                    f4n_32to32_32
+  k_conv_stem_lds (in_nchw)                                         stem_c{1,3}_{32,128,512}_{32b2,64}; cancel_stem
+  k_conv_stem_regw (in_nchw, DLPM_NO_STEM_LDS=1)                    stem cases in the child of test_variant_behind_switch[DLPM_NO_STEM_LDS=1]
+  k_gn_coeffs_stats / gn_coeffs_from_stats_image (gn_stats.h)       test_chain_* (every case above), test_chain_concat_unequal_partials (nt0 != nt1)
+(The sub-pixel kernel's partials: test_gpu_upsample_subpixel.py.  The whole-block kernels' own statistics: test_gpu_kernels.py.)
+
+Bounds.  Partials: |mean - want| < 1e-5 and |M2 - want| / (1 + want) < 1e-5 (the fused blocks' and the sub-pixel test's statistics
+tolerances).  Chain: 3e-6 plain, 4e-6 with scale-shift + SiLU (test_groupnorm_coeffs_against_reference_fixture's, O(1) GroupNorm
+output).  Cancellation cases (|mean| = 100 >> std = 0.05 out of the kernels themselves): 2e-4 for the partials and for the chain, the
+bound and derivation of test_groupnorm_large_offset_is_stable (five chain cases: CANCEL_CHAIN_BOUND, twice their measurement).  x * A + B is evaluated in float64 from the fp32 coefficients, as that
+test does: the coefficients are what the kernels produce."""
+import functools
+import hashlib
+import math
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from dlpm_amd import _lib
+from test_gpu_kernels import DEV, L, run_conv, st
+
+pytestmark = pytest.mark.gpu
+
+ROWS = 'rows'        # px consecutive NHWC pixels per partial (px = H W: the whole image)
+
+
+def BLK(bh, bw):     # blocks of bh x bw output pixels, row-major inside the image
+    return (bh, bw)
+
+
+# name, sel, ks, stride, ups, B, C0, C1, H (input), Cout, coef + SiLU, residual, px, slot layout
+CASES = [
+    # implicit GEMM, default selector: MODE 2 (1x1, full tiles), MODE 0 (Cout % bn != 0), MODE 1 (full tiles, not 1x1 stride 1)
+    ('g1_1x1_64to64_16_b2', 0, 1, 1, 0, 2, 64, 0, 16, 64, False, True, 128, ROWS),           # two tiles per image, two images
+    ('g1_1x1_concat_64_32to128_16', 0, 1, 1, 0, 2, 64, 32, 16, 128, True, False, 128, ROWS),
+    ('m0_1x1_32to96_16', 0, 1, 1, 0, 2, 32, 0, 16, 96, False, True, 128, ROWS),              # 96 of a 128-channel n-tile: the channel guard
+    ('m0_1x1_concat_32_32to96_16', 0, 1, 1, 0, 1, 32, 32, 16, 96, True, False, 128, ROWS),
+    ('m1_3x3s2_32to32_32to16_b2', 0, 3, 2, 0, 2, 32, 0, 32, 32, True, False, 128, ROWS),
+    ('m1_3x3s2_concat_32_32to32', 0, 3, 2, 0, 1, 32, 32, 32, 32, False, True, 128, ROWS),
+    # halo kernels (selector 2: no Winograd)
+    ('halo_32to32_16', 2, 3, 1, 0, 2, 32, 0, 16, 32, False, True, 128, ROWS),
+    ('halo_64to128_32', 2, 3, 1, 0, 1, 64, 0, 32, 128, True, False, 128, ROWS),              # eight tiles of four rows
+    ('halo_ups_32to64_8to16', 2, 3, 1, 1, 2, 32, 0, 8, 64, False, True, 128, ROWS),
+    ('halo_concat_32_32to32_16', 2, 3, 1, 0, 1, 32, 32, 16, 32, True, False, 128, ROWS),
+    # bf16 x 3 split kernel (selector 16): row epilogue of the 4-wave shape, per-image partials of the 8-wave / pipelined shape
+    ('split_1x1_128to128_16', 16, 1, 1, 0, 2, 128, 0, 16, 128, True, False, 128, ROWS),
+    ('split_3x3s2_128to128_32to16', 16, 3, 2, 0, 1, 128, 0, 32, 128, False, True, 128, ROWS),
+    ('split_1x1_concat_64_64to128_16', 16, 1, 1, 0, 1, 64, 64, 16, 128, False, True, 128, ROWS),
+    ('split_1x1_128to128_8_b3', 16, 1, 1, 0, 3, 128, 0, 8, 128, False, True, 64, ROWS),      # M = 192: a full and a half tile, three slots
+    ('split_1x1_concat_64_64to128_8', 16, 1, 1, 0, 2, 64, 64, 8, 128, True, False, 64, ROWS),
+    # Winograd F(2x2,3x3) (default selector, Cout % 64 == 0): one partial per wino_geometry block = 64 tiles (16 x 16 pixels) on
+    # 64-channel n-tiles, 32 tiles (8 rows x 16 columns) on 128-channel ones
+    ('f2_64to64_16', 0, 3, 1, 0, 2, 64, 0, 16, 64, False, True, 256, BLK(16, 16)),
+    ('f2_64to64_32', 0, 3, 1, 0, 1, 64, 0, 32, 64, True, False, 256, BLK(16, 16)),
+    ('f2_32to128_16', 0, 3, 1, 0, 2, 32, 0, 16, 128, True, False, 128, BLK(8, 16)),
+    ('f2_concat_32_32to64_16', 0, 3, 1, 0, 1, 32, 32, 16, 64, False, True, 256, BLK(16, 16)),
+    # Winograd F(4x4,3x3), 128-channel n-tile (selector 8): 16 x 16-pixel blocks row-major, or one partial per 8x8 image
+    ('f4_32to128_16', 8, 3, 1, 0, 2, 32, 0, 16, 128, False, True, 256, BLK(16, 16)),
+    ('f4_32to128_32', 8, 3, 1, 0, 1, 32, 0, 32, 128, True, False, 256, BLK(16, 16)),
+    ('f4_32to128_8_b5', 8, 3, 1, 0, 5, 32, 0, 8, 128, False, True, 64, BLK(8, 8)),           # four images per block, last block ragged
+    ('f4_ups_32to128_8to16', 8, 3, 1, 1, 2, 32, 0, 8, 128, True, False, 256, BLK(16, 16)),
+    ('f4_concat_16_16to128_16', 8, 3, 1, 0, 1, 16, 16, 16, 128, True, False, 256, BLK(16, 16)),   # C0 % 32 != 0: launched directly
+    # ... 64- and 32-channel n-tiles (Cout 96: three 32-channel n-tiles), and the whole-image kernel (32 channels on 32x32: quadrants)
+    ('f4n_32to64_16', 8, 3, 1, 0, 2, 32, 0, 16, 64, False, True, 256, BLK(16, 16)),
+    ('f4n_32to32_16', 8, 3, 1, 0, 2, 32, 0, 16, 32, True, False, 256, BLK(16, 16)),
+    ('f4n_32to96_16', 8, 3, 1, 0, 1, 32, 0, 16, 96, False, True, 256, BLK(16, 16)),
+    ('f4n_32to64_8_b5', 8, 3, 1, 0, 5, 32, 0, 8, 64, True, False, 64, BLK(8, 8)),
+    ('f4n_concat_32_32to64_16', 8, 3, 1, 0, 1, 32, 32, 16, 64, True, False, 256, BLK(16, 16)),
+    ('f4n_32to32_32', 8, 3, 1, 0, 2, 32, 0, 32, 32, True, True, 256, BLK(16, 16)),
+]
+# stem (NCHW input, no table / activation / residual): 1024 consecutive pixels; Cout = 512 has more channels than the block has threads
+for _c0 in (1, 3):
+    for _co in (32, 128, 512):
+        CASES.append(('stem_c%d_%d_32b2' % (_c0, _co), 'nchw', 3, 1, 0, 2, _c0, 0, 32, _co, False, False, 1024, ROWS))   # one per image
+        CASES.append(('stem_c%d_%d_64' % (_c0, _co), 'nchw', 3, 1, 0, 1, _c0, 0, 64, _co, False, False, 1024, ROWS))     # four partials
+# cancellation (test_cancellation_*): bias = 100 + 0.3 randn per channel, convolution term of std 0.05; one per epilogue family, with
+# 4 channels per group and B = 2 as in test_groupnorm_large_offset_is_stable (5 per group where the route needs Cout % 128 != 0)
+CANCEL = [
+    ('cancel_generic_rows', 0, 1, 1, 0, 2, 32, 0, 16, 160, False, False, 128, ROWS),
+    ('cancel_full_rows', 0, 1, 1, 0, 2, 64, 0, 16, 128, False, False, 128, ROWS),
+    ('cancel_halo', 2, 3, 1, 0, 2, 32, 0, 16, 128, False, False, 128, ROWS),
+    ('cancel_split_8x8', 16, 1, 1, 0, 2, 128, 0, 8, 128, False, False, 64, ROWS),
+    ('cancel_f2', 0, 3, 1, 0, 2, 64, 0, 16, 128, False, False, 128, BLK(8, 16)),
+    ('cancel_f4_block', 8, 3, 1, 0, 2, 32, 0, 16, 128, False, False, 256, BLK(16, 16)),
+    ('cancel_f4_image', 8, 3, 1, 0, 2, 32, 0, 8, 128, False, False, 64, BLK(8, 8)),
+    ('cancel_stem', 'nchw', 3, 1, 0, 2, 3, 0, 32, 128, False, False, 1024, ROWS),
+]
+# producers of test_chain_concat_unequal_partials only
+EXTRA = [
+    ('g1_1x1_64to64_32', 0, 1, 1, 0, 2, 64, 0, 32, 64, False, True, 128, ROWS),
+    ('f4n_32to32_8_b2', 8, 3, 1, 0, 2, 32, 0, 8, 32, True, False, 64, BLK(8, 8)),
+    ('split_1x1_128to128_8_b2', 16, 1, 1, 0, 2, 128, 0, 8, 128, True, False, 64, ROWS),
+]
+BY_NAME = {c[0]: c for c in CASES + CANCEL + EXTRA}
+assert len(BY_NAME) == len(CASES) + len(CANCEL) + len(EXTRA)
+
+# Bounds of a case's partials, (mean, M2), where they are not the default 1e-5 / 1e-5.
+# The cancellation cases: 2e-4 (see the module docstring).
+# stem_c3_512_64: M2 at twice the 1.214e-5 measured against float64 on MI355X.  With 512 output channels a stem block has 2 pixels in
+# flight, so a thread's shifted sums run over 512 pixels in sequence before the one Chan merge: 512 fp32 accumulations of (v - K)^2
+# around a pivot K that is a single sample.  The error grows with that run length, at every input width -- measured M2 errors:
+#   Cout = 128 (runs of 128 pixels): 0.83e-6 .. 1.72e-6 over the four stem_c*_128_* cases;  Cout = 512 (runs of 512): stem_c1_512_32b2 5.60e-6,
+#   stem_c3_512_32b2 6.50e-6, stem_c1_512_64 6.85e-6, stem_c3_512_64 1.21e-5 (2048 partials, the most of any case).
+PARTIALS_BOUND = {'stem_c3_512_64': (1e-5, 2 * 1.214e-05)}
+PARTIALS_BOUND.update({c[0]: (2e-4, 2e-4) for c in CANCEL})
+
+
+def make(name):
+    """Seeded inputs as in test_conv; the cancellation cases as test_groupnorm_large_offset_is_stable, produced by the kernel."""
+    _, sel, ks, stride, ups, B, C0, C1, H, Cout, act, use_res, px, lay = BY_NAME[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    Cin = C0 + C1
+    x0 = torch.randn(B, C0, H, H, generator=g)
+    x1 = torch.randn(B, C1, H, H, generator=g) if C1 else None
+    w = torch.randn(Cout, Cin, ks, ks, generator=g) / math.sqrt(Cin * ks * ks)
+    bias = torch.randn(Cout, generator=g)
+    if name.startswith('cancel_'):
+        w, bias = 0.05 * w, 100.0 + 0.3 * bias
+    coef = (1 + 0.3 * torch.randn(B, Cin, generator=g), 0.3 * torch.randn(B, Cin, generator=g)) if act else None
+    Ho = (H * (2 if ups else 1) + 2 * (ks // 2) - ks) // stride + 1
+    res = torch.randn(B, Cout, Ho, Ho, generator=g) if use_res else None
+    kw = dict(stride=stride, ups=ups, coef=coef, silu=act, res=res)
+    if sel == 'nchw':
+        kw['in_nchw'] = True
+    else:
+        kw['force_direct'] = sel
+    return (x0, w, bias, x1), kw
+
+
+@functools.lru_cache(maxsize=None)
+def produce(name):
+    """One launch with statistics per case, shared by the tests (and never modified): (NCHW output, whole NaN-prefilled statistics
+    buffer, pixels per partial)."""
+    args, kw = make(name)
+    return run_conv(*args, stats=True, **kw)
+
+
+def partial_pixels(out, px, lay):
+    """[B][slot][C][px] float64: the output pixels behind each statistics slot, in the slot order of the route."""
+    B, Cc, H, W = out.shape
+    o = out.double()
+    if lay == ROWS:
+        return o.permute(0, 2, 3, 1).reshape(B, H * W // px, px, Cc).permute(0, 1, 3, 2)
+    bh, bw = lay
+    assert bh * bw == px
+    return o.reshape(B, Cc, H // bh, bh, W // bw, bw).permute(0, 2, 4, 1, 3, 5).reshape(B, (H // bh) * (W // bw), Cc, px)
+
+
+def check_partials(name):
+    """The four properties of a route's partials; returns (max mean error, max relative M2 error, finite prefix of the buffer)."""
+    _, sel, ks, stride, ups, B, C0, C1, H, Cout, act, use_res, px_want, lay = BY_NAME[name]
+    out, buf, px = produce(name)
+    args, kw = make(name)
+    plain = run_conv(*args, **kw)
+    assert torch.equal(out, plain), '%s: the launch with statistics wrote another output than the launch without' % name
+    assert px == px_want, (name, px, px_want)
+    HW = out.shape[2] * out.shape[3]
+    n = 2 * B * (HW // px) * Cout
+    assert n <= buf.numel()
+    fin = torch.isfinite(buf)
+    assert bool(fin[:n].all()), '%s: %d of the first %d statistics floats were never written (first at %d)' % (
+        name, int((~fin[:n]).sum()), n, int((~fin[:n]).nonzero()[0]))
+    assert bool(torch.isnan(buf[n:]).all()), '%s: statistics written past the B * (HW / px) * Cout slots the plan allocates' % name
+    part = buf[:n].view(B, HW // px, Cout, 2).double()
+    pix = partial_pixels(out, px, lay)
+    want_m = pix.mean(-1)
+    want_M2 = ((pix - want_m[..., None]) ** 2).sum(-1)
+    e_m = (part[..., 0] - want_m).abs().max().item()
+    e_M2 = ((part[..., 1] - want_M2).abs() / (1 + want_M2)).max().item()
+    tol_m, tol_M2 = PARTIALS_BOUND.get(name, (1e-5, 1e-5))
+    print('%s: px %d, %d slots, max |mean - fp64| %.3g (bound %.3g), max |M2 - fp64| / (1 + M2) %.3g (bound %.3g)' % (
+        name, px, n // 2, e_m, tol_m, e_M2, tol_M2))
+    assert e_m < tol_m and e_M2 < tol_M2, (name, e_m, e_M2)
+    return e_m, e_M2, buf[:n]
+
+
+def coeffs_from_stats(srcs, B, HW, gam, bet, ss=None, ss_stride=0, ss_offset=0):
+    """dlpm_groupnorm_coeffs_from_stats_f32 over one or two sources (flat partials, channels, partials per image)."""
+    dev = [s[0].to(DEV).contiguous() for s in srcs]
+    C0, nt0 = srcs[0][1:]
+    C1, nt1 = srcs[1][1:] if len(srcs) > 1 else (0, 1)
+    Cc = C0 + C1
+    gd, bd = gam.to(DEV), bet.to(DEV)
+    ssd = ss.to(DEV) if ss is not None else None
+    cA, cB = torch.empty(B, Cc, device=DEV), torch.empty(B, Cc, device=DEV)
+    _lib.check(L().dlpm_groupnorm_coeffs_from_stats_f32(dev[0].data_ptr(), dev[1].data_ptr() if len(dev) > 1 else None, C0, C1, B, nt0, nt1,
+                                                        HW, 32, gd.data_ptr(), bd.data_ptr(), ssd.data_ptr() if ss is not None else None,
+                                                        ss_stride, ss_offset, cA.data_ptr(), cB.data_ptr(), st()))
+    torch.cuda.synchronize()
+    return cA.cpu().double()[:, :, None, None], cB.cpu().double()[:, :, None, None]
+
+
+def check_chain(tag, srcs, x, tol_plain, tol_ss):
+    """partials -> coefficients -> x * A + B against GroupNorm(32) of x in float64: plain, then with a padded scale-shift row + SiLU."""
+    B, Cc, H, W = x.shape
+    g = torch.Generator().manual_seed(sum(map(ord, tag)) + 1)
+    gam, bet = 1 + 0.2 * torch.randn(Cc, generator=g), 0.2 * torch.randn(Cc, generator=g)
+    xd = x.double()
+    gn = F.group_norm(xd, 32, gam.double(), bet.double(), 1e-5)
+    cA, cB = coeffs_from_stats(srcs, B, H * W, gam, bet)
+    e_plain = (xd * cA + cB - gn).abs().max().item()
+    ss = 0.3 * torch.randn(B, 2 * Cc, generator=g)
+    ss_pad = torch.zeros(B, 2 * Cc + 7)
+    ss_pad[:, 5:5 + 2 * Cc] = ss
+    cA, cB = coeffs_from_stats(srcs, B, H * W, gam, bet, ss_pad, 2 * Cc + 7, 5)
+    want = F.silu(gn * (1 + ss[:, :Cc].double()[:, :, None, None]) + ss[:, Cc:].double()[:, :, None, None])
+    e_ss = (F.silu(xd * cA + cB) - want).abs().max().item()
+    print('%s: chain max |x A + B - GroupNorm fp64| %.3g (bound %.3g), with scale-shift + SiLU %.3g (bound %.3g); |GN| max %.3g' % (
+        tag, e_plain, tol_plain, e_ss, tol_ss, gn.abs().max().item()))
+    assert e_plain < tol_plain and e_ss < tol_ss, (tag, e_plain, e_ss)
+    return e_plain, e_ss
+
+
+def source(name):
+    out, buf, px = produce(name)
+    B, Cc, H, W = out.shape
+    nt = H * W // px
+    return (buf[:2 * B * nt * Cc], Cc, nt)
+
+
+IDS = [c[0] for c in CASES]
+
+
+@pytest.mark.parametrize('name', IDS)
+def test_partials(name):
+    """(a) Per route: the output is bit-identical to the launch without statistics; px is the stated value; exactly the first
+    B * (HW / px) * Cout float2 slots are written; every partial is the fp64 mean and centred sum of squares of its own pixels of the
+    kernel's output.  Slot order [image][partial][channel]; partial k of an image =
+      implicit-GEMM family (MODE 0 / 1 / 2, halo, split rows): NHWC pixels 128 k .. 128 k + 127;    split / F(4x4) on 8x8: the image;
+      F(2x2): block k, row-major, of 16 x 16 pixels (64-channel n-tiles) or 8 rows x 16 columns (128-channel n-tiles: wino_geometry);
+      F(4x4), every n-tile width: 16 x 16-pixel block k, row-major;    whole-image kernel: quadrant k (the same 16 x 16 blocks);
+      stem: NHWC pixels 1024 k .. 1024 k + 1023."""
+    check_partials(name)
+
+
+@pytest.mark.parametrize('name', IDS)
+def test_chain(name):
+    """(b) The route's partials with nt = HW / px through k_gn_coeffs_stats, 32 groups, against GroupNorm in float64 of the kernel's output."""
+    check_chain(name, [source(name)], produce(name)[0], 3e-6, 4e-6)
+
+
+CONCAT_CHAINS = [
+    # tag, producer of st0, producer of st1, pixels per partial of each   -- the split point cuts a group (C / 32 does not divide C0)
+    ('concat_128px_256px_16x16', 'g1_1x1_64to64_16_b2', 'f4n_32to32_16', 128, 256),      # 64 | 32 channels, nt 2 | 1
+    ('concat_128px_256px_32x32', 'g1_1x1_64to64_32', 'f4n_32to32_32', 128, 256),         # 64 | 32 channels, nt 8 | 4
+    ('concat_64px_64px_8x8', 'split_1x1_128to128_8_b2', 'f4n_32to32_8_b2', 64, 64),      # 128 | 32 channels, per-image partials on both sides
+]
+
+
+@pytest.mark.parametrize('tag,n0,n1,px0,px1', CONCAT_CHAINS, ids=[c[0] for c in CONCAT_CHAINS])
+def test_chain_concat_unequal_partials(tag, n0, n1, px0, px1):
+    """(b) The two halves of a concat from different producers, each with its own partial count and size."""
+    o0, o1 = produce(n0)[0], produce(n1)[0]
+    assert o0.shape[0] == o1.shape[0] and o0.shape[2:] == o1.shape[2:]
+    assert o0.shape[1] % ((o0.shape[1] + o1.shape[1]) // 32) != 0 and (produce(n0)[2], produce(n1)[2]) == (px0, px1)
+    check_chain(tag, [source(n0), source(n1)], torch.cat([o0, o1], 1), 3e-6, 4e-6)
+
+
+@pytest.mark.parametrize('name', [c[0] for c in CANCEL])
+def test_cancellation_partials(name):
+    """(c) |mean| = 100 >> std = 0.05 out of the kernels themselves: the shifted one-pass sums (pivot = a thread's first value, M2 as
+    s2 - s1 * m) and the Chan merges must not cancel.  The checks of (a); mean and M2 within 2e-4."""
+    check_partials(name)
+
+
+# Chain bounds (plain, scale-shift + SiLU) of the cancellation cases where they are not 2e-4: twice the maximum measured against
+# float64 on MI355X, for the component that exceeded 2e-4.  The excess is fp32 rounding of the coefficient FORM, not of the statistics:
+# these cases' partials are within 1.8e-5 of float64 (cancel_f4_image: mean 3.8e-6 = half an ulp of 100, M2 9e-8, and still 2.3e-4
+# here).  The derivation behind 2e-4 takes A ~ 3; with 4 channels of offset 0.3 randn per group some group's standard deviation is
+# ~0.06, so max A = gamma rstd is 11 - 22 and |B| = |mean| A is 1100 - 2200 in these cases.  The EXACT float64 coefficients merely
+# stored in fp32 already give 0.5e-4 - 1.2e-4 (x dA + dB, half an ulp each; cancel_f4_image 1.23e-4, cancel_split_8x8 0.92e-4);
+# k_gn_coeffs_stats adds the rounding of the group mean (dm A, dm ~ one ulp of 100), of mean * a and of fmaf(bb, 1 + scale, shift).
+CANCEL_CHAIN_BOUND = {'cancel_full_rows': (2e-4, 2 * 2.06e-4),       # measured 1.27e-4, 2.06e-4
+                      'cancel_split_8x8': (2e-4, 2 * 2.27e-4),       # 1.77e-4, 2.27e-4
+                      'cancel_f2': (2 * 2.55e-4, 2 * 2.04e-4),       # 2.55e-4, 2.04e-4
+                      'cancel_f4_image': (2 * 2.31e-4, 2 * 2.76e-4),   # 2.31e-4, 2.76e-4
+                      'cancel_stem': (2 * 2.14e-4, 2e-4)}            # 2.14e-4, 1.66e-4
+# (under 2e-4 as measured: cancel_generic_rows 1.52e-4, 1.75e-4; cancel_halo 1.52e-4, 1.80e-4; cancel_f4_block 1.28e-4, 1.44e-4)
+
+
+@pytest.mark.parametrize('name', [c[0] for c in CANCEL])
+def test_cancellation_chain(name):
+    """(c) ... and the chain: x A + B with |x| = 100, A ~ 3 carries ~ 100 * 3 * 6e-8 = 2e-5 of rounding in B (the derivation of
+    test_groupnorm_large_offset_is_stable): 2e-4, except CANCEL_CHAIN_BOUND."""
+    check_chain(name, [source(name)], produce(name)[0], *CANCEL_CHAIN_BOUND.get(name, (2e-4, 2e-4)))
+
+
+REFUSALS = [
+    # name, x shape, Cout, ks, keyword arguments of run_conv -- launches that can emit no statistics: the plan reads the tensor there
+    ('default_28x28', (2, 64, 28, 28), 64, 3, {}),                              # HW % 128 != 0 (and no F(2x2) block shape)
+    ('default_14x14', (2, 64, 14, 14), 64, 3, {}),
+    ('halo_28x28', (2, 64, 28, 28), 64, 3, {'force_direct': 2}),
+    ('halo_14x14', (2, 64, 14, 14), 64, 3, {'force_direct': 2}),
+    ('f2_8x8_two_images_per_block', (2, 64, 8, 8), 64, 3, {}),                  # nimg > 1
+    ('f4_4x4_sixteen_images_per_block', (3, 32, 4, 4), 128, 3, {'force_direct': 8}),
+    ('out_nchw', (2, 64, 16, 16), 64, 1, {'out_nchw': True}),
+    ('residual_concat_r0_30', (2, 64, 16, 16), 64, 1, {'res': 30}),             # R0 % 4 != 0
+    ('stem_cout_48', (2, 3, 32, 32), 48, 3, {'in_nchw': True}),                 # Cout / 4 not a power of two
+    ('direct_kernel', (2, 64, 16, 16), 64, 1, {'force_direct': 1}),             # no statistics epilogue at all
+]
+
+
+@pytest.mark.parametrize('case', REFUSALS, ids=[c[0] for c in REFUSALS])
+def test_refusals(case):
+    """dlpm_conv2d_stats_f32 answers DLPM_ERR_UNSUPPORTED exactly where conv_stats_pixels is 0 -- the condition under which the plan
+    falls back to reading the tensor -- and the same launch without statistics runs."""
+    name, shape, Cout, ks, kw = case
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    x = torch.randn(*shape, generator=g)
+    w = torch.randn(Cout, shape[1], ks, ks, generator=g) / math.sqrt(shape[1] * ks * ks)
+    bias = torch.randn(Cout, generator=g)
+    kw = dict(kw)
+    if isinstance(kw.get('res'), int):
+        r0 = kw['res']
+        kw['res'] = (torch.randn(shape[0], r0, *shape[2:], generator=g), torch.randn(shape[0], Cout - r0, *shape[2:], generator=g))
+    with pytest.raises(_lib.DlpmError, match=r'dlpm status -3\]'):
+        run_conv(x, w, bias, stats=True, **kw)
+    assert bool(torch.isfinite(run_conv(x, w, bias, **kw)).all())
+
+
+# ---- (d) variants behind read-once switches: one child process per setting ------------------------------------------------------
+_CHILD_SCRIPT = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + '/tests')
+import test_gpu_gn_stats as G
+G.child_main(sys.argv[2:])
+"""
+SWITCHES = {
+    # setting: (cases the child re-runs with the asserts of (a), True where the project claims the default's bits)
+    'DLPM_SPLIT_PIPE=0': ([n for n in IDS if n.startswith('split_')] + ['cancel_split_8x8'], True),     # pipelined vs two-barrier kernel
+    'DLPM_WINO4_IMG=0': ([n for n in IDS if n.startswith('f4n_')], True),                               # whole-image vs block shape
+    'DLPM_NO_WS=1': ([n for n in IDS if n.startswith('halo_')] + ['cancel_halo'], False),               # k_conv3x3_halo, own rounding
+    'DLPM_NO_STEM_LDS=1': (['stem_c1_32_32b2', 'stem_c3_128_64', 'stem_c3_512_32b2', 'stem_c1_512_64', 'cancel_stem'], False),
+}
+
+
+def child_main(names):
+    """Inside a child: the checks of (a) for `names`, then one digest line per case over (output, partials)."""
+    for name in names:
+        e_m, e_M2, part = check_partials(name)
+        h = hashlib.sha256(produce(name)[0].numpy().tobytes())
+        h.update(part.numpy().tobytes())
+        print('DIGEST %s %s' % (name, h.hexdigest()))
+
+
+def run_child(script, args, env_set, timeout=300):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    e = {k: v for k, v in os.environ.items() if k not in [s.split('=')[0] for s in SWITCHES] + ['DLPM_NO_GN_FUSION']}
+    e.update(env_set)
+    r = subprocess.run([sys.executable, '-c', script, root] + list(args), env=e, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, (env_set, r.stdout[-3000:], r.stderr[-3000:])
+    return r.stdout
+
+
+def digests(stdout):
+    return {ln.split()[1]: ln.split()[2] for ln in stdout.splitlines() if ln.startswith('DIGEST ')}
+
+
+@functools.lru_cache(maxsize=None)
+def default_digests():
+    names = sorted({n for cases, same in SWITCHES.values() if same for n in cases})
+    return digests(run_child(_CHILD_SCRIPT, names, {}))
+
+
+@pytest.mark.parametrize('setting', list(SWITCHES))
+def test_variant_behind_switch(setting):
+    """(d) The kernel variants a read-once environment switch selects: a child re-runs the affected cases of (a) with the same
+    asserts; where the project claims identical arithmetic (k_conv_split_pipe vs k_conv_split<8, 1, 1>; k_conv3x3_wino4_img vs the
+    2 + 2-wave block shape) output and partials are bit-equal to a child with default settings."""
+    names, same = SWITCHES[setting]
+    k, v = setting.split('=')
+    out = run_child(_CHILD_SCRIPT, names, {k: v})
+    print(out)
+    got = digests(out)
+    assert sorted(got) == sorted(names)
+    if same:
+        want = default_digests()
+        assert got == {n: want[n] for n in names}, setting
+
+
+# ---- (e) the unfused net path ---------------------------------------------------------------------------------------------------
+_NET_SCRIPT = r"""
+import hashlib, sys, torch
+sys.path.insert(0, sys.argv[1])
+import dlpm_amd
+from oracle import nets
+for mc, hw, B, seed in ((128, 16, 3, 31), (32, 32, 2, 41)):
+    torch.manual_seed(seed)
+    net = dlpm_amd.UNetModel(3, mc, 3, 1, [2], channel_mult=[1, 2], num_heads=4, use_scale_shift_norm=True)
+    dlpm_amd.rerandomize_(net, seed + 1)
+    g = torch.Generator().manual_seed(seed + 2)
+    x, t = torch.randn(B, 3, hw, hw, generator=g), torch.rand(B, generator=g)
+    sd = {k: v.detach() for k, v in net.state_dict().items()}
+    with torch.no_grad():
+        want = nets.unet_forward(sd, x, t, 4)
+    got = net(x.to('cuda'), t.to('cuda')).cpu()
+    print('NET mc%d_%dx%d %.6g %s' % (mc, hw, hw, (got - want).abs().max().item(), hashlib.sha256(got.numpy().tobytes()).hexdigest()))
+"""
+
+
+def test_unfused_net_path():
+    """(e) DLPM_NO_GN_FUSION=1 (every GroupNorm by a pass over the tensor) and the default (statistics from the producers' epilogues)
+    on the mc = 128 [1, 2] 16x16 net of test_subpixel_through_the_net and a 32-channel [1, 2] 32x32 net, against the oracle computed in
+    the child: both under the 1e-5 forward bound -- and not the same bits, i.e. the switch selects another path."""
+    res = {}
+    for sw in ('0', '1'):
+        out = run_child(_NET_SCRIPT, [], {'DLPM_NO_GN_FUSION': sw}, timeout=600)
+        res[sw] = {ln.split()[1]: (float(ln.split()[2]), ln.split()[3]) for ln in out.splitlines() if ln.startswith('NET ')}
+    assert sorted(res['0']) == sorted(res['1']) == ['mc128_16x16', 'mc32_32x32']
+    for net in sorted(res['0']):
+        print('%s: max |hip - oracle| fused statistics %.3g, DLPM_NO_GN_FUSION=1 %.3g' % (net, res['0'][net][0], res['1'][net][0]))
+    for net in sorted(res['0']):
+        assert res['0'][net][0] < 1e-5 and res['1'][net][0] < 1e-5, (net, res)
+        assert res['0'][net][1] != res['1'][net][1], 'DLPM_NO_GN_FUSION=1 changed nothing in %s' % net

@@ -35,8 +35,10 @@ def nchw(x):
 
 
 def run_conv(x0, w, bias=None, x1=None, stride=1, ups=0, coef=None, silu=False, res=None, in_nchw=False,
-             out_nchw=False, force_direct=False, scratch_extra=0):
-    """x0/x1: NCHW cpu tensors; returns NCHW cpu output of the HIP conv."""
+             out_nchw=False, force_direct=False, scratch_extra=0, stats=False):
+    """x0/x1: NCHW cpu tensors; returns NCHW cpu output of the HIP conv.  res: the residual, or a pair (res0, res1) = the two halves
+    of a residual concat.  stats=True: the launch through dlpm_conv2d_stats_f32; returns (output, the WHOLE statistics buffer --
+    2 B (Hout Wout / 64) Cout floats, the upper bound a caller allocates, pre-filled with NaN -- as a flat cpu tensor, pixels per partial)."""
     B, C0, Hin, Win = x0.shape
     Cout, Cin, ks, _ = w.shape
     Hi, Wi = (Hin * 2, Win * 2) if ups else (Hin, Win)
@@ -61,13 +63,21 @@ def run_conv(x0, w, bias=None, x1=None, stride=1, ups=0, coef=None, silu=False, 
     if coef is not None:
         a.coefA, a.coefB = dev(coef[0]), dev(coef[1])
     a.act_silu = int(silu)
-    if res is not None:
+    if isinstance(res, tuple):
+        a.res0, a.res1, a.R0 = dev(nhwc(res[0])), dev(nhwc(res[1])), res[0].shape[1]
+    elif res is not None:
         a.res0, a.R0 = dev(nhwc(res)), Cout
     out = torch.empty((B, Cout, Hout, Wout) if out_nchw else (B, Hout, Wout, Cout), device=DEV)
     a.out, a.Cout = out.data_ptr(), Cout
     a.in_nchw, a.out_nchw, a.force_direct = int(in_nchw), int(out_nchw), int(force_direct)
     scratch = torch.empty(9 * w.numel() + 16 * 1024 * (1 + Cout // 32) + scratch_extra, device=DEV)
     a.scratch_floats = scratch.numel()
+    if stats:
+        part = torch.full((2 * B * max(1, Hout * Wout // 64) * Cout,), float('nan'), device=DEV)
+        px = C.c_int32(0)
+        _lib.check(L().dlpm_conv2d_stats_f32(C.byref(a), scratch.data_ptr(), part.data_ptr(), C.byref(px), st()))
+        torch.cuda.synchronize()
+        return (out if out_nchw else nchw(out)).cpu(), part.cpu(), px.value
     _lib.check(L().dlpm_conv2d_f32(C.byref(a), scratch.data_ptr(), st()))
     torch.cuda.synchronize()
     return (out if out_nchw else nchw(out)).cpu()
