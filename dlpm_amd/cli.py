@@ -16,6 +16,10 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_prd REAL.npy --generate N [--prd_seed S]: generate N samples and print the reference's PRD figures between the first N float32
   samples of REAL.npy and them (EvaluationManager.evaluate_prd: precision = max F_8, recall = max F_1/8 of the PRD curve, and their
   F_1; 100 clusters above 2500 samples, else 20).  Together with --eval_mmd the samples are generated once and both are printed.
+  --eval_wass REAL.npy --generate N [--wass_bins K]: generate N samples and print the reference's `wass` figure between the first N
+  float32 samples of REAL.npy and them (EvaluationManager.evaluate_wass: the earth mover's distance between the histograms of the
+  flattened sets, the last sample of each left out as the reference does; 250 bins from 512 samples on, else numpy's 'auto').  With
+  more than one of --eval_wass / --eval_mmd / --eval_prd the samples are generated once and every figure is printed.
 """
 import argparse
 import os
@@ -100,8 +104,14 @@ def main(argv=None):
                          'between the first N float32 samples of this file and the N generated samples; prints `prd precision <p> '
                          'recall <r> f_1_pr <f> over <N> generated vs <N> real samples`')
     ap.add_argument('--prd_seed', type=int, default=0, help='with --eval_prd: seed of the k-means++ draws')
+    ap.add_argument('--eval_wass', default=None, metavar='REAL.npy',
+                    help='with --generate N: the reference\'s Wasserstein figure (compute_wasserstein_distance: histogram earth mover\'s '
+                         'distance of the flattened sets) between the first N float32 samples of this file and the N generated samples; '
+                         'prints `wass <value> over <N> generated vs <N> real samples`')
+    ap.add_argument('--wass_bins', type=int, default=None, help='with --eval_wass: number of bins (default: 250 from 512 samples on, '
+                                                                'else numpy\'s auto rule)')
     a = ap.parse_args(argv)
-    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd)):
+    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -172,26 +182,42 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
-    if a.eval_mmd or a.eval_prd:
+    if a.eval_mmd or a.eval_prd or a.eval_wass:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
         value = samples = None
+        files = {}
+
+        def real_of(path):                          # every file is loaded once, whichever figures name it
+            if path not in files:
+                files[path] = np.load(path)
+            return files[path]
+
+        def generated():                            # the samples are generated once, the way evaluate_mmd generates them
+            s, shape = ev._generate_flat({'default': model}, N, p['eval']['batch_size'], labels, {})
+            return s.reshape((N,) + shape)
         if a.eval_mmd:
-            real = np.load(a.eval_mmd)
-            value, samples = ev.evaluate_mmd({'default': model}, real, N, p['eval']['batch_size'], class_labels=labels, return_samples=True)
+            value, samples = ev.evaluate_mmd({'default': model}, real_of(a.eval_mmd), N, p['eval']['batch_size'], class_labels=labels,
+                                             return_samples=True)
             print('mmd %.9g over %d generated vs %d real samples' % (value, N, N))
         if a.eval_prd:
-            if a.eval_prd != a.eval_mmd:
-                real = np.load(a.eval_prd)
-            if samples is None:                     # no --eval_mmd: generate here, the same way
-                samples, shape = ev._generate_flat({'default': model}, N, p['eval']['batch_size'], labels, {})
-                samples = samples.reshape((N,) + shape)
-            res = ev.evaluate_prd({'default': model}, real, N, p['eval']['batch_size'], seed=a.prd_seed, samples=samples)
+            if samples is None:
+                samples = generated()
+            res = ev.evaluate_prd({'default': model}, real_of(a.eval_prd), N, p['eval']['batch_size'], seed=a.prd_seed, samples=samples)
             print('prd precision %.9g recall %.9g f_1_pr %.9g over %d generated vs %d real samples' % (
                 res['precision'], res['recall'], res['f_1_pr'], N, N))
             if value is not None:
                 res = dict(res, mmd=value)
             value = res
+        if a.eval_wass:
+            if samples is None:
+                samples = generated()
+            w = ev.evaluate_wass({'default': model}, real_of(a.eval_wass), N, p['eval']['batch_size'], bins=a.wass_bins, samples=samples)
+            print('wass %.9g over %d generated vs %d real samples' % (w, N, N))
+            if value is None:
+                value = w
+            else:
+                value = dict(value if isinstance(value, dict) else {'mmd': value}, wass=w)
         if a.out:
             np.save(a.out, samples.cpu().numpy())
         return value

@@ -9,11 +9,13 @@ are the reference's (`<gen_data_path>/<i>.png`, i counting over all chunks).  Wi
 dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so `device_batch` may enlarge the
 chunks beyond `eval.batch_size` without changing a pixel.
 
-Of the metrics half, FID / PRDC need Inception weights and Wasserstein needs pyemd; they are out of scope and `evals` keeps the
-reference's keys for them with nothing appended.  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
+Of the metrics half, FID / PRDC need Inception weights; they are out of scope and `evals` keeps the reference's keys for them
+(`evaluate_metrics_2d` appends the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
 (GenerativeLevyProcess.training_losses), forward only, on held-out samples; `mmd`, which `evaluate_mmd` fills with the reference's
 multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
-the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device (dlpm_amd/metrics.py).
+the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device; `wass`, which
+`evaluate_wass` fills with the reference's histogram earth mover's distance (EvaluationManager.py:146-151); and the reference's whole
+2-D branch from one generation, `evaluate_metrics_2d` (dlpm_amd/metrics.py).
 """
 import copy
 import ctypes as C
@@ -215,7 +217,7 @@ class EvaluationManager:
         return loss
 
     def evaluate_mmd(self, models, real_data, data_to_generate, batch_size, class_labels=None, kernel_mul=2.0, kernel_num=5,
-                     fix_sigma=None, return_samples=False, **kwargs):
+                     fix_sigma=None, return_samples=False, samples=None, **kwargs):
         """Multi-bandwidth Gaussian MMD (the reference's MMD_loss, EvaluationManager.py:153) between `data_to_generate` generated
         samples and `real_data[:data_to_generate]`, as a Python float appended to `evals['mmd']`.
 
@@ -224,17 +226,21 @@ class EvaluationManager:
         `_evaluate_model` -- inside one dataset_stream(), on the device, without declaring a batch -- and every chunk is written after
         GenerationManager's post-processing into one [N, D] device buffer; the metric is ONE dlpm_mmd_f32 call on that buffer.  With
         rng='philox' the figure therefore does not depend on `batch_size`.  `class_labels` and `kwargs` as `_evaluate_model`.
-        `return_samples=True` returns (mmd, the generated samples in their own shape, on the device)."""
+        `return_samples=True` returns (mmd, the generated samples in their own shape, on the device).  `samples=` [N, ...] takes the
+        place of the generation, as in `evaluate_prd`."""
         from . import metrics
         N = int(data_to_generate)
         assert N > 0, 'evaluate_mmd: data_to_generate must be positive'
         real = torch.as_tensor(real_data)
         assert real.dtype == torch.float32, 'evaluate_mmd takes float32 real_data, got %s' % real.dtype
         assert real.shape[0] >= N, 'evaluate_mmd: %d real samples for %d generated' % (real.shape[0], N)
-        if class_labels is not None:
-            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
-        gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
+        if samples is not None:
+            gen, shape = self._given_samples('evaluate_mmd', samples, N)
+        else:
+            if class_labels is not None:
+                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+            gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
         real = real[:N].reshape(N, -1)
         assert real.shape[1] == gen.shape[1], 'evaluate_mmd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
         value = metrics.mmd(gen, real.to(gen.device), kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
@@ -283,10 +289,7 @@ class EvaluationManager:
         if num_clusters is None:
             num_clusters = 100 if N > 2500 else 20
         if samples is not None:
-            gen = torch.as_tensor(samples)
-            assert gen.dtype == torch.float32, 'evaluate_prd takes float32 samples, got %s' % gen.dtype
-            assert gen.shape[0] == N, 'evaluate_prd: %d samples given for data_to_generate = %d' % (gen.shape[0], N)
-            gen = gen.reshape(N, -1)
+            gen, _ = self._given_samples('evaluate_prd', samples, N)
         else:
             if class_labels is not None:
                 class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
@@ -301,6 +304,73 @@ class EvaluationManager:
         res = {'precision': p, 'recall': r, 'f_1_pr': (2 * p * r) / (p + r) if p + r > 0 else 0.}
         for k, v in res.items():
             self.evals[k].append(v)
+        return res
+
+    @staticmethod
+    def _given_samples(who, samples, N):
+        """`samples=` of the evaluate_* methods as ([N, D] tensor, the shape of one sample)."""
+        gen = torch.as_tensor(samples)
+        assert gen.dtype == torch.float32, '%s takes float32 samples, got %s' % (who, gen.dtype)
+        assert gen.shape[0] == N, '%s: %d samples given for data_to_generate = %d' % (who, gen.shape[0], N)
+        return gen.reshape(N, -1), tuple(gen.shape[1:])
+
+    def evaluate_wass(self, models, real_data, data_to_generate, batch_size, class_labels=None, bins=None, samples=None, **kwargs):
+        """The reference's `wass` figure (compute_wasserstein_distance, EvaluationManager.py:146-151) between
+        `real_data[:data_to_generate]` and `data_to_generate` generated samples, as a Python float appended to `evals['wass']`: the
+        earth mover's distance between the histograms of the two FLATTENED sets, the last sample of each left out as the reference's
+        `[:-1]` slice leaves it out (metrics.compute_wasserstein_distance).
+
+        The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`.  `bins=None` is the reference's rule:
+        250 bins from 512 samples on, else numpy's 'auto'.  With rng='philox' the figure does not depend on `batch_size`."""
+        from . import metrics
+        N = int(data_to_generate)
+        assert N > 0, 'evaluate_wass: data_to_generate must be positive'
+        real = torch.as_tensor(real_data)
+        assert real.dtype == torch.float32, 'evaluate_wass takes float32 real_data, got %s' % real.dtype
+        assert real.shape[0] >= N, 'evaluate_wass: %d real samples for %d generated' % (real.shape[0], N)
+        assert N >= 2, 'evaluate_wass: the reference leaves the last sample out, so at least 2 are needed'
+        if bins is None:
+            bins = 250 if N >= 512 else 'auto'                                      # EvaluationManager.py:149
+        if samples is not None:
+            gen, _ = self._given_samples('evaluate_wass', samples, N)
+        else:
+            if class_labels is not None:
+                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+            gen, _ = self._generate_flat(models, N, batch_size, class_labels, kwargs)
+        real = real[:N].reshape(N, -1)
+        assert real.shape[1] == gen.shape[1], 'evaluate_wass: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
+        if gen.is_cuda:
+            real = real.to(gen.device)
+        value = metrics.compute_wasserstein_distance(real, gen, bins=bins)
+        self.evals['wass'].append(value)
+        return value
+
+    def evaluate_metrics_2d(self, models, real_data, data_to_generate, batch_size, class_labels=None, seed=0, **kwargs):
+        """The reference's whole evaluation of a 2-D config (EvaluationManager.py:126-168, :218-230) from ONE generation: `wass`, `mmd`,
+        `precision`, `recall` and `f_1_pr` as `evaluate_wass` / `evaluate_mmd` / `evaluate_prd` compute them on the same samples, and
+        the reference's own constants for the image-only figures: `density` = `coverage` = `fid` = `f_1_dc` = 0.0, `fig` = None.
+        Every key is appended to `evals`; the dict is returned with the generated samples (their own shape, on the device) under
+        'samples'.  `seed` seeds the k-means++ draws of the PRD clustering."""
+        N = int(data_to_generate)
+        assert N > 0, 'evaluate_metrics_2d: data_to_generate must be positive'
+        real = torch.as_tensor(real_data)
+        assert real.dtype == torch.float32, 'evaluate_metrics_2d takes float32 real_data, got %s' % real.dtype
+        assert real.shape[0] >= N, 'evaluate_metrics_2d: %d real samples for %d generated' % (real.shape[0], N)
+        assert N >= 2, 'evaluate_metrics_2d: the reference leaves the last sample out of `wass`, so at least 2 are needed'
+        if class_labels is not None:
+            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
+        samples = gen.reshape((N,) + shape)
+        res = {'wass': self.evaluate_wass(models, real, N, batch_size, samples=samples),
+               'mmd': self.evaluate_mmd(models, real, N, batch_size, samples=samples)}
+        res.update(self.evaluate_prd(models, real, N, batch_size, seed=seed, samples=samples))
+        rest = {'density': 0., 'coverage': 0., 'fid': 0., 'f_1_dc': 0., 'fig': None}
+        for k, v in rest.items():
+            self.evals[k].append(v)
+        res.update(rest)
+        res['samples'] = samples
         return res
 
     def generate_default(self, models, nsamples, **kwargs):

@@ -1,6 +1,7 @@
-"""Sample-quality metrics on the device.  Two are built: the multi-bandwidth Gaussian MMD of the reference
-(bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153) and its PRD
-precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168).
+"""Sample-quality metrics on the device.  Three are built: the multi-bandwidth Gaussian MMD of the reference
+(bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153), its PRD
+precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168) and its Wasserstein figure
+(bem/evaluate/wasserstein.py:47-52 = pyemd.emd_samples, called at EvaluationManager.py:146-151).
 
     mmd(source, target) -> float                      dlpm_mmd_f32: tiled pairwise reduction, no n x n array
     MMD_loss(kernel_mul, kernel_num)(source, target)  drop-in for the reference's class: a 0-dim fp32 tensor
@@ -8,11 +9,13 @@ precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at Eva
     prd(eval_data, ref_data) -> precision, recall     dlpm_prd_f32: clustering, histograms, curve and F pair in one enqueue sequence
     compute_prd_from_embedding, compute_precision_recall_curve, prd_to_max_f_beta_pair, compute_f_beta
                                                       drop-ins under the reference's names and signatures
+    wass(first, second, bins='auto') -> float         dlpm_wass_f32: histogram earth mover's distance in closed form
+    compute_wasserstein_distance(data, gen_samples)   drop-in for the reference's function (its histogram branch)
 
 Inputs are float32 tensors or arrays [N, ...] (rows are flattened), on the host or the GPU; host inputs are copied once.
 Unequal counts are allowed (the reference's broadcast raises on them): sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2).
-`wass` needs pyemd, FID / PRDC need Inception weights; they are not built; neither are the reference's unused get_MMD / MMDStatistic /
-MMD helpers."""
+FID / PRDC need Inception weights; they are not built; neither are the reference's unused get_MMD / MMDStatistic / MMD helpers,
+nor the `manual_compute` branch of compute_wasserstein_distance (a general 2N x 2N transport problem)."""
 import numpy as np
 import torch
 
@@ -272,3 +275,114 @@ def compute_f_beta(prec, rec):
     """prd_legacy.py:13-15."""
     a, b = prd_to_max_f_beta_pair(prec, rec)
     return np.array([a, b])
+
+
+# ---------------------------------------------------------------------------------------------- Wasserstein (histogram EMD)
+MAX_BINS = 1 << 20
+_WASS_STATUS = {1: 'autodetected range is not finite', 2: 'supplied range is not finite',
+                3: 'max must be larger than min in range parameter.', 4: 'Too many bins for data range'}
+
+
+def _wass_values(a, name):
+    t = torch.as_tensor(a)
+    assert t.dtype == torch.float32, 'wass takes float32 %s, got %s' % (name, t.dtype)
+    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], 'wass: %s needs at least one point, got shape %s' % (
+        name, tuple(t.shape))
+    return t.reshape(t.shape[0], -1)
+
+
+def _wass_check(first, second, bins, range, max_bins):
+    x, y = _wass_values(first, 'first'), _wass_values(second, 'second')
+    assert x.shape[1] == y.shape[1], 'wass: first rows hold %d values, second rows %d' % (x.shape[1], y.shape[1])
+    assert int(max_bins) == max_bins and 1 <= max_bins <= MAX_BINS, 'wass: max_bins must be in [1, %d], got %r' % (MAX_BINS, max_bins)
+    if isinstance(bins, str):
+        if bins != 'auto':
+            raise ValueError('%r is not a built estimator for `bins`: \'auto\' or an integer' % (bins,))
+        nb = 0
+    else:
+        nb = int(bins)
+        if nb != bins:
+            raise TypeError('`bins` must be an integer or \'auto\'')
+        if nb < 1:
+            raise ValueError('`bins` must be positive, when an integer')             # numpy's own refusal
+        assert nb <= max_bins, 'wass: %d bins, max_bins is %d' % (nb, max_bins)
+    lo, hi, has = 0.0, 0.0, 0
+    if range is not None:
+        lo, hi = (float(v) for v in range)
+        has = 1
+    return x, y, nb, has, lo, hi, int(max_bins)
+
+
+def _wass_run(first, second, bins, range, max_bins, parts):
+    x, y, nb, has, lo, hi, max_bins = _wass_check(first, second, bins, range, max_bins)
+    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    x, y = x.to(dev).contiguous(), y.to(dev).contiguous()
+    L = _lib.lib()
+    n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    nbytes = L.dlpm_wass_workspace_bytes(n1, n2, D, max_bins)
+    if nbytes < 0:
+        _lib.check(int(nbytes))
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(12, dtype=torch.float64, device=dev)
+        hist = torch.empty((2, max_bins), dtype=torch.int32, device=dev) if parts else None
+        _lib.check(L.dlpm_wass_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, nb, has, lo, hi, max_bins, ws.data_ptr(), nbytes,
+                                   hist.data_ptr() if parts else None, out.data_ptr(), _lib.stream_ptr()))
+    return out, hist
+
+
+def wass_device(first, second, bins='auto', range=None, max_bins=MAX_BINS):
+    """The call itself, without a host synchronisation: a float64 [12] tensor on the GPU holding (wass, bins, lo, hi, bin width, q25,
+    q75, the four order statistics, status).  status != 0 (a non-finite value or range, more than max_bins bins) leaves wass NaN;
+    `wass` raises numpy's ValueError on it.  Enqueued on the current stream; it can be captured in a torch.cuda.graph."""
+    return _wass_run(first, second, bins, range, max_bins, False)[0]
+
+
+def wass(first, second, bins='auto', range=None, return_parts=False):
+    """pyemd.emd_samples(first, second, bins=bins, range=range) with its defaults (Euclidean distance between bin centres, normalised
+    histograms) as a Python float: both arrays flattened, np.histogram's bins over the pooled range, and the 1-D earth mover's
+    distance between the two histograms.  `bins`: an integer or 'auto' (numpy's rule on the pooled values).  `range`: None (pooled
+    min / max) or (lo, hi); values outside are dropped.  ValueError as numpy for non-finite data or a bad range.
+    `return_parts=True` returns (wass, parts) with parts = {'bins', 'lo', 'hi', 'width', 'q25', 'q75', 'order_stats' (float32 [4]: the
+    sorted pooled values at ranks floor / ceil of the 75 % and of the 25 % point), 'hist_first', 'hist_second' (int32 [bins])};
+    q25, q75 and order_stats are None unless bins='auto'.  Under 'auto' the call reserves room for as many bins as there are values
+    (at least 1024) and repeats itself with 2^20 for the rare set that needs more."""
+    if isinstance(bins, str):
+        # 'auto': numpy's count is not known before the call.  Room for as many bins as there are values (at least 1024) keeps the
+        # workspace, the returned histograms and the LDS of the histogram pass small at the toy sizes; the rare set that needs more
+        # (a tiny IQR in a wide range) is run again with the full 2^20
+        max_bins = min(MAX_BINS, max(1024, 1 << (torch.as_tensor(first).numel() + torch.as_tensor(second).numel() - 1).bit_length()))
+    else:
+        max_bins = max(int(bins), 1)
+    out, hist = _wass_run(first, second, bins, range, max_bins, return_parts)
+    o = out.cpu().numpy()
+    status = int(o[11])
+    if status == 4 and max_bins < MAX_BINS:
+        out, hist = _wass_run(first, second, bins, range, MAX_BINS, return_parts)
+        o = out.cpu().numpy()
+        status = int(o[11])
+    if status:
+        raise ValueError(_WASS_STATUS[status] + ' (wass)')
+    if not return_parts:
+        return float(o[0])
+    nb, auto = int(o[1]), isinstance(bins, str)
+    h = hist[:, :nb].cpu().numpy()
+    return float(o[0]), {'bins': nb, 'lo': float(o[2]), 'hi': float(o[3]), 'width': float(o[4]), 'q25': float(o[5]) if auto else None,
+                         'q75': float(o[6]) if auto else None, 'order_stats': o[7:11].astype(np.float32) if auto else None,
+                         'hist_first': h[0], 'hist_second': h[1]}
+
+
+def compute_wasserstein_distance(data, gen_samples, manual_compute=False, num_samples=-1, distance='euclidean', normalized=True,
+                                 bins='auto', _range=None):
+    """bem/evaluate/wasserstein.py:15-52 under its own name and signature, quirks included: the default num_samples=-1 slices
+    `[:-1]`, so the LAST sample of each set is left out, and the generated samples go in first.  Kept as they are, not "fixed": the
+    figures are compared with the reference's.  Not built: manual_compute=True (a general 2N x 2N transport problem), a
+    callable or other `distance`, normalized=False."""
+    if manual_compute:
+        raise NotImplementedError('compute_wasserstein_distance: manual_compute=True is a general 2N x 2N transport problem; only the '
+                                  'histogram form is built (DESIGN 8)')
+    if distance != 'euclidean':
+        raise NotImplementedError('compute_wasserstein_distance: only distance=\'euclidean\' between bin centres is built (DESIGN 8)')
+    if not normalized:
+        raise NotImplementedError('compute_wasserstein_distance: normalized=False is not built (DESIGN 8)')
+    return wass(gen_samples[:num_samples], data[:num_samples], bins=bins, range=_range)

@@ -396,6 +396,33 @@ int dlpm_prd_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2,
                  int32_t *counts_out_dev, double *out_dev, dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-quality metric: the `wass` figure of EvaluationManager.py:146-151, compute_wasserstein_distance
+ * (bem/evaluate/wasserstein.py:47-52) = pyemd.emd_samples between x [n1, D] and y [n2, D], fp32 on the device.  Both arrays are
+ * FLATTENED; the pooled m = (n1 + n2) D scalars give one range [lo, hi] (their fp32 min / max, or the caller's) and one bin count
+ * (the caller's, or numpy's 'auto' rule: width = min(2 IQR m^(-1/3), ptp / (log2 m + 1)) with the exact quartiles of the pooled
+ * values by a 4 x 8-bit radix select, evaluated dtype by dtype as numpy 2 does on fp32 data); the edges are np.linspace(lo, hi,
+ * bins + 1) in fp64, a value x belongs to bin i with edge[i] <= (double)x < edge[i + 1] (the last bin closed) exactly as
+ * np.histogram assigns it, and values outside an explicit range are dropped.  With C1, C2 the cumulative counts (int64) and n1', n2'
+ * the counts inside the range,  wass = sum_{i < bins - 1} |C1_i / n1' - C2_i / n2'| (c_{i+1} - c_i)  over the bin centres c: the
+ * optimum of the transport problem pyemd solves, in closed form (1-D).  Integer atomics only and a fixed summation order: the same
+ * inputs give the same bits.  One enqueue sequence without a host synchronisation (it can be captured in a hipGraph).
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of workspace a call needs; DLPM_ERR_ARG (-1) for n1 < 1, n2 < 1, D < 1, more than 2^31 - 1 values in an array, or max_bins
+ * outside [1, 2^20]. */
+int64_t dlpm_wass_workspace_bytes(int64_t n1, int64_t n2, int64_t D, int64_t max_bins);
+
+/* bins = 0: numpy's 'auto' rule.  has_range = 0: [lo, hi] is the pooled min / max (lo == hi is widened by 0.5 on both sides, as
+ * np.histogram does).  hist_out_dev: null, or int32 [2][max_bins] (the counts of x and of y in their first `bins` entries).
+ * out_dev[12] = wass, bins, lo, hi, bin width, q25, q75, the four order statistics (ranks floor / ceil of the 75 % and of the 25 %
+ * point; NaN unless 'auto'), status.  status: 0 = fine; 1 = a non-finite value in the data (autodetected range); 2 = non-finite
+ * explicit range; 3 = lo > hi; 4 = more than max_bins bins -- wass is then NaN and bins 0.
+ * DLPM_ERR_ARG for the shapes above, bins < 0 or a null / misaligned pointer; DLPM_ERR_NOMEM for a short workspace (which must be
+ * 16-byte aligned) -- before any launch. */
+int dlpm_wass_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, int32_t bins, int32_t has_range, double lo,
+                  double hi, int64_t max_bins, void *workspace_dev, int64_t workspace_bytes, int32_t *hist_out_dev, double *out_dev,
+                  dlpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generated-image dump: what EvaluationManager does with each chunk of samples,
  * bem/evaluate/EvaluationManager.py:174-196 -- `tvu.save_image(samples[i], f"{i+total}.png")` per sample.
  * ------------------------------------------------------------------------------------------ */
