@@ -52,6 +52,21 @@ __device__ inline double block_sum(double v, double *sh) {
     __syncthreads();
     return out;
 }
+
+// the same tree with fmax (prd.hip); a maximum does not depend on the order
+template <int THREADS>
+__device__ inline double block_max(double v, double *sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+    const double out = sh[0];
+    __syncthreads();
+    return out;
+}
 #endif
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute: set it once per (device, kernel), under a lock

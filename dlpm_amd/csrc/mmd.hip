@@ -14,7 +14,7 @@
 // workgroup adds them in a fixed order -- no atomics, the same bits on every call.  All row, pair and tile indices are 64-bit.
 #include <algorithm>
 
-#include "common.h"
+#include "metrics_common.h"
 
 using namespace dlpm;
 
@@ -23,17 +23,9 @@ namespace {
 constexpr int kTile = 128;          // rows and columns of a pair tile
 constexpr int kMaxKernels = 16;     // kernel_num
 constexpr int kDirectMaxD = 16;     // D <= this: direct form
-constexpr int kColChunks = 32;      // row chunks of the column mean
 constexpr int64_t kMaxTilesSide = 65535;   // T (T + 1) / 2 tiles fit a 1-D grid
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-struct Pts {
-    const float *x, *y;
-    int64_t n1, n, D;
-};
-
-__device__ inline const float *row_ptr(const Pts &p, int64_t i) { return i < p.n1 ? p.x + i * p.D : p.y + (i - p.n1) * p.D; }
 
 __device__ inline int64_t tile_row_start(int64_t t, int64_t T) { return t * T - t * (t - 1) / 2; }
 
@@ -135,17 +127,7 @@ __global__ void __launch_bounds__(256) k_mmd_direct(Pts p, int64_t T, const floa
     }
 }
 
-// Column sums of the concatenation, one thread per column and row chunk: colpart[chunk][d]
-__global__ void __launch_bounds__(256) k_mmd_colsum(Pts p, double *colpart) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= p.D) return;
-    const int64_t per = (p.n + kColChunks - 1) / kColChunks;
-    const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < p.n ? r0 + per : p.n;
-    double acc = 0.0;
-    for (int64_t i = r0; i < r1; i++) acc += (double)row_ptr(p, i)[d];
-    colpart[(int64_t)blockIdx.y * p.D + d] = acc;
-}
-
+// the column means of the concatenation from the chunk sums of k_colstats<false>, colpart[chunk][d], added in chunk order
 __global__ void __launch_bounds__(256) k_mmd_colmean(const double *colpart, int64_t n, int64_t D, float *mean) {
     const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (d >= D) return;
@@ -344,8 +326,6 @@ __global__ void __launch_bounds__(256) k_mmd_gram(Pts p, int64_t T, const float 
     write_sums(sums, sh, partials);
 }
 
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 struct Layout {
     int64_t T, tiles;
     int64_t coef, partials, mean, colpart, rn, rsum, total;   // byte offsets
@@ -357,22 +337,16 @@ Layout layout_of(int64_t n, int64_t D) {
     L.T = ceil_div(n, kTile);
     L.tiles = L.T * (L.T + 1) / 2;
     L.gram = D > kDirectMaxD;
-    int64_t o = 0;
-    L.coef = o;
-    o += 256;
-    L.partials = o;
-    o += align256(L.tiles * 3 * (int64_t)sizeof(double));
+    Carve c;
+    L.coef = c.take(kMaxKernels * (int64_t)sizeof(float));
+    L.partials = c.take(L.tiles * 3 * (int64_t)sizeof(double));
     if (L.gram) {
-        L.mean = o;
-        o += align256(D * (int64_t)sizeof(float));
-        L.colpart = o;
-        o += align256(D * kColChunks * (int64_t)sizeof(double));
-        L.rn = o;
-        o += align256(n * (int64_t)sizeof(float));
-        L.rsum = o;
-        o += align256(n * (int64_t)sizeof(double));
+        L.mean = c.take(D * (int64_t)sizeof(float));
+        L.colpart = c.take(D * kColChunks * (int64_t)sizeof(double));
+        L.rn = c.take(n * (int64_t)sizeof(float));
+        L.rsum = c.take(n * (int64_t)sizeof(double));
     }
-    L.total = o;
+    L.total = c.total;
     return L;
 }
 
@@ -421,10 +395,8 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
     DLPM_CHECK_ARG(aligned16(workspace_dev) && reinterpret_cast<uintptr_t>(out_dev) % 8 == 0, "dlpm_mmd_f32: misaligned workspace or output");
     const int64_t n = n1 + n2;
     const Layout L = layout_of(n, D);
-    if (workspace_bytes < L.total) {
-        set_error("dlpm_mmd_f32: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
-        return DLPM_ERR_NOMEM;
-    }
+    const int ws_rc = check_workspace("dlpm_mmd_f32", workspace_dev, workspace_bytes, L.total);
+    if (ws_rc != DLPM_OK) return ws_rc;
     hipStream_t st = as_stream(stream);
     char *ws = static_cast<char *>(workspace_dev);
     float *coef = reinterpret_cast<float *>(ws + L.coef);
@@ -450,7 +422,7 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
         double *colpart = reinterpret_cast<double *>(ws + L.colpart), *rsum = reinterpret_cast<double *>(ws + L.rsum);
         {
             ProfScope ps("mmd_centre", 3.0 * (double)n * D, 8.0 * (double)n * D, st);
-            k_mmd_colsum<<<dim3((unsigned)ceil_div(D, 256), kColChunks), 256, 0, st>>>(p, colpart);
+            k_colstats<false><<<dim3((unsigned)ceil_div(D, 256), kColChunks), 256, 0, st>>>(p, colpart);
             DLPM_LAUNCH_CHECK();
             k_mmd_colmean<<<(unsigned)ceil_div(D, 256), 256, 0, st>>>(colpart, n, D, mean);
             DLPM_LAUNCH_CHECK();

@@ -3,7 +3,7 @@
 // precision-recall curve of the histograms averaged over the runs, and the maxima of F_beta and F_1/beta over the curve.
 // The reference fits sklearn's MiniBatchKMeans(n_init=10) num_runs times, one after the other; here ALL run x init instances advance in
 // lockstep in one grid (blockIdx.y = instance), as full-batch Lloyd iterations from a k-means++ seeding:
-//   * points: the concatenation [eval; ref] (two pointers, like Pts in mmd.hip), fp32 rows; centres, sums, inertias, the curve: fp64.
+//   * points: the concatenation [eval; ref] (two pointers: Pts of metrics_common.h), fp32 rows; centres, sums, inertias, the curve: fp64.
 //   * assign + accumulate, D <= 16: a workgroup stages its instance's K centres in LDS, a thread holds its point in registers (rows
 //     zero-padded to DT), finds the nearest centre by sum (x - c)^2 in fp64 (lowest index on ties), writes the label; then thread (k, d)
 //     scans the chunk's labels in index order and sums its members' coordinates, thread k counts them by set.
@@ -17,7 +17,7 @@
 // No floating-point atomics anywhere, every reduction in a fixed order: the same inputs give the same bits.
 #include <algorithm>
 
-#include "common.h"
+#include "metrics_common.h"
 #include "philox.h"
 
 using namespace dlpm;
@@ -28,17 +28,9 @@ constexpr int kMaxK = 256;          // labels are bytes
 constexpr int kDirectMaxD = 16;     // D <= this: point in registers
 constexpr int64_t kMaxD = 4096;
 constexpr int kMaxChunks = 512;     // point chunks per instance (a chunk is 256 * S points)
-constexpr int kColChunks = 32;      // row chunks of the column statistics
 constexpr int kTileK = 8, kTileD = 32;   // centre tile of the general form
 constexpr int64_t kMaxAngles = 1000000;
 constexpr uint32_t kPurposeSeed = 0x50524431u;   // Philox purpose of the k-means++ draws
-
-struct Pts {
-    const float *x, *y;
-    int64_t n1, n, D;
-};
-
-__device__ inline const float *row_ptr(const Pts &p, int64_t i) { return i < p.n1 ? p.x + i * p.D : p.y + (i - p.n1) * p.D; }
 
 // instance = run * n_init + init; chunk c of an instance covers the points [c * 256 * S, (c + 1) * 256 * S)
 struct Geo {
@@ -71,24 +63,7 @@ __global__ void __launch_bounds__(256) k_prd_init(int I, int32_t *done, int32_t 
     if (i < I) done[i] = iters[i] = fixed[i] = 0;
 }
 
-// sum x and sum x^2 per column and row chunk
-__global__ void __launch_bounds__(256) k_prd_colstats(Pts p, double *colpart) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= p.D) return;
-    const int64_t per = (p.n + kColChunks - 1) / kColChunks;
-    const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < p.n ? r0 + per : p.n;
-    double s = 0.0, q = 0.0;
-    for (int64_t i = r0; i < r1; i++) {
-        const double v = (double)row_ptr(p, i)[d];
-        s += v;
-        q += v * v;
-    }
-    double *o = colpart + ((int64_t)blockIdx.y * p.D + d) * 2;
-    o[0] = s;
-    o[1] = q;
-}
-
-// tolvar = tol * mean over the columns of the (biased) variance: sklearn's _tolerance
+// tolvar = tol * mean over the columns of the (biased) variance: sklearn's _tolerance, from the chunk sums of k_colstats<true>
 __global__ void __launch_bounds__(256) k_prd_tolvar(const double *colpart, int64_t n, int64_t D, double tol, double *tolvar) {
     __shared__ double sh[256];
     double acc = 0.0;
@@ -470,17 +445,10 @@ __global__ void __launch_bounds__(256) k_prd_curve(const int32_t *counts, int64_
         fb = (1.0 + b2) * (pm * rm) / ((b2 * pm) + rm + 1e-10);
         fi = (1.0 + i2) * (pm * rm) / ((i2 * pm) + rm + 1e-10);
     }
-    // maxima over the workgroup: a tree of fmax on the block_sum pattern (order does not matter for a maximum)
-    double v[3] = {fb, fi, raw};
+    const double v[3] = {fb, fi, raw};
     for (int q = 0; q < 3; q++) {
-        sh[threadIdx.x] = v[q];
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) cmax[(int64_t)blockIdx.x * 3 + q] = sh[0];
-        __syncthreads();
+        const double m = block_max<256>(v[q], sh);
+        if (threadIdx.x == 0) cmax[(int64_t)blockIdx.x * 3 + q] = m;
     }
 }
 
@@ -489,14 +457,8 @@ __global__ void __launch_bounds__(256) k_prd_curve_final(const double *cmax, int
     for (int q = 0; q < 3; q++) {
         double m = 0.0;
         for (int b = threadIdx.x; b < blocks; b += 256) m = fmax(m, cmax[(int64_t)b * 3 + q]);
-        sh[threadIdx.x] = m;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out3[q] = sh[0];
-        __syncthreads();
+        m = block_max<256>(m, sh);
+        if (threadIdx.x == 0) out3[q] = m;
     }
 }
 
@@ -504,8 +466,6 @@ __global__ void __launch_bounds__(256) k_prd_copy_f64(const double *src, double 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < count) dst[i] = src[i];
 }
-
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 struct Layout {
     Geo g;
@@ -526,30 +486,25 @@ Layout layout_of(int64_t n, int64_t D, int K, int R, int n_init) {
     g.n_init = n_init;
     g.run0 = 0;
     const int64_t I = g.I, KD = (int64_t)K * D;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t at = o;
-        o += align256(bytes);
-        return at;
-    };
-    L.centres = take(I * KD * 8);
-    L.psum = take(I * g.C * KD * 8);
-    L.pcnt = take(I * g.C * 2 * K * 4);
-    L.pinert = take(I * g.C * 8);
-    L.mind2 = take(I * n * 8);
-    L.bsum = take(I * g.C * 8);
-    L.labels = take(I * n);
-    L.flags = take(3 * I * 4);
-    L.colpart = take((int64_t)kColChunks * D * 2 * 8);
-    L.tolvar = take(8);
-    L.cmax = take(ceil_div(kMaxAngles, 256) * 3 * 8);
-    L.o_centres = take((int64_t)R * KD * 8);
-    L.o_labels = take((int64_t)R * n);
-    L.o_counts = take((int64_t)R * 2 * K * 4);
-    L.o_inertia = take((int64_t)R * 8);
-    L.o_iters = take((int64_t)R * 4);
-    L.o_fixed = take((int64_t)R * 4);
-    L.total = o;
+    Carve c;
+    L.centres = c.take(I * KD * 8);
+    L.psum = c.take(I * g.C * KD * 8);
+    L.pcnt = c.take(I * g.C * 2 * K * 4);
+    L.pinert = c.take(I * g.C * 8);
+    L.mind2 = c.take(I * n * 8);
+    L.bsum = c.take(I * g.C * 8);
+    L.labels = c.take(I * n);
+    L.flags = c.take(3 * I * 4);
+    L.colpart = c.take((int64_t)kColChunks * D * 2 * 8);
+    L.tolvar = c.take(8);
+    L.cmax = c.take(ceil_div(kMaxAngles, 256) * 3 * 8);
+    L.o_centres = c.take((int64_t)R * KD * 8);
+    L.o_labels = c.take((int64_t)R * n);
+    L.o_counts = c.take((int64_t)R * 2 * K * 4);
+    L.o_inertia = c.take((int64_t)R * 8);
+    L.o_iters = c.take((int64_t)R * 4);
+    L.o_fixed = c.take((int64_t)R * 4);
+    L.total = c.total;
     return L;
 }
 
@@ -588,15 +543,6 @@ int check_curve(const char *who, int64_t A, double eps, double beta) {
     DLPM_CHECK_ARG(A >= 3 && A <= kMaxAngles, "%s: num_angles must be in [3, 1e6], got %lld", who, (long long)A);
     DLPM_CHECK_ARG(eps > 0.0 && eps < 0.1, "%s: epsilon must be in (0, 0.1), got %g", who, eps);
     DLPM_CHECK_ARG(beta > 0.0, "%s: beta must be positive, got %g", who, beta);
-    return DLPM_OK;
-}
-
-int check_workspace(const char *who, const void *ws, int64_t have, int64_t need) {
-    DLPM_CHECK_ARG(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "%s: misaligned workspace", who);
-    if (have < need) {
-        set_error("%s: workspace of %lld bytes, %lld needed", who, (long long)have, (long long)need);
-        return DLPM_ERR_NOMEM;
-    }
     return DLPM_OK;
 }
 
@@ -643,7 +589,7 @@ int finish(const Pts &p, const Geo &g, const Work &w, const Outs &o, hipStream_t
 int run_kmeans(const Pts &p, const Geo &g, const Work &w, const Outs &o, int max_iter, double tol, uint64_t seed, hipStream_t st) {
     k_prd_init<<<(unsigned)ceil_div(g.I, 256), 256, 0, st>>>(g.I, w.done, w.iters, w.fixed);
     DLPM_LAUNCH_CHECK();
-    k_prd_colstats<<<dim3((unsigned)ceil_div(g.D, 256), kColChunks), 256, 0, st>>>(p, w.colpart);
+    k_colstats<true><<<dim3((unsigned)ceil_div(g.D, 256), kColChunks), 256, 0, st>>>(p, w.colpart);
     DLPM_LAUNCH_CHECK();
     k_prd_tolvar<<<1, 256, 0, st>>>(w.colpart, g.n, g.D, tol, w.tolvar);
     DLPM_LAUNCH_CHECK();

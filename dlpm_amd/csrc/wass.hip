@@ -10,7 +10,7 @@
 #include <cmath>
 #include <limits>
 
-#include "common.h"
+#include "metrics_common.h"
 
 using namespace dlpm;
 
@@ -400,22 +400,17 @@ __global__ void __launch_bounds__(kThreads) k_wass_emd(const State *s, const int
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 struct Layout {
     int64_t state, digits, hist, total;
 };
 
 Layout layout_of(int64_t max_bins) {
     Layout L{};
-    int64_t o = 0;
-    L.state = o;
-    o += align256((int64_t)sizeof(State));
-    L.digits = o;
-    o += 4 * 256 * (int64_t)sizeof(unsigned long long);
-    L.hist = o;
-    o += align256(2 * max_bins * (int64_t)sizeof(int32_t));
-    L.total = o;
+    Carve c;
+    L.state = c.take((int64_t)sizeof(State));
+    L.digits = c.take(4 * 256 * (int64_t)sizeof(unsigned long long));
+    L.hist = c.take(2 * max_bins * (int64_t)sizeof(int32_t));
+    L.total = c.total;
     return L;
 }
 
@@ -448,10 +443,8 @@ extern "C" int dlpm_wass_f32(const float *x_dev, int64_t n1, const float *y_dev,
                        reinterpret_cast<uintptr_t>(hist_out_dev) % 4 == 0,
                    "dlpm_wass_f32: misaligned pointer");
     const Layout L = layout_of(max_bins);
-    if (workspace_bytes < L.total) {
-        set_error("dlpm_wass_f32: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.total);
-        return DLPM_ERR_NOMEM;
-    }
+    const int ws_rc = check_workspace("dlpm_wass_f32", workspace_dev, workspace_bytes, L.total);
+    if (ws_rc != DLPM_OK) return ws_rc;
     int range_status = kOk;
     if (has_range) {                                   // _get_outer_edges on Python floats: checks, then the widening, in fp64
         if (lo > hi) range_status = kInvertedRange;

@@ -187,9 +187,7 @@ class EvaluationManager:
         kw.update(loss_kwargs)
         outer, inner = int(kw['monte_carlo_outer']), int(kw['monte_carlo_inner'])
         mk = dict(kw['model_kwargs'] or {})
-        if class_labels is not None:
-            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        class_labels = self._labels(class_labels, N)
         dev = torch.device(method.device)
         batch_size = max(1, int(batch_size))
         terms = t_all = None
@@ -229,25 +227,41 @@ class EvaluationManager:
         `return_samples=True` returns (mmd, the generated samples in their own shape, on the device).  `samples=` [N, ...] takes the
         place of the generation, as in `evaluate_prd`."""
         from . import metrics
-        N = int(data_to_generate)
-        assert N > 0, 'evaluate_mmd: data_to_generate must be positive'
-        real = torch.as_tensor(real_data)
-        assert real.dtype == torch.float32, 'evaluate_mmd takes float32 real_data, got %s' % real.dtype
-        assert real.shape[0] >= N, 'evaluate_mmd: %d real samples for %d generated' % (real.shape[0], N)
-        if samples is not None:
-            gen, shape = self._given_samples('evaluate_mmd', samples, N)
-        else:
-            if class_labels is not None:
-                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
-            gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
-        real = real[:N].reshape(N, -1)
-        assert real.shape[1] == gen.shape[1], 'evaluate_mmd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
-        value = metrics.mmd(gen, real.to(gen.device), kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
+        real, gen, shape = self._real_and_samples('evaluate_mmd', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                                  kwargs)
+        value = metrics.mmd(gen, real, kernel_mul=kernel_mul, kernel_num=kernel_num, fix_sigma=fix_sigma)
         self.evals['mmd'].append(value)
         if return_samples:
-            return value, gen.reshape((N,) + shape)
+            return value, gen.reshape((len(gen),) + shape)
         return value
+
+    @staticmethod
+    def _labels(class_labels, N):
+        """`class_labels` of the evaluate_* methods as an int64 host tensor of at least N labels; None stays None."""
+        if class_labels is None:
+            return None
+        class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
+        assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
+        return class_labels
+
+    def _real_and_samples(self, who, models, real_data, data_to_generate, batch_size, class_labels, samples, kwargs, single=None):
+        """What every sample metric starts from, with `who` in the messages: the N = data_to_generate samples, given (`samples=`) or
+        generated (`_generate_flat`), and `real_data[:N]` beside them.  Returns (real [N, D] on the samples' device, samples [N, D], the
+        shape of one sample).  `single`: the refusal of N = 1, for the figures that leave the last sample out.  Every refusal
+        comes before the generation."""
+        N = int(data_to_generate)
+        assert N > 0, '%s: data_to_generate must be positive' % who
+        real = torch.as_tensor(real_data)
+        assert real.dtype == torch.float32, '%s takes float32 real_data, got %s' % (who, real.dtype)
+        assert real.shape[0] >= N, '%s: %d real samples for %d generated' % (who, real.shape[0], N)
+        assert single is None or N >= 2, '%s: %s' % (who, single)
+        if samples is not None:
+            gen, shape = self._given_samples(who, samples, N)
+        else:
+            gen, shape = self._generate_flat(models, N, batch_size, self._labels(class_labels, N), kwargs)
+        real = real[:N].reshape(N, -1)
+        assert real.shape[1] == gen.shape[1], '%s: real samples hold %d values, generated ones %d' % (who, real.shape[1], gen.shape[1])
+        return real.to(gen.device), gen, shape
 
     def _generate_flat(self, models, N, batch_size, class_labels, kwargs):
         """N samples in chunks of `batch_size`, like `_evaluate_model`: inside one dataset_stream(), on the device, without declaring a
@@ -281,24 +295,10 @@ class EvaluationManager:
         is the reference's rule: 100 above 2500 samples, else 20.  `seed` seeds the k-means++ draws.  `density`, `coverage` and
         `fid` are not touched."""
         from . import metrics
-        N = int(data_to_generate)
-        assert N > 0, 'evaluate_prd: data_to_generate must be positive'
-        real = torch.as_tensor(real_data)
-        assert real.dtype == torch.float32, 'evaluate_prd takes float32 real_data, got %s' % real.dtype
-        assert real.shape[0] >= N, 'evaluate_prd: %d real samples for %d generated' % (real.shape[0], N)
+        real, gen, _ = self._real_and_samples('evaluate_prd', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                              kwargs)
         if num_clusters is None:
-            num_clusters = 100 if N > 2500 else 20
-        if samples is not None:
-            gen, _ = self._given_samples('evaluate_prd', samples, N)
-        else:
-            if class_labels is not None:
-                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
-            gen, _ = self._generate_flat(models, N, batch_size, class_labels, kwargs)
-        real = real[:N].reshape(N, -1)
-        assert real.shape[1] == gen.shape[1], 'evaluate_prd: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
-        if gen.is_cuda:
-            real = real.to(gen.device)
+            num_clusters = 100 if len(gen) > 2500 else 20
         _, _, parts = metrics.prd(real, gen, num_clusters=num_clusters, num_angles=num_angles, seed=seed, return_parts=True)
         p, r = parts['f_beta']
         res = {'precision': p, 'recall': r, 'f_1_pr': (2 * p * r) / (p + r) if p + r > 0 else 0.}
@@ -323,25 +323,10 @@ class EvaluationManager:
         The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`.  `bins=None` is the reference's rule:
         250 bins from 512 samples on, else numpy's 'auto'.  With rng='philox' the figure does not depend on `batch_size`."""
         from . import metrics
-        N = int(data_to_generate)
-        assert N > 0, 'evaluate_wass: data_to_generate must be positive'
-        real = torch.as_tensor(real_data)
-        assert real.dtype == torch.float32, 'evaluate_wass takes float32 real_data, got %s' % real.dtype
-        assert real.shape[0] >= N, 'evaluate_wass: %d real samples for %d generated' % (real.shape[0], N)
-        assert N >= 2, 'evaluate_wass: the reference leaves the last sample out, so at least 2 are needed'
+        real, gen, _ = self._real_and_samples('evaluate_wass', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                              kwargs, single='the reference leaves the last sample out, so at least 2 are needed')
         if bins is None:
-            bins = 250 if N >= 512 else 'auto'                                      # EvaluationManager.py:149
-        if samples is not None:
-            gen, _ = self._given_samples('evaluate_wass', samples, N)
-        else:
-            if class_labels is not None:
-                class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-                assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
-            gen, _ = self._generate_flat(models, N, batch_size, class_labels, kwargs)
-        real = real[:N].reshape(N, -1)
-        assert real.shape[1] == gen.shape[1], 'evaluate_wass: real samples hold %d values, generated ones %d' % (real.shape[1], gen.shape[1])
-        if gen.is_cuda:
-            real = real.to(gen.device)
+            bins = 250 if len(gen) >= 512 else 'auto'                               # EvaluationManager.py:149
         value = metrics.compute_wasserstein_distance(real, gen, bins=bins)
         self.evals['wass'].append(value)
         return value
@@ -352,16 +337,10 @@ class EvaluationManager:
         the reference's own constants for the image-only figures: `density` = `coverage` = `fid` = `f_1_dc` = 0.0, `fig` = None.
         Every key is appended to `evals`; the dict is returned with the generated samples (their own shape, on the device) under
         'samples'.  `seed` seeds the k-means++ draws of the PRD clustering."""
-        N = int(data_to_generate)
-        assert N > 0, 'evaluate_metrics_2d: data_to_generate must be positive'
-        real = torch.as_tensor(real_data)
-        assert real.dtype == torch.float32, 'evaluate_metrics_2d takes float32 real_data, got %s' % real.dtype
-        assert real.shape[0] >= N, 'evaluate_metrics_2d: %d real samples for %d generated' % (real.shape[0], N)
-        assert N >= 2, 'evaluate_metrics_2d: the reference leaves the last sample out of `wass`, so at least 2 are needed'
-        if class_labels is not None:
-            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-            assert class_labels.numel() >= N, 'class_labels: %d labels for %d samples' % (class_labels.numel(), N)
-        gen, shape = self._generate_flat(models, N, batch_size, class_labels, kwargs)
+        real, gen, shape = self._real_and_samples(
+            'evaluate_metrics_2d', models, real_data, data_to_generate, batch_size, class_labels, None, kwargs,
+            single='the reference leaves the last sample out of `wass`, so at least 2 are needed')
+        N = len(gen)
         samples = gen.reshape((N,) + shape)
         res = {'wass': self.evaluate_wass(models, real, N, batch_size, samples=samples),
                'mmd': self.evaluate_mmd(models, real, N, batch_size, samples=samples)}
@@ -388,10 +367,7 @@ class EvaluationManager:
         its slice (model_kwargs={'y': ...}), so neither pixels nor labels depend on the chunking, and the image dump writes them to
         `<gen_data_path>/labels.npy` (int64, index i = image i)."""
         if class_labels is not None:
-            class_labels = torch.as_tensor(class_labels).to('cpu', torch.int64).reshape(-1)
-            assert class_labels.numel() >= data_to_generate, 'class_labels: %d labels for %d samples' % (
-                class_labels.numel(), data_to_generate)
-            class_labels = class_labels[:data_to_generate]
+            class_labels = self._labels(class_labels, data_to_generate)[:data_to_generate]
         if not self.is_image:
             if class_labels is not None:
                 kwargs['model_kwargs'] = {'y': class_labels}

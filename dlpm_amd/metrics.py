@@ -24,17 +24,37 @@ from . import _lib
 MAX_KERNELS = 16
 
 
-def _points(a, name):
+def _rows(a, who, name):
+    """Input `name` of the metric `who` as a float32 [N, D] tensor where it lives, rows flattened."""
     t = torch.as_tensor(a)
-    assert t.dtype == torch.float32, 'mmd takes float32 %s, got %s' % (name, t.dtype)
-    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], 'mmd: %s needs at least one point, got shape %s' % (
-        name, tuple(t.shape))
+    assert t.dtype == torch.float32, '%s takes float32 %s, got %s' % (who, name, t.dtype)
+    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], '%s: %s needs at least one point, got shape %s' % (
+        who, name, tuple(t.shape))
     return t.reshape(t.shape[0], -1)
 
 
+def _row_pair(who, a, name_a, b, name_b):
+    x, y = _rows(a, who, name_a), _rows(b, who, name_b)
+    assert x.shape[1] == y.shape[1], '%s: %s rows hold %d values, %s rows %d' % (who, name_a, x.shape[1], name_b, y.shape[1])
+    return x, y
+
+
+def _on_device(x, y):
+    """(x, y, device): both contiguous on the GPU either of them is on, else on the current one.  Called after every refusal."""
+    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
+    return x.to(dev).contiguous(), y.to(dev).contiguous(), dev
+
+
+def _workspace(nbytes, dev):
+    """The answer of a *_workspace_bytes call as a uint8 tensor of that size on `dev`; a negative answer is its error code."""
+    if nbytes < 0:
+        _lib.check(int(nbytes))
+    with torch.cuda.device(dev):
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def _check(source, target, kernel_mul, kernel_num, fix_sigma):
-    x, y = _points(source, 'source'), _points(target, 'target')
-    assert x.shape[1] == y.shape[1], 'mmd: source rows hold %d values, target rows %d' % (x.shape[1], y.shape[1])
+    x, y = _row_pair('mmd', source, 'source', target, 'target')
     assert int(kernel_num) == kernel_num and 1 <= kernel_num <= MAX_KERNELS, 'mmd: kernel_num must be in [1, %d], got %r' % (
         MAX_KERNELS, kernel_num)
     assert kernel_mul > 0, 'mmd: kernel_mul must be positive, got %r' % (kernel_mul,)
@@ -48,17 +68,13 @@ def mmd_device(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
     (mmd, bandwidth before the division by kernel_mul ** (kernel_num // 2), sum XX, sum YY, sum XY).
     Enqueued on the current stream; it can be captured in a torch.cuda.graph."""
     x, y, mul, num, sigma = _check(source, target, kernel_mul, kernel_num, fix_sigma)
-    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    x, y = x.to(dev).contiguous(), y.to(dev).contiguous()
+    x, y, dev = _on_device(x, y)
     L = _lib.lib()
     n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
-    nbytes = L.dlpm_mmd_workspace_bytes(n1, n2, D)
-    if nbytes < 0:
-        _lib.check(int(nbytes))
+    ws = _workspace(L.dlpm_mmd_workspace_bytes(n1, n2, D), dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty(5, dtype=torch.float64, device=dev)
-        _lib.check(L.dlpm_mmd_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, mul, num, sigma, ws.data_ptr(), nbytes, out.data_ptr(),
+        _lib.check(L.dlpm_mmd_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, mul, num, sigma, ws.data_ptr(), ws.numel(), out.data_ptr(),
                                   _lib.stream_ptr()))
     return out
 
@@ -96,17 +112,8 @@ KMEANS_TOL = 1e-4          # sklearn's default: rounds stop at a centre shift <=
 PRD_EPSILON = 1e-10        # compute_prd's default angle offset
 
 
-def _prd_points(a, name):
-    t = torch.as_tensor(a)
-    assert t.dtype == torch.float32, 'prd takes float32 %s, got %s' % (name, t.dtype)
-    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], 'prd: %s needs at least one point, got shape %s' % (
-        name, tuple(t.shape))
-    return t.reshape(t.shape[0], -1)
-
-
 def _prd_check(eval_data, ref_data, num_clusters, num_runs, n_init, max_iter):
-    x, y = _prd_points(eval_data, 'eval_data'), _prd_points(ref_data, 'ref_data')
-    assert x.shape[1] == y.shape[1], 'prd: eval_data rows hold %d values, ref_data rows %d' % (x.shape[1], y.shape[1])
+    x, y = _row_pair('prd', eval_data, 'eval_data', ref_data, 'ref_data')
     assert x.shape[1] <= MAX_WIDTH, 'prd: rows of at most %d values, got %d' % (MAX_WIDTH, x.shape[1])
     n = x.shape[0] + y.shape[0]
     assert int(num_clusters) == num_clusters and 1 <= num_clusters <= min(MAX_CLUSTERS, n), (
@@ -114,8 +121,7 @@ def _prd_check(eval_data, ref_data, num_clusters, num_runs, n_init, max_iter):
     for v, name in ((num_runs, 'num_runs'), (n_init, 'n_init'), (max_iter, 'max_iter')):
         assert int(v) == v and v >= 1, 'prd: %s must be a positive integer, got %r' % (name, v)
     assert num_runs * n_init <= 65535, 'prd: num_runs * n_init must be at most 65535'
-    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    return x.to(dev).contiguous(), y.to(dev).contiguous(), dev
+    return _on_device(x, y)
 
 
 def _curve_check(num_angles, epsilon, beta):
@@ -127,18 +133,12 @@ def _curve_check(num_angles, epsilon, beta):
         raise ValueError('Given parameter beta %s must be positive.' % str(beta))
 
 
-def _workspace(L, n1, n2, D, K, R, n_init, dev):
-    nbytes = L.dlpm_prd_workspace_bytes(n1, n2, D, K, R, n_init)
-    if nbytes < 0:
-        _lib.check(int(nbytes))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
-
-
 def _kmeans_device(x, y, dev, K, runs, n_init, max_iter, seed, tol, first_run):
     L = _lib.lib()
     n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    ws = _workspace(L.dlpm_prd_workspace_bytes(n1, n2, D, K, runs, n_init), dev)
+    nbytes = ws.numel()
     with torch.cuda.device(dev):
-        ws, nbytes = _workspace(L, n1, n2, D, K, runs, n_init, dev)
         centres = torch.empty((runs, K, D), dtype=torch.float64, device=dev)
         labels = torch.empty((runs, n1 + n2), dtype=torch.uint8, device=dev)
         counts = torch.empty((runs, 2, K), dtype=torch.int32, device=dev)
@@ -158,7 +158,7 @@ def kmeans(points, K, n_init=10, max_iter=100, seed=0, runs=1, tol=KMEANS_TOL, f
     Rounds stop at a centre shift <= tol * mean per-feature variance (sklearn's rule); `converged` is set where a round left
     every centre unchanged, i.e. every centre IS the mean of the points labelled with it (always reached with tol=0 and enough
     rounds).  Run r draws from (seed, first_run + r): it is the same whether computed alone or beside others."""
-    pts = _prd_points(points, 'points')
+    pts = _rows(points, 'prd', 'points')
     assert pts.shape[0] >= 2, 'kmeans: needs at least two points, got %d' % pts.shape[0]
     assert tol >= 0, 'kmeans: tol must not be negative, got %r' % (tol,)
     assert int(first_run) == first_run and first_run >= 0, 'kmeans: first_run must be a non-negative integer, got %r' % (first_run,)
@@ -181,8 +181,9 @@ def _prd_run(eval_data, ref_data, num_clusters, num_angles, num_runs, n_init, ma
     K, R = int(K), int(num_runs)
     n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
     L = _lib.lib()
+    ws = _workspace(L.dlpm_prd_workspace_bytes(n1, n2, D, K, R, int(n_init)), dev)
+    nbytes = ws.numel()
     with torch.cuda.device(dev):
-        ws, nbytes = _workspace(L, n1, n2, D, K, R, int(n_init), dev)
         out = torch.empty(2 * A + 3, dtype=torch.float64, device=dev)
         extra = None
         if centers is not None:
@@ -283,17 +284,8 @@ _WASS_STATUS = {1: 'autodetected range is not finite', 2: 'supplied range is not
                 3: 'max must be larger than min in range parameter.', 4: 'Too many bins for data range'}
 
 
-def _wass_values(a, name):
-    t = torch.as_tensor(a)
-    assert t.dtype == torch.float32, 'wass takes float32 %s, got %s' % (name, t.dtype)
-    assert t.dim() >= 1 and t.shape[0] >= 1 and t.numel() >= t.shape[0], 'wass: %s needs at least one point, got shape %s' % (
-        name, tuple(t.shape))
-    return t.reshape(t.shape[0], -1)
-
-
 def _wass_check(first, second, bins, range, max_bins):
-    x, y = _wass_values(first, 'first'), _wass_values(second, 'second')
-    assert x.shape[1] == y.shape[1], 'wass: first rows hold %d values, second rows %d' % (x.shape[1], y.shape[1])
+    x, y = _row_pair('wass', first, 'first', second, 'second')
     assert int(max_bins) == max_bins and 1 <= max_bins <= MAX_BINS, 'wass: max_bins must be in [1, %d], got %r' % (MAX_BINS, max_bins)
     if isinstance(bins, str):
         if bins != 'auto':
@@ -315,18 +307,14 @@ def _wass_check(first, second, bins, range, max_bins):
 
 def _wass_run(first, second, bins, range, max_bins, parts):
     x, y, nb, has, lo, hi, max_bins = _wass_check(first, second, bins, range, max_bins)
-    dev = x.device if x.is_cuda else (y.device if y.is_cuda else torch.device('cuda', torch.cuda.current_device()))
-    x, y = x.to(dev).contiguous(), y.to(dev).contiguous()
+    x, y, dev = _on_device(x, y)
     L = _lib.lib()
     n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
-    nbytes = L.dlpm_wass_workspace_bytes(n1, n2, D, max_bins)
-    if nbytes < 0:
-        _lib.check(int(nbytes))
+    ws = _workspace(L.dlpm_wass_workspace_bytes(n1, n2, D, max_bins), dev)
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty(12, dtype=torch.float64, device=dev)
         hist = torch.empty((2, max_bins), dtype=torch.int32, device=dev) if parts else None
-        _lib.check(L.dlpm_wass_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, nb, has, lo, hi, max_bins, ws.data_ptr(), nbytes,
+        _lib.check(L.dlpm_wass_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, nb, has, lo, hi, max_bins, ws.data_ptr(), ws.numel(),
                                    hist.data_ptr() if parts else None, out.data_ptr(), _lib.stream_ptr()))
     return out, hist
 

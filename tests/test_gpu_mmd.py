@@ -10,6 +10,7 @@ import torch
 
 import dlpm_amd
 from dlpm_amd import metrics
+from metric_helpers import managers, toy
 from test_host_mirror import build_unet
 from test_mmd_cpu import DIRECT, GRAM, case, np_mmd, unequal_case
 
@@ -158,10 +159,8 @@ def test_mmd_loss_class_and_all_equal_points():
 
 
 # ---------------------------------------------------------------- 6. end to end
-def toy():
-    torch.manual_seed(1)
-    net = dlpm_amd.MLPModel(dlpm_amd.load_config('2d_data'))
-    return net, [1, 2], False, dict(reverse_steps=10)
+def toy_mlp():
+    return toy(), [1, 2], False, dict(reverse_steps=10)
 
 
 def tiny_unet():
@@ -170,21 +169,16 @@ def tiny_unet():
 
 @pytest.mark.parametrize('which,N,batches', [('toy', 512, (512, 200, 64)), ('unet', 64, (64, 24))])
 def test_evaluate_mmd_does_not_depend_on_the_chunking(which, N, batches):
-    net, shape, is_image, kw = toy() if which == 'toy' else tiny_unet()
+    net, shape, is_image, kw = toy_mlp() if which == 'toy' else tiny_unet()
     g = torch.Generator().manual_seed(41)
     real = torch.rand([N + 8] + shape, generator=g) if is_image else torch.randn([N + 8] + shape, generator=g)
-
-    def managers():
-        method = dlpm_amd.GenerativeLevyProcess(1.7, DEV, kw['reverse_steps'], rescale_timesteps=True, seed=9)
-        gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(shape), is_image, **kw)
-        return method, gm, dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
     figures = []
     for bs in batches:
-        method, gm, ev = managers()
+        method, gm, ev = managers(shape, is_image, **kw)
         value = ev.evaluate_mmd({'default': net}, real, N, bs)
         assert isinstance(value, float) and ev.evals['mmd'] == [value] and method.calls == 1
         figures.append(value)
-    method, gm, ev = managers()
+    method, gm, ev = managers(shape, is_image, **kw)
     with method.dataset_stream():
         samples = gm.generate({'default': net}, N, to_host=False, declare_batch=False)
     want = metrics.mmd(samples, real[:N])

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import dlpm_amd
 from dlpm_amd import metrics
+from metric_helpers import managers, real_toy, toy
 from test_wass_cpu import AUTO_CASES, auto_ratio, np_wass, sets, value_bound
 
 pytestmark = pytest.mark.gpu
@@ -186,21 +186,6 @@ def test_drop_in_leaves_the_last_sample_out():
 
 
 # ---------------------------------------------------------------- end to end
-def toy():
-    torch.manual_seed(1)
-    return dlpm_amd.MLPModel(dlpm_amd.load_config('2d_data'))
-
-
-def managers():
-    method = dlpm_amd.GenerativeLevyProcess(1.7, DEV, 10, rescale_timesteps=True, seed=9)
-    gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe([1, 2]), False, reverse_steps=10)
-    return method, gm, dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=False)
-
-
-def real_toy(N):
-    return torch.randn([N + 8, 1, 2], generator=torch.Generator().manual_seed(41))
-
-
 def test_evaluate_wass_does_not_depend_on_the_chunking():
     net, N, real = toy(), 512, real_toy(512)
     values = []

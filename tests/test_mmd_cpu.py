@@ -10,6 +10,7 @@ import torch
 from conftest import golden
 import dlpm_amd
 from dlpm_amd import _lib, metrics
+from metric_helpers import buffers
 
 DIRECT = ['toy64', 'toy257', 'toy257_same', 'toy1000', 'd3', 'd16', 'params_k3', 'params_sigma']   # D <= 16
 GRAM = ['d17', 'g147', 'g192', 'g3072_img']                                                        # D > 16
@@ -71,12 +72,6 @@ def test_fixtures_are_small_and_complete():
         assert (f['x'].shape[1] > 16) == (name in GRAM)
 
 
-def _buffers():
-    buf = np.zeros(1 << 16, np.uint8)
-    base = (buf.ctypes.data + 255) // 256 * 256
-    return buf, base
-
-
 def test_workspace_bytes_refusals():
     L = _lib.lib()
     for n1, n2, D in [(0, 4, 2), (4, 0, 2), (4, 4, 0), (-1, 4, 2)]:
@@ -94,7 +89,7 @@ def test_workspace_bytes_refusals():
 def test_mmd_f32_refuses_before_any_launch():
     """No GPU here: every one of these returns before a kernel is launched (the pointers are host addresses, never followed)."""
     L = _lib.lib()
-    buf, base = _buffers()
+    buf, base = buffers()
     x, y, ws, out = base, base + 4096, base + 8192, base + 60000 // 8 * 8
     need = L.dlpm_mmd_workspace_bytes(8, 8, 2)
     good = dict(x=x, n1=8, y=y, n2=8, D=2, mul=2.0, num=5, sigma=0.0, ws=ws, wsb=need, out=out)

@@ -11,6 +11,7 @@ import torch
 from conftest import golden
 import dlpm_amd
 from dlpm_amd import _lib, metrics
+from metric_helpers import buffers
 
 DIRECT = ['toy500_k20', 'toy3000_k100', 'heavy2000_k20', 'same400_k20', 'disjoint300_k20', 'k7_n64', 'd3', 'd16']   # D <= 16
 TILED = ['d17', 'd48', 'd192']                                                                                   # D > 16
@@ -97,12 +98,6 @@ def test_fixtures_are_small_and_complete():
     assert np.array_equal(case('same400_k20')['x'], case('same400_k20')['y'])
 
 
-def _buffers():
-    buf = np.zeros(1 << 16, np.uint8)
-    base = (buf.ctypes.data + 255) // 256 * 256
-    return buf, base
-
-
 def test_workspace_bytes_refusals_and_growth():
     L = _lib.lib()
     ws = L.dlpm_prd_workspace_bytes
@@ -123,7 +118,7 @@ def test_workspace_bytes_refusals_and_growth():
 def test_c_entry_points_refuse_before_any_launch():
     """No GPU here: every one of these returns before a kernel is launched (the pointers are host addresses, never followed)."""
     L = _lib.lib()
-    buf, base = _buffers()
+    buf, base = buffers()
     P = [base + 4096 * i for i in range(12)]
     need = L.dlpm_prd_workspace_bytes(8, 8, 2, 3, 2, 2)
     good = dict(x=P[0], n1=8, y=P[1], n2=8, D=2, K=3, R=2, n_init=2, max_iter=5, tol=1e-4, seed=1, first=0, ws=P[2], wsb=need, cen=P[3],

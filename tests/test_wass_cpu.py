@@ -13,6 +13,7 @@ import torch
 
 import dlpm_amd
 from dlpm_amd import _lib, metrics
+from metric_helpers import buffers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -265,8 +266,7 @@ def test_workspace_bytes_refusals_and_growth():
 def test_c_entry_point_refuses_before_any_launch():
     """No GPU here: every one of these returns before a kernel is launched (the pointers are host addresses, never followed)."""
     L = _lib.lib()
-    buf = np.zeros(1 << 16, np.uint8)
-    base = (buf.ctypes.data + 255) // 256 * 256
+    buf, base = buffers()
     P = [int(base) + 4096 * i for i in range(6)]
     need = L.dlpm_wass_workspace_bytes(8, 6, 2, 32)
     good = dict(x=P[0], n1=8, y=P[1], n2=6, D=2, bins=16, has=0, lo=0.0, hi=0.0, mb=32, ws=P[2], wsb=need, hist=P[3], out=P[4])
