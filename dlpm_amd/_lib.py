@@ -120,6 +120,8 @@ SIGNATURES = {
     'dlpm_prd_f32': (C.c_int, [vp, i64, vp, i64, i64, i32, i32, i32, i32, f64, u64, i32, f64, f64, vp, i64, vp, vp, vp, vp, vp]),
     'dlpm_wass_workspace_bytes': (i64, [i64, i64, i64, i64]),
     'dlpm_wass_f32': (C.c_int, [vp, i64, vp, i64, i64, i32, i32, f64, f64, i64, vp, i64, vp, vp, vp]),
+    'dlpm_prdc_workspace_bytes': (i64, [i64, i64, i64, i32]),
+    'dlpm_prdc_f32': (C.c_int, [vp, i64, vp, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
     'dlpm_images_to_rgb8':(C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
     'dlpm_png_bound': (i64, [i32, i32]),
     'dlpm_png_encode_rgb8': (C.c_int, [vp, i32, i32, i32, vp, i64, C.POINTER(i64)]),

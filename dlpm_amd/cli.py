@@ -19,7 +19,11 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_wass REAL.npy --generate N [--wass_bins K]: generate N samples and print the reference's `wass` figure between the first N
   float32 samples of REAL.npy and them (EvaluationManager.evaluate_wass: the earth mover's distance between the histograms of the
   flattened sets, the last sample of each left out as the reference does; 250 bins from 512 samples on, else numpy's 'auto').  With
-  more than one of --eval_wass / --eval_mmd / --eval_prd the samples are generated once and every figure is printed.
+  more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc the samples are generated once and every figure is printed.
+  --eval_prdc REAL.npy --generate N [--nearest_k K]: generate N samples and print the k-nearest-neighbour precision, recall, density
+  and coverage (the `prdc` package's compute_prdc) between the first N float32 samples of REAL.npy and them, with f_1_pr and f_1_dc
+  (EvaluationManager.evaluate_prdc on the flattened samples; K = 5 neighbours by default).  A feature network is plugged in through
+  the Python call (`features=`), not here; FID is not computed.
 """
 import argparse
 import os
@@ -110,8 +114,14 @@ def main(argv=None):
                          'prints `wass <value> over <N> generated vs <N> real samples`')
     ap.add_argument('--wass_bins', type=int, default=None, help='with --eval_wass: number of bins (default: 250 from 512 samples on, '
                                                                 'else numpy\'s auto rule)')
+    ap.add_argument('--eval_prdc', default=None, metavar='REAL.npy',
+                    help='with --generate N: k-nearest-neighbour precision / recall / density / coverage (compute_prdc of the prdc '
+                         'package) between the first N float32 samples of this file and the N generated samples, flattened; prints '
+                         '`prdc precision <p> recall <r> density <d> coverage <c> f_1_pr <f> f_1_dc <f> over <N> generated vs <N> real '
+                         'samples`')
+    ap.add_argument('--nearest_k', type=int, default=5, help='with --eval_prdc: the number of neighbours (default 5)')
     a = ap.parse_args(argv)
-    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass)):
+    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -182,7 +192,7 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
-    if a.eval_mmd or a.eval_prd or a.eval_wass:
+    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
         value = samples = None
@@ -218,6 +228,17 @@ def main(argv=None):
                 value = w
             else:
                 value = dict(value if isinstance(value, dict) else {'mmd': value}, wass=w)
+        if a.eval_prdc:
+            if samples is None:
+                samples = generated()
+            res = ev.evaluate_prdc({'default': model}, real_of(a.eval_prdc), N, p['eval']['batch_size'], nearest_k=a.nearest_k,
+                                   samples=samples)
+            print('prdc precision %.9g recall %.9g density %.9g coverage %.9g f_1_pr %.9g f_1_dc %.9g over %d generated vs %d real samples'
+                  % (res['precision'], res['recall'], res['density'], res['coverage'], res['f_1_pr'], res['f_1_dc'], N, N))
+            if value is None:
+                value = res
+            else:                                       # beside --eval_prd its PRD figures keep their keys; the k-NN ones go under 'prdc'
+                value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass': value}, prdc=res)
         if a.out:
             np.save(a.out, samples.cpu().numpy())
         return value

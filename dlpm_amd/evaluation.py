@@ -9,13 +9,15 @@ are the reference's (`<gen_data_path>/<i>.png`, i counting over all chunks).  Wi
 dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so `device_batch` may enlarge the
 chunks beyond `eval.batch_size` without changing a pixel.
 
-Of the metrics half, FID / PRDC need Inception weights; they are out of scope and `evals` keeps the reference's keys for them
-(`evaluate_metrics_2d` appends the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
+Of the metrics half, FID and any Inception forward are out of scope (the network needs weights nobody can ship) and `evals` keeps the
+reference's key for it (`evaluate_metrics_2d` appends the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
 (GenerativeLevyProcess.training_losses), forward only, on held-out samples; `mmd`, which `evaluate_mmd` fills with the reference's
 multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
 the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device; `wass`, which
-`evaluate_wass` fills with the reference's histogram earth mover's distance (EvaluationManager.py:146-151); and the reference's whole
-2-D branch from one generation, `evaluate_metrics_2d` (dlpm_amd/metrics.py).
+`evaluate_wass` fills with the reference's histogram earth mover's distance (EvaluationManager.py:146-151); the reference's whole
+2-D branch from one generation, `evaluate_metrics_2d`; and PRDC from features -- `precision`, `recall`, `density`, `coverage`, `f_1_pr`,
+`f_1_dc` as the image branch fills them (:215-225) -- which `evaluate_prdc` computes by k-nearest neighbours on the flattened samples
+or on the features of a callable the caller brings (dlpm_amd/metrics.py).
 """
 import copy
 import ctypes as C
@@ -330,6 +332,50 @@ class EvaluationManager:
         value = metrics.compute_wasserstein_distance(real, gen, bins=bins)
         self.evals['wass'].append(value)
         return value
+
+    def evaluate_prdc(self, models, real_data, data_to_generate, batch_size, class_labels=None, nearest_k=5, features=None, samples=None,
+                      **kwargs):
+        """k-nearest-neighbour precision, recall, density and coverage (the `prdc` package's compute_prdc, the last step of
+        bem/evaluate/fid_score.py:303-336) between `real_data[:data_to_generate]` and `data_to_generate` generated samples: appends
+        them to `evals['precision']`, `['recall']`, `['density']`, `['coverage']` and their two harmonic means to `['f_1_pr']` and
+        `['f_1_dc']` (0 where both terms vanish), as EvaluationManager.py:215-225 does in the image branch, and returns the six as a dict.
+
+        `features`: None -- the flattened samples are the features -- or a callable mapping a float32 GPU batch to [B, F] float32: this
+        is where a caller plugs in an embedding (an Inception network with their own weights, any other feature net).  It receives the
+        samples in their own shape, [B, C, H, W] with values in [0, 1] as GenerationManager leaves them or [B, 1, 2] for 2-D data, in
+        chunks of `batch_size`, and is applied to both sets, chunk by chunk -- it must treat every sample on its own (no batch
+        statistics) for the figures not to depend on `batch_size`.  No feature network is built here, and FID is not computed.
+        The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`."""
+        from . import metrics
+        N = int(data_to_generate)
+        assert int(nearest_k) == nearest_k and 1 <= nearest_k <= metrics.MAX_NEAREST_K, (
+            'evaluate_prdc: nearest_k must be an integer in [1, %d], got %r' % (metrics.MAX_NEAREST_K, nearest_k))
+        assert N <= 0 or nearest_k < N, 'evaluate_prdc: nearest_k = %d needs more than %d samples, got %d' % (nearest_k, nearest_k, N)
+        assert features is None or callable(features), 'evaluate_prdc: features must be None or a callable, got %r' % (features,)
+        real, gen, shape = self._real_and_samples('evaluate_prdc', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                                  kwargs)
+        if features is not None:
+            real, gen = (self._features(features, t, shape, batch_size) for t in (real, gen))
+        fig = metrics.prdc(real, gen, nearest_k=int(nearest_k))
+        res = dict(fig, f_1_pr=metrics.f_1(fig['precision'], fig['recall']), f_1_dc=metrics.f_1(fig['density'], fig['coverage']))
+        for k, v in res.items():
+            self.evals[k].append(v)
+        return res
+
+    @staticmethod
+    def _features(features, flat, shape, batch_size):
+        """`features` applied to the [N, D] set `flat` in chunks of `batch_size`, every chunk in the samples' own shape on the GPU:
+        an [N, F] float32 device tensor."""
+        batch_size = max(1, int(batch_size))
+        dev = flat.device if flat.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        out = []
+        for first in range(0, len(flat), batch_size):
+            x = flat[first:first + batch_size].to(dev).reshape((-1,) + tuple(shape))
+            f = torch.as_tensor(features(x))
+            assert f.dtype == torch.float32 and f.dim() == 2 and f.shape[0] == x.shape[0], (
+                'evaluate_prdc: features must return float32 [B, F], got %s %s for a batch of %d' % (f.dtype, tuple(f.shape), x.shape[0]))
+            out.append(f.to(dev))
+        return torch.cat(out)
 
     def evaluate_metrics_2d(self, models, real_data, data_to_generate, batch_size, class_labels=None, seed=0, **kwargs):
         """The reference's whole evaluation of a 2-D config (EvaluationManager.py:126-168, :218-230) from ONE generation: `wass`, `mmd`,

@@ -1,7 +1,9 @@
-"""Sample-quality metrics on the device.  Three are built: the multi-bandwidth Gaussian MMD of the reference
+"""Sample-quality metrics on the device.  Four are built: the multi-bandwidth Gaussian MMD of the reference
 (bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153), its PRD
-precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168) and its Wasserstein figure
-(bem/evaluate/wasserstein.py:47-52 = pyemd.emd_samples, called at EvaluationManager.py:146-151).
+precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168), its Wasserstein figure
+(bem/evaluate/wasserstein.py:47-52 = pyemd.emd_samples, called at EvaluationManager.py:146-151) and PRDC FROM FEATURES: the
+precision / recall / density / coverage of the `prdc` package's compute_prdc (the last line of bem/evaluate/fid_score.py:303-336),
+which is k-nearest-neighbour geometry on two [N, F] arrays and needs no weights.
 
     mmd(source, target) -> float                      dlpm_mmd_f32: tiled pairwise reduction, no n x n array
     MMD_loss(kernel_mul, kernel_num)(source, target)  drop-in for the reference's class: a 0-dim fp32 tensor
@@ -11,11 +13,15 @@ precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at Eva
                                                       drop-ins under the reference's names and signatures
     wass(first, second, bins='auto') -> float         dlpm_wass_f32: histogram earth mover's distance in closed form
     compute_wasserstein_distance(data, gen_samples)   drop-in for the reference's function (its histogram branch)
+    prdc(real, fake, nearest_k=5) -> dict             dlpm_prdc_f32: k-NN radii by streaming selection, fp64 distances
+    compute_prdc(real_features, fake_features, nearest_k)   drop-in for the `prdc` package's function
 
 Inputs are float32 tensors or arrays [N, ...] (rows are flattened), on the host or the GPU; host inputs are copied once.
 Unequal counts are allowed (the reference's broadcast raises on them): sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2).
-FID / PRDC need Inception weights; they are not built; neither are the reference's unused get_MMD / MMDStatistic / MMD helpers,
-nor the `manual_compute` branch of compute_wasserstein_distance (a general 2N x 2N transport problem)."""
+Not built: FID (mean, covariance and a matrix square root of Inception features) and any Inception forward -- the network needs
+weights nobody can ship; bring the features (`prdc`, `EvaluationManager.evaluate_prdc(features=...)`).  Neither are the reference's
+unused get_MMD / MMDStatistic / MMD helpers, nor the `manual_compute` branch of compute_wasserstein_distance (a general 2N x 2N
+transport problem)."""
 import numpy as np
 import torch
 
@@ -374,3 +380,78 @@ def compute_wasserstein_distance(data, gen_samples, manual_compute=False, num_sa
     if not normalized:
         raise NotImplementedError('compute_wasserstein_distance: normalized=False is not built (DESIGN 8)')
     return wass(gen_samples[:num_samples], data[:num_samples], bins=bins, range=_range)
+
+
+# ---------------------------------------------------------------------------------------------- PRDC (k-NN precision / recall / density / coverage)
+MAX_NEAREST_K = 32
+
+
+def f_1(a, b):
+    """EvaluationManager.py:215-225: 2 a b / (a + b), or 0 when a + b is 0 (f_1_pr of precision / recall, f_1_dc of density / coverage)."""
+    return 2 * a * b / (a + b) if a + b > 0 else 0.
+
+
+def _prdc_check(who, real, fake, nearest_k):
+    x, y = _row_pair(who, real, 'real', fake, 'fake')
+    assert int(nearest_k) == nearest_k and 1 <= nearest_k <= MAX_NEAREST_K, '%s: nearest_k must be an integer in [1, %d], got %r' % (
+        who, MAX_NEAREST_K, nearest_k)
+    assert nearest_k < min(x.shape[0], y.shape[0]), '%s: nearest_k = %d needs more than %d points in both sets, got %d and %d' % (
+        who, nearest_k, nearest_k, x.shape[0], y.shape[0])
+    return x, y, int(nearest_k)
+
+
+def prdc_device(real, fake, nearest_k=5, return_radii=False):
+    """The call itself, without a host synchronisation: (out, counts) on the GPU -- out float64 [8] = precision, recall, density,
+    coverage, f_1_pr, f_1_dc, status, reserved; counts int64 [4] = precision hits, recall hits, density pair count, coverage hits.
+    status 1 (a non-finite input value) leaves the six figures NaN.  `return_radii=True` returns (out, counts, radii_real [n1],
+    radii_fake [n2]), float64: the distance of every point to its nearest_k-th neighbour within its own set.  Enqueued on the
+    current stream; it can be captured in a torch.cuda.graph."""
+    x, y, k = _prdc_check('prdc', real, fake, nearest_k)
+    x, y, dev = _on_device(x, y)
+    L = _lib.lib()
+    n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    ws = _workspace(L.dlpm_prdc_workspace_bytes(n1, n2, D, k), dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        rr = torch.empty(n1, dtype=torch.float64, device=dev) if return_radii else None
+        rf = torch.empty(n2, dtype=torch.float64, device=dev) if return_radii else None
+        _lib.check(L.dlpm_prdc_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, k, ws.data_ptr(), ws.numel(), rr.data_ptr() if return_radii else None,
+                                   rf.data_ptr() if return_radii else None, counts.data_ptr(), out.data_ptr(), _lib.stream_ptr()))
+    return (out, counts, rr, rf) if return_radii else (out, counts)
+
+
+def prdc(real, fake, nearest_k=5, return_parts=False, return_radii=False):
+    """precision, recall, density and coverage (Kynkaanniemi et al. 2019, Naeem et al. 2020; the `prdc` package) of `fake` rows
+    against `real` rows as a dict of Python floats.  With k = nearest_k: the radius of a point is its distance to its k-th nearest
+    neighbour within its own set (the (k+1)-th smallest of its row of distances, itself included); precision = share of fake points
+    inside some real ball, recall = share of real points inside some fake ball, density = number of (real ball, fake point)
+    incidences / (k n_fake), coverage = share of real points whose nearest fake point lies inside their own ball; every comparison
+    strict.  Distances are fp64; rows of more than 16 values go through the centred Gram form, where ties are those of fp64 rounding,
+    not of exact arithmetic.  ValueError on a non-finite input value.
+    `return_parts=True` returns (dict, parts) with parts = {'counts': int64 [4] (precision hits, recall hits, density pair count,
+    coverage hits), 'n1', 'n2', 'nearest_k'}, and with `return_radii=True` also 'radii_real' [n1] and 'radii_fake' [n2], float64."""
+    res = prdc_device(real, fake, nearest_k, return_radii=return_parts and return_radii)
+    o = res[0].cpu().numpy()
+    if int(o[6]):
+        raise ValueError('prdc: a non-finite value in the input')
+    figures = {'precision': float(o[0]), 'recall': float(o[1]), 'density': float(o[2]), 'coverage': float(o[3])}
+    if not return_parts:
+        return figures
+    parts = {'counts': res[1].cpu().numpy(), 'n1': int(np.shape(real)[0]), 'n2': int(np.shape(fake)[0]), 'nearest_k': int(nearest_k)}
+    if return_radii:
+        parts['radii_real'], parts['radii_fake'] = res[2].cpu().numpy(), res[3].cpu().numpy()
+    return figures, parts
+
+
+def compute_prdc(real_features, fake_features, nearest_k):
+    """The `prdc` package's compute_prdc under its own name and keyword names: dict(precision, recall, density, coverage) of two
+    [N, F] feature arrays.  float32 or float64 arrays or tensors; float64 is rounded to float32 ONCE on the way in (the package
+    works on whatever it is given; the distances themselves are fp64 here as there)."""
+    def f32(a, name):
+        t = torch.as_tensor(a)
+        assert t.dtype in (torch.float32, torch.float64), 'compute_prdc takes float32 or float64 %s, got %s' % (name, t.dtype)
+        return t.to(torch.float32)
+    real, fake = f32(real_features, 'real_features'), f32(fake_features, 'fake_features')
+    _prdc_check('compute_prdc', real, fake, nearest_k)
+    return prdc(real, fake, nearest_k=nearest_k)

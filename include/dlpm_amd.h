@@ -423,6 +423,35 @@ int dlpm_wass_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2
                   dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-quality metric: precision / recall / density / coverage of the `prdc` package, compute_prdc(real_features, fake_features,
+ * nearest_k) as bem/evaluate/fid_score.py:303-336 calls it, between real rows x = R [n1, D] and fake rows y = G [n2, D], fp32 on the
+ * device.  Plain k-nearest-neighbour geometry: no network, no weights.  With k = nearest_k and d the Euclidean distance:
+ *   r_i = the (k+1)-th smallest value of {d(R_i, R_l) : all l, l = i included}, counted with multiplicity (np.partition semantics);
+ *   g_j the same within G;
+ *   precision = #{j : there is an i with d(R_i, G_j) < r_i} / n2        recall   = #{i : there is a j with d(R_i, G_j) < g_j} / n1
+ *   density   = #{(i, j) : d(R_i, G_j) < r_i} / (k n2)                  coverage = #{i : min_j d(R_i, G_j) < r_i} / n1
+ * all comparisons strict;  f_1_pr = 2 P R / (P + R) and f_1_dc = 2 D C / (D + C), 0 where the denominator is 0
+ * (EvaluationManager.py:215-225).  Squared distances are fp64 and the comparisons are made on them; sqrt only for the radii written
+ * out.  D <= 16: sum (a - b)^2 in d order on the VALU (exact on integer-valued inputs: ties follow the definition).  D > 16: rows
+ * centred on the pooled mean in fp64, tiles of C C^T on the fp64 MFMA, d^2 = |c_i|^2 + |c_j|^2 - 2 c_i.c_j clamped at 0 (ties are those
+ * of fp64 rounding, not of exact arithmetic).  No n x n array is stored: a streaming selection of the k+1 smallest per row and column
+ * segment, then one walk over the R x G tiles combined with integer atomics only -- the same inputs give the same bits.  One enqueue
+ * sequence without a host synchronisation (it can be captured in a hipGraph).
+ * ------------------------------------------------------------------------------------------ */
+/* Bytes of workspace a call needs, O((n1 + n2) (k + 1) segments); DLPM_ERR_ARG (-1) for n1 < 1, n2 < 1, D < 1, more than 2^22 rows in a
+ * set, nearest_k outside 1..32 or nearest_k >= min(n1, n2). */
+int64_t dlpm_prdc_workspace_bytes(int64_t n1, int64_t n2, int64_t D, int32_t nearest_k);
+
+/* radii_real_out_dev: null or double [n1] = r_i; radii_fake_out_dev: null or double [n2] = g_j.  counts_out_dev: int64 [4] =
+ * (precision hits, recall hits, density pair count, coverage hits).  out_dev: double [8] = precision, recall, density, coverage,
+ * f_1_pr, f_1_dc, status, reserved.  status 1 = a non-finite input value: the six figures are NaN, the counts 0, nothing faults.
+ * DLPM_ERR_ARG for the shapes above or a null / misaligned pointer; DLPM_ERR_NOMEM for a short workspace (which must be 16-byte
+ * aligned) -- before any launch. */
+int dlpm_prdc_f32(const float *x_dev, int64_t n1, const float *y_dev, int64_t n2, int64_t D, int32_t nearest_k, void *workspace_dev,
+                  int64_t workspace_bytes, double *radii_real_out_dev, double *radii_fake_out_dev, int64_t *counts_out_dev,
+                  double *out_dev, dlpm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Generated-image dump: what EvaluationManager does with each chunk of samples,
  * bem/evaluate/EvaluationManager.py:174-196 -- `tvu.save_image(samples[i], f"{i+total}.png")` per sample.
  * ------------------------------------------------------------------------------------------ */
