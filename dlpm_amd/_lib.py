@@ -187,6 +187,14 @@ SIGNATURES = {
     'dlpm_sampler_destroy': (None, [vp]),
 }
 
+# the same for include/dlpm_amd_fd.h (the Frechet distance); lib() applies it after SIGNATURES
+SIGNATURES_FD = {
+    'dlpm_fd_workspace_bytes': (i64, [i64, i64, i64]),
+    'dlpm_fd_stats_f32': (C.c_int, [vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    'dlpm_fd_from_stats_f64': (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp]),
+    'dlpm_fd_f32': (C.c_int, [vp, i64, vp, i64, i64, vp, i64, vp, vp]),
+}
+
 _lib = None
 
 
@@ -202,7 +210,7 @@ def lib():
             raise DlpmError('libdlpm_amd.so is missing at %s -- run `python -m dlpm_amd.build` '
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -19,11 +19,16 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_wass REAL.npy --generate N [--wass_bins K]: generate N samples and print the reference's `wass` figure between the first N
   float32 samples of REAL.npy and them (EvaluationManager.evaluate_wass: the earth mover's distance between the histograms of the
   flattened sets, the last sample of each left out as the reference does; 250 bins from 512 samples on, else numpy's 'auto').  With
-  more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc the samples are generated once and every figure is printed.
+  more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc / --eval_fid the samples are generated once and every figure is printed.
   --eval_prdc REAL.npy --generate N [--nearest_k K]: generate N samples and print the k-nearest-neighbour precision, recall, density
   and coverage (the `prdc` package's compute_prdc) between the first N float32 samples of REAL.npy and them, with f_1_pr and f_1_dc
   (EvaluationManager.evaluate_prdc on the flattened samples; K = 5 neighbours by default).  A feature network is plugged in through
-  the Python call (`features=`), not here; FID is not computed.
+  the Python call (`features=`), not here.
+  --eval_fid REAL.npy|STATS.npz --generate N [--save_fid_stats OUT.npz]: generate N samples and print the Frechet distance
+  (calculate_frechet_distance on mean / covariance statistics) between the first N float32 samples of REAL.npy -- or the precomputed
+  `mu` / `sigma` of STATS.npz -- and them (EvaluationManager.evaluate_fid on the flattened samples, at most 4096 values each; the name
+  FID belongs to Inception features, which come in through the Python call's `features=`).  --save_fid_stats writes the real set's
+  `mu` / `sigma` (float64) for later runs.  It shares the one generation with the other --eval_* flags.
 """
 import argparse
 import os
@@ -120,8 +125,17 @@ def main(argv=None):
                          '`prdc precision <p> recall <r> density <d> coverage <c> f_1_pr <f> f_1_dc <f> over <N> generated vs <N> real '
                          'samples`')
     ap.add_argument('--nearest_k', type=int, default=5, help='with --eval_prdc: the number of neighbours (default 5)')
+    ap.add_argument('--eval_fid', default=None, metavar='REAL.npy|STATS.npz',
+                    help='with --generate N: Frechet distance between the mean / covariance of the first N float32 samples of REAL.npy (or '
+                         'the mu / sigma of STATS.npz) and those of the N generated samples, flattened; prints `fid <value> over <N> '
+                         'generated vs <N> real samples` (`vs precomputed statistics` for an .npz)')
+    ap.add_argument('--save_fid_stats', default=None, metavar='OUT.npz',
+                    help='with --eval_fid REAL.npy: write the real set\'s mu / sigma (float64) to this file')
     a = ap.parse_args(argv)
-    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc)):
+    if a.save_fid_stats and not (a.eval_fid and not a.eval_fid.endswith('.npz')):
+        raise SystemExit('--save_fid_stats needs --eval_fid REAL.npy')
+    for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc),
+                        ('--eval_fid', a.eval_fid)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -192,7 +206,7 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
-    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc:
+    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
         value = samples = None
@@ -239,6 +253,23 @@ def main(argv=None):
                 value = res
             else:                                       # beside --eval_prd its PRD figures keep their keys; the k-NN ones go under 'prdc'
                 value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass': value}, prdc=res)
+        if a.eval_fid:
+            if samples is None:
+                samples = generated()
+            if a.eval_fid.endswith('.npz'):
+                f = ev.evaluate_fid({'default': model}, None, N, p['eval']['batch_size'], real_stats=a.eval_fid, samples=samples)
+                print('fid %.9g over %d generated vs precomputed statistics' % (f, N))
+            else:
+                real = real_of(a.eval_fid)
+                f = ev.evaluate_fid({'default': model}, real, N, p['eval']['batch_size'], samples=samples)
+                print('fid %.9g over %d generated vs %d real samples' % (f, N, N))
+                if a.save_fid_stats:
+                    mu, sigma = dlpm_amd.feature_statistics(torch.as_tensor(real)[:N])
+                    np.savez(a.save_fid_stats, mu=mu.cpu().numpy(), sigma=sigma.cpu().numpy())
+            if value is None:
+                value = f
+            else:
+                value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass': value}, fid=f)
         if a.out:
             np.save(a.out, samples.cpu().numpy())
         return value

@@ -9,8 +9,9 @@ are the reference's (`<gen_data_path>/<i>.png`, i counting over all chunks).  Wi
 dump is one `dataset_stream()`: sample i is the same whatever the chunk size, so `device_batch` may enlarge the
 chunks beyond `eval.batch_size` without changing a pixel.
 
-Of the metrics half, FID and any Inception forward are out of scope (the network needs weights nobody can ship) and `evals` keeps the
-reference's key for it (`evaluate_metrics_2d` appends the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
+Of the metrics half, any Inception forward is out of scope (the network needs weights nobody can ship); `fid` is filled by
+`evaluate_fid` with the Frechet distance of the features the caller brings, or of the flattened samples (`evaluate_metrics_2d` appends
+the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
 (GenerativeLevyProcess.training_losses), forward only, on held-out samples; `mmd`, which `evaluate_mmd` fills with the reference's
 multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
 the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device; `wass`, which
@@ -362,8 +363,51 @@ class EvaluationManager:
             self.evals[k].append(v)
         return res
 
+    def evaluate_fid(self, models, real_data, data_to_generate, batch_size, class_labels=None, features=None, real_stats=None,
+                     samples=None, **kwargs):
+        """Frechet distance (calculate_frechet_distance on np.mean / np.cov statistics, bem/evaluate/fid_score.py:118-171, the `fid` of
+        EvaluationManager.py:198-205) between `real_data[:data_to_generate]` and `data_to_generate` generated samples, as a Python float
+        appended to `evals['fid']`.
+        The name FID belongs to Inception pool3 features: this is the Frechet distance of whatever `features` returns.
+
+        `features`: None -- the flattened samples are the features (at most 4096 values) -- or a callable as in `evaluate_prdc`.
+        `real_stats`: None, a pair (mu [F], sigma [F, F]) of float64 arrays or tensors, or the path of an .npz holding `mu` and `sigma`
+        (the reference's precomputed-statistics files, compute_statistics_of_path): it takes the place of the real set's statistics,
+        and `real_data` may then be None.  The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`."""
+        from . import metrics
+        N = int(data_to_generate)
+        assert N >= 2, 'evaluate_fid: a covariance needs at least 2 samples, got data_to_generate = %d' % N
+        assert features is None or callable(features), 'evaluate_fid: features must be None or a callable, got %r' % (features,)
+        if real_stats is not None:
+            if isinstance(real_stats, (str, os.PathLike)):
+                with np.load(real_stats) as z:
+                    real_stats = (z['mu'], z['sigma'])
+            assert len(real_stats) == 2, 'evaluate_fid: real_stats must be (mu, sigma) or the path of an .npz with mu and sigma'
+            mu1, sigma1 = (torch.as_tensor(v) for v in real_stats)
+            assert mu1.dtype == torch.float64 and sigma1.dtype == torch.float64, 'evaluate_fid takes float64 real_stats, got %s and %s' % (
+                mu1.dtype, sigma1.dtype)
+            assert mu1.dim() == 1 and tuple(sigma1.shape) == (mu1.shape[0],) * 2, 'evaluate_fid: real_stats of shapes %s and %s' % (
+                tuple(mu1.shape), tuple(sigma1.shape))
+            if samples is not None:
+                gen, shape = self._given_samples('evaluate_fid', samples, N)
+            else:
+                gen, shape = self._generate_flat(models, N, batch_size, self._labels(class_labels, N), kwargs)
+            real = None
+        else:
+            real, gen, shape = self._real_and_samples('evaluate_fid', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                                      kwargs)
+        if features is not None:
+            real, gen = (None if t is None else self._features(features, t, shape, batch_size, who='evaluate_fid') for t in (real, gen))
+        if real is not None:
+            value = metrics.fd(real, gen)
+        else:
+            assert gen.shape[1] == mu1.shape[0], 'evaluate_fid: real_stats of %d features, the samples have %d' % (mu1.shape[0], gen.shape[1])
+            value = metrics.calculate_frechet_distance(mu1, sigma1, *metrics.feature_statistics(gen))
+        self.evals['fid'].append(value)
+        return value
+
     @staticmethod
-    def _features(features, flat, shape, batch_size):
+    def _features(features, flat, shape, batch_size, who='evaluate_prdc'):
         """`features` applied to the [N, D] set `flat` in chunks of `batch_size`, every chunk in the samples' own shape on the GPU:
         an [N, F] float32 device tensor."""
         batch_size = max(1, int(batch_size))
@@ -373,7 +417,7 @@ class EvaluationManager:
             x = flat[first:first + batch_size].to(dev).reshape((-1,) + tuple(shape))
             f = torch.as_tensor(features(x))
             assert f.dtype == torch.float32 and f.dim() == 2 and f.shape[0] == x.shape[0], (
-                'evaluate_prdc: features must return float32 [B, F], got %s %s for a batch of %d' % (f.dtype, tuple(f.shape), x.shape[0]))
+                '%s: features must return float32 [B, F], got %s %s for a batch of %d' % (who, f.dtype, tuple(f.shape), x.shape[0]))
             out.append(f.to(dev))
         return torch.cat(out)
 

@@ -1,9 +1,10 @@
-"""Sample-quality metrics on the device.  Four are built: the multi-bandwidth Gaussian MMD of the reference
+"""Sample-quality metrics on the device.  Five are built: the multi-bandwidth Gaussian MMD of the reference
 (bem/evaluate/mmd_loss.py:5-37, `MMD_loss(kernel_mul, kernel_num)(source, target)`, called at EvaluationManager.py:153), its PRD
 precision / recall (bem/evaluate/prd_score.py, prd_legacy.py:6-16, called at EvaluationManager.py:157-168), its Wasserstein figure
 (bem/evaluate/wasserstein.py:47-52 = pyemd.emd_samples, called at EvaluationManager.py:146-151) and PRDC FROM FEATURES: the
 precision / recall / density / coverage of the `prdc` package's compute_prdc (the last line of bem/evaluate/fid_score.py:303-336),
-which is k-nearest-neighbour geometry on two [N, F] arrays and needs no weights.
+which is k-nearest-neighbour geometry on two [N, F] arrays and needs no weights; and the FRECHET DISTANCE FROM FEATURES
+(calculate_frechet_distance, fid_score.py:118-171, on np.mean / np.cov statistics), which is what FID is once the features exist.
 
     mmd(source, target) -> float                      dlpm_mmd_f32: tiled pairwise reduction, no n x n array
     MMD_loss(kernel_mul, kernel_num)(source, target)  drop-in for the reference's class: a 0-dim fp32 tensor
@@ -15,11 +16,14 @@ which is k-nearest-neighbour geometry on two [N, F] arrays and needs no weights.
     compute_wasserstein_distance(data, gen_samples)   drop-in for the reference's function (its histogram branch)
     prdc(real, fake, nearest_k=5) -> dict             dlpm_prdc_f32: k-NN radii by streaming selection, fp64 distances
     compute_prdc(real_features, fake_features, nearest_k)   drop-in for the `prdc` package's function
+    fd(real, fake) -> float                           dlpm_fd_f32: fp64 covariances on the MFMA, two Jacobi eigen-solves
+    feature_statistics(features) -> mu, sigma         dlpm_fd_stats_f32: the device version of calculate_activation_statistics
+    calculate_frechet_distance(mu1, sigma1, mu2, sigma2)    drop-in for the reference's function, dlpm_fd_from_stats_f64
 
 Inputs are float32 tensors or arrays [N, ...] (rows are flattened), on the host or the GPU; host inputs are copied once.
 Unequal counts are allowed (the reference's broadcast raises on them): sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2).
-Not built: FID (mean, covariance and a matrix square root of Inception features) and any Inception forward -- the network needs
-weights nobody can ship; bring the features (`prdc`, `EvaluationManager.evaluate_prdc(features=...)`).  Neither are the reference's
+Not built: any Inception forward -- the network needs weights nobody can ship; bring the features (`prdc`, `fd`,
+`EvaluationManager.evaluate_prdc(features=...)`, `evaluate_fid(features=...)`).  Neither are the reference's
 unused get_MMD / MMDStatistic / MMD helpers, nor the `manual_compute` branch of compute_wasserstein_distance (a general 2N x 2N
 transport problem)."""
 import numpy as np
@@ -455,3 +459,130 @@ def compute_prdc(real_features, fake_features, nearest_k):
     real, fake = f32(real_features, 'real_features'), f32(fake_features, 'fake_features')
     _prdc_check('compute_prdc', real, fake, nearest_k)
     return prdc(real, fake, nearest_k=nearest_k)
+
+
+# ---------------------------------------------------------------------------------------------- Frechet distance from features
+MAX_FEATURES = 4096
+FD_MAX_SWEEPS = 60
+
+
+def _fd_rows(who, a, name):
+    x = _rows(a, who, name)
+    assert x.shape[0] >= 2, '%s: a covariance needs at least 2 rows, %s has %d' % (who, name, x.shape[0])
+    assert x.shape[1] <= MAX_FEATURES, '%s: rows of at most %d values, %s has %d (bring an embedding: features=)' % (
+        who, MAX_FEATURES, name, x.shape[1])
+    return x
+
+
+def _fd_check(who, real, fake):
+    x, y = _fd_rows(who, real, 'real'), _fd_rows(who, fake, 'fake')
+    assert x.shape[1] == y.shape[1], '%s: real rows hold %d values, fake rows %d' % (who, x.shape[1], y.shape[1])
+    return x, y
+
+
+def _fd_raise(o):
+    if int(o[5]) == 1:
+        raise ValueError('fd: a non-finite value in the input')
+    if int(o[5]) == 2:
+        raise RuntimeError('fd: a Jacobi solve still rotated in sweep %d (sweeps %d and %d)' % (FD_MAX_SWEEPS, int(o[6]), int(o[7])))
+
+
+def fd_device(real, fake):
+    """The call itself: a float64 [8] tensor on the GPU holding (fd, |mu1 - mu2|^2, tr sigma1, tr sigma2, tr (sigma1 sigma2)^1/2, status,
+    sweeps of the eigen-solve of sigma1, sweeps of the eigen-solve of K).  status 1 (a non-finite input value) leaves the five figures
+    NaN; status 2: a solve still rotated in its 60th sweep.  Enqueued on the current stream, but NOT graph-capturable: the host reads
+    the device's rotation counter once per Jacobi sweep, so the call waits on the stream."""
+    x, y = _fd_check('fd', real, fake)
+    x, y, dev = _on_device(x, y)
+    L = _lib.lib()
+    n1, n2, F = x.shape[0], y.shape[0], x.shape[1]
+    ws = _workspace(L.dlpm_fd_workspace_bytes(n1, n2, F), dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        _lib.check(L.dlpm_fd_f32(x.data_ptr(), n1, y.data_ptr(), n2, F, ws.data_ptr(), ws.numel(), out.data_ptr(), _lib.stream_ptr()))
+    return out
+
+
+def _feature_statistics(x, dev):
+    L = _lib.lib()
+    n, F = x.shape
+    ws = _workspace(L.dlpm_fd_workspace_bytes(n, n, F), dev)
+    with torch.cuda.device(dev):
+        mu = torch.empty(F, dtype=torch.float64, device=dev)
+        sigma = torch.empty((F, F), dtype=torch.float64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(L.dlpm_fd_stats_f32(x.data_ptr(), n, F, ws.data_ptr(), ws.numel(), mu.data_ptr(), sigma.data_ptr(), status.data_ptr(),
+                                       _lib.stream_ptr()))
+    return mu, sigma, status
+
+
+def feature_statistics(features):
+    """(mu [F], sigma [F, F]), float64 tensors on the GPU: np.mean(features, axis=0) and np.cov(features, rowvar=False) of float32
+    `features` [N >= 2, ...] (rows flattened, at most 4096 values) -- the device version of calculate_activation_statistics
+    (fid_score.py:173-193) without its network.  sigma is symmetric bit for bit.  ValueError on a non-finite input value."""
+    x = _fd_rows('feature_statistics', features, 'features')
+    x, _, dev = _on_device(x, x)
+    mu, sigma, status = _feature_statistics(x, dev)
+    if int(status.cpu()[0]):
+        raise ValueError('feature_statistics: a non-finite value in the input')
+    return mu, sigma
+
+
+def _from_stats(mu1, sigma1, mu2, sigma2, dev):
+    L = _lib.lib()
+    F = mu1.shape[0]
+    ws = _workspace(L.dlpm_fd_workspace_bytes(2, 2, F), dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        _lib.check(L.dlpm_fd_from_stats_f64(mu1.data_ptr(), sigma1.data_ptr(), mu2.data_ptr(), sigma2.data_ptr(), F, ws.data_ptr(), ws.numel(),
+                                            out.data_ptr(), _lib.stream_ptr()))
+    return out
+
+
+def fd(real, fake, return_parts=False):
+    """Frechet distance between the Gaussians fitted to the float32 rows `real` [n1 >= 2, ...] and `fake` [n2 >= 2, ...] (flattened,
+    at most 4096 values) as a Python float: |mu1 - mu2|^2 + tr sigma1 + tr sigma2 - 2 tr (sigma1 sigma2)^1/2, in fp64 on the device.
+    It is not clamped: as in the reference it may come out slightly negative for (nearly) equal sets.  ValueError on a non-finite
+    input value, RuntimeError if an eigen-solve has not converged in 60 sweeps.
+    `return_parts=True` returns (fd, parts) with parts = {'mu1', 'sigma1', 'mu2', 'sigma2' (float64 device tensors), 'mean_term',
+    'tr_sigma1', 'tr_sigma2', 'tr_sqrt', 'sweeps' (of the two solves), 'n1', 'n2'}; the figure is the same bits either way."""
+    if not return_parts:
+        o = fd_device(real, fake).cpu().numpy()
+        _fd_raise(o)
+        return float(o[0])
+    x, y = _fd_check('fd', real, fake)
+    x, y, dev = _on_device(x, y)
+    mu1, sigma1, st1 = _feature_statistics(x, dev)
+    mu2, sigma2, st2 = _feature_statistics(y, dev)
+    if int(st1.cpu()[0]) or int(st2.cpu()[0]):
+        raise ValueError('fd: a non-finite value in the input')
+    o = _from_stats(mu1, sigma1, mu2, sigma2, dev).cpu().numpy()
+    _fd_raise(o)
+    return float(o[0]), {'mu1': mu1, 'sigma1': sigma1, 'mu2': mu2, 'sigma2': sigma2, 'mean_term': float(o[1]), 'tr_sigma1': float(o[2]),
+                         'tr_sigma2': float(o[3]), 'tr_sqrt': float(o[4]), 'sweeps': (int(o[6]), int(o[7])), 'n1': int(x.shape[0]),
+                         'n2': int(y.shape[0])}
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """fid_score.py:118-171 under its own name and argument names, on the device: float64 arrays or tensors mu [F], sigma [F, F]
+    (symmetric; F <= 4096), returns a Python float.  `eps` is accepted and unused: the reference adds it to both diagonals when
+    fractional_matrix_power of the (nearly) singular product sigma1 sigma2 comes out non-finite; the symmetric form used here
+    (eigenvalues of sigma1^1/2 sigma2 sigma1^1/2) has no such branch and no imaginary parts.  ValueError / RuntimeError as `fd`."""
+    def f64(a, name, dims):
+        t = torch.as_tensor(a)
+        assert t.dtype == torch.float64, 'calculate_frechet_distance takes float64 %s, got %s' % (name, t.dtype)
+        t = t.reshape(1) if (dims == 1 and t.dim() == 0) else t
+        t = t.reshape(1, 1) if (dims == 2 and t.dim() < 2 and t.numel() == 1) else t
+        assert t.dim() == dims, 'calculate_frechet_distance: %s must have %d dimension(s), got shape %s' % (name, dims, tuple(t.shape))
+        return t
+    m1, s1, m2, s2 = f64(mu1, 'mu1', 1), f64(sigma1, 'sigma1', 2), f64(mu2, 'mu2', 1), f64(sigma2, 'sigma2', 2)
+    assert m1.shape == m2.shape, 'Training and test mean vectors have different lengths'                # the reference's own words
+    assert s1.shape == s2.shape, 'Training and test covariances have different dimensions'
+    F = m1.shape[0]
+    assert s1.shape == (F, F), 'calculate_frechet_distance: sigma must be [%d, %d], got %s' % (F, F, tuple(s1.shape))
+    assert 1 <= F <= MAX_FEATURES, 'calculate_frechet_distance: at most %d features, got %d' % (MAX_FEATURES, F)
+    dev = next((t.device for t in (m1, s1, m2, s2) if t.is_cuda), None) or torch.device('cuda', torch.cuda.current_device())
+    m1, s1, m2, s2 = (t.to(dev).contiguous() for t in (m1, s1, m2, s2))
+    o = _from_stats(m1, s1, m2, s2, dev).cpu().numpy()
+    _fd_raise(o)
+    return float(o[0])
