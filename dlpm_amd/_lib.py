@@ -51,6 +51,12 @@ class LossArgs(C.Structure):
                 ('clamp_a', f64), ('seed', u64), ('sample_offset', i64)]
 
 
+class LimLossArgs(C.Structure):      # dlpm_lim_loss_args, include/dlpm_amd_lim.h
+    _fields_ = [('x0_dev', vp), ('t_dev', vp), ('e_dev', vp), ('x_coeff_dev', vp), ('sigma_dev', vp), ('x_t_dev', vp), ('score_dev', vp),
+                ('tvec_out_dev', vp), ('a_out_dev', vp), ('e_out_dev', vp), ('x_coeff_out_dev', vp), ('sigma_out_dev', vp),
+                ('B', i64), ('D', i64), ('alpha', f64), ('clamp_eps', f64), ('t_max', f64), ('seed', u64), ('sample_offset', i64)]
+
+
 class UNetConfig(C.Structure):
     _fields_ = [('in_channels', i32), ('model_channels', i32), ('out_channels', i32), ('num_res_blocks', i32),
                 ('num_heads', i32), ('image_size', i32), ('n_mult', i32), ('channel_mult', i32 * 8), ('n_attn', i32),
@@ -195,6 +201,12 @@ SIGNATURES_FD = {
     'dlpm_fd_f32': (C.c_int, [vp, i64, vp, i64, i64, vp, i64, vp, vp]),
 }
 
+# the same for include/dlpm_amd_lim.h (the LIM held-out loss)
+SIGNATURES_LIM = {
+    'dlpm_lim_loss_elements_f32': (C.c_int, [C.POINTER(LimLossArgs), vp]),
+    'dlpm_lim_coeffs_f32': (C.c_int, [vp, i64, f64, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -210,7 +222,7 @@ def lib():
             raise DlpmError('libdlpm_amd.so is missing at %s -- run `python -m dlpm_amd.build` '
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

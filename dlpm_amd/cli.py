@@ -9,7 +9,8 @@ or given directly with --checkpoint FILE; --ema_eval [--ema_index I] evaluates a
 Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-193).
   --eval_loss DATA.npy [--lploss P] [--median OUTER INNER]: instead of generating, the held-out denoising loss of the checkpoint on
   the float32 samples of DATA.npy (already in the net's range), EvaluationManager.evaluate_loss; --lploss / --median as the
-  reference's training flags.  The figure does not depend on --batch_size.
+  reference's training flags.  The figure does not depend on --batch_size.  With --method lim it is LIM's own objective
+  (training_losses_lim), which has no --lploss / --median.
   --eval_mmd REAL.npy --generate N: generate N samples and print the reference's multi-bandwidth Gaussian MMD between them and the
   first N float32 samples of REAL.npy (EvaluationManager.evaluate_mmd; images in [0, 1], 2-D points as they are).  May be combined
   with --out, not with --gen_data_path.  With --rng philox the figure does not depend on --batch_size.
@@ -146,6 +147,8 @@ def main(argv=None):
     if a.method is not None:
         p['method'] = a.method
     m = p['method']
+    if a.eval_loss and m == 'lim' and (a.lploss is not None or a.median is not None):
+        ap.error('--lploss / --median belong to the DLPM loss; --method lim evaluates training_losses_lim, which has neither')
     if a.alpha is not None:
         p[m]['alpha'] = a.alpha
     if a.non_iso:
@@ -192,8 +195,9 @@ def main(argv=None):
     if a.eval_loss:
         data = np.load(a.eval_loss)
         tr = dict((p.get('training') or {}).get(m) or {})      # a reference-schema YAML carries the loss settings of its training run
-        kw = {k: tr[k] for k in ('lploss', 'loss_monte_carlo', 'monte_carlo_outer', 'monte_carlo_inner', 'clamp_a', 'clamp_eps')
-              if k in tr}
+        keys = ('clamp_a', 'clamp_eps') if m == 'lim' else ('lploss', 'loss_monte_carlo', 'monte_carlo_outer', 'monte_carlo_inner',
+                                                          'clamp_a', 'clamp_eps')
+        kw = {k: tr[k] for k in keys if k in tr}
         if a.lploss is not None:
             kw['lploss'] = a.lploss
         if a.median is not None:

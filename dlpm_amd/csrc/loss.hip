@@ -8,6 +8,7 @@
 // with 16-byte accesses.  x_0 is read by index b for every replica r; nothing is repeated in memory.
 #include <algorithm>
 
+#include "cms.h"
 #include "common.h"
 #include "philox.h"
 
@@ -22,33 +23,7 @@ constexpr int kPurposeLossA = 8;      // isotropic a, replica r mod outer
 constexpr int kPurposeLossAElem = 9;  // non-isotropic a per element, replica r mod outer
 constexpr int kPurposeLossZ = 10;     // the Gaussian z, replica r
 
-// CMS in fp64 exactly as noise.hip's k_skewed_levy evaluates it (S1, beta = 1, stability alpha/2)
-struct Cms {
-    double a, zeta, th0, scale;
-};
-
-__device__ inline Cms cms_setup(double alpha) {
-    const double pi = 3.141592653589793;
-    Cms c;
-    c.a = alpha * 0.5;
-    c.zeta = tan(pi * c.a * 0.5);
-    c.th0 = atan(c.zeta) / c.a;
-    c.scale = 2.0 * pow(cos(pi * alpha * 0.25), 2.0 / alpha);
-    return c;
-}
-
-__device__ inline float cms_draw(const Cms &c, uint64_t seed, uint64_t gidx, uint32_t row, uint32_t purpose, uint32_t rep) {
-    const double pi = 3.141592653589793;
-    uint4 r = philox4x32_10(make_uint4((uint32_t)gidx, (uint32_t)(gidx >> 32), row, purpose | (rep << 8)), seed);
-    double U = ((double)(((uint64_t)r.x << 21) ^ (r.y >> 11)) + 0.5) * (1.0 / 9007199254740992.0);
-    double V = ((double)(((uint64_t)r.z << 21) ^ (r.w >> 11)) + 0.5) * (1.0 / 9007199254740992.0);
-    double W = -log(V);
-    double th = U * pi + (-pi / 2.0);
-    double ath = c.a * th, cs = cos(th), tg = tan(th);
-    double lead = W / (cs / tan(c.a * (c.th0 + th)) + sin(th));
-    double core = (cos(ath) + sin(ath) * tg - c.zeta * (sin(ath) - cos(ath) * tg)) / W;
-    return (float)(lead * pow(core, 1.0 / c.a) * c.scale);
-}
+// (11-13 belong to the LIM loss: lim_loss.hip)
 
 __device__ inline float draw_a(const dlpm_loss_args &p, const Cms &c, uint64_t gidx, uint32_t row, uint32_t purpose, uint32_t rep) {
     if (p.alpha == 2.0) return 2.0f;

@@ -12,8 +12,8 @@ chunks beyond `eval.batch_size` without changing a pixel.
 Of the metrics half, any Inception forward is out of scope (the network needs weights nobody can ship); `fid` is filled by
 `evaluate_fid` with the Frechet distance of the features the caller brings, or of the flattened samples (`evaluate_metrics_2d` appends
 the reference's own 0.0 for a 2-D config).  Built are: `losses`, which `evaluate_loss` fills with the reference's own objective
-(GenerativeLevyProcess.training_losses), forward only, on held-out samples; `mmd`, which `evaluate_mmd` fills with the reference's
-multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
+(GenerativeLevyProcess.training_losses: the DLPM loss, or LIM's own for a LIM method), forward only, on held-out samples; `mmd`,
+which `evaluate_mmd` fills with the reference's multi-bandwidth Gaussian MMD between generated and real samples; and `precision` / `recall` / `f_1_pr`, which `evaluate_prd` fills with
 the reference's PRD figures (EvaluationManager.py:157-168, :218-221) from a k-means clustering on the device; `wass`, which
 `evaluate_wass` fills with the reference's histogram earth mover's distance (EvaluationManager.py:146-151); the reference's whole
 2-D branch from one generation, `evaluate_metrics_2d`; and PRDC from features -- `precision`, `recall`, `density`, `coverage`, `f_1_pr`,
@@ -172,10 +172,23 @@ class EvaluationManager:
         slot of an [outer * inner * N] device buffer that ONE call on all N samples would put them in, and the estimator runs
         once at the end -- so with rng='philox' the figure is bit-identical for every batch_size.  (rng='reference' continues the
         host streams chunk by chunk, as successive reference calls would.)  One non-finite check for the whole pass.
-        `per_timestep=True` returns (loss, t[N] int32, terms[outer * inner * N]) on the host."""
+        `per_timestep=True` returns (loss, t[N] int32, terms[outer * inner * N]) on the host.
+
+        A LIM method (`method.LIM`) is evaluated on its own objective, training_losses_lim (GenerativeLevyProcess.py:680-709), the same
+        way: one dataset_stream(), one [N] buffer of per-sample terms, one reduce, bit-identical for every batch_size under Philox;
+        `per_timestep=True` returns (loss, t[N] float32, terms[N]).  Its `loss_kwargs` are clamp_a and clamp_eps; the DLPM-only ones
+        (lploss, loss_monte_carlo, monte_carlo_*, loss_type) and class labels are refused before any device work."""
         method = self.method
         if method.LIM:
-            raise NotImplementedError('evaluate_loss covers the DLPM loss; training_losses_lim is outside this build')
+            dlpm_only = sorted(set(loss_kwargs) & {'lploss', 'loss_monte_carlo', 'monte_carlo_outer', 'monte_carlo_inner', 'loss_type'})
+            if dlpm_only:
+                raise TypeError('evaluate_loss: {} belong to the DLPM loss; training_losses_lim takes clamp_a and clamp_eps'.format(
+                    ', '.join(dlpm_only)))
+            assert set(loss_kwargs) <= {'clamp_a', 'clamp_eps'}, 'unknown loss arguments {}'.format(
+                sorted(set(loss_kwargs) - {'clamp_a', 'clamp_eps'}))
+            if class_labels is not None:
+                raise NotImplementedError('training_losses_lim takes unconditional nets only: the reference hard-wires y = None '
+                                          '(dlpm/methods/GenerativeLevyProcess.py:706)')
         model = models['default']
         if not torch.is_tensor(data) and not isinstance(data, np.ndarray):
             data = [torch.as_tensor(b[0] if isinstance(b, (tuple, list)) else b) for b in data]
@@ -184,6 +197,9 @@ class EvaluationManager:
         N = int(data.shape[0])
         assert N > 0, 'evaluate_loss: no data'
         assert data.dtype == torch.float32, 'evaluate_loss takes float32 data in the net\'s range, got %s' % data.dtype
+        if method.LIM:
+            return self._evaluate_loss_lim(model, data, N, batch_size, per_timestep, loss_kwargs.get('clamp_a'),
+                                           loss_kwargs.get('clamp_eps'))
         kw = dict(loss_type='EPS_LOSS', lploss=2.0, loss_monte_carlo='mean', monte_carlo_outer=1, monte_carlo_inner=1,
                   model_kwargs=None, clamp_a=None, clamp_eps=None)
         assert set(loss_kwargs) <= set(kw), 'unknown loss arguments {}'.format(sorted(set(loss_kwargs) - set(kw)))
@@ -212,6 +228,35 @@ class EvaluationManager:
                                        out_offset=first, t_out=t_all[first:first + x.shape[0]])
             with torch.inference_mode():
                 loss = float(method._loss_reduce(terms, N, outer, inner, kw['loss_monte_carlo'], check_finite=True))
+        self.evals['losses'] = np.append(self.evals['losses'], np.float32(loss))
+        if per_timestep:
+            return loss, t_all.cpu(), terms.cpu()
+        return loss
+
+    def _evaluate_loss_lim(self, model, data, N, batch_size, per_timestep, clamp_a, clamp_eps):
+        """evaluate_loss for a LIM method: the same chunk loop inside one dataset_stream(), the per-sample terms written at their
+        global slot of one [N] device buffer, one reduce at the end."""
+        method = self.method
+        dev = torch.device(method.device)
+        batch_size = max(1, int(batch_size))
+        if dev.type != 'cuda':
+            raise NotImplementedError('training_losses_lim runs on the GPU only; there is no CPU fallback')
+        terms = t_all = None
+        with method.dataset_stream():
+            for first in range(0, N, batch_size):
+                x = data[first:first + batch_size].to(dev)
+                noise = method._lim_check_args(model, x)
+                if terms is None:
+                    method.dlpm.gen_a.setParams(clamp_a=clamp_a)
+                    method.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
+                    if hasattr(model, 'eval'):
+                        model.eval()
+                    terms = torch.empty(N, dtype=torch.float32, device=dev)
+                    t_all = torch.empty(N, dtype=torch.float32, device=dev)
+                with torch.inference_mode():
+                    method._lim_loss_terms(model, x, clamp_eps, noise, out=terms, out_offset=first, t_out=t_all[first:first + x.shape[0]])
+            with torch.inference_mode():
+                loss = float(method._loss_reduce(terms, N, 1, 1, 'mean', check_finite=True))
         self.evals['losses'] = np.append(self.evals['losses'], np.float32(loss))
         if per_timestep:
             return loss, t_all.cpu(), terms.cpu()

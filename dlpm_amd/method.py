@@ -12,7 +12,9 @@ dlpm/methods/GenerativeLevyProcess.py:48-90,512-569 (what `GenerationManager.gen
 
 `training_losses(...)` is the forward half of the reference's objective as a held-out evaluation metric (no
 backward pass): forward noising at a per-sample timestep, the net, the loss terms and the mean / median-of-means
-estimator, three kernels of libdlpm_amd around one forward.
+estimator, three kernels of libdlpm_amd around one forward.  With LIM=True it is LIM's own objective (training_losses_lim): a
+symmetric alpha-stable draw, a continuous time, x_t from the VPSDE coefficients, the net, and the mean smooth-L1 against -e / alpha
+-- one kernel of its own (k_lim_loss_elements) and the terms / estimator kernels of the DLPM loss.
 
 Two RNG modes:
   rng='philox'     device Philox4x32-10 keyed by (seed, GLOBAL sample index, step, element): the
@@ -741,17 +743,166 @@ class GenerativeLevyProcess:
             loss = self._loss_reduce(r['losses'], x_start.shape[0], outer, inner, loss_monte_carlo, check_finite)
         return (loss, r['losses'], r['t']) if return_terms else loss
 
+    # -------------------------------------------------------------------------------- BEM: held-out loss, LIM
+    def _lim_loss_host_draws(self, shape, clamp_eps):
+        """rng='reference': the draws of training_losses_lim on the host in the reference's order (GenerativeLevyProcess.py:691-705,
+        Distributions.py:57-73).  alpha != 2: B unclamped skewed-Levy draws on the restated numpy stream, `randn(shape)` then
+        `rand(B)` on ReferenceStreams.G, e = clamp(sqrt(a) z) in fp32 (the root correctly rounded, the product and the clamp torch's);
+        alpha = 2: `randn`, then `rand`.  Returns
+        {'t', 'e', 'a' (None at alpha = 2), 'z'} on the CPU."""
+        st = self._streams()
+        B = shape[0]
+        if self.alpha == 2.0:
+            a, z = None, torch.randn(list(shape), generator=st.G)
+            e = z
+        else:
+            a = st.skewed_levy(self.alpha, B, None)
+            z = torch.randn(list(shape), generator=st.G)
+            # sqrt(a) as the correctly rounded fp32 root (the fp64 one rounded once: 53 >= 2 * 24 + 2 bits).  torch.sqrt on a CPU is
+            # within 1 ulp of it but not the same value on every host (0.7 % of 2^20 inputs differ from the IEEE root on the host that
+            # recorded F22, 19 % on an MI355X host), and the reference's recorded e is the product with the IEEE root in every F22 case
+            root = torch.from_numpy(np.sqrt(a.numpy().astype(np.float64)).astype(np.float32))
+            e = root.view(-1, *([1] * (len(shape) - 1))) * z
+            if clamp_eps is not None:
+                e = torch.clamp(e, -clamp_eps, clamp_eps)
+        t = torch.rand(B, generator=st.G) * (self.sde.T - 1e-5) + 1e-5
+        return {'t': t, 'e': e, 'a': a, 'z': z}
+
+    def _lim_check_args(self, model, x_start, y=None, noise=None):
+        """Every argument check of training_losses_lim that needs no device.  Returns the injected draws as a dict of contiguous
+        fp32 tensors (on whatever device the caller left them)."""
+        from .mlp import MLPModel
+        assert self.LIM, 'training_losses_lim belongs to a method built with LIM=True'
+        if y is not None or getattr(model, 'num_classes', None) is not None:
+            raise NotImplementedError('training_losses_lim takes unconditional nets only: the reference hard-wires y = None '
+                                      '(dlpm/methods/GenerativeLevyProcess.py:706)')
+        assert torch.is_tensor(x_start) and x_start.dim() >= 2 and x_start.shape[0] >= 1, 'x_start must be a [B, ...] tensor'
+        if isinstance(model, MLPModel):
+            assert x_start.dim() == 3 and tuple(x_start.shape[1:]) == (1, model.nfeatures), x_start.shape
+        noise = dict(noise or {})
+        keys = {'t', 'e', 'x_coeff', 'sigma'}
+        assert set(noise) <= keys, 'noise takes the keys {}; got {}'.format(sorted(keys), sorted(noise))
+        noise = {k: torch.as_tensor(v).to(torch.float32).contiguous() for k, v in noise.items() if v is not None}
+        if ('x_coeff' in noise) != ('sigma' in noise):
+            raise ValueError('noise: x_coeff and sigma are given together or not at all')
+        B = x_start.shape[0]
+        for k in ('t', 'x_coeff', 'sigma'):
+            assert k not in noise or tuple(noise[k].shape) == (B,), '{} must be [B] = [{}], got {}'.format(k, B, tuple(noise[k].shape))
+        assert 'e' not in noise or noise['e'].shape == x_start.shape, 'e must have the shape of x_start {}, got {}'.format(
+            tuple(x_start.shape), tuple(noise['e'].shape))
+        return noise
+
+    def _lim_loss_terms(self, model, x_start, clamp_eps, noise, out=None, out_offset=0, t_out=None, keep=False):
+        """The launches before the estimator: k_lim_loss_elements, the net, k_loss_terms (smooth-L1).  `noise`: the dict
+        _lim_check_args returned.  Terms go to `out[out_offset + b]` (default: a fresh [B] buffer), the times to `t_out` (default:
+        a fresh [B] buffer).  Returns {'losses', 't'} and, with `keep`, 'x_t', 'score', 'e', 'a', 'x_coeff', 'sigma', 'output'.
+        No synchronisation and no host read unless rng='reference' (whose draws are made on the host)."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        L, st = _lib.lib(), _lib.stream_ptr()
+        dev = x_start.device
+        shape = list(x_start.shape)
+        B, D = shape[0], int(np.prod(shape[1:]))
+        x0 = x_start.contiguous().float()
+        if not noise and self.rng == 'reference':
+            d = self._lim_loss_host_draws(shape, clamp_eps)
+            noise = {'t': d['t'], 'e': d['e'].contiguous()}
+        if 't' in noise and 'x_coeff' not in noise and not noise['t'].is_cuda:
+            # a time known on the host: the reference's own evaluation, torch's fp32 ops on the CPU (loss.py:20-21)
+            t_host = noise['t']
+            noise = dict(noise, sigma=self.sde.marginal_std(t_host).contiguous(), x_coeff=self.sde.diffusion_coeff(t_host).contiguous())
+        inj = {k: v.to(dev) for k, v in noise.items()}
+        x_t = torch.empty(shape, dtype=torch.float32, device=dev)
+        score = torch.empty(shape, dtype=torch.float32, device=dev)
+        if t_out is None:
+            t_out = torch.empty(B, dtype=torch.float32, device=dev)
+        kept = {}
+        if keep:
+            kept = dict(e=torch.empty(shape, dtype=torch.float32, device=dev))
+            kept.update({k: torch.empty(B, dtype=torch.float32, device=dev) for k in ('a', 'x_coeff', 'sigma')})
+        seed, offset = self._philox_key()
+        a = _lib.LimLossArgs()
+        a.x0_dev, a.t_dev, a.e_dev = x0.data_ptr(), _lib.ptr(inj.get('t')), _lib.ptr(inj.get('e'))
+        a.x_coeff_dev, a.sigma_dev = _lib.ptr(inj.get('x_coeff')), _lib.ptr(inj.get('sigma'))
+        a.x_t_dev, a.score_dev, a.tvec_out_dev = x_t.data_ptr(), score.data_ptr(), _lib.ptr(t_out)
+        a.a_out_dev, a.e_out_dev = _lib.ptr(kept.get('a')), _lib.ptr(kept.get('e'))
+        a.x_coeff_out_dev, a.sigma_out_dev = _lib.ptr(kept.get('x_coeff')), _lib.ptr(kept.get('sigma'))
+        a.B, a.D, a.alpha, a.t_max = B, D, float(self.alpha), float(self.sde.T)
+        a.clamp_eps = -1.0 if clamp_eps is None else float(clamp_eps)
+        a.seed, a.sample_offset = seed, offset
+        _lib.check(L.dlpm_lim_loss_elements_f32(C.byref(a), st))
+
+        if isinstance(model, UNetModel):
+            output = model._forward_checked(x_t, t_out, None)
+        elif isinstance(model, MLPModel):
+            output = model(x_t, t_out)
+        else:
+            output = model(x_t, t_out).contiguous().float()                                      # loss.py:32
+        assert output.shape == x_t.shape, 'the model returned {}, expected {}'.format(tuple(output.shape), tuple(x_t.shape))
+
+        if out is None:
+            out = torch.empty(B, dtype=torch.float32, device=dev)
+        # F.smooth_l1_loss(output, score, beta=1, reduction='mean') (loss.py:39) is the mean of the per-sample means: every row has D
+        # elements
+        _lib.check(L.dlpm_loss_terms_f32(output.data_ptr(), score.data_ptr(), out.data_ptr(), B, 1, D, 1, out.numel(), out_offset, st))
+        if self._dataset is not None:
+            self._dataset['next'] += B
+        else:
+            self.calls += 1
+        res = {'losses': out, 't': t_out}
+        if keep:
+            res.update(kept, x_t=x_t, score=score, output=output)
+        return res
+
+    def training_losses_lim(self, model, x_start, y=None, clamp_a=None, clamp_eps=None, noise=None, return_terms=False,
+                            check_finite=True):
+        """Forward-only, under torch.inference_mode(): LIM's objective (GenerativeLevyProcess.training_losses_lim, :680-709, and
+        loss_fn, LIM/functions/loss.py:12-41) as an evaluation metric, not a training step.
+
+        One kernel of its own (k_lim_loss_elements: e, t, x_t = x0 diffusion_coeff(t) + e marginal_std(t), score = -e / alpha),
+        one forward of the net on (x_t, t), then the DLPM loss's terms kernel (smooth-L1, beta = 1) and its estimator (the mean,
+        with the non-finite flag that stands for the reference's `Nan in losses` assertion, read only with `check_finite`).
+        Returns the 0-dim fp32 loss on the device (with `return_terms`: (loss, terms[B], t[B] float32)).  `clamp_a` is accepted and
+        stored as the reference does; gen_sas draws its a without it.  Unconditional nets only.
+
+        Draws.  rng='philox': all on the device, keyed as sample() keys its own (dataset_stream() and sample_offset mean the
+        same here).  rng='reference': the reference's host order (_lim_loss_host_draws).  `noise=` injects any of 't' [B], 'e'
+        (shape of x_start, used as given), 'x_coeff' and 'sigma' [B] (together).
+
+        Coefficients.  diffusion_coeff(t) and marginal_std(t) are differences of nearly equal numbers, and the reference's fp32
+        evaluation destroys them: against fp64, marginal_std is off by 6-12 % as t -> 1e-5 (1.614e-4 against 1.541e-4 at t = 1e-5,
+        alpha = 1.7), by more than 1e-3 relative on 0.04-0.07 % of uniform draws and by more than 1e-5 on 1.8-2.7 %;
+        diffusion_coeff by up to 1.8e-5.  What a given fp32 evaluation returns there depends on its libm, so no device formula can
+        agree with it.  Hence: when t is known on the host (rng='reference', or an injected 't' that is a CPU tensor or an
+        array) and no coefficients are injected, they are computed there with lim.VPSDE's torch ops, the reference's own
+        sequence, and passed to the kernel as arrays; when t is drawn on the device (or injected as a device tensor) the kernel
+        evaluates them in fp64 from the fp32 t and rounds once."""
+        if not (torch.is_tensor(x_start) and x_start.is_cuda):
+            raise NotImplementedError('training_losses_lim runs on the GPU only; there is no CPU fallback')
+        noise = self._lim_check_args(model, x_start, y, noise)
+        self.dlpm.gen_a.setParams(clamp_a=clamp_a)          # stateful, as in the reference (:688-689)
+        self.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
+        if hasattr(model, 'eval'):
+            model.eval()
+        with torch.inference_mode():
+            r = self._lim_loss_terms(model, x_start, clamp_eps, noise)
+            loss = self._loss_reduce(r['losses'], x_start.shape[0], 1, 1, 'mean', check_finite)
+        return (loss, r['losses'], r['t']) if return_terms else loss
+
     def training_losses(self, models, x_start, model_kwargs=None, **kwargs):
         """Forward-only, under torch.inference_mode(): the result carries no autograd graph.  GenerativeLevyProcess.training_losses
         (:581-609) as a held-out metric: {'loss': 0-dim fp32 tensor on the device, 'losses': the per-extended-sample terms
         [outer * inner * B] (this build's addition), 't': the timesteps [B]}.  `model_kwargs={'y': labels}` reaches a
         class-conditional net with the labels following their sample into every replica; the nested form
         {'model_kwargs': {'y': labels}} (the only one the reference's own splat lets through) is accepted too.  Other keywords
-        as training_losses_dlpm."""
-        if self.LIM:
-            raise NotImplementedError('training_losses_lim (LIM\'s own loss and nets) is outside this build; LIM=False evaluates '
-                                      'the DLPM loss')
+        as training_losses_dlpm.  With LIM=True the call goes to training_losses_lim (`model_kwargs` is splatted into it as the
+        reference does, :606, so {'y': ...} reaches its refusal); 'losses' are then the [B] per-sample terms and 't' the
+        continuous times, float32."""
         model = models['default']
+        if self.LIM:
+            assert 'return_terms' not in kwargs
+            loss, losses, t = self.training_losses_lim(model, x_start, **dict(model_kwargs or {}), return_terms=True, **kwargs)
+            return {'loss': loss, 'losses': losses, 't': t}
         mk = dict(model_kwargs or {})
         if set(mk) == {'model_kwargs'}:
             mk = dict(mk['model_kwargs'] or {})

@@ -7,7 +7,9 @@ the library's per-launch timing (dlpm_prof_*: HIP events around every launch) an
 launch and the algorithmic bytes moved / time against the HBM peak of 8 TB/s.  The forward is not changed by the loss path; the
 sha256 over the forward's sources is printed so that a reader can compare it with any other revision.
 Run under `rocprofv3 --kernel-trace --stats -- python tools/bench_loss.py --only mnist --rounds 1` for the profiler's own kernel times.
-Usage: python tools/bench_loss.py [--rounds 5] [--calls 20] [--warmup 3] [--only cifar10|mnist|2d_data] [--kernels]"""
+`--method lim` times LIM's objective instead (training_losses_lim, Philox draws, coefficients in fp64 in the kernel); with --kernels
+its elements kernel is reported as lim_loss_elements beside the shared loss_terms / loss_reduce.
+Usage: python tools/bench_loss.py [--rounds 5] [--calls 20] [--warmup 3] [--only cifar10|mnist|2d_data] [--kernels] [--method dlpm|lim]"""
 import argparse
 import hashlib
 import json
@@ -29,7 +31,7 @@ def forward_sources_digest():
     csrc = os.path.join(ROOT, 'dlpm_amd', 'csrc')
     h = hashlib.sha256()
     for fn in sorted(os.listdir(csrc)):
-        if fn != 'loss.hip':
+        if fn not in ('loss.hip', 'lim_loss.hip'):
             h.update(fn.encode())
             h.update(open(os.path.join(csrc, fn), 'rb').read())
     return h.hexdigest()
@@ -52,6 +54,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--only', default=None)
     ap.add_argument('--kernels', action='store_true')
+    ap.add_argument('--method', default='dlpm', choices=['dlpm', 'lim'])
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'bench_loss.py needs the MI355X'
     digest = forward_sources_digest()
@@ -65,7 +68,7 @@ def main():
         shape = [B] + dlpm_amd.config.sample_shape(p)
         x = (0.5 * torch.randn(shape, generator=torch.Generator().manual_seed(1))).to('cuda')
         t = torch.rand(B, generator=torch.Generator().manual_seed(2)).to('cuda')
-        meth = dlpm_amd.GenerativeLevyProcess(ALPHA, 'cuda', T, rescale_timesteps=True, seed=1)
+        meth = dlpm_amd.GenerativeLevyProcess(ALPHA, 'cuda', T, rescale_timesteps=True, seed=1, LIM=a.method == 'lim')
         out = {}
 
         def forward():
@@ -73,7 +76,10 @@ def main():
                 out['eps'] = net(x, t)
 
         def loss():
-            out['loss'] = meth.training_losses_dlpm(net, x, clamp_a=20, check_finite=False)
+            if a.method == 'lim':
+                out['loss'] = meth.training_losses_lim(net, x, clamp_eps=20, check_finite=False)
+            else:
+                out['loss'] = meth.training_losses_dlpm(net, x, clamp_a=20, check_finite=False)
         timed(forward, a.warmup)
         timed(loss, a.warmup)
         ms = {'forward': [], 'loss': []}
@@ -82,7 +88,7 @@ def main():
                 ms[tag].append(timed(fn, a.calls))
         med = {k: statistics.median(v) for k, v in ms.items()}
         D = x[0].numel()
-        res = {'workload': '%s_b%d_T%d' % (config, B, T), 'elements': B * D, 'ms_forward': round(med['forward'], 4),
+        res = {'workload': '%s_b%d_T%d' % (config, B, T), 'method': a.method, 'elements': B * D, 'ms_forward': round(med['forward'], 4),
                'ms_loss_call': round(med['loss'], 4), 'ms_beyond_forward': round(med['loss'] - med['forward'], 4),
                'overhead_pct': round(100 * (med['loss'] / med['forward'] - 1), 3), 'loss': float(out['loss']),
                'rounds': a.rounds, 'calls_per_round': a.calls, 'all_ms': {k: [round(v, 4) for v in vs] for k, vs in ms.items()},
@@ -100,7 +106,7 @@ def main():
             kernels = {}
             for line in cbuf.value.decode().splitlines():
                 f = line.split()
-                if len(f) >= 5 and f[0].startswith('loss_'):
+                if len(f) >= 5 and f[0].startswith(('loss_', 'lim_loss_')):
                     n, total_ms, nbytes = int(f[1]), float(f[2]), float(f[4])
                     us = 1e3 * total_ms / n
                     kernels[f[0]] = {'launches': n, 'us_per_launch': round(us, 2), 'bytes_per_launch': nbytes / n,
