@@ -22,3 +22,5 @@ from .metrics import fd, fd_device, feature_statistics, calculate_frechet_distan
 from .weights import rerandomize_  # noqa: F401
 from .config import load_config, is_image_dataset, init_model_by_parameter  # noqa: F401
 from . import checkpoint  # noqa: F401
+from . import datasets  # noqa: F401
+from .datasets import Generator, get_dataset, ToyLoader  # noqa: F401

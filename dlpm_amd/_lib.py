@@ -57,6 +57,12 @@ class LimLossArgs(C.Structure):      # dlpm_lim_loss_args, include/dlpm_amd_lim.
                 ('B', i64), ('D', i64), ('alpha', f64), ('clamp_eps', f64), ('t_max', f64), ('seed', u64), ('sample_offset', i64)]
 
 
+class ToyDrawArgs(C.Structure):      # dlpm_toy_draw_args, include/dlpm_amd_toy.h
+    _fields_ = [('out_dev', vp), ('perm_out_dev', vp), ('weights_host', vp), ('cum_dev', vp), ('bounds_dev', vp), ('N', i64),
+                ('first_index', i64), ('kind', i32), ('n_mixture', i32), ('count', i32), ('isotropic', i32), ('std', f64), ('theta', f64),
+                ('data_alpha', f64), ('seed', u64), ('stream', u32), ('reserved', u32)]
+
+
 class UNetConfig(C.Structure):
     _fields_ = [('in_channels', i32), ('model_channels', i32), ('out_channels', i32), ('num_res_blocks', i32),
                 ('num_heads', i32), ('image_size', i32), ('n_mult', i32), ('channel_mult', i32 * 8), ('n_attn', i32),
@@ -207,6 +213,13 @@ SIGNATURES_LIM = {
     'dlpm_lim_coeffs_f32': (C.c_int, [vp, i64, f64, vp, vp, vp]),
 }
 
+# the same for include/dlpm_amd_toy.h (the 2-D toy data distributions)
+SIGNATURES_TOY = {
+    'dlpm_toy_draw_f32': (C.c_int, [C.POINTER(ToyDrawArgs), vp]),
+    'dlpm_toy_workspace_bytes': (i64, [i64]),
+    'dlpm_toy_finish_f32': (C.c_int, [vp, i64, i32, i32, i32, f64, vp, i64, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -222,7 +235,8 @@ def lib():
             raise DlpmError('libdlpm_amd.so is missing at %s -- run `python -m dlpm_amd.build` '
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
+                list(SIGNATURES_TOY.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -30,6 +30,11 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   `mu` / `sigma` of STATS.npz -- and them (EvaluationManager.evaluate_fid on the flattened samples, at most 4096 values each; the name
   FID belongs to Inception features, which come in through the Python call's `features=`).  --save_fid_stats writes the real set's
   `mu` / `sigma` (float64) for later runs.  It shares the one generation with the other --eval_* flags.
+  --eval_2d --generate N [--dataset NAME] [--dump_dataset OUT.npy]: the reference's whole 2-D evaluation (EvaluationManager.
+  evaluate_metrics_2d: wass, mmd, precision, recall, f_1_pr) of N generated samples against N real samples drawn on the device from the
+  config's own `data:` description (dlpm_amd/datasets.py; the draw is keyed by --set_seed), so no data file is needed.  --dataset
+  overrides data.dataset (gmm_2, gmm_grid, swiss_roll, sas_grid; gmm_2 gets equal weights when the config's weights are another
+  mixture's); --dump_dataset writes the N real samples ([N, 1, dim] float32).
 """
 import argparse
 import os
@@ -132,11 +137,18 @@ def main(argv=None):
                          'generated vs <N> real samples` (`vs precomputed statistics` for an .npz)')
     ap.add_argument('--save_fid_stats', default=None, metavar='OUT.npz',
                     help='with --eval_fid REAL.npy: write the real set\'s mu / sigma (float64) to this file')
+    ap.add_argument('--eval_2d', action='store_true',
+                    help='with --generate N on a 2-D config: wass / mmd / PRD figures against N real samples drawn from the config\'s own '
+                         'data distribution; prints `eval_2d wass <w> mmd <m> precision <p> recall <r> f_1_pr <f> over <N> generated vs '
+                         '<N> real samples`')
+    ap.add_argument('--dataset', default=None, metavar='NAME', help='override data.dataset')
+    ap.add_argument('--dump_dataset', default=None, metavar='OUT.npy',
+                    help='on a 2-D config: write the --generate N real samples drawn from the config\'s data distribution to this file')
     a = ap.parse_args(argv)
     if a.save_fid_stats and not (a.eval_fid and not a.eval_fid.endswith('.npz')):
         raise SystemExit('--save_fid_stats needs --eval_fid REAL.npy')
     for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc),
-                        ('--eval_fid', a.eval_fid)):
+                        ('--eval_fid', a.eval_fid), ('--eval_2d', a.eval_2d), ('--dump_dataset', a.dump_dataset)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -144,6 +156,14 @@ def main(argv=None):
 
     p = dlpm_amd.load_config(a.config)
     p['device'] = 'cuda'
+    if a.dataset is not None:
+        p['data']['dataset'] = a.dataset
+        w = p['data'].get('weights')
+        if a.dataset.lower() == 'gmm_2' and w is not None and len(w) != 2:
+            # the config's weights belong to the mixture it names; gmm_2 has two components
+            print('--dataset gmm_2: the config gives %d weights for another mixture; its two components get equal weights' % len(w),
+                  file=sys.stderr)
+            p['data']['weights'] = None
     if a.method is not None:
         p['method'] = a.method
     m = p['method']
@@ -209,7 +229,23 @@ def main(argv=None):
         return loss
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
-    gm = dlpm_amd.GenerationManager(method, dlpm_amd.ShapeProbe(sample_shape(p)), is_image, **p['eval'][m])
+    loader = dlpm_amd.ShapeProbe(sample_shape(p))
+    if a.eval_2d or a.dump_dataset:
+        if is_image:
+            raise SystemExit('--eval_2d / --dump_dataset draw the 2-D toy distributions; %s is an image dataset' % p['data']['dataset'])
+        loader = dlpm_amd.ToyLoader(dlpm_amd.get_dataset(p, 'cuda', seed or 0)[0], p['eval']['batch_size'])
+    gm = dlpm_amd.GenerationManager(method, loader, is_image, **p['eval'][m])
+    if a.dump_dataset:
+        np.save(a.dump_dataset, gm.load_original_data(p['eval']['data_to_generate']).cpu().numpy())
+    if a.eval_2d:
+        N = p['eval']['data_to_generate']
+        ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=False)
+        res = ev.evaluate_metrics_2d({'default': model}, None, N, p['eval']['batch_size'], class_labels=labels, seed=a.prd_seed)
+        print('eval_2d wass %.9g mmd %.9g precision %.9g recall %.9g f_1_pr %.9g over %d generated vs %d real samples' % (
+            res['wass'], res['mmd'], res['precision'], res['recall'], res['f_1_pr'], N, N))
+        if a.out:
+            np.save(a.out, res['samples'].cpu().numpy())
+        return res
     if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)

@@ -1,4 +1,4 @@
-// metrics_common.h -- what the device metrics (mmd.hip, prd.hip, wass.hip) share: the point set behind two pointers, the carving of a
+// metrics_common.h -- what the device metrics (mmd.hip, prd.hip, wass.hip) and toy.hip share: the point set behind two pointers, the carving of a
 // workspace into 256-byte aligned regions and its check, and the chunked fp64 column statistics.  Everything here has internal
 // linkage; what a region holds stays in each file's own Layout.
 #pragma once
@@ -54,6 +54,14 @@ __global__ void __launch_bounds__(256) k_colstats(Pts p, double *colpart) {
     o[0] = acc;
     if (SQ) o[1] = q;
 }
+
+// order-preserving 32-bit key of an fp32 (-0.0 sorts just below +0.0) and its inverse: what the exact selects of wass.hip and
+// toy.hip sort by
+__device__ inline unsigned int key_of(float v) {
+    const unsigned int u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float value_of(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 }  // namespace
 }  // namespace dlpm

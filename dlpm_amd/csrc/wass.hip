@@ -34,13 +34,6 @@ struct State {
     float os[4];
 };
 
-// order-preserving 32-bit key of an fp32 (-0.0 sorts just below +0.0)
-__device__ inline unsigned int key_of(float v) {
-    const unsigned int u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float value_of(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 // every value of p[0 .. count) once across the grid: 16-byte loads from the first aligned element, scalar head and tail
 template <class F>
 __device__ inline void for_values(const float *p, int64_t count, F f) {

@@ -295,10 +295,13 @@ class EvaluationManager:
     def _real_and_samples(self, who, models, real_data, data_to_generate, batch_size, class_labels, samples, kwargs, single=None):
         """What every sample metric starts from, with `who` in the messages: the N = data_to_generate samples, given (`samples=`) or
         generated (`_generate_flat`), and `real_data[:N]` beside them.  Returns (real [N, D] on the samples' device, samples [N, D], the
-        shape of one sample).  `single`: the refusal of N = 1, for the figures that leave the last sample out.  Every refusal
-        comes before the generation."""
+        shape of one sample).  `real_data=None`: the real samples are the generation manager's own, `load_original_data(N)`, as in the
+        reference.  `single`: the refusal of N = 1, for the figures that leave the last sample out.  Every refusal comes before the
+        generation."""
         N = int(data_to_generate)
         assert N > 0, '%s: data_to_generate must be positive' % who
+        if real_data is None:                                                       # EvaluationManager.py:140
+            real_data = self.gen_manager.load_original_data(N)
         real = torch.as_tensor(real_data)
         assert real.dtype == torch.float32, '%s takes float32 real_data, got %s' % (who, real.dtype)
         assert real.shape[0] >= N, '%s: %d real samples for %d generated' % (who, real.shape[0], N)

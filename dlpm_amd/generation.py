@@ -3,7 +3,8 @@
 `generate(models, nsamples, ...)` probes the dataloader for the per-sample shape, calls
 `method.sample`, clamps to +-1 (images) / +-6 (2-D), applies the inverse affine transform (x+1)/2 for
 images (bem/datasets/__init__.py:108-109) on the GPU, and leaves CPU tensors in `.samples` /
-`.history`.  Plotting / animation helpers of the reference file are out of scope.
+`.history`.  `load_original_data(nsamples)` (:65-74) collects the real samples from the dataloader.  Plotting / animation helpers
+of the reference file are out of scope.
 """
 import copy
 
@@ -69,3 +70,20 @@ class GenerationManager:
             self.samples = self._post(x[..., :nfeat], to_host)
             self.history = []
         return self.samples
+
+    def load_original_data(self, nsamples):
+        """The first `nsamples` samples of the dataloader, batches concatenated in its order, images mapped back to [0, 1] by the
+        inverse affine transform (GenerationManager.py:65-74).  The tensors stay where the loader keeps them."""
+        assert nsamples > 0, 'nsamples must be greater than 0, got {}'.format(nsamples)
+        if isinstance(self.original_data, ShapeProbe):
+            raise ValueError('load_original_data: this manager was given a ShapeProbe, which carries a shape and no data; build it with '
+                             'a loader of real samples, e.g. dlpm_amd.ToyLoader(dlpm_amd.get_dataset(p, device, seed)[0], batch_size)')
+        parts, size = [], 0
+        for data, _ in self.original_data:
+            parts.append((data + 1) / 2 if self.is_image else data)
+            size += data.shape[0]
+            if size >= nsamples:
+                break
+        if size < nsamples:
+            raise ValueError('load_original_data: the dataloader holds %d samples, %d asked for' % (size, nsamples))
+        return torch.cat(parts)[:nsamples]
