@@ -219,6 +219,12 @@ SIGNATURES_TOY = {
     'dlpm_toy_workspace_bytes': (i64, [i64]),
     'dlpm_toy_finish_f32': (C.c_int, [vp, i64, i32, i32, i32, f64, vp, i64, vp, vp, vp]),
 }
+# the same for include/dlpm_amd_chains.h (the sampler's two-chain step)
+SIGNATURES_CHAINS = {
+    'dlpm_unet_chain_workspace': (i64, [vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+    'dlpm_sampler_chains': (i32, [vp]),
+    'dlpm_sampler_graph_captures': (i64, [vp]),
+}
 
 _lib = None
 
@@ -236,7 +242,7 @@ def lib():
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
-                list(SIGNATURES_TOY.items()):
+                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

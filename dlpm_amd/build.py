@@ -48,6 +48,7 @@ def build(force=False, verbose=True):
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_fd.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_lim.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_toy.h'))
+    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_chains.h'))
     jobs = []
     objs = []
     for src in SOURCES:

@@ -84,6 +84,10 @@ int unet_time_mlp_rows(dlpm_unet *net, const float *t_dev, int64_t M, float *out
 int unet_forward_update_labels(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const int64_t *y_dev,
                                const dlpm_update_args *upd, float *eps_scratch_dev, int64_t B, void *workspace_dev,
                                int64_t workspace_bytes, hipStream_t stream);
+// the same step on a row range of the batch (the sampler's chains): see unet.hip
+bool unet_head_carries_update(const dlpm_unet *net);
+int unet_forward_update_rows(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const dlpm_update_args *upd, int64_t Bc,
+                             void *workspace_dev, int64_t workspace_bytes, hipStream_t stream);
 
 // Optional per-launch timing (dlpm_prof_enable): brackets one launch with HIP events on its stream.
 bool prof_enabled();

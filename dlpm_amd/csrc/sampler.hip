@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/dlpm_amd_chains.h"
 
 using namespace dlpm;
 
@@ -33,7 +34,8 @@ struct dlpm_sampler {
     int64_t *labels = nullptr;     // [B] class labels (dlpm_sampler_set_labels), read by the captured graph
     bool labels_set = false;
     int32_t *t_dev = nullptr;
-    uint64_t *key_dev = nullptr;   // {seed, sample_offset}: read by the update kernel, so reseeding keeps the graph
+    uint64_t *key_dev = nullptr;   // {seed, sample_offset}: read by the update kernel, so reseeding keeps the graph; one pair per
+                                   // chain ({seed, sample_offset + first row of the chain}), the whole batch's = chain 0's first
     int graph_steps = 0;           // steps inside the captured graph
     void *ws = nullptr;
     int64_t ws_bytes = 0;
@@ -47,6 +49,16 @@ struct dlpm_sampler {
     // with events at both ends of every dlpm_sampler_steps call.
     hipStream_t own = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    // The two-chain step (one_step): rows [0, B/2) on the stream of the step, rows [B/2, B) on `side`, forked and joined with
+    // events -- under capture two parallel branches of the one graph.  `chains` is what the net, the variant and the workspace
+    // admit (chain_layout: 1 or 2); rows and arenas per chain below.
+    int chains = 1;
+    int64_t row0[DLPM_MAX_CHAINS] = {0, 0}, nrows[DLPM_MAX_CHAINS] = {0, 0};
+    int64_t ws_off[DLPM_MAX_CHAINS] = {0, 0}, ws_len[DLPM_MAX_CHAINS] = {0, 0};
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int graph_chains = 0;          // chains of the step the live graph was captured with
+    int64_t captures = 0;          // graphs captured so far (dlpm_sampler_graph_captures)
 };
 
 namespace {
@@ -54,8 +66,8 @@ namespace {
 __global__ void k_set_t(int32_t *t, int32_t v) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *t = v;
 }
-__global__ void k_set_key(uint64_t *key, uint64_t seed, uint64_t offset) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { key[0] = seed; key[1] = offset; }
+__global__ void k_set_key(uint64_t *key, uint64_t seed, uint64_t offset, uint64_t row1) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { key[0] = seed; key[1] = offset; key[2] = seed; key[3] = offset + row1; }
 }
 __global__ void k_set_ptr(float **cell, float *v) {
     if (threadIdx.x == 0 && blockIdx.x == 0) *cell = v;
@@ -105,6 +117,56 @@ int build_time_table(dlpm_sampler *s) {
     return r;
 }
 
+// DLPM_SAMPLER_CHAINS (read once): 1 = every step is one chain of kernels on one stream, 2 (default) = two half-batch chains where
+// the step admits them
+int chains_wanted() {
+    static int v = -1;
+    if (v < 0) { const char *e = getenv("DLPM_SAMPLER_CHAINS"); v = (e && e[0] == '1' && !e[1]) ? 1 : 2; }
+    return v;
+}
+
+void drop_graph(dlpm_sampler *s) {
+    if (s->exec) (void)hipGraphExecDestroy(s->exec);
+    if (s->graph) (void)hipGraphDestroy(s->graph);
+    s->exec = nullptr;
+    s->graph = nullptr;
+    s->graph_chains = 0;
+}
+
+// Rows and arenas of the chains, and the workspace the sampler needs: *need = the single arena of B, or the two arenas together
+// where they exceed it by the rounding of the arena's blocks (they are both walks of the same plan, every block of which is
+// proportional to the batch: dlpm_unet_chain_workspace).  What of the step can be decided once per sampler and plan is decided here;
+// history, injected z and the profiling pass are looked at per step (chains_now).
+// The chained form needs B >= 2: kernel choice reads the DECLARED dispatch batch and the layer alone (conv_wino4.hip wino4_nq_for /
+// wino4_geometry, conv_splitk.hip conv_ksplit_for, the block_small selectors), never the batch of a launch, so the declared
+// policy keeps its kernels down to a chain of ONE sample and the threshold is 2 x 1.  An odd B splits as B/2 and B - B/2 rows.
+// One chain stays: the MLP sampler; LIM, DLIM, clip and non-isotropic tables; mean types other than eps (predict + update run as
+// kernels of their own); label-conditional nets; input scaling (its scaled copy is one buffer); a net whose head cannot carry the
+// update; a half-batch whose first row is not 16-byte aligned in the state (the fused head stores float4).
+int chain_layout(dlpm_sampler *s, int64_t *need) {
+    const dlpm_sampler_config &c = s->cfg;
+    s->chains = 1;
+    s->row0[0] = 0; s->nrows[0] = c.B; s->ws_off[0] = 0;
+    const int64_t single = dlpm_unet_workspace_bytes(c.unet, c.B);
+    if (single < 0) return DLPM_ERR_STATE;
+    s->ws_len[0] = single;
+    *need = single;
+    const bool plain = !s->lim && !s->elem && !s->cond && !s->in_scale && c.mean_type == DLPM_MEAN_EPSILON &&
+                       !(c.flags & (DLPM_UPD_DLIM | DLPM_UPD_CLIP | DLPM_UPD_ELEMENTWISE));
+    if (chains_wanted() < 2 || !plain || c.B < 2 || !unet_head_carries_update(c.unet) || ((c.B / 2) * s->D) % 4 != 0) return DLPM_OK;
+    int64_t r0[DLPM_MAX_CHAINS], n[DLPM_MAX_CHAINS], off[DLPM_MAX_CHAINS], len[DLPM_MAX_CHAINS], one = 0, slack = 0;
+    const int64_t both = dlpm_unet_chain_workspace(c.unet, c.B, 2, r0, n, off, len, &one, &slack);
+    if (both < 0) return DLPM_ERR_STATE;
+    // The halves must not cost memory the whole does not.  Both are walks of one plan whose blocks are proportional to the batch,
+    // so the two peaks exceed the one by the rounding of the blocks at most -- unless a best-fit choice of the arena falls the
+    // other way at the smaller size, which no configuration here does; such a batch stays on one chain.
+    if (both > one + slack) return DLPM_OK;
+    s->chains = 2;
+    for (int i = 0; i < 2; i++) { s->row0[i] = r0[i]; s->nrows[i] = n[i]; s->ws_off[i] = off[i]; s->ws_len[i] = len[i]; }
+    if (both > *need) *need = both;
+    return DLPM_OK;
+}
+
 // The net's launch plan may change under a live sampler (dlpm_unet_set_conv_policy / set_gemm_policy, re-uploaded weights):
 // drop the captured graph, re-size the activation workspace and rebuild the time table before the next step.
 int sync_plan(dlpm_sampler *s) {
@@ -112,12 +174,10 @@ int sync_plan(dlpm_sampler *s) {
     const int64_t v = dlpm_unet_plan_version(s->cfg.unet);
     if (v == s->plan_version) return DLPM_OK;
     DLPM_HIP(hipDeviceSynchronize());
-    if (s->exec) (void)hipGraphExecDestroy(s->exec);
-    if (s->graph) (void)hipGraphDestroy(s->graph);
-    s->exec = nullptr;
-    s->graph = nullptr;
-    const int64_t need = dlpm_unet_workspace_bytes(s->cfg.unet, s->cfg.B);
-    if (need < 0) return DLPM_ERR_STATE;
+    drop_graph(s);
+    int64_t need = 0;
+    TRY(chain_layout(s, &need));
+    s->key_dirty = true;           // (the second chain's first row may have moved with the layout)
     if (need > s->ws_bytes) {
         if (s->ws) DLPM_HIP(hipFree(s->ws));
         s->ws = nullptr;
@@ -156,6 +216,10 @@ int model_forward(dlpm_sampler *s, hipStream_t st) {
         return dlpm_unet_forward_uniform_t(s->cfg.unet, xin, s->tvec, s->eps, s->cfg.B, s->ws, s->ws_bytes, st);   // t = [i] * B
     return dlpm_mlp_forward(s->cfg.mlp, xin, s->tvec, s->eps, s->cfg.B, st);
 }
+
+// chains of the next plain step: what chain_layout admitted, unless this step records history (the history row is addressed through
+// a device cell, whole batch only), takes injected z, or runs under the per-launch profiler (one stream, one launch at a time)
+int chains_now(const dlpm_sampler *s, const float *z) { return (s->chains == 2 && !s->hist && !z && !prof_enabled()) ? 2 : 1; }
 
 int one_step(dlpm_sampler *s, const float *z, bool advance, hipStream_t st) {
     if (s->lim) {
@@ -198,6 +262,38 @@ int one_step(dlpm_sampler *s, const float *z, bool advance, hipStream_t st) {
         a.flags &= ~DLPM_UPD_CLIP;
         return dlpm_update_f32(&a, st);
     }
+    if (s->cfg.unet && chains_now(s, z) == 2) {
+        // Two independent chains of kernels, one per half of the batch: nothing of a step crosses samples before the state is
+        // read back (GroupNorm statistics are per image, the noise is keyed by global sample index, the step counter is only
+        // read), so while one chain sits in a launch gap, a one-workgroup coefficient kernel or an epilogue burst the other's
+        // convolution has the CUs.  Each chain launches the kernels the whole batch would (the policy reads the declared batch).
+        if (!s->side) {
+            DLPM_HIP(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
+            DLPM_HIP(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
+            DLPM_HIP(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+        }
+        DLPM_HIP(hipEventRecord(s->ev_fork, st));
+        DLPM_HIP(hipStreamWaitEvent(s->side, s->ev_fork, 0));
+        TimeTableBinding bound(s);
+        a.flags &= ~(DLPM_UPD_ADVANCE | DLPM_UPD_HIST_ON);
+        a.hist_pp = nullptr;
+        int r = DLPM_OK;
+        for (int c = 0; c < 2 && r == DLPM_OK; c++) {
+            dlpm_update_args h = a;             // h.B stays the row pitch of the [T,B] tables
+            h.x_dev = s->x + s->row0[c] * s->D;
+            h.c_eps_dev = s->c_eps + s->row0[c];
+            h.c_noise_dev = s->c_noise + s->row0[c];
+            h.sample_offset = s->cfg.sample_offset + s->row0[c];
+            h.key_dev = s->key_dev + 2 * c;
+            r = unet_forward_update_rows(s->cfg.unet, h.x_dev, s->tvec, &h, s->nrows[c], static_cast<char *>(s->ws) + s->ws_off[c],
+                                         s->ws_len[c], c == 0 ? st : s->side);
+        }
+        // join even after a failed enqueue: a capture in progress must not be left with an unjoined branch
+        DLPM_HIP(hipEventRecord(s->ev_join, s->side));
+        DLPM_HIP(hipStreamWaitEvent(st, s->ev_join, 0));
+        TRY(r);
+        return advance ? launch_step_advance(s->t_dev, st) : DLPM_OK;   // both chains have read t
+    }
     if (s->cfg.unet) {   // the UNet's head convolution applies the update itself where the variant allows (eps stays on chip)
         const float *xin = s->x;
         if (s->in_scale) {
@@ -214,7 +310,7 @@ int one_step(dlpm_sampler *s, const float *z, bool advance, hipStream_t st) {
 
 int flush_key(dlpm_sampler *s, hipStream_t st) {
     if (!s->key_dirty) return DLPM_OK;
-    k_set_key<<<1, 64, 0, st>>>(s->key_dev, s->cfg.seed, (uint64_t)s->cfg.sample_offset);
+    k_set_key<<<1, 64, 0, st>>>(s->key_dev, s->cfg.seed, (uint64_t)s->cfg.sample_offset, (uint64_t)s->row0[1]);
     DLPM_LAUNCH_CHECK();
     s->key_dirty = false;
     return DLPM_OK;
@@ -346,17 +442,20 @@ extern "C" int dlpm_sampler_create(const dlpm_sampler_config *cfg, dlpm_sampler 
     if ((e = hipMalloc(&s->tvec, (size_t)B * sizeof(float))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&s->t_dev, sizeof(int32_t))) != hipSuccess) return fail(e);
     if (cond && (e = hipMalloc(&s->labels, (size_t)B * sizeof(int64_t))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&s->key_dev, 2 * sizeof(uint64_t))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&s->key_dev, 2 * DLPM_MAX_CHAINS * sizeof(uint64_t))) != hipSuccess) return fail(e);
+    s->nrows[0] = B;
+    if (cfg->unet) {
+        int r = chain_layout(s, &s->ws_bytes);
+        if (r != DLPM_OK) {
+            dlpm_sampler_destroy(s);
+            return r;
+        }
+    }
     {
-        uint64_t key[2] = {cfg->seed, (uint64_t)cfg->sample_offset};
+        uint64_t key[4] = {cfg->seed, (uint64_t)cfg->sample_offset, cfg->seed, (uint64_t)(cfg->sample_offset + s->row0[1])};
         if ((e = hipMemcpy(s->key_dev, key, sizeof(key), hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
     }
     if (cfg->unet) {
-        s->ws_bytes = dlpm_unet_workspace_bytes(cfg->unet, B);
-        if (s->ws_bytes < 0) {
-            dlpm_sampler_destroy(s);
-            return DLPM_ERR_STATE;
-        }
         if ((e = hipMalloc(&s->ws, (size_t)s->ws_bytes)) != hipSuccess) return fail(e);
         s->plan_version = dlpm_unet_plan_version(cfg->unet);
         int r = build_time_table(s);
@@ -458,6 +557,8 @@ static int steps_on(dlpm_sampler *s, int32_t nsteps, hipStream_t st, bool graph)
             DLPM_HIP(e);
             DLPM_HIP(hipGraphInstantiate(&s->exec, s->graph, nullptr, nullptr, 0));
             s->graph_steps = gs;
+            s->graph_chains = chains_now(s, nullptr);
+            s->captures++;
             // capture only records: nothing ran, so t is unchanged and the replays below do the work
         }
     }
@@ -497,6 +598,10 @@ extern "C" int dlpm_sampler_steps(dlpm_sampler *s, int32_t nsteps, dlpm_stream_t
     }
     const bool graph = s->cfg.use_graph && !prof_enabled();
     if (!graph) return steps_on(s, nsteps, st, false);
+    if (s->exec && s->graph_chains != chains_now(s, nullptr)) {   // a history buffer came or went since the capture
+        DLPM_HIP(hipDeviceSynchronize());
+        drop_graph(s);
+    }
     if (!s->own) {
         DLPM_HIP(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
         DLPM_HIP(hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming));
@@ -539,6 +644,8 @@ extern "C" int dlpm_sampler_copy_state(dlpm_sampler *s, float *out_dev, dlpm_str
 
 extern "C" float *dlpm_sampler_state(dlpm_sampler *s) { return s ? s->x : nullptr; }
 extern "C" int32_t dlpm_sampler_t(const dlpm_sampler *s) { return s ? s->t_host : -1; }
+extern "C" int32_t dlpm_sampler_chains(const dlpm_sampler *s) { return s ? chains_now(s, nullptr) : -1; }
+extern "C" int64_t dlpm_sampler_graph_captures(const dlpm_sampler *s) { return s ? s->captures : -1; }
 extern "C" float *dlpm_sampler_table(dlpm_sampler *s, int which) {
     if (!s) return nullptr;
     switch (which) {
@@ -556,7 +663,10 @@ extern "C" void dlpm_sampler_destroy(dlpm_sampler *s) {
     if (s->graph) (void)hipGraphDestroy(s->graph);
     if (s->ev_in) (void)hipEventDestroy(s->ev_in);
     if (s->ev_out) (void)hipEventDestroy(s->ev_out);
+    if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
+    if (s->ev_join) (void)hipEventDestroy(s->ev_join);
     if (s->own) (void)hipStreamDestroy(s->own);
+    if (s->side) (void)hipStreamDestroy(s->side);
     void *bufs[] = {s->g, s->bg, s->s, s->bs, s->A, s->c_eps == s->A ? nullptr : s->c_eps, s->c_noise, s->x, s->eps, s->tvec, s->emb_tab,
                     s->t_dev, s->key_dev, s->ws, s->hist_cell, s->lim_ts, s->lim_tmp, s->lim_cx, s->lim_cs, s->lim_cn,
                     s->in_scale, s->xin, s->labels};

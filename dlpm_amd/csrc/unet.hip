@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conv.h"
+#include "../../include/dlpm_amd_chains.h"
 
 using namespace dlpm;
 
@@ -79,7 +80,7 @@ struct Tensor4 {
 // from a fake base, never dereferenced) replays the same alloc / release sequence to size the workspace = the peak.
 struct Bump {
     char *base = nullptr;
-    int64_t cap = 0, off = 0, peak = 0;
+    int64_t cap = 0, off = 0, peak = 0, nalloc = 0;
     bool dry = false, overflow = false, reuse = true;
     std::vector<std::pair<int64_t, int64_t>> holes;     // (offset, bytes), sorted by offset, coalesced
     std::map<int64_t, int64_t> live;                    // offset -> bytes
@@ -87,6 +88,7 @@ struct Bump {
     float *alloc(int64_t nfloats) {
         const int64_t bytes = (nfloats * 4 + 255) / 256 * 256;
         int64_t at = -1;
+        nalloc++;
         if (reuse) {
             size_t best = holes.size();                  // best fit: the smallest hole that holds the request
             for (size_t i = 0; i < holes.size(); i++)
@@ -1141,7 +1143,8 @@ extern "C" int dlpm_unet_bind_time_table(dlpm_unet *net, const float *table_dev,
 
 extern "C" int64_t dlpm_unet_plan_version(const dlpm_unet *u) { return u ? u->plan_version : -1; }
 
-extern "C" int64_t dlpm_unet_workspace_bytes(const dlpm_unet *net, int64_t B) {
+// the dry run of the plan at batch B: the arena's peak, and how many blocks the plan asks the arena for
+static int64_t dry_walk(const dlpm_unet *net, int64_t B, int64_t *nalloc) {
     if (!net || B <= 0) return -1;
     Ctx cx;
     cx.u = const_cast<dlpm_unet *>(net);
@@ -1152,7 +1155,39 @@ extern "C" int64_t dlpm_unet_workspace_bytes(const dlpm_unet *net, int64_t B) {
     std::vector<Tensor4> keep = net->feats;
     int r = walk(cx.u, cx, nullptr, nullptr, nullptr);
     cx.u->feats = keep;
+    if (nalloc) *nalloc = cx.ws.nalloc;
     return r == DLPM_OK ? cx.ws.peak : -1;
+}
+
+extern "C" int64_t dlpm_unet_workspace_bytes(const dlpm_unet *net, int64_t B) { return dry_walk(net, B, nullptr); }
+
+// The workspace of a batch walked as `chains` independent row ranges (dlpm_sampler's two-chain step): chain c covers rows
+// [rows_off[c], rows_off[c] + rows[c]) -- B / chains each, the remainder going to the last chains, so B = 5 is 2 + 3 -- and owns the
+// arena [arena_off[c], arena_off[c] + arena_bytes[c]) of the one allocation, sized by dlpm_unet_workspace_bytes(net, rows[c]).  Every
+// block of the plan is proportional to the batch and rounded up to the arena's 256-byte granule, so the arenas together may exceed
+// the single arena of B only by that rounding: *slack_bytes = 256 bytes per block the plan asks for, per chain.  Returns the bytes the
+// arenas need together (compare with *single_bytes + *slack_bytes), -1 on error.
+extern "C" int64_t dlpm_unet_chain_workspace(const dlpm_unet *net, int64_t B, int32_t chains, int64_t *rows_off, int64_t *rows,
+                                             int64_t *arena_off, int64_t *arena_bytes, int64_t *single_bytes, int64_t *slack_bytes) {
+    if (!net || chains < 1 || chains > DLPM_MAX_CHAINS || B < chains || !rows_off || !rows || !arena_off || !arena_bytes) {
+        set_error("dlpm_unet_chain_workspace: bad argument");
+        return -1;
+    }
+    const int64_t single = dry_walk(net, B, nullptr);
+    if (single < 0) return -1;
+    int64_t at = 0, b0 = 0, slack = 0;
+    for (int c = 0; c < chains; c++) {
+        const int64_t n = B / chains + (c >= chains - B % chains ? 1 : 0);
+        int64_t blocks = 0;
+        const int64_t need = dry_walk(net, n, &blocks);
+        if (need < 0) return -1;
+        rows_off[c] = b0; rows[c] = n;
+        arena_off[c] = at; arena_bytes[c] = need;      // (a peak is a sum of 256-byte blocks: every arena starts on a granule)
+        b0 += n; at += need; slack += 256 * blocks;
+    }
+    if (single_bytes) *single_bytes = single;
+    if (slack_bytes) *slack_bytes = slack;
+    return at;
 }
 
 static int unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, void *workspace_dev,
@@ -1233,6 +1268,36 @@ int dlpm::unet_forward_update_labels(dlpm_unet *net, const float *x_in_dev, cons
     if (r != DLPM_OK) return r;
     if (upd->flags & DLPM_UPD_ADVANCE) return launch_step_advance(const_cast<int32_t *>(upd->t_dev), stream);
     return DLPM_OK;
+}
+
+// Whether the plain reverse update of this net rides in its head convolution (what unet_forward_update_labels decides per call)
+bool dlpm::unet_head_carries_update(const dlpm_unet *net) { return net && net->finalized && head_fusable(net); }
+
+// The forward + fused update of Bc rows of a larger batch (dlpm_sampler's chains): `upd` describes the rows -- x_dev, c_eps_dev and
+// c_noise_dev point at the first of them, upd->B stays the row pitch of the [T,B] tables, the key holds the global index of the first
+// row -- and the net walks Bc samples in a workspace of its own.  The plain stochastic update only, never advances the step counter
+// (the caller does, once all chains have read it), no history row.  Kernel choice follows the declared dispatch batch as in every
+// other forward, so the rows get the bits the whole batch would give them.
+int dlpm::unet_forward_update_rows(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const dlpm_update_args *upd, int64_t Bc,
+                                   void *workspace_dev, int64_t workspace_bytes, hipStream_t stream) {
+    DLPM_CHECK_ARG(net && x_in_dev && t_dev && upd && upd->x_dev && upd->t_dev && upd->g_dev && upd->c_eps_dev && upd->c_noise_dev,
+                   "unet_forward_update_rows: null argument");
+    DLPM_CHECK_ARG(Bc > 0 && Bc <= upd->B, "unet_forward_update_rows: %lld rows of a batch of %lld", (long long)Bc, (long long)upd->B);
+    const int64_t D = (int64_t)net->cfg.out_channels * net->cfg.image_size * net->cfg.image_size;
+    DLPM_CHECK_ARG(upd->D == D, "unet_forward_update_rows: state of %lld elements per sample, the net emits %lld", (long long)upd->D,
+                   (long long)D);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(upd->x_dev) | reinterpret_cast<uintptr_t>(upd->z_dev)) % 16) == 0;
+    if (!dlpm::unet_head_carries_update(net) || !aligned || net->num_classes > 0 || upd->hist_pp ||
+        (upd->flags & (DLPM_UPD_DLIM | DLPM_UPD_CLIP | DLPM_UPD_ELEMENTWISE | DLPM_UPD_ADVANCE))) {
+        set_error("unet_forward_update_rows: only the plain update fused into the head convolution runs on a row range");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    HeadUpdate hu;
+    hu.x = upd->x_dev; hu.z = upd->z_dev; hu.t = upd->t_dev; hu.g = upd->g_dev; hu.c_eps = upd->c_eps_dev; hu.c_noise = upd->c_noise_dev;
+    hu.key = upd->key_dev; hu.seed = upd->seed; hu.sample_offset = upd->sample_offset;
+    hu.T = upd->T; hu.B = upd->B;
+    float dummy;   // walk() wants a non-null eps pointer; the fused head never writes it
+    return unet_forward(net, x_in_dev, t_dev, &dummy, Bc, workspace_dev, workspace_bytes, stream, true, nullptr, &hu);
 }
 
 static int unet_forward(dlpm_unet *net, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, void *workspace_dev,
