@@ -25,23 +25,19 @@
 #include <cmath>
 
 #include "metrics_common.h"
+#include "mfma64_tile.h"
 #include "../../include/dlpm_amd_fd.h"
 
 using namespace dlpm;
 
 namespace {
 
-constexpr int kTile = 128;
-constexpr int kThreads = 256;
-constexpr int kKC = 16, kLD = kKC + 1;      // K step of the tile loop, LDS row pitch in doubles
 constexpr int64_t kMaxF = 4096;
 constexpr int64_t kMaxRows = 1ll << 31;
 constexpr int kMaxSweeps = 60;
 constexpr int64_t kTargetBlocks = 512;      // workgroups the covariance pass aims at (two per CU)
 constexpr int64_t kMaxChunks = 64;
 constexpr int64_t kMinChunkRows = 256;
-
-typedef double doublex4 __attribute__((ext_vector_type(4)));
 
 struct Header {
     int nonfinite, rotations;
@@ -66,16 +62,6 @@ Chunks chunks_of(int64_t n, int64_t F) {
     return Chunks{per, ceil_div(n, per)};
 }
 
-// upper-triangle tile number -> (ti <= tj) of a T x T tiling, rows of the triangle in order
-__device__ inline void tri_tile(int b, int T, int &ti, int &tj) {
-    ti = 0;
-    while (b >= T - ti) {
-        b -= T - ti;
-        ti++;
-    }
-    tj = ti + b;
-}
-
 struct TileJob {
     // covariance partials: rows [chunk * per, ...) of x, centred on mean; part[(chunk * ntiles + tile)][128][128]
     const float *x;
@@ -89,26 +75,23 @@ struct TileJob {
     int T;
 };
 
-// 128 x 128 tile on v_mfma_f64_16x16x4_f64, the loop of k_prdc_gram: 4 waves as 2 x 2, each 64 x 64 = 4 x 4 accumulators, K in steps
-// of 16 through one LDS image (rows padded to 17 doubles), the next step's global loads in flight under the MFMAs.  A/B operand: lane
-// l holds [row l & 15][k = l >> 4]; C/D: col = lane & 15, row = (lane >> 4) + 4 reg.
+// 128 x 128 tile on the tile loop of mfma64_tile.h.
 // COV: K runs over the samples of a chunk; a step is 16 samples x 128 features of the two feature blocks, thread = (sample, 8
 // features 16 apart), centred in fp64 as it is staged.  NT: K runs along the rows of A and B, thread = (row, 8-value half of the step).
 template <bool COV>
 __global__ void __launch_bounds__(kThreads) k_fd_tile(TileJob w) {
-    __shared__ double smem[2 * kTile * kLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, l15 = lane & 15, lk = lane >> 4;
-    int ti, tj;
-    if (COV) tri_tile((int)blockIdx.x, w.T, ti, tj);
+    __shared__ double smem[kImage];
+    const int tid = threadIdx.x;
+    const Lanes l = lanes_of(tid);
+    int64_t ti, tj;
+    if (COV) tile_of(blockIdx.x, w.T, ti, tj);
     else {
-        ti = (int)blockIdx.x / w.T;
-        tj = (int)blockIdx.x - ti * w.T;
+        ti = blockIdx.x / w.T;
+        tj = blockIdx.x - ti * w.T;
     }
-    const int64_t i0 = (int64_t)ti * kTile, j0 = (int64_t)tj * kTile, F = w.F;
+    const int64_t i0 = ti * kTile, j0 = tj * kTile, F = w.F;
     const int64_t r0 = COV ? (int64_t)blockIdx.y * w.per : 0;
     const int64_t r1 = COV ? (r0 + w.per < w.n ? r0 + w.per : w.n) : F;
-    const int64_t nsteps = (r1 - r0 + kKC - 1) / kKC;
-    double *As = smem, *Bs = smem + kTile * kLD;
     double va[8], vb[8];
     // COV: sample ck of the step, features cf + 16 e.  NT: row sr, values sk .. sk + 7 of the step.
     const int ck = tid >> 4, cf = tid & 15, sr = tid >> 1, sk = (tid & 1) * 8;
@@ -121,7 +104,7 @@ __global__ void __launch_bounds__(kThreads) k_fd_tile(TileJob w) {
             mb[e] = fb < F ? w.mean[fb] : 0.0;
         }
     }
-    auto load_step = [&](int64_t s) {
+    auto load = [&](int64_t s) {
         if (COV) {
             const int64_t r = r0 + s * kKC + ck;
             const bool rok = r < r1;
@@ -144,44 +127,22 @@ __global__ void __launch_bounds__(kThreads) k_fd_tile(TileJob w) {
         }
     };
 
-    doublex4 acc[4][4];
+    auto store = [&]() {
+        if (COV) {
 #pragma unroll
-    for (int bi = 0; bi < 4; bi++)
-#pragma unroll
-        for (int bj = 0; bj < 4; bj++) acc[bi][bj] = doublex4{0.0, 0.0, 0.0, 0.0};
-
-    load_step(0);
-    for (int64_t s = 0; s < nsteps; s++) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-            if (COV) {
-                As[(cf + 16 * e) * kLD + ck] = va[e];
-                Bs[(cf + 16 * e) * kLD + ck] = vb[e];
-            } else {
-                As[sr * kLD + sk + e] = va[e];
-                Bs[sr * kLD + sk + e] = vb[e];
+            for (int e = 0; e < 8; e++) {
+                smem[(cf + 16 * e) * kLD + ck] = va[e];
+                smem[kTile * kLD + (cf + 16 * e) * kLD + ck] = vb[e];
             }
+        } else {
+            store_rows(smem, sr, sk, va, vb);
         }
-        __syncthreads();
-        if (s + 1 < nsteps) load_step(s + 1);
-        const double *ap = As + (wm * 64 + l15) * kLD + lk, *bp = Bs + (wn * 64 + l15) * kLD + lk;
-#pragma unroll
-        for (int kk = 0; kk < kKC / 4; kk++) {
-            double af[4], bf[4];
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-                af[b] = ap[b * 16 * kLD + kk * 4];
-                bf[b] = bp[b * 16 * kLD + kk * 4];
-            }
-#pragma unroll
-            for (int bi = 0; bi < 4; bi++)
-#pragma unroll
-                for (int bj = 0; bj < 4; bj++) acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[bi], bf[bj], acc[bi][bj], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    };
 
-    // element (bi, bj, reg) of a lane: tile row wm 64 + bi 16 + lk + 4 reg, tile column wn 64 + bj 16 + l15
+    Acc acc;
+    acc_zero(acc);
+    tile_loop(smem, r1 - r0, l, acc, load, store);
+
     const int64_t ntiles = (int64_t)w.T * (w.T + 1) / 2;
     double *pt = COV ? w.part + ((int64_t)blockIdx.y * ntiles + blockIdx.x) * (kTile * kTile) : nullptr;
 #pragma unroll
@@ -190,7 +151,7 @@ __global__ void __launch_bounds__(kThreads) k_fd_tile(TileJob w) {
         for (int bj = 0; bj < 4; bj++)
 #pragma unroll
             for (int reg = 0; reg < 4; reg++) {
-                const int rl = wm * 64 + bi * 16 + lk + 4 * reg, cl = wn * 64 + bj * 16 + l15;
+                const int rl = tile_row(l, bi, reg), cl = tile_col(l, bj);
                 const double v = acc[bi][bj][reg];
                 if (COV) {
                     pt[rl * kTile + cl] = v;                   // the whole tile, its zero padding included: always inside `part`
@@ -203,10 +164,10 @@ __global__ void __launch_bounds__(kThreads) k_fd_tile(TileJob w) {
 
 // S[i][j] = S[j][i] = (sum over the chunks, in chunk order) / (n - 1) for i <= j.  Grid (ntiles, 64), thread = one tile element.
 __global__ void __launch_bounds__(256) k_fd_cov_reduce(const double *part, int64_t chunks, int T, int64_t F, int64_t n, double *sigma) {
-    int ti, tj;
-    tri_tile((int)blockIdx.x, T, ti, tj);
+    int64_t ti, tj;
+    tile_of(blockIdx.x, T, ti, tj);
     const int e = (int)blockIdx.y * 256 + threadIdx.x, rl = e >> 7, cl = e & (kTile - 1);
-    const int64_t gi = (int64_t)ti * kTile + rl, gj = (int64_t)tj * kTile + cl;
+    const int64_t gi = ti * kTile + rl, gj = tj * kTile + cl;
     if (gi > gj || gj >= F) return;
     const int64_t ntiles = (int64_t)T * (T + 1) / 2;
     double acc = 0.0;
@@ -216,22 +177,14 @@ __global__ void __launch_bounds__(256) k_fd_cov_reduce(const double *part, int64
     sigma[gj * F + gi] = acc;
 }
 
-__global__ void __launch_bounds__(256) k_fd_colmean(const double *colpart, int64_t n, int64_t F, double *mean) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= F) return;
-    double acc = 0.0;
-    for (int c = 0; c < kColChunks; c++) acc += colpart[(int64_t)c * F + d];
-    mean[d] = acc / (double)n;
-}
-
 __global__ void k_fd_init(Header *h) {
     h->nonfinite = 0;
     h->rotations = 0;
     h->norm2 = 0.0;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) k_fd_finite(const T *p, int64_t total, Header *h) {
+// the statistics handed to dlpm_fd_from_stats_f64; the fp32 rows go through k_nonfinite
+__global__ void __launch_bounds__(256) k_fd_finite(const double *p, int64_t total, Header *h) {
     bool bad = false;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) bad |= !isfinite(p[e]);
     if (bad) atomicOr(&h->nonfinite, 1);
@@ -387,8 +340,6 @@ int check_shape(const char *who, int64_t n1, int64_t n2, int64_t F) {
     return DLPM_OK;
 }
 
-bool mis(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
 struct Ws {
     Header *hdr;
     double *colpart, *rowsq, *mu1, *mu2, *sigma1, *sigma2, *W, *Vt, *T, *part;
@@ -401,19 +352,17 @@ Ws carve(void *workspace, const Layout &L) {
               d(L.Vt), d(L.T), d(L.part)};
 }
 
-unsigned grid_for(int64_t total) { return (unsigned)std::min<int64_t>(ceil_div(total, 256), 2048); }
-
 // mean and covariance of one set; the header has been initialised
 int stats_run(const float *x, int64_t n, int64_t F, const Chunks &ch, const Ws &w, double *mu, double *sigma, hipStream_t st) {
     ProfScope ps("fd_stats", 2.0 * (double)n * F * F, 4.0 * (double)n * F, st);
     const int T = (int)ceil_div(F, kTile);
     const int64_t ntiles = tiles_of(F);
-    k_fd_finite<float><<<grid_for(n * F), 256, 0, st>>>(x, n * F, w.hdr);
-    DLPM_LAUNCH_CHECK();
     const Pts p{x, x, n, n, F};
+    k_nonfinite<256><<<scan_grid(n * F), 256, 0, st>>>(p, &w.hdr->nonfinite);
+    DLPM_LAUNCH_CHECK();
     k_colstats<false><<<dim3((unsigned)ceil_div(F, 256), kColChunks), 256, 0, st>>>(p, w.colpart);
     DLPM_LAUNCH_CHECK();
-    k_fd_colmean<<<(unsigned)ceil_div(F, 256), 256, 0, st>>>(w.colpart, n, F, mu);
+    k_colmean<double><<<(unsigned)ceil_div(F, 256), 256, 0, st>>>(w.colpart, n, F, mu);
     DLPM_LAUNCH_CHECK();
     TileJob j{};
     j.x = x;
@@ -478,10 +427,10 @@ int jacobi_run(const char *name, double *W, double *Vt, int64_t F, const Ws &w, 
 // the figure from two pairs of statistics; the header has been initialised
 int figure_run(const double *mu1, const double *s1, const double *mu2, const double *s2, int64_t F, const Ws &w, double *out, hipStream_t st) {
     const int64_t mat = F * F;
-    k_fd_finite<double><<<grid_for(F), 256, 0, st>>>(mu1, F, w.hdr);
-    k_fd_finite<double><<<grid_for(F), 256, 0, st>>>(mu2, F, w.hdr);
-    k_fd_finite<double><<<grid_for(mat), 256, 0, st>>>(s1, mat, w.hdr);
-    k_fd_finite<double><<<grid_for(mat), 256, 0, st>>>(s2, mat, w.hdr);
+    k_fd_finite<<<scan_grid(F), 256, 0, st>>>(mu1, F, w.hdr);
+    k_fd_finite<<<scan_grid(F), 256, 0, st>>>(mu2, F, w.hdr);
+    k_fd_finite<<<scan_grid(mat), 256, 0, st>>>(s1, mat, w.hdr);
+    k_fd_finite<<<scan_grid(mat), 256, 0, st>>>(s2, mat, w.hdr);
     DLPM_LAUNCH_CHECK();
     DLPM_HIP(hipMemcpyAsync(w.W, s1, (size_t)mat * sizeof(double), hipMemcpyDeviceToDevice, st));
     k_fd_identity<<<(unsigned)ceil_div(mat, 256), 256, 0, st>>>(w.Vt, F);
@@ -524,7 +473,7 @@ extern "C" int dlpm_fd_stats_f32(const float *x_dev, int64_t n, int64_t F, void 
     const int rc = check_shape("dlpm_fd_stats_f32", n, n, F);
     if (rc != DLPM_OK) return rc;
     DLPM_CHECK_ARG(x_dev && workspace_dev && mu_out_dev && sigma_out_dev && status_out_dev, "dlpm_fd_stats_f32: null pointer");
-    DLPM_CHECK_ARG(!mis(x_dev, 4) && !mis(mu_out_dev, 8) && !mis(sigma_out_dev, 8) && !mis(status_out_dev, 4),
+    DLPM_CHECK_ARG(aligned(x_dev, 4) && aligned(mu_out_dev, 8) && aligned(sigma_out_dev, 8) && aligned(status_out_dev, 4),
                    "dlpm_fd_stats_f32: misaligned input or output");
     const Layout L = layout_of(n, n, F);
     const int ws_rc = check_workspace("dlpm_fd_stats_f32", workspace_dev, workspace_bytes, L.total);
@@ -545,7 +494,7 @@ extern "C" int dlpm_fd_from_stats_f64(const double *mu1_dev, const double *sigma
     const int rc = check_shape("dlpm_fd_from_stats_f64", 2, 2, F);
     if (rc != DLPM_OK) return rc;
     DLPM_CHECK_ARG(mu1_dev && sigma1_dev && mu2_dev && sigma2_dev && workspace_dev && out_dev, "dlpm_fd_from_stats_f64: null pointer");
-    DLPM_CHECK_ARG(!mis(mu1_dev, 8) && !mis(sigma1_dev, 8) && !mis(mu2_dev, 8) && !mis(sigma2_dev, 8) && !mis(out_dev, 8),
+    DLPM_CHECK_ARG(aligned(mu1_dev, 8) && aligned(sigma1_dev, 8) && aligned(mu2_dev, 8) && aligned(sigma2_dev, 8) && aligned(out_dev, 8),
                    "dlpm_fd_from_stats_f64: misaligned input or output");
     const Layout L = layout_of(2, 2, F);
     const int ws_rc = check_workspace("dlpm_fd_from_stats_f64", workspace_dev, workspace_bytes, L.total);
@@ -562,7 +511,7 @@ extern "C" int dlpm_fd_f32(const float *x_dev, int64_t n1, const float *y_dev, i
     const int rc = check_shape("dlpm_fd_f32", n1, n2, F);
     if (rc != DLPM_OK) return rc;
     DLPM_CHECK_ARG(x_dev && y_dev && workspace_dev && out_dev, "dlpm_fd_f32: null pointer");
-    DLPM_CHECK_ARG(!mis(x_dev, 4) && !mis(y_dev, 4) && !mis(out_dev, 8), "dlpm_fd_f32: misaligned input or output");
+    DLPM_CHECK_ARG(aligned(x_dev, 4) && aligned(y_dev, 4) && aligned(out_dev, 8), "dlpm_fd_f32: misaligned input or output");
     const Layout L = layout_of(n1, n2, F);
     const int ws_rc = check_workspace("dlpm_fd_f32", workspace_dev, workspace_bytes, L.total);
     if (ws_rc != DLPM_OK) return ws_rc;

@@ -27,19 +27,6 @@ constexpr int64_t kMaxTilesSide = 65535;   // T (T + 1) / 2 tiles fit a 1-D grid
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-__device__ inline int64_t tile_row_start(int64_t t, int64_t T) { return t * T - t * (t - 1) / 2; }
-
-// upper-triangle tile b -> (ti, tj), ti <= tj: row t holds the tiles (t, t) .. (t, T - 1)
-__device__ inline void tile_of(int64_t b, int64_t T, int64_t &ti, int64_t &tj) {
-    const double s = 2.0 * (double)T + 1.0;
-    int64_t t = (int64_t)((s - sqrt(fmax(s * s - 8.0 * (double)b, 0.0))) * 0.5);
-    t = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
-    while (t > 0 && tile_row_start(t, T) > b) t--;
-    while (t + 1 < T && tile_row_start(t + 1, T) <= b) t++;
-    ti = t;
-    tj = t + (b - tile_row_start(t, T));
-}
-
 struct Sums {
     double xx, yy, xy;
 };
@@ -125,15 +112,6 @@ __global__ void __launch_bounds__(256) k_mmd_direct(Pts p, int64_t T, const floa
         const double t = block_sum<256>(l2sum, sh);
         if (threadIdx.x == 0) partials[blockIdx.x] = t;
     }
-}
-
-// the column means of the concatenation from the chunk sums of k_colstats<false>, colpart[chunk][d], added in chunk order
-__global__ void __launch_bounds__(256) k_mmd_colmean(const double *colpart, int64_t n, int64_t D, float *mean) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= D) return;
-    double acc = 0.0;
-    for (int c = 0; c < kColChunks; c++) acc += colpart[(int64_t)c * D + d];
-    mean[d] = (float)(acc / (double)n);
 }
 
 // |p_i - m|^2 of the fp32 centred row (the very values the Gram tiles multiply), one workgroup per row
@@ -360,20 +338,13 @@ int check_shape(const char *who, int64_t n1, int64_t n2, int64_t D) {
     return DLPM_OK;
 }
 
-template <int DT>
 void launch_direct(bool kern, const Pts &p, const Layout &L, const float *coef, int num, double *partials, hipStream_t st) {
-    if (kern) k_mmd_direct<DT, true><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, coef, num, partials);
-    else k_mmd_direct<DT, false><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, coef, num, partials);
+    with_dt(p.D, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (kern) k_mmd_direct<DT, true><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, coef, num, partials);
+        else k_mmd_direct<DT, false><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, coef, num, partials);
+    });
 }
-
-void launch_direct_any(bool kern, const Pts &p, const Layout &L, const float *coef, int num, double *partials, hipStream_t st) {
-    if (p.D <= 2) launch_direct<2>(kern, p, L, coef, num, partials, st);
-    else if (p.D <= 4) launch_direct<4>(kern, p, L, coef, num, partials, st);
-    else if (p.D <= 8) launch_direct<8>(kern, p, L, coef, num, partials, st);
-    else launch_direct<16>(kern, p, L, coef, num, partials, st);
-}
-
-bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 }  // namespace
 
@@ -392,7 +363,7 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
                    kernel_num);
     DLPM_CHECK_ARG(kernel_mul > 0.0, "dlpm_mmd_f32: kernel_mul must be positive, got %g", kernel_mul);
     DLPM_CHECK_ARG(x_dev && y_dev && workspace_dev && out_dev, "dlpm_mmd_f32: null pointer");
-    DLPM_CHECK_ARG(aligned16(workspace_dev) && reinterpret_cast<uintptr_t>(out_dev) % 8 == 0, "dlpm_mmd_f32: misaligned workspace or output");
+    DLPM_CHECK_ARG(aligned(workspace_dev, 16) && aligned(out_dev, 8), "dlpm_mmd_f32: misaligned workspace or output");
     const int64_t n = n1 + n2;
     const Layout L = layout_of(n, D);
     const int ws_rc = check_workspace("dlpm_mmd_f32", workspace_dev, workspace_bytes, L.total);
@@ -407,14 +378,14 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
     if (!L.gram) {
         if (from_data) {
             ProfScope ps("mmd_direct_l2", 1.5 * (double)n * n * D, 4.0 * (double)n * D, st);
-            launch_direct_any(false, p, L, coef, kernel_num, partials, st);
+            launch_direct(false, p, L, coef, kernel_num, partials, st);
             DLPM_LAUNCH_CHECK();
         }
         k_mmd_bandwidth<<<1, 1024, 0, st>>>(partials, from_data ? L.tiles : 0, 1.0 / pairs, fix_sigma, kernel_mul, kernel_num, coef, out_dev);
         DLPM_LAUNCH_CHECK();
         {
             ProfScope ps("mmd_direct_kernels", 1.5 * (double)n * n * D, 4.0 * (double)n * D, st);
-            launch_direct_any(true, p, L, coef, kernel_num, partials, st);
+            launch_direct(true, p, L, coef, kernel_num, partials, st);
             DLPM_LAUNCH_CHECK();
         }
     } else {
@@ -424,7 +395,7 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
             ProfScope ps("mmd_centre", 3.0 * (double)n * D, 8.0 * (double)n * D, st);
             k_colstats<false><<<dim3((unsigned)ceil_div(D, 256), kColChunks), 256, 0, st>>>(p, colpart);
             DLPM_LAUNCH_CHECK();
-            k_mmd_colmean<<<(unsigned)ceil_div(D, 256), 256, 0, st>>>(colpart, n, D, mean);
+            k_colmean<float><<<(unsigned)ceil_div(D, 256), 256, 0, st>>>(colpart, n, D, mean);
             DLPM_LAUNCH_CHECK();
             k_mmd_rownorm<<<(unsigned)n, 256, 0, st>>>(p, mean, rn, rsum);
             DLPM_LAUNCH_CHECK();
@@ -434,7 +405,7 @@ extern "C" int dlpm_mmd_f32(const float *x_dev, int64_t n1, const float *y_dev, 
         {
             // the upper triangle with its diagonal tiles: T (T + 1) / 2 tiles of 128 x 128 x D multiply-adds
             ProfScope ps("mmd_gram", 2.0 * (double)L.tiles * kTile * kTile * D, 8.0 * (double)L.tiles * kTile * D, st);
-            if (D % 4 == 0 && aligned16(x_dev) && aligned16(y_dev))
+            if (D % 4 == 0 && aligned(x_dev, 16) && aligned(y_dev, 16))
                 k_mmd_gram<true><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, mean, rn, coef, kernel_num, partials);
             else
                 k_mmd_gram<false><<<(unsigned)L.tiles, 256, 0, st>>>(p, L.T, mean, rn, coef, kernel_num, partials);

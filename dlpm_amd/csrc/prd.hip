@@ -548,10 +548,7 @@ int check_curve(const char *who, int64_t A, double eps, double beta) {
 
 int launch_assign(const Pts &p, const Geo &g, const Work &w, int force, hipStream_t st) {
     const dim3 grid((unsigned)g.C, (unsigned)g.I);
-    if (g.D <= 2) k_prd_assign<2><<<grid, 256, 0, st>>>(p, g, w, force);
-    else if (g.D <= 4) k_prd_assign<4><<<grid, 256, 0, st>>>(p, g, w, force);
-    else if (g.D <= 8) k_prd_assign<8><<<grid, 256, 0, st>>>(p, g, w, force);
-    else if (g.D <= kDirectMaxD) k_prd_assign<16><<<grid, 256, 0, st>>>(p, g, w, force);
+    if (g.D <= kDirectMaxD) with_dt(g.D, [&](auto dt) { k_prd_assign<decltype(dt)::value><<<grid, 256, 0, st>>>(p, g, w, force); });
     else k_prd_assign_general<<<grid, 256, 0, st>>>(p, g, w, force);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;

@@ -21,19 +21,17 @@
 #include <cmath>
 
 #include "metrics_common.h"
+#include "mfma64_tile.h"
 
 using namespace dlpm;
 
 namespace {
 
-constexpr int kTile = 128;              // rows and columns of a pair tile
-constexpr int kThreads = 256;
 constexpr int kDirectMaxD = 16;         // D <= this: direct form
 constexpr int kMaxK = 32;               // nearest_k
 constexpr int64_t kMaxRows = 1ll << 22; // per set: T1 * T2 cross tiles fit a 1-D grid
 constexpr int64_t kTargetBlocks = 512;  // workgroups of a radii pass the segment rule aims at (two per CU)
 
-typedef double doublex4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 struct Set {
@@ -216,15 +214,6 @@ __global__ void __launch_bounds__(kThreads) k_prdc_direct(Walk w) {
     if (!CROSS) write_survivors(w, lst, seg, half, i);
 }
 
-// the pooled column means in fp64 from the chunk sums of k_colstats<false>, added in chunk order
-__global__ void __launch_bounds__(256) k_prdc_colmean(const double *colpart, int64_t n, int64_t D, double *mean) {
-    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (d >= D) return;
-    double acc = 0.0;
-    for (int c = 0; c < kColChunks; c++) acc += colpart[(int64_t)c * D + d];
-    mean[d] = acc / (double)n;
-}
-
 // |p_i - m|^2 of the fp64 centred row (the very values the Gram tiles multiply), one workgroup per row of the concatenation
 __global__ void __launch_bounds__(256) k_prdc_rownorm(Pts p, const double *mean, double *rn) {
     __shared__ double sh[256];
@@ -239,27 +228,23 @@ __global__ void __launch_bounds__(256) k_prdc_rownorm(Pts p, const double *mean,
     if (threadIdx.x == 0) rn[i] = t;
 }
 
-// Gram form: 128 x 128 tiles of C C^T, 4 waves as 2 x 2, each 64 x 64 = 4 x 4 accumulators of the 16x16x4 fp64 MFMA; K in steps of 16
-// through one LDS image (rows padded to 17 doubles), the next step's global loads in flight under the MFMAs; thread = (row, 8-value
-// half of the step), centred in fp64 while staged.  A/B operand: lane l holds [row l & 15][k = l >> 4]; C/D of the fp64 MFMA:
-// col = lane & 15, row = (lane >> 4) + 4 reg -- NOT the map of the other MFMAs.
+// Gram form: 128 x 128 tiles of C C^T on the tile loop of mfma64_tile.h; thread = (row, 8-value half of the step), centred in fp64
+// while staged.
 template <bool CROSS>
 __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
-    constexpr int KC = 16, LD = KC + 1, SLAB = 32, SLD = SLAB + 1;
-    static_assert(kTile * SLD <= 2 * kTile * LD, "the distance slab lives in the staging image");
-    __shared__ double smem[2 * kTile * LD];
+    constexpr int SLAB = 32, SLD = SLAB + 1;
+    static_assert(kTile * SLD <= kImage, "the distance slab lives in the staging image");
+    __shared__ double smem[kImage];
     __shared__ double s_rna[kTile], s_rnb[kTile];
     __shared__ CrossLds cs;
     extern __shared__ double lists[];
     int64_t ti, seg, t0, t1;
     tiles_of(w, CROSS, ti, seg, t0, t1);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, l15 = lane & 15, lk = lane >> 4;
-    const int sr = tid >> 1, sk = (tid & 1) * 8;
+    const int tid = threadIdx.x, sr = tid >> 1, sk = (tid & 1) * 8;
+    const Lanes l = lanes_of(tid);
     const int64_t i0 = ti * kTile;
     const bool a_ok = i0 + sr < w.a.n;
     const float *pa = w.a.p + (a_ok ? i0 + sr : 0) * w.D;
-    const int64_t nsteps = (w.D + KC - 1) / KC;
-    double *As = smem, *Bs = smem + kTile * LD;
     Top top;
     double *lst = lists + tid;
     if (!CROSS) top_init(lst, w.K1, kThreads, top);
@@ -269,10 +254,10 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
         const bool b_ok = j0 + sr < w.b.n;
         const float *pb = w.b.p + (b_ok ? j0 + sr : 0) * w.D;
         double va[8], vb[8];
-        auto load_step = [&](int64_t s) {
+        auto load = [&](int64_t s) {
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                const int64_t k = s * KC + sk + e;
+                const int64_t k = s * kKC + sk + e;
                 const bool ok = k < w.D;
                 const double m = ok ? w.mean[k] : 0.0;
                 va[e] = (ok && a_ok) ? (double)pa[k] - m : 0.0;
@@ -284,39 +269,11 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
         else s_rnb[tid - kTile] = j0 + tid - kTile < w.b.n ? w.rnb[j0 + tid - kTile] : 0.0;
         if (CROSS) cross_begin(w, cs, i0, j0);
 
-        doublex4 acc[4][4];
-#pragma unroll
-        for (int bi = 0; bi < 4; bi++)
-#pragma unroll
-            for (int bj = 0; bj < 4; bj++) acc[bi][bj] = doublex4{0.0, 0.0, 0.0, 0.0};
+        Acc acc;
+        acc_zero(acc);
+        tile_loop(smem, w.D, l, acc, load, [&]() { store_rows(smem, sr, sk, va, vb); });
 
-        load_step(0);
-        for (int64_t s = 0; s < nsteps; s++) {
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                As[sr * LD + sk + e] = va[e];
-                Bs[sr * LD + sk + e] = vb[e];
-            }
-            __syncthreads();
-            if (s + 1 < nsteps) load_step(s + 1);
-            const double *ap = As + (wm * 64 + l15) * LD + lk, *bp = Bs + (wn * 64 + l15) * LD + lk;
-#pragma unroll
-            for (int kk = 0; kk < KC / 4; kk++) {
-                double af[4], bf[4];
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    af[b] = ap[b * 16 * LD + kk * 4];
-                    bf[b] = bp[b * 16 * LD + kk * 4];
-                }
-#pragma unroll
-                for (int bi = 0; bi < 4; bi++)
-#pragma unroll
-                    for (int bj = 0; bj < 4; bj++) acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[bi], bf[bj], acc[bi][bj], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-
-        // ---- epilogue.  Element (bi, bj, reg) of a lane: tile row wm 64 + bi 16 + lk + 4 reg, tile column wn 64 + bj 16 + l15.
+        // ---- epilogue
         if (CROSS) {
             double rmin[4][4];
 #pragma unroll
@@ -325,7 +282,7 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
                 for (int reg = 0; reg < 4; reg++) rmin[bi][reg] = INFINITY;
 #pragma unroll
             for (int bj = 0; bj < 4; bj++) {
-                const int cl = wn * 64 + bj * 16 + l15;
+                const int cl = tile_col(l, bj);
                 if (j0 + cl >= w.b.n) continue;
                 const double rj = s_rnb[cl], g2c = cs.g2[cl];
                 int cnt = 0;
@@ -333,7 +290,7 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
                 for (int bi = 0; bi < 4; bi++)
 #pragma unroll
                     for (int reg = 0; reg < 4; reg++) {
-                        const int rl = wm * 64 + bi * 16 + lk + 4 * reg;
+                        const int rl = tile_row(l, bi, reg);
                         if (i0 + rl >= w.a.n) continue;
                         const double g = acc[bi][bj][reg];
                         const double d2 = fmax((s_rna[rl] + rj) - (g + g), 0.0);
@@ -348,7 +305,7 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
 #pragma unroll
                 for (int reg = 0; reg < 4; reg++)
                     if (rmin[bi][reg] < INFINITY)
-                        atomicMin(&cs.mn[wm * 64 + bi * 16 + lk + 4 * reg], (u64)__double_as_longlong(rmin[bi][reg]));
+                        atomicMin(&cs.mn[tile_row(l, bi, reg)], (u64)__double_as_longlong(rmin[bi][reg]));
             __syncthreads();
             cross_publish(w, cs, i0, j0);
         } else {
@@ -358,23 +315,23 @@ __global__ void __launch_bounds__(kThreads) k_prdc_gram(Walk w) {
             const int r = tid & (kTile - 1), half = tid >> 7;
 #pragma unroll
             for (int sbi = 0; sbi < 4; sbi++) {
-                if (wn == (sbi >> 1)) {
+                if (l.wn == (sbi >> 1)) {
 #pragma unroll
                     for (int jj = 0; jj < 2; jj++) {
                         const int bj = 2 * (sbi & 1) + jj;
-                        const int cl = wn * 64 + bj * 16 + l15;
+                        const int cl = tile_col(l, bj);
                         const int64_t j = j0 + cl;
                         const double rj = s_rnb[cl];
 #pragma unroll
                         for (int bi = 0; bi < 4; bi++)
 #pragma unroll
                             for (int reg = 0; reg < 4; reg++) {
-                                const int rl = wm * 64 + bi * 16 + lk + 4 * reg;
+                                const int rl = tile_row(l, bi, reg);
                                 const double g = acc[bi][bj][reg];
                                 double d2 = fmax((s_rna[rl] + rj) - (g + g), 0.0);
                                 if (w.within && i0 + rl == j) d2 = 0.0;
                                 if (j >= w.b.n) d2 = INFINITY;
-                                slab[rl * SLD + jj * 16 + l15] = d2;
+                                slab[rl * SLD + jj * 16 + l.l15] = d2;
                             }
                     }
                 }
@@ -416,16 +373,6 @@ __global__ void __launch_bounds__(256) k_prdc_init(Header *h, int *colcnt, int64
         rowflag[t] = 0;
         rowmin[t] = (u64)__double_as_longlong(INFINITY);
     }
-}
-
-__global__ void __launch_bounds__(256) k_prdc_finite(Pts p, Header *h) {
-    const int64_t total = p.n * p.D, first = p.n1 * p.D;
-    bool bad = false;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const float v = e < first ? p.x[e] : p.y[e - first];
-        bad |= !isfinite(v);
-    }
-    if (bad) atomicOr(&h->nonfinite, 1);
 }
 
 template <int THREADS>
@@ -522,21 +469,13 @@ int check_shape(const char *who, int64_t n1, int64_t n2, int64_t D, int32_t k) {
 template <bool CROSS>
 int launch_walk(const Walk &w, bool gram, unsigned grid, hipStream_t st) {
     const size_t shmem = CROSS ? 0 : (size_t)kThreads * w.K1 * sizeof(double);
-    const void *fn;
-    if (gram) fn = reinterpret_cast<const void *>(&k_prdc_gram<CROSS>);
-    else if (w.D <= 2) fn = reinterpret_cast<const void *>(&k_prdc_direct<2, CROSS>);
-    else if (w.D <= 4) fn = reinterpret_cast<const void *>(&k_prdc_direct<4, CROSS>);
-    else if (w.D <= 8) fn = reinterpret_cast<const void *>(&k_prdc_direct<8, CROSS>);
-    else fn = reinterpret_cast<const void *>(&k_prdc_direct<16, CROSS>);
+    using Kernel = void (*)(Walk);
+    const Kernel fn = gram ? &k_prdc_gram<CROSS> : with_dt(w.D, [](auto dt) -> Kernel { return &k_prdc_direct<decltype(dt)::value, CROSS>; });
     if (!CROSS) {                                          // the lists of k = 32 (66 KB) beside the tile image pass 64 KB of LDS; the limit counts against 160 KB minus the static 36 KB
-        const int r = ensure_dynamic_lds(fn, 96 * 1024);
+        const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 96 * 1024);
         if (r != DLPM_OK) return r;
     }
-    if (gram) k_prdc_gram<CROSS><<<grid, kThreads, shmem, st>>>(w);
-    else if (w.D <= 2) k_prdc_direct<2, CROSS><<<grid, kThreads, shmem, st>>>(w);
-    else if (w.D <= 4) k_prdc_direct<4, CROSS><<<grid, kThreads, shmem, st>>>(w);
-    else if (w.D <= 8) k_prdc_direct<8, CROSS><<<grid, kThreads, shmem, st>>>(w);
-    else k_prdc_direct<16, CROSS><<<grid, kThreads, shmem, st>>>(w);
+    fn<<<grid, kThreads, shmem, st>>>(w);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }
@@ -555,9 +494,8 @@ extern "C" int dlpm_prdc_f32(const float *x_dev, int64_t n1, const float *y_dev,
     const int rc = check_shape("dlpm_prdc_f32", n1, n2, D, nearest_k);
     if (rc != DLPM_OK) return rc;
     DLPM_CHECK_ARG(x_dev && y_dev && workspace_dev && counts_out_dev && out_dev, "dlpm_prdc_f32: null pointer");
-    auto mis = [](const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    DLPM_CHECK_ARG(!mis(x_dev, 4) && !mis(y_dev, 4) && !mis(radii_real_out_dev, 8) && !mis(radii_fake_out_dev, 8) && !mis(counts_out_dev, 8) &&
-                       !mis(out_dev, 8),
+    DLPM_CHECK_ARG(aligned(x_dev, 4) && aligned(y_dev, 4) && aligned(radii_real_out_dev, 8) && aligned(radii_fake_out_dev, 8) &&
+                       aligned(counts_out_dev, 8) && aligned(out_dev, 8),
                    "dlpm_prdc_f32: misaligned input or output");
     const Layout L = layout_of(n1, n2, D, nearest_k);
     const int ws_rc = check_workspace("dlpm_prdc_f32", workspace_dev, workspace_bytes, L.total);
@@ -576,13 +514,13 @@ extern "C" int dlpm_prdc_f32(const float *x_dev, int64_t n1, const float *y_dev,
 
     k_prdc_init<<<(unsigned)ceil_div(std::max(n1, n2), 256), 256, 0, st>>>(hdr, colcnt, n2, rowflag, rowmin, n1);
     DLPM_LAUNCH_CHECK();
-    k_prdc_finite<<<(unsigned)std::min<int64_t>(ceil_div(n * D, 256), 2048), 256, 0, st>>>(p, hdr);
+    k_nonfinite<256><<<scan_grid(n * D), 256, 0, st>>>(p, &hdr->nonfinite);
     DLPM_LAUNCH_CHECK();
     if (L.gram) {
         ProfScope ps("prdc_centre", 3.0 * (double)n * D, 8.0 * (double)n * D, st);
         k_colstats<false><<<dim3((unsigned)ceil_div(D, 256), kColChunks), 256, 0, st>>>(p, colpart);
         DLPM_LAUNCH_CHECK();
-        k_prdc_colmean<<<(unsigned)ceil_div(D, 256), 256, 0, st>>>(colpart, n, D, mean);
+        k_colmean<double><<<(unsigned)ceil_div(D, 256), 256, 0, st>>>(colpart, n, D, mean);
         DLPM_LAUNCH_CHECK();
         k_prdc_rownorm<<<(unsigned)n, 256, 0, st>>>(p, mean, rn);
         DLPM_LAUNCH_CHECK();

@@ -105,6 +105,21 @@ def test_sizes_around_the_edges(edge_pool, n, F):
     check_stats('edge real', x, parts['mu1'], parts['sigma1'])
 
 
+@pytest.mark.parametrize('F', [20, 130])
+def test_a_covariance_cut_into_two_row_chunks(F):
+    """n1 = 600 and n2 = 520 rows are cut into 304 + 296 and 272 + 248 (the chunk rule: no chunk under 256 rows, a multiple of 16 per
+    chunk), so every tile adds two partials, each with a ragged last chunk and a ragged last K step; F = 130 has three triangle
+    tiles, so the partials are indexed by chunk x tile."""
+    rs = np.random.RandomState(600 + F)
+    s = 0.5 + np.arange(F) / F
+    x = (rs.standard_normal((600, F)) * s).astype(np.float32)
+    y = (rs.standard_normal((520, F)) * 1.2 * s + 0.1).astype(np.float32)
+    o, bound = model_of(x, y)
+    value, parts = check_against('two chunks, F = %d' % F, x, y, o['fd'], bound, oracle=o)
+    check_stats('two chunks real', x, parts['mu1'], parts['sigma1'])
+    check_stats('two chunks fake', y, parts['mu2'], parts['sigma2'])
+
+
 # ---------------------------------------------------------------- 4, 5: closed forms
 def test_fake_equal_to_real_is_zero_within_the_bound_and_not_clamped():
     x = fixture('gauss300x260x64')['real']

@@ -45,7 +45,8 @@ def sets(torch, n, D):
 def pass_of(kernel):
     if 'k_prdc_direct' in kernel or 'k_prdc_gram' in kernel:
         return 'cross' if ('true>' in kernel.replace(' ', '') or ', true' in kernel) else 'radii'
-    return 'rest' if ('k_prdc_' in kernel or 'k_colstats' in kernel) else None
+    shared = ('k_colstats', 'k_colmean', 'k_nonfinite')         # of metrics_common.h
+    return 'rest' if ('k_prdc_' in kernel or any(s in kernel for s in shared)) else None
 
 
 def profile_passes(name, calls=2):
