@@ -50,11 +50,15 @@ struct ConvW {            // one convolution's weights
     float *w_wino4sp = nullptr; // Upsample convolutions with cout % 128 == 0: the parity classes' F(4x4,2x2) weights (conv_wino4.hip: k_conv3x3_wino4sp)
     float *w_small = nullptr;// 3x3 with cout <= 4 (head): [tap][cin][4]
     float *w_taps = nullptr; // 3x3 with cout <= 3 (head): [9 cout -> 32][cin], the head as a 1x1 GEMM + gather (conv_direct.hip)
-    void *w_split = nullptr; // 1x1 with cout % 128 == 0, cin % 32 == 0: three bf16 planes in stage-tile order (conv_split.hip)
+    float *w_split = nullptr;// 1x1 with cout % 128 == 0, cin % 32 == 0: three bf16 planes in stage-tile order (conv_split.hip)
     float *w_rs = nullptr;   // 64-channel layers: fragment order of the fused small-image blocks (block_small.hip)
     float *w_hfused = nullptr;  // head: fragment order of the one-pass head + update kernel (head_fused.hip)
     bool owns = false;
 };
+// the layouts a ConvW always owns (w_dev only where `owns` says so); the copies that exist only under a small declared batch, by n-tile width
+constexpr float *ConvW::*OWNED_LAYOUTS[] = {&ConvW::w_frag, &ConvW::w_wino, &ConvW::w_wino4, &ConvW::w_wino4_n64, &ConvW::w_wino4_n32, &ConvW::w_wino4sp,
+                                            &ConvW::w_small, &ConvW::w_taps, &ConvW::w_split, &ConvW::w_rs, &ConvW::w_hfused};
+constexpr struct { int nq; float *ConvW::*copy; } NARROW_LAYOUTS[] = {{64, &ConvW::w_wino4_n64}, {32, &ConvW::w_wino4_n32}};
 
 struct Layer {
     LayerKind kind;
@@ -77,7 +81,8 @@ struct Tensor4 {
 // Activation arena: a first-fit free list over the caller's workspace.  Launches are stream-ordered, so a buffer can be
 // handed out again as soon as every launch that touches it has been ENQUEUED; the plan releases each tensor right after
 // its last consumer (skip-connection tensors when their output block pops them).  A dry run (no base pointer: offsets
-// from a fake base, never dereferenced) replays the same alloc / release sequence to size the workspace = the peak.
+// from a fake base, never dereferenced) runs the same walk with every launch suppressed to size the workspace = the peak.  A real
+// walk that outgrows the caller's workspace sets `overflow`, and from then on nothing is enqueued (Ctx: PLAN_ENQUEUES).
 struct Bump {
     char *base = nullptr;
     int64_t cap = 0, off = 0, peak = 0, nalloc = 0;
@@ -123,40 +128,6 @@ struct Bump {
         holes.insert(holes.begin() + i, std::make_pair(lo, n));
     }
 };
-
-void policy_of(const dlpm_unet *u, ConvLaunch &L);   // copies the net's conv policy into a launch (defined below the struct)
-
-// GroupNorm statistics can ride on the producing conv's epilogue when its pixel tiles stay inside one image
-// and the conv runs on the MFMA kernels with the row epilogue.  Decides (at plan time) whether `t`, produced by
-// conv `c` with the given geometry, carries statistics, and allocates them: tile size per conv_stats_pixels.
-void plan_stats(const dlpm_unet *u, Bump &ws, Tensor4 &t, const ConvW &c, int B, int C0, int stride, int ups, bool stem = false) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_GN_FUSION"); off = (e && e[0] == '1') ? 1 : 0; }
-    t.stats = nullptr;
-    t.stats_px = 0;
-    if (off || (!c.use_igemm && !stem)) return;
-    ConvLaunch L;
-    L.w_wino = c.w_wino; L.w_wino4 = c.w_wino4; L.w_wino4_n64 = c.w_wino4_n64; L.w_wino4_n32 = c.w_wino4_n32; L.w_wino4sp = c.w_wino4sp; L.w_split = c.w_split; L.ks = c.ks; L.stride = stride; L.ups = ups; L.Hout = t.H; L.Wout = t.W; L.Cout = c.cout;
-    L.Hin = ups ? t.H / 2 : t.H * stride; L.Win = ups ? t.W / 2 : t.W * stride;
-    L.C0 = C0; L.C1 = c.cin - C0; L.B = B;
-    L.in_nchw = stem ? 1 : 0;
-    policy_of(u, L);
-    const int px = conv_stats_pixels(L);
-    if (px <= 0) return;
-    t.stats_px = px;
-    t.stats = reinterpret_cast<float2 *>(ws.alloc((int64_t)2 * B * (t.H * t.W / px) * t.C));
-}
-
-// GroupNorm(+scale/shift) coefficients of the virtual concat [x0 | x1]
-int gn_any(Tensor4 x0, Tensor4 x1, int B, int groups, const float *gamma, const float *beta, const float *ss,
-           int64_t ss_stride, int64_t ss_offset, float *cA, float *cB, hipStream_t st) {
-    const int HW = x0.H * x0.W;
-    if (x0.stats && (x1.C == 0 || x1.stats))
-        return launch_gn_coeffs_from_stats(x0.stats, x1.stats, x0.C, x1.C, B, HW / x0.stats_px, x1.C ? HW / x1.stats_px : 1, HW,
-                                           groups, gamma, beta, ss, ss_stride, ss_offset, cA, cB, st);
-    return launch_gn_coeffs(x0.p, x1.p, x0.C, x1.C, B, HW, groups, gamma, beta, ss, ss_stride, ss_offset, cA, cB, st);
-}
-
 
 void drop(Bump &ws, Tensor4 &t) {   // release a tensor and the statistics that ride with it
     ws.release(t.p);
@@ -384,7 +355,7 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  /
     return relayout_weight(src, c.w_dev, c.cout, c.cin, c.ks, c.use_igemm, nullptr);
 }
 
-// the launch descriptor with the net's policy and this convolution's weight layouts attached
+// the launch descriptor with the net's policy and this convolution's weight layouts attached: the ONE place a ConvW is copied into a launch
 void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
     policy_of(u, L);
     L.w = c.w_dev;
@@ -403,20 +374,7 @@ void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
 }
 
 int run_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch L, hipStream_t st, const HeadUpdate *hu = nullptr, float *head_scratch = nullptr) {
-    policy_of(u, L);
-    L.w = c.w_dev;
-    L.w_frag = c.w_frag;
-    L.w_wino = c.w_wino;
-    L.w_wino4 = c.w_wino4;
-    L.w_wino4_n64 = c.w_wino4_n64;
-    L.w_wino4_n32 = c.w_wino4_n32;
-    L.w_wino4sp = c.w_wino4sp;
-    L.w_small = c.w_small;
-    L.w_taps = c.w_taps;
-    L.w_hfused = c.w_hfused;
-    L.w_split = c.w_split;
-    L.ks = c.ks;
-    L.Cout = c.cout;
+    attach_conv(u, c, L);      // (the time path describes its launches by hand; a descriptor from conv_io carries the same values already)
     if (head_fused_ok(L)) return launch_conv_head_fused(L, hu, st);
     if (head_scratch && head_gemm_ok(L)) return launch_conv_head_gemm(L, hu, head_scratch, st);
     if (head_conv_ok(L)) return launch_conv_head(L, hu, st);
@@ -444,39 +402,97 @@ struct Ctx {
     bool dry() const { return ws.dry; }
 };
 
-// Split-K factor of a 3x3 stride-1 convolution of the plan (conv_splitk.hip: conv_ksplit_for): a function of the layer and the declared batch
-int ksplit_of(const Ctx &cx, const ConvW &c, ConvLaunch L) {
-    attach_conv(cx.u, c, L);
-    L.bias = nullptr;
-    return conv_ksplit_for(L);
+// ONE walk sizes the workspace and launches the plan: the code below allocates, releases and describes its launches the same way in both
+// modes, and everything it enqueues goes through a helper that opens with PLAN_ENQUEUES.  A dry run enqueues nothing.  A real walk
+// whose arena has outgrown the caller's workspace -- it asked for more than the dry run did -- refuses instead of writing past the end.
+int arena_overflow(const Ctx &cx) {
+    set_error("unet plan: the walk at batch %d asked the arena for %lld bytes, past the workspace of %lld bytes that dlpm_unet_workspace_bytes sized",
+              cx.B, (long long)cx.ws.peak, (long long)cx.ws.cap);
+    return DLPM_ERR_NOMEM;
 }
-// ... and the launch: S grid copies write their partial outputs into a workspace buffer, launch_splitk_reduce adds bias / residual.  (The
-// caller's dry run reserves the buffer with reserve_ksplit at the point where this runs.)
+#define PLAN_ENQUEUES(cx)                                   \
+    do {                                                    \
+        if ((cx).dry()) return DLPM_OK;                     \
+        if ((cx).ws.overflow) return arena_overflow(cx);    \
+    } while (0)
+
+// any launch_* function of conv.h that takes its stream last
+template <class Fn, class... A>
+int enqueue(Ctx &cx, Fn launch, const A &...a) {
+    PLAN_ENQUEUES(cx);
+    return launch(a..., cx.st);
+}
+
+int run_conv(Ctx &cx, const ConvW &c, const ConvLaunch &L, const HeadUpdate *hu = nullptr, float *head_scratch = nullptr) {
+    PLAN_ENQUEUES(cx);
+    return run_conv(cx.u, c, L, cx.st, hu, head_scratch);
+}
+
+Tensor4 new_tensor(Ctx &cx, int C, int H, int W) {
+    Tensor4 t;
+    t.C = C; t.H = H; t.W = W;
+    t.p = cx.ws.alloc((int64_t)cx.B * H * W * C);
+    return t;
+}
+
+// The launch of convolution `c` of the plan on [x0 | x1] -> o, the descriptor the plan asks the selectors about AND runs: layouts, policy,
+// sources, batch, bias, output, and the geometry the two sizes give (same size; a smaller output is the stride-2 downsampling convolution, a
+// larger one the nearest x2 upsample).  The call site adds what the layer fuses: GroupNorm coefficients, SiLU, residual, a boundary layout.
+ConvLaunch conv_io(const Ctx &cx, const ConvW &c, const Tensor4 &x0, const Tensor4 &x1, const Tensor4 &o) {
+    ConvLaunch L;
+    attach_conv(cx.u, c, L);
+    L.src0 = x0.p; L.src1 = x1.p; L.C0 = x0.C; L.C1 = x1.C; L.B = cx.B;
+    L.Hin = x0.H; L.Win = x0.W; L.Hout = o.H; L.Wout = o.W;
+    L.stride = o.H < x0.H ? 2 : 1; L.ups = o.H > x0.H ? 1 : 0;
+    L.bias = cx.u->params[c.p_b].dev; L.out = o.p;
+    return L;
+}
+
+// GroupNorm statistics can ride on the producing conv's epilogue when its pixel tiles stay inside one image and the conv runs on the
+// MFMA kernels with the row epilogue (or the stem kernels).  Decides whether `t`, the output of launch `L` of conv `c`, carries
+// statistics, allocates them (tile size per conv_stats_pixels, asked about the launch itself) and points the launch at them.
+void plan_stats(Ctx &cx, Tensor4 &t, const ConvW &c, ConvLaunch &L) {
+    static int off = -1;
+    if (off < 0) { const char *e = getenv("DLPM_NO_GN_FUSION"); off = (e && e[0] == '1') ? 1 : 0; }
+    t.stats = nullptr;
+    t.stats_px = 0;
+    if (off || (!c.use_igemm && !L.in_nchw)) return;
+    const int px = conv_stats_pixels(L);
+    if (px <= 0) return;
+    t.stats_px = px;
+    t.stats = L.stats_out = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * cx.B * (t.H * t.W / px) * t.C));
+}
+
+// GroupNorm(+scale/shift from the emb rows at column ss_offset) coefficients of the virtual concat [x0 | x1], from the producers' statistics where both carry them
+int gn_any(Ctx &cx, Tensor4 x0, Tensor4 x1, int p_gamma, int p_beta, const float *ss, int64_t ss_offset, float *cA, float *cB) {
+    PLAN_ENQUEUES(cx);
+    const int HW = x0.H * x0.W, C = x0.C + x1.C, groups = C < 32 ? C : 32;
+    const float *gamma = cx.u->params[p_gamma].dev, *beta = cx.u->params[p_beta].dev;
+    const int64_t ss_stride = ss ? cx.emb_pitch() : 0;   // row pitch 0: all samples read the one emb row
+    if (x0.stats && (x1.C == 0 || x1.stats))
+        return launch_gn_coeffs_from_stats(x0.stats, x1.stats, x0.C, x1.C, cx.B, HW / x0.stats_px, x1.C ? HW / x1.stats_px : 1, HW,
+                                           groups, gamma, beta, ss, ss_stride, ss_offset, cA, cB, cx.st);
+    return launch_gn_coeffs(x0.p, x1.p, x0.C, x1.C, cx.B, HW, groups, gamma, beta, ss, ss_stride, ss_offset, cA, cB, cx.st);
+}
+
+// A 3x3 stride-1 convolution of the plan, cut over S = conv_ksplit_for grid copies where the layer and the declared batch ask for it
+// (conv_splitk.hip): the copies write their partial outputs into an arena buffer, launch_splitk_reduce adds bias / residual.
 int run_conv3(Ctx &cx, const ConvW &c, const ConvLaunch &L) {
-    const int S = ksplit_of(cx, c, L);
-    if (S <= 1) return run_conv(cx.u, c, L, cx.st);
+    const int S = conv_ksplit_for(L);
+    if (S <= 1) return run_conv(cx, c, L);
     const int64_t npix = (int64_t)L.B * L.Hout * L.Wout;
     float *part = cx.ws.alloc((int64_t)S * npix * c.cout);
     ConvLaunch P = L;
     P.bias = nullptr; P.res0 = nullptr; P.res1 = nullptr; P.R0 = 0; P.stats_out = nullptr; P.out = part; P.ksplit = S;
-    int rc = run_conv(cx.u, c, P, cx.st);
-    if (rc == DLPM_OK) rc = launch_splitk_reduce(part, S, npix, c.cout, L.bias, L.res0, L.res1, L.R0, L.out, cx.st);
+    int rc = run_conv(cx, c, P);
+    if (rc == DLPM_OK) rc = enqueue(cx, launch_splitk_reduce, part, S, npix, c.cout, L.bias, L.res0, L.res1, L.R0, L.out);
     cx.ws.release(part);
     return rc;
 }
-void reserve_ksplit(Ctx &cx, const ConvW &c, const ConvLaunch &L) {     // dry run: the partial buffer's share of the workspace peak
-    const int S = ksplit_of(cx, c, L);
-    if (S > 1) cx.ws.release(cx.ws.alloc((int64_t)S * L.B * L.Hout * L.Wout * c.cout));
-}
 
-void release_res_temps(Ctx &cx, float *cA1, float *cB1, Tensor4 &h1, float *cA2, float *cB2, float *sk) {
-    cx.ws.release(cA1);
-    cx.ws.release(cB1);
-    drop(cx.ws, h1);
-    cx.ws.release(cA2);
-    cx.ws.release(cB2);
-    cx.ws.release(sk);
-}
+// The whole-image ResBlock kernel reads its residual as ONE tensor of Cout channels per pixel: the skip convolution's output, or an input
+// that is not a concat (an identity residual over [x0 | x1] would be read from x0 with the wrong pitch).  run_res and dlpm_resblock_img_f32 ask.
+bool res_img_residual_ok(bool has_skip, int C1) { return has_skip || C1 == 0; }
 
 int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
     dlpm_unet *u = cx.u;
@@ -489,18 +505,16 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
         r.x0 = x0.p; r.x1 = x1.p; r.C0 = C0; r.C1 = C1; r.B = B; r.H = H; r.W = W;
         r.w1f = L.c1.w_rs; r.w2f = L.c2.w_rs; r.wsf = L.has_skip ? L.skip.w_rs : nullptr;
         if (u->gen == DLPM_CONV_AUTO && Co == 64 && (!L.has_skip || r.wsf) && res_small_ok(r)) {
-            float *o = cx.ws.alloc((int64_t)B * HW * Co);
-            out->p = o; out->C = Co; out->H = H; out->W = W;
+            *out = new_tensor(cx, Co, H, W);
             out->stats = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * B * Co));
             out->stats_px = HW;
-            if (cx.dry()) return DLPM_OK;
             r.gn1_w = u->params[L.p_gn1_w].dev; r.gn1_b = u->params[L.p_gn1_b].dev;
             r.gn2_w = u->params[L.p_gn2_w].dev; r.gn2_b = u->params[L.p_gn2_b].dev;
             r.b1 = u->params[L.c1.p_b].dev; r.b2 = u->params[L.c2.p_b].dev;
             r.bs = L.has_skip ? u->params[L.skip.p_b].dev : nullptr;
             r.emb = cx.embout; r.emb_stride = cx.emb_pitch(); r.emb_off = L.emb_off;
-            r.out = o; r.stats_out = out->stats;
-            return launch_resblock_small(r, cx.st);
+            r.out = out->p; r.stats_out = out->stats;
+            return enqueue(cx, launch_resblock_small, r);
         }
     }
     if (u->gen == DLPM_CONV_AUTO && ((Co == 32 && H == 32 && W == 32) || (Co == 64 && H == 16 && W == 16)) && L.c1.w_wino4 && L.c2.w_wino4) {
@@ -513,162 +527,117 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
         const bool from_stats = x0.stats && (C1 == 0 || x1.stats);
         r.w1 = L.c1.w_wino4; r.w2 = L.c2.w_wino4;
         float *cA1 = from_stats ? nullptr : cx.ws.alloc((int64_t)B * Cin), *cB1 = from_stats ? nullptr : cx.ws.alloc((int64_t)B * Cin);
-        float *sk = L.has_skip ? cx.ws.alloc((int64_t)B * HW * Co) : nullptr;
-        float *hb = H == 32 ? cx.ws.alloc((int64_t)B * HW * Co) : nullptr;
-        float *o = cx.ws.alloc((int64_t)B * HW * Co);
-        r.hbuf = hb; r.res = L.has_skip ? sk : x0.p;
+        Tensor4 sk = L.has_skip ? new_tensor(cx, Co, H, W) : Tensor4();
+        Tensor4 hb = H == 32 ? new_tensor(cx, Co, H, W) : Tensor4();     // the activated intermediate (it stays in LDS at 16x16)
+        Tensor4 o = new_tensor(cx, Co, H, W);
+        r.hbuf = hb.p; r.res = L.has_skip ? sk.p : x0.p;
         if (from_stats) {
             r.st0 = x0.stats; r.nt0 = HW / x0.stats_px;
             if (C1) { r.st1 = x1.stats; r.nt1 = HW / x1.stats_px; }
         } else {
             r.coefA1 = cA1; r.coefB1 = cB1;
         }
-        if ((L.has_skip || C1 == 0) && res_img_ok(r)) {
-            out->p = o; out->C = Co; out->H = H; out->W = W;
-            plan_stats(cx.u, cx.ws, *out, L.c2, B, Co, 1, 0);
-            auto done = [&]() { cx.ws.release(cA1); cx.ws.release(cB1); cx.ws.release(sk); cx.ws.release(hb); };
-            if (cx.dry()) { done(); return DLPM_OK; }
-            if (!from_stats)
-                TRY(gn_any(x0, x1, B, Cin < 32 ? Cin : 32, u->params[L.p_gn1_w].dev, u->params[L.p_gn1_b].dev, nullptr, 0, 0, cA1, cB1, cx.st));
-            if (L.has_skip) {
-                ConvLaunch s;
-                s.src0 = x0.p; s.src1 = x1.p; s.C0 = C0; s.C1 = C1; s.B = B; s.Hin = s.Hout = H; s.Win = s.Wout = W;
-                s.bias = u->params[L.skip.p_b].dev; s.out = sk;
-                TRY(run_conv(u, L.skip, s, cx.st));
-            }
+        const bool take = res_img_residual_ok(L.has_skip, C1) && res_img_ok(r);
+        if (take) {
+            *out = o;
+            hb.C = Co; hb.H = H; hb.W = W;
+            ConvLaunch b = conv_io(cx, L.c2, hb, Tensor4(), o);     // the kernel emits the output statistics that conv2's own launch would
+            plan_stats(cx, *out, L.c2, b);
+            if (!from_stats) TRY(gn_any(cx, x0, x1, L.p_gn1_w, L.p_gn1_b, nullptr, 0, cA1, cB1));
+            if (L.has_skip) TRY(run_conv(cx, L.skip, conv_io(cx, L.skip, x0, x1, sk)));
             r.gn1_w = u->params[L.p_gn1_w].dev; r.gn1_b = u->params[L.p_gn1_b].dev;
             r.gn2_w = u->params[L.p_gn2_w].dev; r.gn2_b = u->params[L.p_gn2_b].dev;
             r.b1 = u->params[L.c1.p_b].dev; r.b2 = u->params[L.c2.p_b].dev;
             r.emb = cx.embout; r.emb_stride = cx.emb_pitch(); r.emb_off = L.emb_off;
-            r.out = o; r.stats_out = out->stats;
-            TRY(launch_resblock_img(r, cx.st));
-            done();
-            return DLPM_OK;
+            r.out = o.p; r.stats_out = out->stats;
+            TRY(enqueue(cx, launch_resblock_img, r));
         }
-        cx.ws.release(cA1); cx.ws.release(cB1); cx.ws.release(sk); cx.ws.release(hb); cx.ws.release(o);
+        cx.ws.release(cA1); cx.ws.release(cB1); cx.ws.release(sk.p); cx.ws.release(hb.p);
+        if (take) return DLPM_OK;
+        cx.ws.release(o.p);
     }
     float *cA1 = cx.ws.alloc((int64_t)B * Cin), *cB1 = cx.ws.alloc((int64_t)B * Cin);
-    Tensor4 h1;
-    h1.C = Co; h1.H = H; h1.W = W;
-    h1.p = cx.ws.alloc((int64_t)B * HW * Co);
-    plan_stats(cx.u, cx.ws, h1, L.c1, B, C0, 1, 0);
+    Tensor4 h1 = new_tensor(cx, Co, H, W);
+    ConvLaunch a = conv_io(cx, L.c1, x0, x1, h1);
+    a.coefA = cA1; a.coefB = cB1; a.act_silu = 1;
+    plan_stats(cx, h1, L.c1, a);
     float *cA2 = cx.ws.alloc((int64_t)B * Co), *cB2 = cx.ws.alloc((int64_t)B * Co);
-    float *sk = L.has_skip ? cx.ws.alloc((int64_t)B * HW * Co) : nullptr;
-    float *o = cx.ws.alloc((int64_t)B * HW * Co);
-    out->p = o; out->C = Co; out->H = H; out->W = W;
-    plan_stats(cx.u, cx.ws, *out, L.c2, B, Co, 1, 0);
-    if (cx.dry()) {
-        ConvLaunch g;      // (geometry of the block's two 3x3 convolutions: what ksplit_of looks at)
-        g.C0 = C0; g.C1 = C1; g.B = B; g.Hin = g.Hout = H; g.Win = g.Wout = W;
-        reserve_ksplit(cx, L.c1, g);
-        g.C0 = Co; g.C1 = 0;
-        reserve_ksplit(cx, L.c2, g);
-        release_res_temps(cx, cA1, cB1, h1, cA2, cB2, sk);
-        return DLPM_OK;
-    }
-    const int G1 = Cin < 32 ? Cin : 32, G2 = Co < 32 ? Co : 32;
-    TRY(gn_any(x0, x1, B, G1, u->params[L.p_gn1_w].dev, u->params[L.p_gn1_b].dev, nullptr, 0, 0, cA1, cB1, cx.st));
-    ConvLaunch a;
-    a.src0 = x0.p; a.src1 = x1.p; a.C0 = C0; a.C1 = C1; a.B = B; a.Hin = a.Hout = H; a.Win = a.Wout = W;
-    a.bias = u->params[L.c1.p_b].dev; a.coefA = cA1; a.coefB = cB1; a.act_silu = 1; a.out = h1.p; a.stats_out = h1.stats;
+    Tensor4 sk = L.has_skip ? new_tensor(cx, Co, H, W) : Tensor4();
+    *out = new_tensor(cx, Co, H, W);
+    ConvLaunch b = conv_io(cx, L.c2, h1, Tensor4(), *out);
+    b.coefA = cA2; b.coefB = cB2; b.act_silu = 1;
+    if (L.has_skip) { b.res0 = sk.p; b.R0 = Co; }
+    else { b.res0 = x0.p; b.res1 = x1.p; b.R0 = C0; }
+    plan_stats(cx, *out, L.c2, b);
+    TRY(gn_any(cx, x0, x1, L.p_gn1_w, L.p_gn1_b, nullptr, 0, cA1, cB1));
     TRY(run_conv3(cx, L.c1, a));
-    TRY(gn_any(h1, Tensor4(), B, G2, u->params[L.p_gn2_w].dev, u->params[L.p_gn2_b].dev, cx.embout,
-               cx.emb_pitch(), L.emb_off, cA2, cB2, cx.st));   // row pitch 0: all samples read the one emb row
-    ConvLaunch b;
-    b.src0 = h1.p; b.C0 = Co; b.B = B; b.Hin = b.Hout = H; b.Win = b.Wout = W;
-    b.bias = u->params[L.c2.p_b].dev; b.coefA = cA2; b.coefB = cB2; b.act_silu = 1; b.out = o; b.stats_out = out->stats;
-    if (L.has_skip) {
-        ConvLaunch s;
-        s.src0 = x0.p; s.src1 = x1.p; s.C0 = C0; s.C1 = C1; s.B = B; s.Hin = s.Hout = H; s.Win = s.Wout = W;
-        s.bias = u->params[L.skip.p_b].dev; s.out = sk;
-        TRY(run_conv(u, L.skip, s, cx.st));
-        b.res0 = sk; b.R0 = Co;
-    } else {
-        b.res0 = x0.p; b.res1 = x1.p; b.R0 = C0;
-    }
+    TRY(gn_any(cx, h1, Tensor4(), L.p_gn2_w, L.p_gn2_b, cx.embout, L.emb_off, cA2, cB2));
+    if (L.has_skip) TRY(run_conv(cx, L.skip, conv_io(cx, L.skip, x0, x1, sk)));
     TRY(run_conv3(cx, L.c2, b));
-    release_res_temps(cx, cA1, cB1, h1, cA2, cB2, sk);
+    cx.ws.release(cA1);
+    cx.ws.release(cB1);
+    drop(cx.ws, h1);
+    cx.ws.release(cA2);
+    cx.ws.release(cB2);
+    cx.ws.release(sk.p);
     return DLPM_OK;
 }
 
 int run_attn(Ctx &cx, const Layer &L, Tensor4 x, Tensor4 *out) {
     dlpm_unet *u = cx.u;
     const int B = cx.B, C = x.C, T = x.H * x.W;
-    {
-        // small images: GroupNorm -> qkv -> attention -> proj -> + x in one launch, one workgroup per image (block_small.hip)
-        AttnSmallLaunch a;
-        a.x = x.p; a.C = C; a.heads = u->cfg.num_heads; a.B = B; a.H = x.H; a.W = x.W;
-        a.wqkv = L.c1.w_rs; a.wproj = L.c2.w_rs;
-        const bool whole16 = attn16_ok(a);
-        if (u->gen == DLPM_CONV_AUTO && (attn_small_ok(a) || whole16)) {
-            *out = x;
-            out->p = cx.ws.alloc((int64_t)B * T * C);
-            out->stats = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * B * C));
-            out->stats_px = T;
-            if (cx.dry()) return DLPM_OK;
-            a.gn_w = u->params[L.p_gn1_w].dev; a.gn_b = u->params[L.p_gn1_b].dev;
-            a.bqkv = u->params[L.c1.p_b].dev; a.bproj = u->params[L.c2.p_b].dev;
-            a.out = out->p; a.stats_out = out->stats;
-            return whole16 ? launch_attnblock16(a, cx.st) : launch_attnblock_small(a, cx.st);
-        }
+    // small images: GroupNorm -> qkv -> attention -> proj -> + x in one launch, one workgroup per image (block_small.hip); 16x16 images
+    // that do not take it: GroupNorm + qkv of one image in one launch
+    AttnSmallLaunch a;
+    a.x = x.p; a.C = C; a.heads = u->cfg.num_heads; a.B = B; a.H = x.H; a.W = x.W;
+    a.wqkv = L.c1.w_rs; a.wproj = L.c2.w_rs;
+    a.gn_w = u->params[L.p_gn1_w].dev; a.gn_b = u->params[L.p_gn1_b].dev;
+    a.bqkv = u->params[L.c1.p_b].dev; a.bproj = u->params[L.c2.p_b].dev;
+    const bool whole16 = attn16_ok(a);
+    if (u->gen == DLPM_CONV_AUTO && (attn_small_ok(a) || whole16)) {
+        *out = new_tensor(cx, C, x.H, x.W);
+        out->stats = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * B * C));
+        out->stats_px = T;
+        a.out = out->p; a.stats_out = out->stats;
+        return enqueue(cx, whole16 ? launch_attnblock16 : launch_attnblock_small, a);
     }
     float *cA = cx.ws.alloc((int64_t)B * C), *cB = cx.ws.alloc((int64_t)B * C);
-    float *qkv = cx.ws.alloc((int64_t)B * T * 3 * C);
-    float *av = cx.ws.alloc((int64_t)B * T * C);
-    float *o = cx.ws.alloc((int64_t)B * T * C);
-    const Tensor4 xin = x;
-    *out = x;
-    out->p = o;
-    plan_stats(cx.u, cx.ws, *out, L.c2, B, C, 1, 0);
-    auto done = [&]() { cx.ws.release(cA); cx.ws.release(cB); cx.ws.release(qkv); cx.ws.release(av); };
-    if (cx.dry()) {
-        done();
-        return DLPM_OK;
-    }
-    AttnSmallLaunch gq;
-    gq.x = x.p; gq.C = C; gq.heads = u->cfg.num_heads; gq.B = B; gq.H = x.H; gq.W = x.W; gq.wqkv = L.c1.w_rs;
-    if (u->gen == DLPM_CONV_AUTO && gnqkv_small_ok(gq)) {
-        // 16x16 images: GroupNorm + qkv of one image in one launch (block_small.hip)
-        gq.gn_w = u->params[L.p_gn1_w].dev; gq.gn_b = u->params[L.p_gn1_b].dev; gq.bqkv = u->params[L.c1.p_b].dev; gq.out = qkv;
-        TRY(launch_gnqkv_small(gq, cx.st));
+    Tensor4 qkv = new_tensor(cx, 3 * C, x.H, x.W), av = new_tensor(cx, C, x.H, x.W);
+    *out = new_tensor(cx, C, x.H, x.W);
+    ConvLaunch p = conv_io(cx, L.c2, av, Tensor4(), *out);
+    p.res0 = x.p; p.R0 = C;
+    plan_stats(cx, *out, L.c2, p);
+    a.wproj = nullptr; a.bproj = nullptr; a.out = qkv.p;
+    if (u->gen == DLPM_CONV_AUTO && gnqkv_small_ok(a)) {
+        TRY(enqueue(cx, launch_gnqkv_small, a));
     } else {
-        TRY(gn_any(xin, Tensor4(), B, C < 32 ? C : 32, u->params[L.p_gn1_w].dev, u->params[L.p_gn1_b].dev, nullptr, 0, 0, cA, cB,
-                   cx.st));
-        ConvLaunch q;
-        q.src0 = x.p; q.C0 = C; q.B = B; q.Hin = q.Hout = x.H; q.Win = q.Wout = x.W;
-        q.bias = u->params[L.c1.p_b].dev; q.coefA = cA; q.coefB = cB; q.out = qkv;
-        TRY(run_conv(u, L.c1, q, cx.st));
+        TRY(gn_any(cx, x, Tensor4(), L.p_gn1_w, L.p_gn1_b, nullptr, 0, cA, cB));
+        ConvLaunch q = conv_io(cx, L.c1, x, Tensor4(), qkv);
+        q.coefA = cA; q.coefB = cB;
+        TRY(run_conv(cx, L.c1, q));
     }
-    TRY(launch_attention(qkv, av, B, T, C, u->cfg.num_heads, cx.st));
-    ConvLaunch p;
-    p.src0 = av; p.C0 = C; p.B = B; p.Hin = p.Hout = x.H; p.Win = p.Wout = x.W;
-    p.bias = u->params[L.c2.p_b].dev; p.res0 = x.p; p.R0 = C; p.out = o; p.stats_out = out->stats;
-    TRY(run_conv(u, L.c2, p, cx.st));
-    done();
+    TRY(enqueue(cx, launch_attention, qkv.p, av.p, B, T, C, u->cfg.num_heads));
+    TRY(run_conv(cx, L.c2, p));
+    cx.ws.release(cA);
+    cx.ws.release(cB);
+    cx.ws.release(qkv.p);
+    cx.ws.release(av.p);
     return DLPM_OK;
 }
 
 // free0 / free1: the sequence is the last consumer of x0 / x1 (released once its first layer has been enqueued)
-int run_seq(Ctx &cx, const std::vector<Layer> &seq, Tensor4 x0, Tensor4 x1, const float *x_nchw, Tensor4 *out, bool free0 = false,
-            bool free1 = false) {
-    dlpm_unet *u = cx.u;
-    const int B = cx.B;
+int run_seq(Ctx &cx, const std::vector<Layer> &seq, Tensor4 x0, Tensor4 x1, Tensor4 *out, bool free0 = false, bool free1 = false) {
     Tensor4 h = x0;
     for (size_t i = 0; i < seq.size(); i++) {
         const Layer &L = seq[i];
         Tensor4 o;
         switch (L.kind) {
-            case L_STEM: {
-                const int S = u->cfg.image_size;
-                o.C = L.cout; o.H = S; o.W = S;
-                o.p = cx.ws.alloc((int64_t)B * S * S * L.cout);
-                plan_stats(cx.u, cx.ws, o, L.c1, B, L.cin, 1, 0, true);
-                if (!cx.dry()) {
-                    ConvLaunch a;
-                    a.src0 = x_nchw; a.C0 = L.cin; a.B = B; a.Hin = a.Hout = S; a.Win = a.Wout = S;
-                    a.bias = u->params[L.c1.p_b].dev; a.out = o.p; a.in_nchw = 1; a.stats_out = o.stats;
-                    TRY(run_conv(u, L.c1, a, cx.st));
-                }
+            case L_STEM: {     // h is the (B,C,H,W) input image
+                o = new_tensor(cx, L.cout, h.H, h.W);
+                ConvLaunch a = conv_io(cx, L.c1, h, Tensor4(), o);
+                a.in_nchw = 1;
+                plan_stats(cx, o, L.c1, a);
+                TRY(run_conv(cx, L.c1, a));
                 break;
             }
             case L_RES:
@@ -680,19 +649,10 @@ int run_seq(Ctx &cx, const std::vector<Layer> &seq, Tensor4 x0, Tensor4 x1, cons
             case L_DOWN:
             case L_UP: {
                 const bool up = L.kind == L_UP;
-                o.C = h.C;
-                o.H = up ? h.H * 2 : (h.H - 1) / 2 + 1;
-                o.W = up ? h.W * 2 : (h.W - 1) / 2 + 1;
-                o.p = cx.ws.alloc((int64_t)B * o.H * o.W * o.C);
-                plan_stats(cx.u, cx.ws, o, L.c1, B, h.C, up ? 1 : 2, up ? 1 : 0);
-                {
-                    ConvLaunch a;
-                    a.src0 = h.p; a.C0 = h.C; a.B = B; a.Hin = h.H; a.Win = h.W; a.Hout = o.H; a.Wout = o.W;
-                    a.stride = up ? 1 : 2; a.ups = up ? 1 : 0;
-                    a.bias = u->params[L.c1.p_b].dev; a.out = o.p; a.stats_out = o.stats;
-                    if (cx.dry()) { if (up) reserve_ksplit(cx, L.c1, a); }
-                    else TRY(up ? run_conv3(cx, L.c1, a) : run_conv(u, L.c1, a, cx.st));
-                }
+                o = new_tensor(cx, h.C, up ? h.H * 2 : (h.H - 1) / 2 + 1, up ? h.W * 2 : (h.W - 1) / 2 + 1);
+                ConvLaunch a = conv_io(cx, L.c1, h, Tensor4(), o);
+                plan_stats(cx, o, L.c1, a);
+                TRY(up ? run_conv3(cx, L.c1, a) : run_conv(cx, L.c1, a));
                 break;
             }
         }
@@ -745,52 +705,50 @@ thread_local const dlpm_unet *tl_time_net = nullptr;
 thread_local const float *tl_time_table = nullptr;
 thread_local const int32_t *tl_time_index = nullptr;
 
-int walk(dlpm_unet *u, Ctx &cx, const float *x, const float *t, float *eps) {
-    const int B = cx.B, mc = u->cfg.model_channels, ted = u->ted;
-    // time embedding -> time MLP -> the per-ResBlock emb linears (unet.py:147-150, 336-338, 470).  In the sampling loop t is
-    // the same for the whole batch (GenerativeLevyProcess.py:319), so these run for one row instead of B identical ones
-    // (a row's dot products do not depend on how many rows the GEMM has: bit-identical to the batched form)
-    const int Bt = cx.uniform_t ? 1 : B;
-    float *e0 = cx.ws.alloc((int64_t)B * mc), *e1 = cx.ws.alloc((int64_t)B * ted), *e2 = cx.ws.alloc((int64_t)B * ted);
-    cx.embout = cx.ws.alloc((int64_t)B * u->emb_total);
-    if (!cx.dry() && u->num_classes > 0) {
+// The plan's scale/shift rows cx.embout: time embedding -> time MLP -> the per-ResBlock emb linears (unet.py:147-150, 336-338, 470).  In
+// the sampling loop t is the same for the whole batch (GenerativeLevyProcess.py:319), so these run for one row instead of B identical
+// ones (a row's dot products do not depend on how many rows the GEMM has: bit-identical to the batched form)
+int emb_rows(Ctx &cx, const float *t, float *e0, float *e1, float *e2) {
+    PLAN_ENQUEUES(cx);
+    dlpm_unet *u = cx.u;
+    const int B = cx.B, Bt = cx.uniform_t ? 1 : B;
+    const bool table = cx.uniform_t && tl_time_net == u && tl_time_table;
+    if (u->num_classes > 0) {
         // class-conditional: emb = time_embed(t) + label_emb(y) per sample (unet.py:470-473), then the emb linears over B rows.  The
         // time-MLP row comes from the bound [T][ted] table (the sampler's), from one row (uniform t) or from B rows; the rows a GEMM
         // produces do not depend on how many it has, so a sample's emb row has the same bits on all three paths
-        const float *src = e2;
-        const int32_t *row = nullptr;
-        int stride = cx.uniform_t ? 0 : 1;
-        if (cx.uniform_t && tl_time_net == u && tl_time_table) {
-            src = tl_time_table;
-            row = tl_time_index;
-        } else {
-            TRY(time_mlp(u, t, Bt, e0, e1, e2, cx.st));
-        }
-        TRY(launch_label_embedding_add(src, row, stride, u->params[u->p_label].dev, cx.y, u->num_classes, B, ted, e1, cx.st));
-        TRY(emb_linears(u, e1, B, cx.embout, cx.st));
-    } else if (!cx.dry()) {
-        if (cx.uniform_t && tl_time_net == u && tl_time_table) {
-            // the whole time path is a function of the step index alone: its output for every step was computed once
-            // (dlpm_unet_time_embeddings, same kernels, one row per step -- same bits) and the step reads its row
-            k_table_row<<<(unsigned)ceil_div(u->emb_total, 256), 256, 0, cx.st>>>(tl_time_table, tl_time_index, u->emb_total, cx.embout);
-            DLPM_LAUNCH_CHECK();
-        } else {
-            TRY(time_path(u, t, Bt, e0, e1, e2, cx.embout, cx.st));
-        }
+        if (!table) TRY(time_mlp(u, t, Bt, e0, e1, e2, cx.st));
+        TRY(launch_label_embedding_add(table ? tl_time_table : e2, table ? tl_time_index : nullptr, cx.uniform_t ? 0 : 1,
+                                       u->params[u->p_label].dev, cx.y, u->num_classes, B, u->ted, e1, cx.st));
+        return emb_linears(u, e1, B, cx.embout, cx.st);
     }
+    if (!table) return time_path(u, t, Bt, e0, e1, e2, cx.embout, cx.st);
+    // the whole time path is a function of the step index alone: its output for every step was computed once
+    // (dlpm_unet_time_embeddings, same kernels, one row per step -- same bits) and the step reads its row
+    k_table_row<<<(unsigned)ceil_div(u->emb_total, 256), 256, 0, cx.st>>>(tl_time_table, tl_time_index, u->emb_total, cx.embout);
+    DLPM_LAUNCH_CHECK();
+    return DLPM_OK;
+}
+
+int walk(dlpm_unet *u, Ctx &cx, const float *x, const float *t, float *eps) {
+    const int B = cx.B, mc = u->cfg.model_channels, ted = u->ted;
+    float *e0 = cx.ws.alloc((int64_t)B * mc), *e1 = cx.ws.alloc((int64_t)B * ted), *e2 = cx.ws.alloc((int64_t)B * ted);
+    cx.embout = cx.ws.alloc((int64_t)B * u->emb_total);
+    TRY(emb_rows(cx, t, e0, e1, e2));
     cx.ws.release(e0);
     cx.ws.release(e1);
     cx.ws.release(e2);
     u->feats.clear();
     std::vector<Tensor4> hs;
-    Tensor4 h;
+    Tensor4 h;     // the (B,C,H,W) input image first: the stem only reads it, and it is not the arena's to release
+    h.p = const_cast<float *>(x); h.C = u->cfg.in_channels; h.H = h.W = u->cfg.image_size;
     // every input-block output waits on the skip stack for its output block; the middle block's input is the last of them
     for (auto &seq : u->in_blocks) {
-        TRY(run_seq(cx, seq, h, Tensor4(), x, &h));
+        TRY(run_seq(cx, seq, h, Tensor4(), &h));
         hs.push_back(h);
         u->feats.push_back(h);
     }
-    TRY(run_seq(cx, u->mid, h, Tensor4(), nullptr, &h));
+    TRY(run_seq(cx, u->mid, h, Tensor4(), &h));
     u->feats.push_back(h);
     for (auto &seq : u->out_blocks) {
         Tensor4 skip = hs.back();
@@ -800,60 +758,69 @@ int walk(dlpm_unet *u, Ctx &cx, const float *x, const float *t, float *eps) {
                       skip.H, skip.W, h.H, h.W);
             return DLPM_ERR_ARG;
         }
-        TRY(run_seq(cx, seq, h, skip, nullptr, &h, true, true));   // last readers of the previous output and of the skip tensor
+        TRY(run_seq(cx, seq, h, skip, &h, true, true));   // last readers of the previous output and of the skip tensor
         u->feats.push_back(h);
     }
     float *cA = cx.ws.alloc((int64_t)B * h.C), *cB = cx.ws.alloc((int64_t)B * h.C);
+    Tensor4 e;     // eps, (B,C,H,W) in the caller's buffer
+    e.p = eps; e.C = u->head.cout; e.H = h.H; e.W = h.W;
+    ConvLaunch a = conv_io(cx, u->head, h, Tensor4(), e);
+    a.coefA = cA; a.coefB = cB; a.act_silu = 1; a.out_nchw = 1;
     // the head as a GEMM onto its 9 Cout tap channels + gather: the tap-channel tensor P lives in the arena
-    float *P = nullptr;
-    {
-        ConvLaunch a;
-        a.C0 = h.C; a.B = B; a.Hin = a.Hout = h.H; a.Win = a.Wout = h.W; a.ks = 3; a.Cout = u->head.cout; a.w_taps = u->head.w_taps; a.out_nchw = 1;
-        a.w_hfused = u->head.w_hfused; a.coefA = cA; a.coefB = cB; a.act_silu = 1;
-        if (!head_fused_ok(a) && head_gemm_ok(a)) P = cx.ws.alloc(head_gemm_scratch_floats(a));
-    }
-    if (!cx.dry()) {
-        TRY(gn_any(h, Tensor4(), B, h.C < 32 ? h.C : 32, u->params[u->p_head_gn_w].dev, u->params[u->p_head_gn_b].dev, nullptr,
-                   0, 0, cA, cB, cx.st));
-        ConvLaunch a;
-        a.src0 = h.p; a.C0 = h.C; a.B = B; a.Hin = a.Hout = h.H; a.Win = a.Wout = h.W;
-        a.bias = u->params[u->head.p_b].dev; a.coefA = cA; a.coefB = cB; a.act_silu = 1; a.out = eps; a.out_nchw = 1;
-        TRY(run_conv(u, u->head, a, cx.st, cx.hu, P));
-    }
+    float *P = (!head_fused_ok(a) && head_gemm_ok(a)) ? cx.ws.alloc(head_gemm_scratch_floats(a)) : nullptr;
+    TRY(gn_any(cx, h, Tensor4(), u->p_head_gn_w, u->p_head_gn_b, nullptr, 0, cA, cB));
+    TRY(run_conv(cx, u->head, a, cx.hu, P));
     if (!cx.ws.reuse) return DLPM_OK;
     for (auto &f : u->feats) f.p = nullptr;     // the arena has recycled them: dlpm_unet_get_feature needs dlpm_unet_keep_features
     return DLPM_OK;
 }
 
+// every layer in the order the plan runs them; fn(layer, cat): cat marks the first layer of an output block, whose input is [h | skip]
+template <class F>
+void for_each_layer(dlpm_unet *u, F fn) {
+    for (auto &s : u->in_blocks)
+        for (auto &L : s) fn(L, false);
+    for (auto &L : u->mid) fn(L, false);
+    for (auto &s : u->out_blocks)
+        for (size_t i = 0; i < s.size(); i++) fn(s[i], i == 0);
+}
+
+// ... and every convolution, the time MLP's and the head included
+template <class F>
+void for_each_conv(dlpm_unet *u, F fn) {
+    for_each_layer(u, [&](Layer &L, bool) {
+        fn(L.c1);
+        if (L.kind == L_RES || L.kind == L_ATTN) fn(L.c2);
+        if (L.kind == L_RES && L.has_skip) fn(L.skip);
+    });
+    fn(u->te0);
+    fn(u->te2);
+    fn(u->head);
+}
+
 int64_t count_flops(dlpm_unet *u) {
     // 2*MAC per sample: conv / linear / attention matmuls
     int64_t f = 0;
-    const int S = u->cfg.image_size;
     auto convf = [&](const ConvW &c, int H, int W) { f += 2LL * c.cout * c.cin * c.ks * c.ks * H * W; };
     convf(u->te0, 1, 1);
     convf(u->te2, 1, 1);
     f += 2LL * u->emb_total * u->ted;
-    int H = S;
-    auto seqf = [&](const std::vector<Layer> &seq) {
-        for (auto &L : seq) {
-            switch (L.kind) {
-                case L_STEM: convf(L.c1, H, H); break;
-                case L_RES:
-                    convf(L.c1, H, H); convf(L.c2, H, H);
-                    if (L.has_skip) convf(L.skip, H, H);
-                    break;
-                case L_ATTN:
-                    convf(L.c1, H, H); convf(L.c2, H, H);
-                    f += 4LL * (H * H) * (H * H) * L.cin;
-                    break;
-                case L_DOWN: H = (H - 1) / 2 + 1; convf(L.c1, H, H); break;
-                case L_UP: H *= 2; convf(L.c1, H, H); break;
-            }
+    int H = u->cfg.image_size;
+    for_each_layer(u, [&](const Layer &L, bool) {
+        switch (L.kind) {
+            case L_STEM: convf(L.c1, H, H); break;
+            case L_RES:
+                convf(L.c1, H, H); convf(L.c2, H, H);
+                if (L.has_skip) convf(L.skip, H, H);
+                break;
+            case L_ATTN:
+                convf(L.c1, H, H); convf(L.c2, H, H);
+                f += 4LL * (H * H) * (H * H) * L.cin;
+                break;
+            case L_DOWN: H = (H - 1) / 2 + 1; convf(L.c1, H, H); break;
+            case L_UP: H *= 2; convf(L.c1, H, H); break;
         }
-    };
-    for (auto &s : u->in_blocks) seqf(s);
-    seqf(u->mid);
-    for (auto &s : u->out_blocks) seqf(s);
+    });
     convf(u->head, H, H);
     return f;
 }
@@ -909,47 +876,16 @@ extern "C" int dlpm_unet_set_param(dlpm_unet *net, const char *key, const float 
     return DLPM_OK;
 }
 
-static void free_conv(ConvW &c) {
-    if (c.owns && c.w_dev) (void)hipFree(c.w_dev);
-    if (c.w_frag) (void)hipFree(c.w_frag);
-    c.w_frag = nullptr;
-    if (c.w_wino) (void)hipFree(c.w_wino);
-    c.w_wino = nullptr;
-    if (c.w_wino4) (void)hipFree(c.w_wino4);
-    c.w_wino4 = nullptr;
-    if (c.w_wino4_n64) (void)hipFree(c.w_wino4_n64);
-    if (c.w_wino4_n32) (void)hipFree(c.w_wino4_n32);
-    c.w_wino4_n64 = c.w_wino4_n32 = nullptr;
-    if (c.w_wino4sp) (void)hipFree(c.w_wino4sp);
-    c.w_wino4sp = nullptr;
-    if (c.w_small) (void)hipFree(c.w_small);
-    c.w_small = nullptr;
-    if (c.w_taps) (void)hipFree(c.w_taps);
-    c.w_taps = nullptr;
-    if (c.w_rs) (void)hipFree(c.w_rs);
-    c.w_rs = nullptr;
-    if (c.w_hfused) (void)hipFree(c.w_hfused);
-    c.w_hfused = nullptr;
-    if (c.w_split) (void)hipFree(c.w_split);
-    c.w_split = nullptr;
-    c.w_dev = nullptr;
-    c.owns = false;
+static void free_dev(float *&p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
 }
 
-static void for_each_conv(dlpm_unet *u, void (*fn)(ConvW &)) {
-    auto seq = [&](std::vector<Layer> &s) {
-        for (auto &L : s) {
-            fn(L.c1);
-            if (L.kind == L_RES || L.kind == L_ATTN) fn(L.c2);
-            if (L.kind == L_RES && L.has_skip) fn(L.skip);
-        }
-    };
-    for (auto &s : u->in_blocks) seq(s);
-    seq(u->mid);
-    for (auto &s : u->out_blocks) seq(s);
-    fn(u->te0);
-    fn(u->te2);
-    fn(u->head);
+static void free_conv(ConvW &c) {
+    if (!c.owns) c.w_dev = nullptr;      // (the parameter itself, or the stacked emb weights)
+    free_dev(c.w_dev);
+    for (auto layout : OWNED_LAYOUTS) free_dev(c.*layout);
+    c.owns = false;
 }
 
 // Round 6: under a small DECLARED batch (dlpm_unet_set_conv_policy's dispatch_batch) the 128-channel-multiple F(4x4) layers may run on 64- / 32-
@@ -959,33 +895,37 @@ constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
 static int narrow_wino4_copies(dlpm_unet *u) {
     const bool want = u->dispatch_B > 0 && u->dispatch_B <= NARROW_COPIES_MAX_BATCH;
     int rc = DLPM_OK;
-    auto one = [&](ConvW &c) {
-        if (rc != DLPM_OK || !c.w_wino4 || c.cout % 128 != 0) return;
-        if (!want) {
-            if (c.w_wino4_n64) (void)hipFree(c.w_wino4_n64);
-            if (c.w_wino4_n32) (void)hipFree(c.w_wino4_n32);
-            c.w_wino4_n64 = c.w_wino4_n32 = nullptr;
-            return;
+    for_each_conv(u, [&](ConvW &c) {
+        if (!c.w_wino4 || c.cout % 128 != 0) return;      // (the ResBlock and Upsample convolutions that carry F(4x4) weights)
+        for (auto &n : NARROW_LAYOUTS) {
+            float *&dst = c.*n.copy;
+            if (!want) free_dev(dst);
+            if (!want || dst || rc != DLPM_OK) continue;
+            if (hipMalloc(&dst, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)) != hipSuccess) { dst = nullptr; rc = DLPM_ERR_HIP; set_error("narrow_wino4_copies: hipMalloc failed"); continue; }
+            rc = relayout_weight_wino4(u->params[c.p_w].dev, dst, c.cout, c.cin, nullptr, n.nq);
         }
-        for (int nq : {64, 32}) {
-            float *&dst = nq == 64 ? c.w_wino4_n64 : c.w_wino4_n32;
-            if (dst) continue;
-            if (hipMalloc(&dst, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)) != hipSuccess) { dst = nullptr; rc = DLPM_ERR_HIP; set_error("narrow_wino4_copies: hipMalloc failed"); return; }
-            rc = relayout_weight_wino4(u->params[c.p_w].dev, dst, c.cout, c.cin, nullptr, nq);
-            if (rc != DLPM_OK) return;
-        }
-    };
-    auto seq = [&](std::vector<Layer> &s) {
-        for (auto &L : s) {
-            one(L.c1);
-            if (L.kind == L_RES) one(L.c2);
-        }
-    };
-    for (auto &s : u->in_blocks) seq(s);
-    seq(u->mid);
-    for (auto &s : u->out_blocks) seq(s);
+    });
     if (rc == DLPM_OK && hipDeviceSynchronize() != hipSuccess) { set_error("narrow_wino4_copies: synchronize failed"); rc = DLPM_ERR_HIP; }
     return rc;
+}
+
+// per-conv weight layouts of one layer; C0: channels of the first concat source (an output block's first layer), res: the image size
+// at the layer (as run_seq walks it)
+static int prep_layer(dlpm_unet *u, Layer &L, int C0, int &res) {
+    TRY(prep_conv(u, L.c1, C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0));
+    if (L.kind == L_DOWN) res = (res - 1) / 2 + 1;
+    if (L.kind == L_UP) res *= 2;
+    if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0));
+    if (L.kind == L_RES && L.has_skip) TRY(prep_conv(u, L.skip, C0, 0));
+    return DLPM_OK;
+}
+
+// fused emb GEMM: this ResBlock's emb_layers.1 rows into the stacked weights
+static int stack_emb(dlpm_unet *u, const Layer &L) {
+    DLPM_HIP(hipMemcpy(u->embcat_w + (size_t)L.emb_off * u->ted, u->params[L.p_emb_w].dev, (size_t)2 * L.cout * u->ted * sizeof(float),
+                       hipMemcpyDeviceToDevice));
+    DLPM_HIP(hipMemcpy(u->embcat_b + L.emb_off, u->params[L.p_emb_b].dev, (size_t)2 * L.cout * sizeof(float), hipMemcpyDeviceToDevice));
+    return DLPM_OK;
 }
 
 extern "C" int dlpm_unet_finalize(dlpm_unet *u) {
@@ -996,52 +936,20 @@ extern "C" int dlpm_unet_finalize(dlpm_unet *u) {
             return DLPM_ERR_STATE;
         }
     for_each_conv(u, free_conv);
-    // per-conv weight layouts; C0 matters only for the concat inputs of the output blocks
-    int res = u->cfg.image_size;     // image size at the layer being prepared (as run_seq walks it)
-    auto prep_seq = [&](std::vector<Layer> &s, int C0_first) -> int {
-        for (size_t i = 0; i < s.size(); i++) {
-            Layer &L = s[i];
-            const bool cat = (i == 0 && L.kind == L_RES && C0_first > 0);
-            const int C0 = cat ? C0_first : L.c1.cin;
-            TRY(prep_conv(u, L.c1, L.kind == L_STEM ? L.c1.cin : C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0));
-            if (L.kind == L_DOWN) res = (res - 1) / 2 + 1;
-            if (L.kind == L_UP) res *= 2;
-            if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0));
-            if (L.kind == L_RES && L.has_skip) TRY(prep_conv(u, L.skip, cat ? C0_first : L.skip.cin, 0));
-        }
-        return DLPM_OK;
-    };
-    for (auto &s : u->in_blocks) TRY(prep_seq(s, 0));
-    TRY(prep_seq(u->mid, 0));
-    {
-        // channels of h entering each output block = previous block's cout (or the middle's)
-        int ch = u->mid.back().cout;
-        for (auto &s : u->out_blocks) {
-            TRY(prep_seq(s, ch));
-            ch = s[0].cout;
-        }
-    }
-    TRY(prep_conv(u, u->te0, u->te0.cin, 3));   // 3: the time path stays on the fp32 pipe whatever its row count
-    TRY(prep_conv(u, u->te2, u->te2.cin, 3));
-    TRY(prep_conv(u, u->head, u->head.cin, 2));
-    // fused emb GEMM: rows of every emb_layers.1.weight stacked in ResBlock order
     if (u->embcat_w) (void)hipFree(u->embcat_w);
     if (u->embcat_b) (void)hipFree(u->embcat_b);
     DLPM_HIP(hipMalloc(&u->embcat_w, (size_t)u->emb_total * u->ted * sizeof(float)));
     DLPM_HIP(hipMalloc(&u->embcat_b, (size_t)u->emb_total * sizeof(float)));
-    auto cat_seq = [&](std::vector<Layer> &s) -> int {
-        for (auto &L : s)
-            if (L.kind == L_RES) {
-                DLPM_HIP(hipMemcpy(u->embcat_w + (size_t)L.emb_off * u->ted, u->params[L.p_emb_w].dev,
-                                   (size_t)2 * L.cout * u->ted * sizeof(float), hipMemcpyDeviceToDevice));
-                DLPM_HIP(hipMemcpy(u->embcat_b + L.emb_off, u->params[L.p_emb_b].dev, (size_t)2 * L.cout * sizeof(float),
-                                   hipMemcpyDeviceToDevice));
-            }
-        return DLPM_OK;
-    };
-    for (auto &s : u->in_blocks) TRY(cat_seq(s));
-    TRY(cat_seq(u->mid));
-    for (auto &s : u->out_blocks) TRY(cat_seq(s));
+    int rc = DLPM_OK, res = u->cfg.image_size, ch = 0;      // ch: channels of h entering the layer = the previous layer's cout
+    for_each_layer(u, [&](Layer &L, bool cat) {
+        if (rc == DLPM_OK) rc = prep_layer(u, L, cat ? ch : L.c1.cin, res);
+        if (rc == DLPM_OK && L.kind == L_RES) rc = stack_emb(u, L);
+        ch = L.cout;
+    });
+    TRY(rc);
+    TRY(prep_conv(u, u->te0, u->te0.cin, 3));   // 3: the time path stays on the fp32 pipe whatever its row count
+    TRY(prep_conv(u, u->te2, u->te2.cin, 3));
+    TRY(prep_conv(u, u->head, u->head.cin, 2));
     u->embcat.cout = u->emb_total; u->embcat.cin = u->ted; u->embcat.ks = 1;
     {
         ConvLaunch probe;
@@ -1217,14 +1125,21 @@ extern "C" int dlpm_unet_forward_uniform_t_labels(dlpm_unet *net, const float *x
     return unet_forward(net, x_dev, t_dev, eps_dev, B, workspace_dev, workspace_bytes, stream, true, y_dev);
 }
 
+// the reverse update as the head convolution's epilogue carries it
+static HeadUpdate head_update_of(const dlpm_update_args *upd) {
+    HeadUpdate hu;
+    hu.x = upd->x_dev; hu.z = upd->z_dev; hu.t = upd->t_dev; hu.g = upd->g_dev; hu.c_eps = upd->c_eps_dev; hu.c_noise = upd->c_noise_dev;
+    hu.key = upd->key_dev; hu.seed = upd->seed; hu.sample_offset = upd->sample_offset; hu.hist_pp = upd->hist_pp;
+    hu.T = upd->T; hu.B = upd->B;
+    return hu;
+}
+
 // Whether this net's head convolution runs on the kernel that can carry the update (a property of the architecture).
 static bool head_fusable(const dlpm_unet *u) {
     ConvLaunch L;
     const int H = u->cfg.image_size;
-    L.C0 = u->head.cin; L.Hin = L.Hout = H; L.Win = L.Wout = H; L.ks = 3; L.Cout = u->head.cout; L.out_nchw = 1;
-    L.w_small = u->head.w_small;
-    L.w_taps = u->head.w_taps;
-    L.w_hfused = u->head.w_hfused;
+    attach_conv(u, u->head, L);
+    L.C0 = u->head.cin; L.Hin = L.Hout = H; L.Win = L.Wout = H; L.out_nchw = 1;
     L.coefA = L.coefB = reinterpret_cast<const float *>(u);   // (the head always carries its GroupNorm: only non-null matters here)
     L.act_silu = 1;
     return head_fused_ok(L) || head_gemm_ok(L) || head_conv_ok(L);
@@ -1258,10 +1173,7 @@ int dlpm::unet_forward_update_labels(dlpm_unet *net, const float *x_in_dev, cons
         a.eps_dev = eps_scratch_dev;
         return dlpm_update_f32(&a, stream);
     }
-    HeadUpdate hu;
-    hu.x = upd->x_dev; hu.z = upd->z_dev; hu.t = upd->t_dev; hu.g = upd->g_dev; hu.c_eps = upd->c_eps_dev; hu.c_noise = upd->c_noise_dev;
-    hu.key = upd->key_dev; hu.seed = upd->seed; hu.sample_offset = upd->sample_offset; hu.hist_pp = upd->hist_pp;
-    hu.T = upd->T; hu.B = B;
+    const HeadUpdate hu = head_update_of(upd);     // (upd->B == B, checked above)
     float dummy;   // walk() wants a non-null eps pointer; the fused head never writes it
     int r = unet_forward(net, x_in_dev, t_dev, eps_scratch_dev ? eps_scratch_dev : &dummy, B, workspace_dev, workspace_bytes, stream, true,
                          y_dev, &hu);
@@ -1292,10 +1204,7 @@ int dlpm::unet_forward_update_rows(dlpm_unet *net, const float *x_in_dev, const 
         set_error("unet_forward_update_rows: only the plain update fused into the head convolution runs on a row range");
         return DLPM_ERR_UNSUPPORTED;
     }
-    HeadUpdate hu;
-    hu.x = upd->x_dev; hu.z = upd->z_dev; hu.t = upd->t_dev; hu.g = upd->g_dev; hu.c_eps = upd->c_eps_dev; hu.c_noise = upd->c_noise_dev;
-    hu.key = upd->key_dev; hu.seed = upd->seed; hu.sample_offset = upd->sample_offset;
-    hu.T = upd->T; hu.B = upd->B;
+    const HeadUpdate hu = head_update_of(upd);     // (no history row: refused above)
     float dummy;   // walk() wants a non-null eps pointer; the fused head never writes it
     return unet_forward(net, x_in_dev, t_dev, &dummy, Bc, workspace_dev, workspace_bytes, stream, true, nullptr, &hu);
 }
@@ -1596,6 +1505,9 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
     const int Cin = a->C0 + a->C1;
     DLPM_CHECK_ARG(Cin >= 32 && Cin <= 128 && Cin % 8 == 0 && a->C0 % 8 == 0, "dlpm_resblock_img_f32: %d + %d input channels", a->C0, a->C1);
     DLPM_CHECK_ARG((Cin == CO) == (a->skip_w == nullptr) && (!a->skip_w || a->skip_b), "dlpm_resblock_img_f32: skip_w / skip_b (required unless C0 + C1 = the output channels)");
+    DLPM_CHECK_ARG(res_img_residual_ok(a->skip_w != nullptr, a->C1),
+                   "dlpm_resblock_img_f32: a concat input (C1 = %d) needs the skip weights skip_w / skip_b: without them the residual is x0 alone, %d of the %d channels per pixel",
+                   a->C1, a->C0, CO);
     DLPM_CHECK_ARG(scratch_floats >= dlpm_resblock_img_scratch_floats(a->B, Cin), "dlpm_resblock_img_f32: scratch of %lld floats, need %lld",
                    (long long)scratch_floats, (long long)dlpm_resblock_img_scratch_floats(a->B, Cin));
     hipStream_t st = as_stream(stream);
@@ -1623,7 +1535,12 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
         r.res = a->x0;
     }
     if (!res_img_ok(r)) {
-        set_error("dlpm_resblock_img_f32: the whole-image ResBlock kernel is switched off (DLPM_RES_IMG=0 / DLPM_WINO_F4=0)");
+        ResImgLaunch plain = r;      // 64 input channels from one source: refused only when the kernel is switched off
+        plain.C0 = 64; plain.C1 = 0;
+        if (!res_img_ok(plain))
+            set_error("dlpm_resblock_img_f32: the whole-image ResBlock kernel is switched off (DLPM_RES_IMG=0 / DLPM_RES_IMG16=0 / DLPM_WINO_F4=0)");
+        else
+            set_error("dlpm_resblock_img_f32: the whole-image ResBlock kernel does not take %d + %d input channels on %d x %d images", a->C0, a->C1, a->H, a->W);
         return DLPM_ERR_UNSUPPORTED;
     }
     return launch_resblock_img(r, st);

@@ -146,6 +146,40 @@ def test_unet_uniform_t_forward_is_bit_identical(name):
     assert np.abs(got[:nb].cpu().numpy() - f['y_same_t']).max() < 1e-4
 
 
+@pytest.mark.parametrize('name,size,B,declared', [
+    ('tiny2', 16, 5, None),     # the fused small-image ResBlocks and attention blocks
+    ('mnist', 32, 2, None),     # the whole-image ResBlocks at 32x32 and 16x16
+    ('wide', 16, 2, 2),         # a declared batch of 2: narrow n-tiles, split-K partial buffers, the general path
+])
+def test_unet_forward_stays_inside_the_planned_workspace(name, size, B, declared):
+    """The sized plan is the launched plan: dlpm_unet_workspace_bytes is a dry run of the very walk that launches, so a forward handed
+    exactly `need` bytes leaves a guard region behind them untouched and gives the bits of net(x, t); 256 bytes (one arena granule)
+    less is refused with the no-memory status before anything runs."""
+    import ctypes as C
+    from dlpm_amd import _lib
+    net, _ = build_unet(name)
+    if declared:
+        net.set_conv_policy('auto', declared)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, UNETS[name]['in_ch'], size, size, generator=g).to(DEV)
+    t = torch.rand(B, generator=g).to(DEV)
+    want = net(x, t)
+    L, h = _lib.lib(), net.native_handle(size)
+    need = L.dlpm_unet_workspace_bytes(h, B)
+    assert need > 0 and need % 256 == 0
+    guard = 1 << 20
+    buf = torch.empty(need + guard, dtype=torch.uint8, device=DEV)
+    buf[need:] = 0xA5
+    got = torch.full_like(want, float('nan'))
+    _lib.check(L.dlpm_unet_forward(h, x.data_ptr(), t.data_ptr(), got.data_ptr(), B, buf.data_ptr(), need, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    assert bool((buf[need:] == 0xA5).all())
+    assert torch.equal(got, want)
+    rc = L.dlpm_unet_forward(h, x.data_ptr(), t.data_ptr(), got.data_ptr(), B, buf.data_ptr(), need - 256, _lib.stream_ptr())
+    assert rc == -5, rc                                            # DLPM_ERR_NOMEM
+    assert torch.equal(got, want)                                  # ... and nothing was enqueued
+
+
 def test_unet_zero_init_outputs_zero_and_state_dict_roundtrip():
     """Reference default init (zero_module) gives eps == 0 exactly; load_state_dict re-uploads."""
     torch.manual_seed(0)

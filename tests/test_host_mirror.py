@@ -269,6 +269,23 @@ def test_activation_arena_recycles_buffers():
         L.dlpm_unet_destroy(h)
 
 
+def test_whole_image_resblock_refuses_a_concat_without_skip_weights():
+    """dlpm_resblock_img_f32 with C0 + C1 = the output channels, C1 != 0 and no skip_w would take x0 -- C0 channels per pixel -- as
+    the residual and read it with the pitch of the output channels (round-6 advisor finding; the UNet plan guards the same
+    condition).  Refused on its arguments, before any device work: the pointers below are never dereferenced."""
+    L = _lib.lib()
+    dummy = 4096
+    a = _lib.ResBlockArgs()
+    a.x0, a.x1, a.C0, a.C1, a.B, a.H, a.W = dummy, dummy, 16, 16, 2, 32, 32
+    a.gn1_w = a.gn1_b = a.conv1_w = a.conv1_b = a.ss = a.gn2_w = a.gn2_b = a.conv2_w = a.conv2_b = a.out = dummy
+    a.skip_w = a.skip_b = None
+    n = L.dlpm_resblock_img_scratch_floats(2, 32)
+    assert n > 0
+    rc = L.dlpm_resblock_img_f32(C.byref(a), dummy, n, None)
+    assert rc == -1, rc                                            # DLPM_ERR_ARG
+    assert 'skip_w' in L.dlpm_last_error().decode()
+
+
 def test_split_epilogue_ragged_tile_addresses_stay_inside_the_tensor():
     """conv_split.hip, split_store_from_registers<MASKED>: on a ragged last tile (B * HW not a multiple of 128) every lane's
     residual READ and output WRITE must land on a row below M, also for lanes whose first row already lies beyond it (round-2
