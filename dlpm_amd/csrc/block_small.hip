@@ -807,8 +807,7 @@ size_t res_small_lds_bytes(int HS, int Cin) {
 }  // namespace
 
 bool small_blocks_enabled() {   // DLPM_NO_FUSED_BLOCKS=1: every block through the tiled per-layer kernels (A/B runs)
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_FUSED_BLOCKS"); off = (e && e[0] == '1') ? 1 : 0; }
+    static const int off = env_switch("DLPM_NO_FUSED_BLOCKS", 0, true);
     return !off;
 }
 
@@ -841,8 +840,7 @@ bool attn_small_ok(const AttnSmallLaunch &a) {
 // 16x16 images, round 6: the whole block in one launch, one head at a time (k_attnblock16).  DLPM_ATTN16=0 (A/B runs) restores round 4's
 // GroupNorm + qkv launch followed by attention.hip's kernel and the proj GEMM.
 bool attn16_ok(const AttnSmallLaunch &a) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("DLPM_ATTN16"); on = e ? atoi(e) : 1; }
+    static const int on = env_switch("DLPM_ATTN16", 1);
     return on && small_blocks_enabled() && a.wqkv && a.wproj && a.C == AB_C && a.heads == AB_HEADS && a.H == 16 && a.W == 16;
 }
 

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/dlpm_amd.h"
@@ -35,6 +36,13 @@ inline hipStream_t as_stream(dlpm_stream_t s) { return reinterpret_cast<hipStrea
 #define DLPM_LAUNCH_CHECK() DLPM_HIP(hipGetLastError())
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// An environment switch: `dflt` when unset; when set its atoi, or for an on/off `flag` 1 exactly when the value begins with '1'.
+// Every use keeps the result in a function-local static (static const int v = env_switch(...)): the environment is read once per process.
+inline int env_switch(const char *name, int dflt, bool flag = false) {
+    const char *e = getenv(name);
+    return !e ? dflt : flag ? e[0] == '1' : atoi(e);
+}
 
 #ifdef __HIPCC__   // device code: host.cpp and png.cpp are also built by a plain C++ compiler (tests/test_host_sanitizers.py)
 // fixed-order sum of one fp64 partial per thread of a THREADS-wide workgroup (sh: THREADS doubles of LDS): the same tree whatever

@@ -19,7 +19,7 @@ struct ConvLaunch {
     const float *w_wino4_n64 = nullptr, *w_wino4_n32 = nullptr;   // optional, Cout % 128 == 0 only: the same weights in the fragment order of 64- / 32-channel
                                    // n-tiles (round 6: at a small DECLARED batch the narrow shapes give 2-4x as many workgroups; same bits)
     const float *w_wino4sp = nullptr; // optional, ups launches with Cout % 128 == 0 only: the four parity classes' F(4x4,2x2) weights
-                                   // (conv_wino4.hip: k_conv3x3_wino4sp); taken where wino4sp_preferred says so
+                                   // (conv_wino4.hip: k_conv3x3_wino4sp); taken where wino4_route says so
     const void *w_split = nullptr; // optional: the weights as three bf16 planes in stage-tile order (conv_split.hip); a 3x3 launch
                                    // that carries it is a stride-2 downsampling convolution, or a test forcing the path
     const float *w_small = nullptr;// optional, 3x3 with Cout <= 4 (the head): [tap][Cin][4] for k_conv3x3_head
@@ -40,14 +40,14 @@ struct ConvLaunch {
     int gen = 0;
     int64_t dispatch_B = 0;
     int gemm = 0;                   // DLPM_GEMM_AUTO / _F32 / _BF16X3: which matrix pipe the 1x1 and downsampling convolutions take (conv_split.hip)
-    // Round 6, split-K (conv_ksplit_for): > 1 = the launch runs `ksplit` copies of its grid, copy s walking the input channels
+    // Round 6, split-K (ConvRoute::ksplit): > 1 = the launch runs `ksplit` copies of its grid, copy s walking the input channels
     // [s Cin / ksplit, (s + 1) Cin / ksplit) and writing its partial outputs to out + s B Hout Wout Cout (bias / residual / statistics
     // are null in such a launch: launch_splitk_reduce adds them).  Taken by the narrow F(4x4) shapes and the F(2x2) kernel only.
     int ksplit = 0;
     // Optional fused GroupNorm statistics of the OUTPUT: per (image, pixel tile, channel) the
     // pair (mean, centred sum of squares) over the tile's pixels, written by the MFMA kernels'
     // epilogue when the tile lies inside one image.  [B][HW/tile][Cout] float2 with tile =
-    // conv_stats_pixels(launch): 128 for the implicit-GEMM kernels, 256 for the Winograd kernel
+    // conv_route(launch).stats_px: 128 for the implicit-GEMM kernels, 256 for the Winograd kernel
     // (the sub-pixel kernel: one partial per block AND parity class, [B][HW/256][Cout] in (block, class) order, or [B][4 classes][Cout]).
     float2 *stats_out = nullptr;
 #ifdef DLPM_PHASE_TIMING
@@ -55,9 +55,33 @@ struct ConvLaunch {
 #endif
 };
 
-// true when the MFMA implicit-GEMM kernel covers this shape
+// true when the MFMA implicit-GEMM kernel covers this shape (prep_conv chooses the weight layout by it)
 bool igemm_supported(const ConvLaunch &c);
-int launch_conv_igemm(const ConvLaunch &c, hipStream_t st);
+
+// The ONE routing decision of a convolution launch: which kernel family runs it, on what block geometry, and what follows from
+// that for the plan (statistics tile, split-K factor, head scratch).  conv_route computes it, launch_conv launches it, the UNet plan
+// and dlpm_conv2d_f32 read it -- nobody re-derives a part of it.  Two invariants:
+//  * the route is a function of the LAYER and the declared policy (gen, dispatch_B, gemm), never of the batch the launch happens to carry:
+//    the generations round differently, and a sample must not depend on how its batch was sharded or chunked;
+//  * the single exception is the F(2x2) small-launch shape (conv_wino.hip: wino_small_launch), bit-identical either way.
+// Order of the cascade: the head kernels; bf16x3 split; sub-pixel F(4x4); F(4x4) (both also where igemm_supported is false: their input
+// channels come in multiples of 8); then, where igemm_supported: F(2x2), the implicit-GEMM kernels; otherwise the stem or the direct kernel.
+enum ConvFamily { CONV_HEAD_FUSED, CONV_HEAD_GEMM, CONV_HEAD, CONV_SPLIT, CONV_WINO4SP, CONV_WINO4, CONV_WINO, CONV_IGEMM, CONV_STEM, CONV_DIRECT };
+struct ConvRoute {
+    ConvFamily family = CONV_DIRECT;
+    int bh = 0, bw = 0, nimg = 0;   // Winograd families: tiles per block (rows, columns), images per block
+    int nq = 0;                     // Winograd families: n-tile width in channels
+    int64_t grid = 0;               // Winograd families under a declared batch: workgroups at dispatch_B (what AUTO and split-K weigh)
+    int stats_px = 0;               // pixels behind one stats_out partial (0: the kernel that will run cannot emit statistics)
+    int ksplit = 1;                 // split-K factor (1: none), see ConvLaunch::ksplit
+    int64_t scratch_floats = 0;     // CONV_HEAD_GEMM: the tap-channel tensor launch_conv wants as head_scratch
+    char name[96] = "";             // profiler class of the MFMA families (the VALU launchers -- heads, stem, direct -- name their own scope)
+    bool head() const { return family <= CONV_HEAD; }
+};
+ConvRoute conv_route(const ConvLaunch &c);
+struct HeadUpdate;
+// computes the route and launches it; hu: the sampler's update in the head's epilogue (head families only); head_scratch: see scratch_floats
+int launch_conv(const ConvLaunch &c, const HeadUpdate *hu, float *head_scratch, hipStream_t st);
 int launch_conv_direct(const ConvLaunch &c, hipStream_t st);
 int launch_conv_stem(const ConvLaunch &c, hipStream_t st);
 // head convolution (Cout <= 4) as a VALU kernel (conv_direct.hip), optionally with the sampler's reverse update fused into
@@ -90,25 +114,21 @@ bool head_fused_ok(const ConvLaunch &c);
 int64_t head_fused_weight_floats(int Cin);
 int relayout_weight_head_fused(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 int launch_conv_head_fused(const ConvLaunch &c, const HeadUpdate *hu, hipStream_t st);
-// Winograd F(2x2,3x3) path (conv_wino.hip)
-bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg);
-int wino_tiles(const ConvLaunch &c);   // 2x2 output tiles per workgroup (64 or 32)
-int launch_conv_wino(const ConvLaunch &c, hipStream_t st);
+// Winograd F(2x2,3x3) path (conv_wino.hip); wino_route: geometry -> r (family CONV_WINO), false where the kernel does not take the launch
+bool wino_route(const ConvLaunch &c, ConvRoute *r);
+int launch_conv_wino(const ConvLaunch &c, const ConvRoute &r, hipStream_t st);
 int64_t wino_weight_floats(int Cout, int Cin);
 int relayout_weight_wino(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 // Winograd F(4x4,3x3) path (conv_wino4.hip): 16 tiles of 4x4 outputs x 128 channels per workgroup
 bool wino4_enabled();                  // DLPM_WINO_F4
-bool wino4_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg);
-bool wino4_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg);   // geometry + dispatch policy
-int launch_conv_wino4(const ConvLaunch &c, hipStream_t st);
+bool wino4_route(const ConvLaunch &c, ConvRoute *r);   // geometry + dispatch policy -> r (family CONV_WINO4 or CONV_WINO4SP), false where neither takes the launch
+int launch_conv_wino4(const ConvLaunch &c, const ConvRoute &r, hipStream_t st);
 int64_t wino4_weight_floats(int Cout, int Cin);
 int relayout_weight_wino4(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st, int nq = 0);   // nq: n-tile width (0: the layer's own)
 // the nearest-x2 Upsample convolutions as four parity-class F(4x4,2x2) convolutions on the low-res image (conv_wino4.hip: k_conv3x3_wino4sp)
 bool wino4sp_enabled();                // DLPM_WINO4_SUBPIX
 bool wino4sp_layer_ok(int Cout, int Cin, int Hlo, int Wlo);               // worth building the weights for
-bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg);
-bool wino4sp_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg); // geometry + dispatch policy (generations AUTO / F4, 128-channel n-tile)
-int launch_conv_wino4sp(const ConvLaunch &c, hipStream_t st);
+int launch_conv_wino4sp(const ConvLaunch &c, const ConvRoute &r, hipStream_t st);
 int64_t wino4sp_weight_floats(int Cout, int Cin);
 int relayout_weight_wino4sp(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
 // A WHOLE ResBlock with 32 output channels on 32x32 images in one launch (round 6, conv_wino4.hip: k_resblock_wino4_img): GroupNorm-1
@@ -146,27 +166,9 @@ bool conv_split_ok(const ConvLaunch &c);
 int launch_conv_split(const ConvLaunch &c, hipStream_t st);
 int64_t split_weight_floats(int Cout, int Cin, int taps);
 int relayout_weight_split(const float *oihw_dev, void *dst_dev, int Cout, int Cin, int taps, hipStream_t st);
-// pixels behind one stats_out partial for this launch (0: the launch cannot emit statistics)
-int conv_stats_pixels(const ConvLaunch &c);
-// Split-K factor of a 3x3 stride-1 launch under the AUTO policy with a DECLARED batch (1: none): when the kernel this layer takes would
-// put workgroups on at most half of the 256 CUs at that batch (8x8 / 4x4 levels at batch <= 128), its K loop -- 32-64 serial phases --
-// is cut over 2 / 4 / 8 grid copies.  A function of the layer and the declaration only.  DLPM_KSPLIT=0 switches it off.
-int conv_ksplit_for(const ConvLaunch &c);
-int wino4_launch_nq(const ConvLaunch &c);      // the n-tile width launch_conv_wino4 would use
-int64_t wino_grid_at(const ConvLaunch &c, int64_t B);   // workgroups of the F(2x2) kernel at batch B
 // out = bias + sum_s part[s] (+ residual [res0 | res1]) over n = B Hout Wout pixels x Cout channels, partials summed in ascending s
 int launch_splitk_reduce(const float *part, int S, int64_t npix, int Cout, const float *bias, const float *res0, const float *res1, int R0,
                          float *out, hipStream_t st);
-// non-MFMA shapes: the stem kernel when it applies, the generic direct kernel otherwise
-inline bool conv_takes_stem(const ConvLaunch &L) {   // NCHW in, 3x3 s1, Cout % 4 == 0, direct weight layout
-    return L.in_nchw && !L.out_nchw && L.ks == 3 && L.stride == 1 && !L.ups && L.C1 == 0 && L.Cout % 4 == 0 && !L.coefA &&
-           !L.act_silu && !L.res0 && L.bias;
-}
-inline int launch_conv_fallback(const ConvLaunch &L, hipStream_t st) {
-    if (conv_takes_stem(L)) return launch_conv_stem(L, st);
-    return launch_conv_direct(L, st);
-}
-
 // weight re-layout kernels: OIHW -> [tap][Cout][Cin] (igemm) or [tap][Cin][Cout] (direct)
 int relayout_weight(const float *oihw_dev, float *dst_dev, int Cout, int Cin, int ks, bool for_igemm, hipStream_t st);
 // OIHW 3x3 -> fragment order for k_conv3x3_halo_ws; dst holds frag_weight_floats(Cout, Cin) floats

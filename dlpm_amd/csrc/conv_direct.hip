@@ -368,8 +368,7 @@ namespace dlpm {
 static int head_rows(const ConvLaunch &c) { return std::min(c.Hout, 512 / c.Wout); }   // rows of a workgroup's tile (<= 512 pixels)
 
 bool head_conv_ok(const ConvLaunch &c) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_HEADK"); off = (e && e[0] == '1') ? 1 : 0; }
+    static const int off = env_switch("DLPM_NO_HEADK", 0, true);
     if (off || !c.w_small || c.ks != 3 || c.stride != 1 || c.ups || c.in_nchw || c.C1 != 0 || c.res0) return false;
     if (c.Cout < 1 || c.Cout > 4 || c.C0 % 16 != 0 || c.Hin != c.Hout || c.Win != c.Wout) return false;
     const int W = c.Wout, H = c.Hout;
@@ -410,8 +409,7 @@ static int head_gather_rows(const ConvLaunch &c) {   // rows of a gather workgro
 }
 
 bool head_gemm_ok(const ConvLaunch &c) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_HEAD_GEMM"); off = (e && e[0] == '1') ? 1 : 0; }
+    static const int off = env_switch("DLPM_NO_HEAD_GEMM", 0, true);
     if (off || !c.w_taps || c.ks != 3 || c.stride != 1 || c.ups || c.in_nchw || c.C1 != 0 || c.res0) return false;
     if (c.Cout < 1 || c.Cout > 3 || c.C0 % 32 != 0 || c.Hin != c.Hout || c.Win != c.Wout) return false;
     const int W = c.Wout, H = c.Hout;
@@ -428,7 +426,7 @@ int launch_conv_head_gemm(const ConvLaunch &c, const HeadUpdate *hu, float *P, h
     ConvLaunch g = c;
     g.ks = 1; g.w = c.w_taps; g.w_frag = nullptr; g.w_wino = nullptr; g.w_wino4 = nullptr; g.w_small = nullptr; g.w_split = nullptr;
     g.w_taps = nullptr; g.bias = nullptr; g.out = P; g.out_nchw = 0; g.Cout = Np; g.stats_out = nullptr; g.gemm = DLPM_GEMM_F32;
-    int r = launch_conv_igemm(g, st);
+    int r = launch_conv(g, nullptr, nullptr, st);   // (a 1x1 launch with none of the special layouts: the implicit GEMM)
     if (r != DLPM_OK) return r;
     const int W = c.Wout, H = c.Hout, TH = head_gather_rows(c);
     const int64_t M = (int64_t)c.B * H * W;

@@ -1016,14 +1016,12 @@ bool igemm_supported(const ConvLaunch &c) {
 }
 
 static bool ws_disabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_NO_WS"); v = (e && e[0] == '1') ? 1 : 0; }
+    static const int v = env_switch("DLPM_NO_WS", 0, true);
     return v == 1;
 }
 
 static bool halo_ok(const ConvLaunch &c, int *th, int *nimg) {
-    static int disabled = -1;
-    if (disabled < 0) { const char *e = getenv("DLPM_NO_HALO"); disabled = (e && e[0] == '1') ? 1 : 0; }
+    static const int disabled = env_switch("DLPM_NO_HALO", 0, true);
     if (disabled || c.ks != 3 || c.stride != 1) return false;
     if (c.ups && (!c.w_frag || ws_disabled() || (c.Wout & 1) || (c.Hout & 1))) return false;   // upsample: weight-streaming kernel only
     const int W = c.Wout, HW = c.Hout * c.Wout;
@@ -1095,8 +1093,7 @@ int launch_conv_stem(const ConvLaunch &c, hipStream_t st) {
         return DLPM_ERR_UNSUPPORTED;
     }
     // whole rows of one image per block, W a power of two: the input patch goes through LDS (k_conv_stem_lds)
-    static int nolds = -1;
-    if (nolds < 0) { const char *e = getenv("DLPM_NO_STEM_LDS"); nolds = (e && e[0] == '1') ? 1 : 0; }
+    static const int nolds = env_switch("DLPM_NO_STEM_LDS", 0, true);
     const int W = c.Wout;
     const bool lds_ok = !nolds && regw && c.Hin == c.Hout && c.Win == c.Wout && (W & (W - 1)) == 0 && W >= 4 && W <= 64 && ppb % W == 0 &&
                         ((int64_t)c.Hout * W) % ppb == 0 && c.bias;
@@ -1117,80 +1114,112 @@ int launch_conv_stem(const ConvLaunch &c, hipStream_t st) {
     return DLPM_OK;
 }
 
-int conv_stats_pixels(const ConvLaunch &c) {
-    int a, b, n;
-    if (conv_ksplit_for(c) > 1) return 0;      // a split-K launch emits partial outputs: no statistics (the consumer's GroupNorm reads the tensor)
-    if (c.in_nchw) return stem_stats_ok(c) ? 1024 : 0;
-    // same order as launch_conv_igemm's dispatch: a launch that carries split weights runs k_conv_split whatever else it carries
-    // (k_conv_split: per 128-pixel tile through the 4-wave row epilogue, or per whole 8x8 image from the registers of the 8-wave shape)
-    if (conv_split_ok(c)) {
-        const int64_t hw = (int64_t)c.Hout * c.Wout;
-        return (c.R0 & 3) ? 0 : hw % BM == 0 ? BM : hw == 64 ? 64 : 0;
-    }
-    if (wino4sp_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4) ? 64 : 0;   // per (block | image, parity class)
-    if (wino4_preferred(c, &a, &b, &n)) return n == 1 ? 256 : (n == 4 && a * b == 4) ? 64 : 0;   // (four whole 8x8 images per block: one partial per image)
-    if (wino_geometry(c, &a, &b, &n)) return n == 1 ? 4 * wino_tiles(c) : 0;
-    if (c.out_nchw || (c.Cout & 3) || (c.R0 & 3)) return 0;
-    return ((int64_t)c.Hout * c.Wout) % BM == 0 ? BM : 0;
+// non-MFMA shapes take the stem kernel when it applies (NCHW in, 3x3 s1, Cout % 4 == 0, direct weight layout), the generic direct kernel otherwise
+static bool conv_takes_stem(const ConvLaunch &L) {
+    return L.in_nchw && !L.out_nchw && L.ks == 3 && L.stride == 1 && !L.ups && L.C1 == 0 && L.Cout % 4 == 0 && !L.coefA &&
+           !L.act_silu && !L.res0 && L.bias;
 }
 
-int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
+// Split-K factor of a Winograd launch under the AUTO policy with a DECLARED batch (1: none): when the kernel this layer takes would put
+// `grid` workgroups on at most half of the 256 CUs at that batch (8x8 / 4x4 levels at batch <= 128), its K loop -- 32-64 serial phases --
+// is cut over 2 / 4 / 8 grid copies.  A function of the layer and the declaration only.  DLPM_KSPLIT=0 switches it off.
+static int ksplit_for(const ConvLaunch &c, int64_t grid) {
+    static const int on = env_switch("DLPM_KSPLIT", 1);
+    if (!on || c.gen != DLPM_CONV_AUTO || c.dispatch_B <= 0 || grid <= 0) return 1;
+    const int nchunks = (c.C0 + c.C1) / 8;
+    int S = 1;
+    while (S < 8 && grid * S * 2 <= 256 && nchunks % (S * 2) == 0 && nchunks / (S * 2) >= 4) S *= 2;
+    return S;
+}
+
+ConvRoute conv_route(const ConvLaunch &c) {
+    ConvRoute r;
+    const int64_t hw = (int64_t)c.Hout * c.Wout;
+    int th, nimg;
+    const char *cls = nullptr;      // profiler class
+    if (head_fused_ok(c)) {
+        r.family = CONV_HEAD_FUSED;
+    } else if (head_gemm_ok(c)) {
+        r.family = CONV_HEAD_GEMM;
+        r.scratch_floats = head_gemm_scratch_floats(c);
+    } else if (head_conv_ok(c)) {
+        r.family = CONV_HEAD;
+    } else if (conv_split_ok(c)) {   // a launch that carries split weights runs k_conv_split whatever else it carries
+        r.family = CONV_SPLIT;
+        cls = c.ks == 1 ? "conv1x1_bf16x3" : "conv3x3_bf16x3";
+        // per 128-pixel tile through the 4-wave row epilogue, or per whole 8x8 image from the registers of the 8-wave shape
+        r.stats_px = (c.R0 & 3) ? 0 : hw % BM == 0 ? BM : hw == 64 ? 64 : 0;
+    } else if (wino4_route(c, &r)) {
+        cls = r.family == CONV_WINO4SP ? "conv3x3_wino4sp" : "conv3x3_wino4";   // (a class of its own: 100 multiplies per 64 outputs, conv3x3_wino4 144)
+        // the 8-wave, sub-pixel and whole-image shapes carry no split
+        if (r.family == CONV_WINO4 && r.nq != 128 && !(c.Cout == 32 && c.Hout == 32 && c.Wout == 32)) r.ksplit = ksplit_for(c, r.grid);
+    } else if (!igemm_supported(c)) {
+        r.family = conv_takes_stem(c) ? CONV_STEM : CONV_DIRECT;
+        if (r.family == CONV_STEM && stem_stats_ok(c)) r.stats_px = 1024;
+    } else if (wino_route(c, &r)) {
+        cls = "conv3x3_wino";
+        r.ksplit = ksplit_for(c, r.grid);
+    } else {
+        r.family = CONV_IGEMM;
+        cls = c.ks == 3 ? (halo_ok(c, &th, &nimg) ? "conv3x3_halo" : "conv3x3_igemm") : "conv1x1_igemm";
+        r.stats_px = (c.out_nchw || (c.Cout & 3) || (c.R0 & 3)) ? 0 : hw % BM == 0 ? BM : 0;
+    }
+    if (r.ksplit > 1) r.stats_px = 0;   // a split-K launch emits partial outputs: no statistics (the consumer's GroupNorm reads the tensor)
+    if (!cls) return r;
+    if (prof_enabled() && prof_detail()) {     // one class per distinct launch shape
+        const bool gemm = r.family == CONV_SPLIT || r.family == CONV_IGEMM;
+        char base[32], s_[16] = "", u_[16] = "";
+        if (gemm) snprintf(base, sizeof(base), "conv%dx%d_%s", c.ks, c.ks, r.family == CONV_SPLIT ? "bf16x3" : "igemm");
+        if (gemm) snprintf(s_, sizeof(s_), ":s%d", c.stride);
+        if (r.family != CONV_SPLIT) snprintf(u_, sizeof(u_), ":u%d", c.ups);
+        snprintf(r.name, sizeof(r.name), "%s:H%d:Cin%d+%d:Cout%d%s%s:coef%d", gemm ? base : cls, c.Hout, c.C0, c.C1, c.Cout, s_, u_, c.coefA ? 1 : 0);
+    } else {
+        snprintf(r.name, sizeof(r.name), "%s", cls);
+    }
+    return r;
+}
+
+static int launch_igemm(const ConvLaunch &c, hipStream_t st);
+
+int launch_conv(const ConvLaunch &c, const HeadUpdate *hu, float *head_scratch, hipStream_t st) {
+    const ConvRoute r = conv_route(c);
+    if (hu && !r.head()) {
+        set_error("unet: the head convolution of this net cannot carry the fused update");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    switch (r.family) {     // the VALU launchers open their own profiler scope (the heads' depends on the update they carry)
+        case CONV_HEAD_FUSED: return launch_conv_head_fused(c, hu, st);
+        case CONV_HEAD_GEMM:
+            DLPM_CHECK_ARG(head_scratch, "launch_conv: the GEMM + gather head needs its scratch tensor (ConvRoute::scratch_floats)");
+            return launch_conv_head_gemm(c, hu, head_scratch, st);
+        case CONV_HEAD: return launch_conv_head(c, hu, st);
+        case CONV_STEM: return launch_conv_stem(c, st);
+        case CONV_DIRECT: return launch_conv_direct(c, st);
+        default: break;
+    }
     const int64_t M = (int64_t)c.B * c.Hout * c.Wout;
-    const int64_t mt = ceil_div(M, BM);
     const double K = (double)(c.C0 + c.C1) * c.ks * c.ks;
-    // algorithmic bytes: input once + weights once + output once (+ residual)
+    // ALGORITHMIC flops (direct-conv count) and bytes: input once + weights once + output once (+ residual); the bf16x3 weights are
+    // 6 B per element
     const double bytes = 4.0 * ((double)c.B * c.Hin * c.Win * (c.C0 + c.C1) + K * c.Cout + (double)M * c.Cout * (c.res0 ? 2 : 1));
-    char pname[96];
-    int th = 0, nimg = 1;
-    if (prof_enabled() && prof_detail())
-        snprintf(pname, sizeof(pname), "conv%dx%d_igemm:H%d:Cin%d+%d:Cout%d:s%d:u%d:coef%d", c.ks, c.ks, c.Hout, c.C0, c.C1, c.Cout,
-                 c.stride, c.ups, c.coefA ? 1 : 0);
-    else
-        snprintf(pname, sizeof(pname), "%s", c.ks == 3 ? (halo_ok(c, &th, &nimg) ? "conv3x3_halo" : "conv3x3_igemm") : "conv1x1_igemm");
-    if (conv_split_ok(c)) {
-        if (prof_enabled() && prof_detail())
-            snprintf(pname, sizeof(pname), "conv%dx%d_bf16x3:H%d:Cin%d+%d:Cout%d:s%d:coef%d", c.ks, c.ks, c.Hout, c.C0, c.C1, c.Cout, c.stride,
-                     c.coefA ? 1 : 0);
-        else
-            snprintf(pname, sizeof(pname), c.ks == 1 ? "conv1x1_bf16x3" : "conv3x3_bf16x3");
-        // bytes as the kernel moves them: the weights are 6 B per element here
-        ProfScope pss(pname, 2.0 * M * c.Cout * K, bytes + 2.0 * K * c.Cout, st);
-#ifdef DLPM_PHASE_TIMING
-        const_cast<ConvLaunch &>(c).phase = phase_buffer();
-#endif
-        return launch_conv_split(c, st);
-    }
-    {
-        int wb, ww, wi;
-        if (wino4sp_preferred(c, &wb, &ww, &wi)) {   // a class of its own: it executes 100 multiplies per 64 outputs, conv3x3_wino4 144
-            if (prof_enabled() && prof_detail())
-                snprintf(pname, sizeof(pname), "conv3x3_wino4sp:H%d:Cin%d+%d:Cout%d:u%d:coef%d", c.Hout, c.C0, c.C1, c.Cout, c.ups, c.coefA ? 1 : 0);
-            else
-                snprintf(pname, sizeof(pname), "conv3x3_wino4sp");
-            ProfScope psw(pname, 2.0 * M * c.Cout * K, bytes, st);   // ALGORITHMIC flops (direct-conv count)
-            return launch_conv_wino4sp(c, st);
-        }
-        if (wino4_preferred(c, &wb, &ww, &wi)) {
-            if (prof_enabled() && prof_detail())
-                snprintf(pname, sizeof(pname), "conv3x3_wino4:H%d:Cin%d+%d:Cout%d:u%d:coef%d", c.Hout, c.C0, c.C1, c.Cout, c.ups, c.coefA ? 1 : 0);
-            else
-                snprintf(pname, sizeof(pname), "conv3x3_wino4");
-            ProfScope psw(pname, 2.0 * M * c.Cout * K, bytes, st);   // ALGORITHMIC flops (direct-conv count)
-            return launch_conv_wino4(c, st);
-        }
-        if (wino_geometry(c, &wb, &ww, &wi)) {
-            if (prof_enabled() && prof_detail())
-                snprintf(pname, sizeof(pname), "conv3x3_wino:H%d:Cin%d+%d:Cout%d:u%d:coef%d", c.Hout, c.C0, c.C1, c.Cout, c.ups, c.coefA ? 1 : 0);
-            else
-                snprintf(pname, sizeof(pname), "conv3x3_wino");
-            ProfScope psw(pname, 2.0 * M * c.Cout * K, bytes, st);   // ALGORITHMIC flops (direct-conv count)
-            return launch_conv_wino(c, st);
-        }
-    }
-    ProfScope ps(pname, 2.0 * M * c.Cout * K, bytes, st);
+    ProfScope ps(r.name, 2.0 * M * c.Cout * K, bytes + (r.family == CONV_SPLIT ? 2.0 * K * c.Cout : 0.0), st);
 #ifdef DLPM_PHASE_TIMING
     const_cast<ConvLaunch &>(c).phase = phase_buffer();
 #endif
+    switch (r.family) {
+        case CONV_SPLIT: return launch_conv_split(c, st);
+        case CONV_WINO4SP: return launch_conv_wino4sp(c, r, st);
+        case CONV_WINO4: return launch_conv_wino4(c, r, st);
+        case CONV_WINO: return launch_conv_wino(c, r, st);
+        default: return launch_igemm(c, st);
+    }
+}
+
+// the implicit-GEMM family: the halo kernels (weight-streaming or not), k_conv_igemm modes 0 to 2
+static int launch_igemm(const ConvLaunch &c, hipStream_t st) {
+    const int64_t M = (int64_t)c.B * c.Hout * c.Wout;
+    const int64_t mt = ceil_div(M, BM);
+    int th = 0, nimg = 1;
     if (halo_ok(c, &th, &nimg)) {
         int r;
         if (c.w_frag && !ws_disabled() && (c.C0 + c.C1) % KC == 0) {
@@ -1209,8 +1238,7 @@ int launch_conv_igemm(const ConvLaunch &c, hipStream_t st) {
         return DLPM_OK;
     }
     // full tiles take the lean epilogue (MODE 1); 1x1 NHWC convolutions also the pointer-walking gather (MODE 2)
-    static int nofast = -1;
-    if (nofast < 0) { const char *e = getenv("DLPM_NO_FAST_IGEMM"); nofast = (e && e[0] == '1') ? 1 : 0; }
+    static const int nofast = env_switch("DLPM_NO_FAST_IGEMM", 0, true);
     const int bn = c.Cout > 64 ? 128 : c.Cout > 32 ? 64 : 32;
     const bool full = !nofast && M % BM == 0 && c.Cout % bn == 0 && !c.out_nchw && (c.R0 & 3) == 0;
     const bool g1 = full && c.ks == 1 && c.stride == 1 && !c.ups && !c.in_nchw && c.C0 % KC == 0 && (c.C0 + c.C1) % KC == 0;

@@ -717,8 +717,7 @@ int launch_conv_split(const ConvLaunch &c, hipStream_t st) {
     // Round 5: the pipelined kernel (one k-step per LDS stage, two stages, one barrier per k-step) wherever the 8-wave shape ran;
     // DLPM_SPLIT_PIPE=0 restores k_conv_split<8, 1, *> for A/B runs (same bits).  The 4-wave shape carries the row epilogue with the
     // fused statistics.  All shapes accumulate every output in the same order: which one runs does not change a bit of the result.
-    static int pipe = -1;
-    if (pipe < 0) { const char *e = getenv("DLPM_SPLIT_PIPE"); pipe = e ? atoi(e) : 1; }
+    static const int pipe = env_switch("DLPM_SPLIT_PIPE", 1);
     // (the pipelined kernel's LDS limit is 80 KB = 48 KB of stages + the fused GroupNorm coefficients, nsamp x Cin x 8 bytes; launches
     //  beyond it -- Cin > 4096 with coefficients -- stay on k_conv_split<8, 1, 1>, whose 104-KB limit takes Cin up to 7168: ADVICE r05)
     const int lds_p = 48 * 1024 + (c.coefA ? nsamp * (c.C0 + c.C1) * 8 : 0);

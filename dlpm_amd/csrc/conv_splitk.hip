@@ -1,7 +1,7 @@
 // conv_splitk.hip -- the reduction behind a split-K convolution launch (round 6).
 //
 // At a small DECLARED batch the 8x8 / 4x4 levels of a UNet launch 16-128 workgroups that each walk a K loop of 32-64 serial phases
-// (the CIFAR net at B = 64: 14 F(2x2) launches of ~100 us on 16 workgroups).  conv_ksplit_for cuts that loop over 2 / 4 / 8 grid copies
+// (the CIFAR net at B = 64: 14 F(2x2) launches of ~100 us on 16 workgroups).  conv_route (ConvRoute::ksplit) cuts that loop over 2 / 4 / 8 grid copies
 // (ConvLaunch::ksplit: the narrow F(4x4) shapes and the F(2x2) kernel); copy s leaves the partial OUTPUTS of its channel range -- the
 // Winograd output transform is linear, so partial sums may be transformed before they are added -- in part[s], and this kernel forms
 //     out = bias + (((part[0] + part[1]) + part[2]) + ...) (+ residual)
@@ -48,31 +48,6 @@ int launch_splitk_reduce(const float *part, int S, int64_t npix, int Cout, const
     k_splitk_reduce<<<(unsigned)ceil_div(n4, 256), 256, 0, st>>>(part, S, n4, n4, Cout, bias, res0, res1, R0 ? R0 : Cout, out);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
-}
-
-int conv_ksplit_for(const ConvLaunch &c) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("DLPM_KSPLIT"); on = e ? atoi(e) : 1; }
-    if (!on || c.gen != DLPM_CONV_AUTO || c.dispatch_B <= 0 || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return 1;
-    if ((c.Cout & 3) || conv_split_ok(c)) return 1;
-    int a, b, n, nchunks;
-    int64_t grid;
-    if (wino4_preferred(c, &a, &b, &n)) {
-        const int nq = wino4_launch_nq(c);
-        if (nq == 128 || (c.Cout == 32 && c.Hout == 32 && c.Wout == 32)) return 1;      // the 8-wave and whole-image shapes carry no split
-        const int64_t tiles = c.dispatch_B * (c.Hout / 4) * (c.Wout / 4);
-        grid = (n == 1 ? tiles / 16 : ceil_div(c.dispatch_B, (int64_t)n)) * (c.Cout / nq);
-        nchunks = (c.C0 + c.C1) / 8;
-    } else if (wino_geometry(c, &a, &b, &n)) {
-        grid = wino_grid_at(c, c.dispatch_B);
-        nchunks = (c.C0 + c.C1) / 8;
-    } else {
-        return 1;
-    }
-    if (grid <= 0) return 1;
-    int S = 1;
-    while (S < 8 && grid * S * 2 <= 256 && nchunks % (S * 2) == 0 && nchunks / (S * 2) >= 4) S *= 2;
-    return S;
 }
 
 }  // namespace dlpm

@@ -439,12 +439,10 @@ __global__ void k_relayout_weight_wino_q(const float *oihw, float *dst, int Cout
 }  // namespace
 
 static bool wino_disabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_NO_WINO"); v = (e && e[0] == '1') ? 1 : 0; }
+    static const int v = env_switch("DLPM_NO_WINO", 0, true);
     return v == 1;
 }
 
-int wino_waves(const ConvLaunch &c);
 // Small launches of 64-channel-multiple layers (the MNIST-width nets): when a 64-tile block would hold SEVERAL whole
 // images (8x8 / 4x4-pixel tensors) and the grid of 64-tile x 64-channel blocks would leave most CUs empty, the 4-wave
 // 32-tile x 64-channel shape is used instead: twice the workgroups, two per CU.  Per (tile, channel) the arithmetic is the
@@ -459,16 +457,21 @@ static bool wino_small_launch(const ConvLaunch &c) {
     return wgs64 < 256;
 }
 
+// waves per workgroup of the 8-wave kernel family: 4 (two workgroups per CU, 32 x 64 blocks) for small launches
+static int wino_waves(const ConvLaunch &c) { return wino_small_launch(c) ? 4 : 8; }
+
 // tiles per workgroup: 32 (x 128 output channels) for the 8-wave kernel when Cout allows it, else 64 (x 64 channels)
-int wino_tiles(const ConvLaunch &c) {
+static int wino_tiles(const ConvLaunch &c) {
     if (wino_waves(c) == 4) return 32;
     return c.Cout % 128 == 0 ? 32 : 64;
 }
 
-// waves per workgroup of the 8-wave kernel family: 4 (two workgroups per CU, 32 x 64 blocks) for small launches
-int wino_waves(const ConvLaunch &c) { return wino_small_launch(c) ? 4 : 8; }
+// m-blocks of mt tiles at batch B: blocks inside one image, or nimg whole small images per block
+static int64_t f2_mblocks(const ConvLaunch &c, int64_t B, int mt, int nimg) {
+    return nimg == 1 ? B * (c.Hout / 2) * (c.Wout / 2) / mt : ceil_div(B, (int64_t)nimg);
+}
 
-bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+static bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
     if (wino_disabled() || c.gen == DLPM_CONV_IGEMM || !c.w_wino || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
     if ((c.Hout & 1) || (c.Wout & 1) || c.Cout % WN != 0 || (c.C0 + c.C1) % WKC != 0 || c.C0 % WKC != 0) return false;
     if ((c.R0 & 3) != 0) return false;
@@ -494,15 +497,22 @@ bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
     return true;
 }
 
-int launch_conv_wino(const ConvLaunch &c, hipStream_t st) {
+bool wino_route(const ConvLaunch &c, ConvRoute *r) {
+    if (!wino_geometry(c, &r->bh, &r->bw, &r->nimg)) return false;
+    const int mt = wino_tiles(c);
+    r->family = CONV_WINO;
+    r->nq = wino_waves(c) == 8 ? 4096 / mt : 64;
+    r->grid = c.dispatch_B > 0 ? f2_mblocks(c, c.dispatch_B, mt, r->nimg) * (c.Cout / r->nq) : 0;
+    r->stats_px = r->nimg == 1 ? 4 * mt : 0;
+    return true;
+}
+
+int launch_conv_wino(const ConvLaunch &c, const ConvRoute &rt, hipStream_t st) {
     int bh, bw, nimg;
-    if (!wino_geometry(c, &bh, &bw, &nimg)) {
+    if (rt.family != CONV_WINO || !wino_geometry(c, &bh, &bw, &nimg)) {
         set_error("launch_conv_wino: unsupported shape");
         return DLPM_ERR_UNSUPPORTED;
     }
-#ifdef DLPM_PHASE_TIMING
-    const_cast<ConvLaunch &>(c).phase = phase_buffer();
-#endif
     using KFn = void (*)(ConvLaunch, int, int, int);
     const int mt = wino_tiles(c);
     const int nw = wino_waves(c);
@@ -514,30 +524,19 @@ int launch_conv_wino(const ConvLaunch &c, hipStream_t st) {
         int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), 160 * 1024);
         if (r != DLPM_OK) return r;
     }
-    const int nq = nw == 8 ? 4096 / mt : 64;
+    const int nq = rt.nq;
     size_t shmem = (size_t)(2 * 16 * mt * (KC + 4) + 2 * (mt == 64 ? RAW_MAXPIX : RAW_MAXPIX / 2) * (KC + 4) + 2 * 16 * 2 * KC) * sizeof(float);
     const size_t epi = (size_t)((nw / 2) * 4 * 16 * 64 + 4 * mt * (nq + 4)) * sizeof(float);   // exchange + row image
     if (shmem < epi) shmem = epi;
-    const int64_t tiles = (int64_t)c.B * (c.Hout / 2) * (c.Wout / 2);
-    const int64_t mblocks = nimg == 1 ? tiles / mt : ceil_div(c.B, nimg);
+    const int64_t mblocks = f2_mblocks(c, c.B, mt, rt.nimg);
     const int ks = c.ksplit > 1 ? c.ksplit : 1;
     if (ks > 1 && (c.bias || c.res0 || c.stats_out || ((c.C0 + c.C1) / KC) % ks != 0)) {
         set_error("launch_conv_wino: a split-K launch carries no bias / residual / statistics and divides its chunks evenly");
         return DLPM_ERR_ARG;
     }
-    fn<<<(unsigned)(mblocks * (c.Cout / nq) * ks), nw * 64, shmem, st>>>(c, bh, bw, nimg);
+    fn<<<(unsigned)(mblocks * (c.Cout / nq) * ks), nw * 64, shmem, st>>>(c, rt.bh, rt.bw, rt.nimg);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
-}
-
-int64_t wino_grid_at(const ConvLaunch &c, int64_t B) {
-    int bh, bw, nimg;
-    if (!wino_geometry(c, &bh, &bw, &nimg)) return 0;
-    const int mt = wino_tiles(c), nw = wino_waves(c);
-    const int nq = nw == 8 ? 4096 / mt : 64;
-    const int64_t tiles = B * (c.Hout / 2) * (c.Wout / 2);
-    const int64_t mblocks = nimg == 1 ? tiles / mt : ceil_div(B, (int64_t)nimg);
-    return mblocks * (c.Cout / nq);
 }
 
 int64_t wino_weight_floats(int Cout, int Cin) {

@@ -1722,8 +1722,7 @@ __global__ void k_relayout_weight_wino4sp(const float *oihw, float *dst, int Cou
 }
 
 int f4_mode() {   // DLPM_WINO_F4=0: keep every 3x3 layer on the F(2x2,3x3) kernel (default: F(4x4) where the shape qualifies)
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WINO_F4"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("DLPM_WINO_F4", 1);
     return v;
 }
 
@@ -1733,10 +1732,25 @@ bool wino4_enabled() { return f4_mode() != 0; }
 
 // DLPM_WINO4_NARROW=0 (A/B runs): the 64- / 32-channel n-tile shapes off -- those layers take F(2x2) / the implicit GEMM as in rounds 1-4
 static bool narrow_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WINO4_NARROW"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("DLPM_WINO4_NARROW", 1);
     return v != 0;
 }
+
+// The block of F4_TILES tiles on images of TH x TW tiles: h x w tiles inside one image, or n whole small images (all four F(4x4) kernels)
+static bool f4_block(int TH, int TW, int *h, int *w, int *n) {
+    if (TH * TW >= F4_TILES) {       // a block inside one image
+        *w = TW < 4 ? TW : 4;
+        if (F4_TILES % *w != 0) return false;
+        *h = F4_TILES / *w;
+        *n = 1;
+        return TW % *w == 0 && TH % *h == 0;
+    }
+    if (F4_TILES % (TH * TW) != 0) return false;   // several whole small images per block
+    *h = TH; *w = TW; *n = F4_TILES / (TH * TW);
+    return true;
+}
+// its m-blocks at batch B
+static int64_t f4_mblocks(int64_t B, int TH, int TW, int nimg) { return nimg == 1 ? B * TH * TW / F4_TILES : ceil_div(B, (int64_t)nimg); }
 
 // geometry of a launch on n-tiles of nq channels (the narrow shapes' raw buffer holds halo patches of <= 400 pixels)
 static bool wino4_geometry_nq(const ConvLaunch &c, int nq, int *bh, int *bw, int *nimg) {
@@ -1745,18 +1759,8 @@ static bool wino4_geometry_nq(const ConvLaunch &c, int nq, int *bh, int *bw, int
     if ((c.Hout & 3) || (c.Wout & 3) || c.Cout % 32 != 0 || (c.C0 + c.C1) % F4_KC != 0 || c.C0 % F4_KC != 0) return false;
     const int rawpix = nq == F4_NQ ? F4_RAWPIX : F4_RAWPIX_N;
     if ((c.R0 & 15) != 0) return false;   // a wave's 16 output channels stay on one side of a residual concat
-    const int TH = c.Hout / 4, TW = c.Wout / 4;
     int h, w, n;
-    if (TH * TW >= F4_TILES) {       // a block inside one image
-        w = TW < 4 ? TW : 4;
-        if (F4_TILES % w != 0) return false;
-        h = F4_TILES / w;
-        if (TW % w != 0 || TH % h != 0) return false;
-        n = 1;
-    } else {                         // several whole small images per block
-        if (F4_TILES % (TH * TW) != 0) return false;
-        h = TH; w = TW; n = F4_TILES / (TH * TW);
-    }
+    if (!f4_block(c.Hout / 4, c.Wout / 4, &h, &w, &n)) return false;
     const int RH = c.ups ? 2 * h + 2 : 4 * h + 2, RW = c.ups ? 2 * w + 2 : 4 * w + 2;
     if (n * RH * RW > rawpix) return false;
     *bh = h; *bw = w; *nimg = n;
@@ -1771,8 +1775,7 @@ static bool wino4_geometry_nq(const ConvLaunch &c, int nq, int *bh, int *bw, int
 static int wino4_nq_for(const ConvLaunch &c) {
     const int base = f4_nq_of(c.Cout);
     if (base != F4_NQ || c.dispatch_B <= 0 || (!c.w_wino4_n64 && !c.w_wino4_n32)) return base;
-    static int floor_nq = -1;
-    if (floor_nq < 0) { const char *e = getenv("DLPM_WINO4_NQ"); floor_nq = e ? atoi(e) : 32; }
+    static const int floor_nq = env_switch("DLPM_WINO4_NQ", 32);
     int best = F4_NQ;
     for (int nq = F4_NQ; nq >= 32 && nq >= floor_nq; nq >>= 1) {
         if (nq == 64 && !c.w_wino4_n64) continue;
@@ -1780,18 +1783,12 @@ static int wino4_nq_for(const ConvLaunch &c) {
         int h, w, n;
         if (!wino4_geometry_nq(c, nq, &h, &w, &n)) continue;
         best = nq;
-        const int64_t tiles = c.dispatch_B * (c.Hout / 4) * (c.Wout / 4);
-        const int64_t mblocks = n == 1 ? tiles / F4_TILES : ceil_div(c.dispatch_B, (int64_t)n);
-        if (mblocks * (c.Cout / nq) >= 256) break;
+        if (f4_mblocks(c.dispatch_B, c.Hout / 4, c.Wout / 4, n) * (c.Cout / nq) >= 256) break;
     }
     return best;
 }
 
-bool wino4_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) { return wino4_geometry_nq(c, wino4_nq_for(c), bh, bw, nimg); }
-int wino4_launch_nq(const ConvLaunch &c) { return wino4_nq_for(c); }
-
-// dispatch policy (a function of the layer and of ConvLaunch::gen / dispatch_B, never of the batch in this launch:
-// the generations round differently and a sample must not depend on how its batch was sharded or chunked):
+// dispatch policy on n-tiles of nq = wino4_nq_for(c) channels (a function of the layer and of ConvLaunch::gen / dispatch_B, see ConvRoute):
 //   DLPM_CONV_F4     F(4x4) wherever the geometry qualifies;
 //   DLPM_CONV_F2 / DLPM_CONV_IGEMM   never;
 //   DLPM_CONV_AUTO   F(4x4) wherever it applies, except -- when the F(2x2) weights are there too --
@@ -1799,51 +1796,44 @@ int wino4_launch_nq(const ConvLaunch &c) { return wino4_nq_for(c); }
 //     * with a caller-declared dispatch batch: launches whose grid would leave CUs empty AT THAT BATCH (fewer than 256
 //       workgroups of 256 pixels x 128 channels, e.g. 8x8 tensors at batch 256): the F(2x2) kernel's 128-pixel blocks give
 //       twice as many workgroups.
-bool wino4_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+static bool wino4_preferred(const ConvLaunch &c, int nq, int *bh, int *bw, int *nimg) {
     if (c.gen == DLPM_CONV_F2 || c.gen == DLPM_CONV_IGEMM) return false;
-    if (!wino4_geometry(c, bh, bw, nimg)) return false;
+    if (!wino4_geometry_nq(c, nq, bh, bw, nimg)) return false;
     if (!c.w_wino || c.gen == DLPM_CONV_F4) return true;
     if (*nimg > 4) return false;
     if (c.dispatch_B <= 0) return true;
-    const int64_t tiles = c.dispatch_B * (c.Hout / 4) * (c.Wout / 4);
-    const int64_t mblocks = *nimg == 1 ? tiles / F4_TILES : ceil_div(c.dispatch_B, (int64_t)*nimg);
-    return mblocks * (c.Cout / wino4_nq_for(c)) >= 256;
+    return f4_mblocks(c.dispatch_B, c.Hout / 4, c.Wout / 4, *nimg) * (c.Cout / nq) >= 256;
 }
 
 // DLPM_WINO4_IMG=0 (A/B runs): the 32-channel 32x32 layers on the 2 + 2-wave 16-tile shape as in round 5 (same bits either way).  A
 // function of the layer's geometry only, like every other kernel choice.
 static bool wino4_whole_image(const ConvLaunch &c) {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WINO4_IMG"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("DLPM_WINO4_IMG", 1);
     return v != 0 && c.Cout == 32 && !c.ups && c.Hout == 32 && c.Wout == 32 && (c.C0 + c.C1) <= 1024;
 }
 
 static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int nimg, hipStream_t st);
 
-int launch_conv_wino4(const ConvLaunch &c, hipStream_t st) {
+int launch_conv_wino4(const ConvLaunch &c, const ConvRoute &rt, hipStream_t st) {
     int bh, bw, nimg;
-    if (!wino4_geometry(c, &bh, &bw, &nimg)) {
+    if (rt.family != CONV_WINO4 || !wino4_geometry_nq(c, rt.nq, &bh, &bw, &nimg)) {
         set_error("launch_conv_wino4: unsupported shape");
         return DLPM_ERR_UNSUPPORTED;
     }
-#ifdef DLPM_PHASE_TIMING
-    const_cast<ConvLaunch &>(c).phase = phase_buffer();
-#endif
-    const int nq = wino4_nq_for(c);
+    const int nq = rt.nq;
     if (nq != f4_nq_of(c.Cout)) {     // a 128-multiple layer on narrow n-tiles: the matching fragment stream
         ConvLaunch cn = c;
         cn.w_wino4 = nq == 64 ? c.w_wino4_n64 : c.w_wino4_n32;
         cn.w_wino4_n64 = cn.w_wino4_n32 = nullptr;
         cn.dispatch_B = 0;
-        return launch_conv_wino4_nq(cn, nq, bh, bw, nimg, st);
+        return launch_conv_wino4_nq(cn, nq, rt.bh, rt.bw, rt.nimg, st);
     }
-    return launch_conv_wino4_nq(c, nq, bh, bw, nimg, st);
+    return launch_conv_wino4_nq(c, nq, rt.bh, rt.bw, rt.nimg, st);
 }
 
 static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int nimg, hipStream_t st) {
     using KFn = void (*)(ConvLaunch, int, int, int);
-    const int64_t tiles = (int64_t)c.B * (c.Hout / 4) * (c.Wout / 4);
-    const int64_t mblocks = nimg == 1 ? tiles / F4_TILES : ceil_div(c.B, nimg);
+    const int64_t mblocks = f4_mblocks(c.B, c.Hout / 4, c.Wout / 4, nimg);
     if (wino4_whole_image(c)) {   // 32 channels on 32x32 images: one workgroup per image, 8 MFMA waves (round 6)
         const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_wino4_img), 160 * 1024);
         if (r != DLPM_OK) return r;
@@ -1884,14 +1874,12 @@ static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int
 
 // DLPM_RES_IMG=0 (A/B runs): the 32-channel 32x32 ResBlocks as separate launches (conv, GroupNorm coefficients, conv) as before -- same bits
 bool res_img_ok(const ResImgLaunch &r) {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_RES_IMG"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("DLPM_RES_IMG", 1);
     const int Cin = r.C0 + r.C1;
     const bool common = v != 0 && wino4_enabled() && r.w1 && r.w2 && r.res && Cin <= 128 && Cin >= 32 &&
                         (r.st0 ? (r.C1 == 0 || r.st1 != nullptr) : (r.coefA1 && r.coefB1));
     if (r.H == 16) {     // 64 output channels on 16x16 images (k_resblock_wino4_img16): 16-channel chunks that stay inside one concat source
-        static int v16 = -1;
-        if (v16 < 0) { const char *e = getenv("DLPM_RES_IMG16"); v16 = e ? atoi(e) : 1; }
+        static const int v16 = env_switch("DLPM_RES_IMG16", 1);
         return common && v16 != 0 && Cin % F6_KC == 0 && r.C0 % F6_KC == 0;
     }
     return common && r.H == 32 && r.hbuf && Cin % F4_KC == 0 && r.C0 % F4_KC == 0;
@@ -1940,26 +1928,15 @@ int relayout_weight_wino4(const float *oihw_dev, float *dst_dev, int Cout, int C
 // ---- the sub-pixel form of the Upsample convolutions (k_conv3x3_wino4sp)
 // DLPM_WINO4_SUBPIX=0 (A/B runs): those layers on the UPS instantiation of k_conv3x3_wino4 as before; their sub-pixel weights are not built
 bool wino4sp_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_WINO4_SUBPIX"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("DLPM_WINO4_SUBPIX", 1);
     return v != 0 && wino4_enabled();
 }
 
 // block shape of a layer with Cout output channels on low-res images of Hlo x Wlo pixels (the rule of wino4_geometry_nq on the low-res tiles)
 static bool wino4sp_block(int Cout, int Cin, int Hlo, int Wlo, int *bh, int *bw, int *nimg) {
     if (Cout % F4_NQ != 0 || Cin % F4_KC != 0 || Hlo <= 0 || Wlo <= 0 || (Hlo & 3) || (Wlo & 3)) return false;
-    const int TH = Hlo / 4, TW = Wlo / 4;
     int h, w, n;
-    if (TH * TW >= F4_TILES) {
-        w = TW < 4 ? TW : 4;
-        if (F4_TILES % w != 0) return false;
-        h = F4_TILES / w;
-        if (TW % w != 0 || TH % h != 0) return false;
-        n = 1;
-    } else {
-        if (F4_TILES % (TH * TW) != 0) return false;
-        h = TH; w = TW; n = F4_TILES / (TH * TW);
-    }
+    if (!f4_block(Hlo / 4, Wlo / 4, &h, &w, &n)) return false;
     if (n > 4) return false;       // sixteen one-tile images (4x4 low-res): stays on the UPS instantiation
     if (n * (4 * h + 1) * (4 * w + 1) > FS_RAWPIX) return false;
     *bh = h; *bw = w; *nimg = n;
@@ -1970,35 +1947,38 @@ bool wino4sp_layer_ok(int Cout, int Cin, int Hlo, int Wlo) {
     return wino4sp_enabled() && wino4sp_block(Cout, Cin, Hlo, Wlo, &h, &w, &n);
 }
 
-bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+static bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
     if (!c.ups || !c.w_wino4sp || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
     if (c.Hout != 2 * c.Hin || c.Wout != 2 * c.Win || c.C0 % F4_KC != 0 || (c.R0 & 15) != 0 || c.ksplit > 1) return false;
     return wino4sp_block(c.Cout, c.C0 + c.C1, c.Hin, c.Win, bh, bw, nimg);
 }
 
-// dispatch: a launch that the F(4x4) policy takes (wino4_preferred: generations AUTO and F4) on the 128-channel n-tile, and that carries the
-// sub-pixel weights -- a function of the layer and the declared policy only
-bool wino4sp_preferred(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
-    int a, b, n;
-    if (!c.ups || !c.w_wino4sp || !wino4sp_enabled() || !wino4_preferred(c, &a, &b, &n) || wino4_nq_for(c) != F4_NQ) return false;
-    return wino4sp_geometry(c, bh, bw, nimg);
+// The F(4x4) families' part of the route.  The sub-pixel kernel: a launch that the F(4x4) policy takes (generations AUTO and F4) on the
+// 128-channel n-tile, and that carries the sub-pixel weights -- a function of the layer and the declared policy only.
+bool wino4_route(const ConvLaunch &c, ConvRoute *r) {
+    const int nq = wino4_nq_for(c);
+    int bh, bw, nimg;
+    if (!wino4_preferred(c, nq, &bh, &bw, &nimg)) return false;
+    r->family = CONV_WINO4;
+    if (c.ups && c.w_wino4sp && wino4sp_enabled() && nq == F4_NQ && wino4sp_geometry(c, &bh, &bw, &nimg)) r->family = CONV_WINO4SP;
+    else if (c.dispatch_B > 0) r->grid = f4_mblocks(c.dispatch_B, c.Hout / 4, c.Wout / 4, nimg) * (c.Cout / nq);
+    r->bh = bh; r->bw = bw; r->nimg = nimg; r->nq = nq;
+    // one partial per block, or per image of four whole 8x8 images; the sub-pixel kernel: per (block | image, parity class)
+    r->stats_px = nimg == 1 ? 256 : (nimg == 4 && bh * bw == 4) ? 64 : 0;
+    return true;
 }
 
-int launch_conv_wino4sp(const ConvLaunch &c, hipStream_t st) {
+int launch_conv_wino4sp(const ConvLaunch &c, const ConvRoute &rt, hipStream_t st) {
     int bh, bw, nimg;
-    if (!wino4sp_geometry(c, &bh, &bw, &nimg)) {
+    if (rt.family != CONV_WINO4SP || !wino4sp_geometry(c, &bh, &bw, &nimg)) {
         set_error("launch_conv_wino4sp: unsupported shape");
         return DLPM_ERR_UNSUPPORTED;
     }
-#ifdef DLPM_PHASE_TIMING
-    const_cast<ConvLaunch &>(c).phase = phase_buffer();
-#endif
-    const int64_t tiles = (int64_t)c.B * (c.Hin / 4) * (c.Win / 4);
-    const int64_t mblocks = nimg == 1 ? tiles / F4_TILES : ceil_div(c.B, nimg);
+    const int64_t mblocks = f4_mblocks(c.B, c.Hin / 4, c.Win / 4, rt.nimg);
     const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_wino4sp), 160 * 1024);
     if (r != DLPM_OK) return r;
     const size_t lds = (size_t)(2 * FS_VBUF + 2 * FS_RAWBUF + 2 * F4_CFS) * sizeof(float);
-    k_conv3x3_wino4sp<<<(unsigned)(mblocks * (c.Cout / F4_NQ) * 4), F4_NT, lds, st>>>(c, bh, bw, nimg);
+    k_conv3x3_wino4sp<<<(unsigned)(mblocks * (c.Cout / F4_NQ) * 4), F4_NT, lds, st>>>(c, rt.bh, rt.bw, rt.nimg);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

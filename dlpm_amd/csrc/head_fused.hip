@@ -448,8 +448,7 @@ __global__ void k_relayout_weight_head_fused_bf(const float *oihw, uint4 *dst, i
 }
 
 bool head_fused_bf(const ConvLaunch &c) {     // which matrix pipe: bf16 x 3 unless the fp32 GEMM policy (or DLPM_HEAD_F32=1) asks otherwise
-    static int f32 = -1;
-    if (f32 < 0) { const char *e = getenv("DLPM_HEAD_F32"); f32 = (e && e[0] == '1') ? 1 : 0; }
+    static const int f32 = env_switch("DLPM_HEAD_F32", 0, true);
     return !f32 && c.gemm != DLPM_GEMM_F32;
 }
 
@@ -462,8 +461,7 @@ size_t head_fused_lds_floats(const ConvLaunch &c) {
 }  // namespace
 
 bool head_fused_ok(const ConvLaunch &c) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_HEAD_FUSED"); off = (e && e[0] == '1') ? 1 : 0; }
+    static const int off = env_switch("DLPM_NO_HEAD_FUSED", 0, true);
     if (off || !c.w_hfused || c.ks != 3 || c.stride != 1 || c.ups || c.in_nchw || c.C1 != 0 || c.res0 || !c.coefA || !c.act_silu) return false;
     if (c.Cout < 1 || c.Cout > 3 || c.C0 % 32 != 0 || c.C0 > 32 * HF_MAXCH || c.Hin != c.Hout || c.Win != c.Wout) return false;
     if (c.Wout != 32 && c.Wout != 64) return false;

@@ -53,8 +53,7 @@ unsigned long long *phase_buffer() {
 }
 #endif
 bool prof_detail() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("DLPM_PROF_DETAIL"); v = (e && e[0] == '1') ? 1 : 0; }
+    static const int v = env_switch("DLPM_PROF_DETAIL", 0, true);
     return v == 1;
 }
 ProfScope::ProfScope(const char *n, double fl, double by, hipStream_t s) : name(n), flops(fl), bytes(by), st(s) {

@@ -137,8 +137,8 @@ void drop_graph(dlpm_sampler *s) {
 // where they exceed it by the rounding of the arena's blocks (they are both walks of the same plan, every block of which is
 // proportional to the batch: dlpm_unet_chain_workspace).  What of the step can be decided once per sampler and plan is decided here;
 // history, injected z and the profiling pass are looked at per step (chains_now).
-// The chained form needs B >= 2: kernel choice reads the DECLARED dispatch batch and the layer alone (conv_wino4.hip wino4_nq_for /
-// wino4_geometry, conv_splitk.hip conv_ksplit_for, the block_small selectors), never the batch of a launch, so the declared
+// The chained form needs B >= 2: kernel choice reads the DECLARED dispatch batch and the layer alone (conv_route: conv_wino4.hip
+// wino4_nq_for, the split-K factor; the block_small selectors), never the batch of a launch, so the declared
 // policy keeps its kernels down to a chain of ONE sample and the threshold is 2 x 1.  An odd B splits as B/2 and B - B/2 rows.
 // One chain stays: the MLP sampler; LIM, DLIM, clip and non-isotropic tables; mean types other than eps (predict + update run as
 // kernels of their own); label-conditional nets; input scaling (its scaled copy is one buffer); a net whose head cannot carry the

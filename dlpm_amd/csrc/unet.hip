@@ -40,7 +40,7 @@ enum LayerKind { L_STEM, L_RES, L_ATTN, L_DOWN, L_UP };
 struct ConvW {            // one convolution's weights
     int p_w = -1, p_b = -1;  // param indices
     int cout = 0, cin = 0, ks = 1;
-    bool use_igemm = false;
+    bool use_igemm = false;  // prep_conv: which layout w_dev holds (igemm_supported of the layer); the launch asks conv_route
     float *w_dev = nullptr;  // re-laid-out copy (or the original for 1x1 igemm)
     float *w_frag = nullptr; // 3x3 only: MFMA fragment order for the weight-streaming halo kernel
     float *w_wino = nullptr; // 3x3 only: Winograd-domain weights in fragment order (conv_wino.hip)
@@ -375,11 +375,7 @@ void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
 
 int run_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch L, hipStream_t st, const HeadUpdate *hu = nullptr, float *head_scratch = nullptr) {
     attach_conv(u, c, L);      // (the time path describes its launches by hand; a descriptor from conv_io carries the same values already)
-    if (head_fused_ok(L)) return launch_conv_head_fused(L, hu, st);
-    if (head_scratch && head_gemm_ok(L)) return launch_conv_head_gemm(L, hu, head_scratch, st);
-    if (head_conv_ok(L)) return launch_conv_head(L, hu, st);
-    if (hu) { set_error("unet: the head convolution of this net cannot carry the fused update"); return DLPM_ERR_UNSUPPORTED; }
-    return c.use_igemm ? launch_conv_igemm(L, st) : launch_conv_fallback(L, st);
+    return launch_conv(L, hu, head_scratch, st);
 }
 
 #define TRY(expr)                  \
@@ -449,15 +445,13 @@ ConvLaunch conv_io(const Ctx &cx, const ConvW &c, const Tensor4 &x0, const Tenso
 }
 
 // GroupNorm statistics can ride on the producing conv's epilogue when its pixel tiles stay inside one image and the conv runs on the
-// MFMA kernels with the row epilogue (or the stem kernels).  Decides whether `t`, the output of launch `L` of conv `c`, carries
-// statistics, allocates them (tile size per conv_stats_pixels, asked about the launch itself) and points the launch at them.
-void plan_stats(Ctx &cx, Tensor4 &t, const ConvW &c, ConvLaunch &L) {
-    static int off = -1;
-    if (off < 0) { const char *e = getenv("DLPM_NO_GN_FUSION"); off = (e && e[0] == '1') ? 1 : 0; }
+// MFMA kernels with the row epilogue (or the stem kernels).  Decides whether `t`, the output of launch `L`, carries statistics,
+// allocates them (tile size per the route of the launch itself) and points the launch at them.
+void plan_stats(Ctx &cx, Tensor4 &t, ConvLaunch &L) {
+    static const int off = env_switch("DLPM_NO_GN_FUSION", 0, true);
     t.stats = nullptr;
     t.stats_px = 0;
-    if (off || (!c.use_igemm && !L.in_nchw)) return;
-    const int px = conv_stats_pixels(L);
+    const int px = off ? 0 : conv_route(L).stats_px;
     if (px <= 0) return;
     t.stats_px = px;
     t.stats = L.stats_out = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * cx.B * (t.H * t.W / px) * t.C));
@@ -475,10 +469,10 @@ int gn_any(Ctx &cx, Tensor4 x0, Tensor4 x1, int p_gamma, int p_beta, const float
     return launch_gn_coeffs(x0.p, x1.p, x0.C, x1.C, cx.B, HW, groups, gamma, beta, ss, ss_stride, ss_offset, cA, cB, cx.st);
 }
 
-// A 3x3 stride-1 convolution of the plan, cut over S = conv_ksplit_for grid copies where the layer and the declared batch ask for it
+// A 3x3 stride-1 convolution of the plan, cut over S = ConvRoute::ksplit grid copies where the layer and the declared batch ask for it
 // (conv_splitk.hip): the copies write their partial outputs into an arena buffer, launch_splitk_reduce adds bias / residual.
 int run_conv3(Ctx &cx, const ConvW &c, const ConvLaunch &L) {
-    const int S = conv_ksplit_for(L);
+    const int S = conv_route(L).ksplit;
     if (S <= 1) return run_conv(cx, c, L);
     const int64_t npix = (int64_t)L.B * L.Hout * L.Wout;
     float *part = cx.ws.alloc((int64_t)S * npix * c.cout);
@@ -542,7 +536,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
             *out = o;
             hb.C = Co; hb.H = H; hb.W = W;
             ConvLaunch b = conv_io(cx, L.c2, hb, Tensor4(), o);     // the kernel emits the output statistics that conv2's own launch would
-            plan_stats(cx, *out, L.c2, b);
+            plan_stats(cx, *out, b);
             if (!from_stats) TRY(gn_any(cx, x0, x1, L.p_gn1_w, L.p_gn1_b, nullptr, 0, cA1, cB1));
             if (L.has_skip) TRY(run_conv(cx, L.skip, conv_io(cx, L.skip, x0, x1, sk)));
             r.gn1_w = u->params[L.p_gn1_w].dev; r.gn1_b = u->params[L.p_gn1_b].dev;
@@ -560,7 +554,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
     Tensor4 h1 = new_tensor(cx, Co, H, W);
     ConvLaunch a = conv_io(cx, L.c1, x0, x1, h1);
     a.coefA = cA1; a.coefB = cB1; a.act_silu = 1;
-    plan_stats(cx, h1, L.c1, a);
+    plan_stats(cx, h1, a);
     float *cA2 = cx.ws.alloc((int64_t)B * Co), *cB2 = cx.ws.alloc((int64_t)B * Co);
     Tensor4 sk = L.has_skip ? new_tensor(cx, Co, H, W) : Tensor4();
     *out = new_tensor(cx, Co, H, W);
@@ -568,7 +562,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
     b.coefA = cA2; b.coefB = cB2; b.act_silu = 1;
     if (L.has_skip) { b.res0 = sk.p; b.R0 = Co; }
     else { b.res0 = x0.p; b.res1 = x1.p; b.R0 = C0; }
-    plan_stats(cx, *out, L.c2, b);
+    plan_stats(cx, *out, b);
     TRY(gn_any(cx, x0, x1, L.p_gn1_w, L.p_gn1_b, nullptr, 0, cA1, cB1));
     TRY(run_conv3(cx, L.c1, a));
     TRY(gn_any(cx, h1, Tensor4(), L.p_gn2_w, L.p_gn2_b, cx.embout, L.emb_off, cA2, cB2));
@@ -606,7 +600,7 @@ int run_attn(Ctx &cx, const Layer &L, Tensor4 x, Tensor4 *out) {
     *out = new_tensor(cx, C, x.H, x.W);
     ConvLaunch p = conv_io(cx, L.c2, av, Tensor4(), *out);
     p.res0 = x.p; p.R0 = C;
-    plan_stats(cx, *out, L.c2, p);
+    plan_stats(cx, *out, p);
     a.wproj = nullptr; a.bproj = nullptr; a.out = qkv.p;
     if (u->gen == DLPM_CONV_AUTO && gnqkv_small_ok(a)) {
         TRY(enqueue(cx, launch_gnqkv_small, a));
@@ -636,7 +630,7 @@ int run_seq(Ctx &cx, const std::vector<Layer> &seq, Tensor4 x0, Tensor4 x1, Tens
                 o = new_tensor(cx, L.cout, h.H, h.W);
                 ConvLaunch a = conv_io(cx, L.c1, h, Tensor4(), o);
                 a.in_nchw = 1;
-                plan_stats(cx, o, L.c1, a);
+                plan_stats(cx, o, a);
                 TRY(run_conv(cx, L.c1, a));
                 break;
             }
@@ -651,7 +645,7 @@ int run_seq(Ctx &cx, const std::vector<Layer> &seq, Tensor4 x0, Tensor4 x1, Tens
                 const bool up = L.kind == L_UP;
                 o = new_tensor(cx, h.C, up ? h.H * 2 : (h.H - 1) / 2 + 1, up ? h.W * 2 : (h.W - 1) / 2 + 1);
                 ConvLaunch a = conv_io(cx, L.c1, h, Tensor4(), o);
-                plan_stats(cx, o, L.c1, a);
+                plan_stats(cx, o, a);
                 TRY(up ? run_conv3(cx, L.c1, a) : run_conv(cx, L.c1, a));
                 break;
             }
@@ -767,7 +761,8 @@ int walk(dlpm_unet *u, Ctx &cx, const float *x, const float *t, float *eps) {
     ConvLaunch a = conv_io(cx, u->head, h, Tensor4(), e);
     a.coefA = cA; a.coefB = cB; a.act_silu = 1; a.out_nchw = 1;
     // the head as a GEMM onto its 9 Cout tap channels + gather: the tap-channel tensor P lives in the arena
-    float *P = (!head_fused_ok(a) && head_gemm_ok(a)) ? cx.ws.alloc(head_gemm_scratch_floats(a)) : nullptr;
+    const int64_t nP = conv_route(a).scratch_floats;
+    float *P = nP ? cx.ws.alloc(nP) : nullptr;
     TRY(gn_any(cx, h, Tensor4(), u->p_head_gn_w, u->p_head_gn_b, nullptr, 0, cA, cB));
     TRY(run_conv(cx, u->head, a, cx.hu, P));
     if (!cx.ws.reuse) return DLPM_OK;
@@ -1142,7 +1137,7 @@ static bool head_fusable(const dlpm_unet *u) {
     L.C0 = u->head.cin; L.Hin = L.Hout = H; L.Win = L.Wout = H; L.out_nchw = 1;
     L.coefA = L.coefB = reinterpret_cast<const float *>(u);   // (the head always carries its GroupNorm: only non-null matters here)
     L.act_silu = 1;
-    return head_fused_ok(L) || head_gemm_ok(L) || head_conv_ok(L);
+    return conv_route(L).head();
 }
 
 extern "C" int dlpm_unet_forward_update(dlpm_unet *net, const float *x_in_dev, const float *t_dev, const dlpm_update_args *upd,
@@ -1291,8 +1286,7 @@ extern "C" int dlpm_conv2d_stats_f32(const dlpm_conv_args *a, float *scratch_dev
     DLPM_CHECK_ARG(stats_out && stats_px, "dlpm_conv2d_stats_f32: null argument");
     return conv2d_entry(a, scratch_dev, stats_out, stats_px, stream);
 }
-// stats_out: the launch also emits the GroupNorm statistics partials of its output, wherever the route the selectors pick can emit them
-// (conv_stats_pixels > 0 on the MFMA dispatch, the directly launched F(4x4) kernels and the stem kernels -- the routes plan_stats admits)
+// stats_out: the launch also emits the GroupNorm statistics partials of its output, wherever its route can (ConvRoute::stats_px > 0)
 static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(a && a->src0 && a->weight && a->out && scratch_dev, "dlpm_conv2d_f32: null argument");
     DLPM_CHECK_ARG(a->ksize == 1 || a->ksize == 3, "dlpm_conv2d_f32: ksize must be 1 or 3");
@@ -1344,86 +1338,67 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     }
     // bit 8: the F(4x4,3x3) kernel where the shape qualifies (128-, 64- or 32-channel n-tiles; its weights go behind the F(2x2) copy).  The
     // kernel takes input channels in multiples of 8, also where the implicit GEMM (multiples of 32) does not
+    bool ask_f4 = false;
     if (wino_shape && (a->force_direct & (8 | 256)) && a->Cout % 32 == 0 && Cin_ % 8 == 0 &&
         a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
         float *w4 = scratch_dev + used;
         TRY(relayout_weight_wino4(a->weight, w4, a->Cout, Cin_, st));
         L.w_wino4 = w4;
-        // bit 8 ASKS for the F(4x4) kernel: a geometry it rejects (e.g. 16 one-tile 4x4 images on a 64- / 32-channel n-tile: 576 halo
-        // pixels > F4_RAWPIX_N) is an error, not a silent drop to the implicit GEMM -- tests that compare "the F(4x4) kernel" with the
-        // default path must not pass for the wrong reason
-        int bh_, bw_, ni_;
-        if (!wino4_geometry(L, &bh_, &bw_, &ni_)) {
-            set_error("dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry");
-            return DLPM_ERR_UNSUPPORTED;
-        }
         L.w_wino = nullptr;   // no F(2x2) alternative: the launch takes the F(4x4) kernel
         used += wino4_weight_floats(a->Cout, Cin_);
+        ask_f4 = true;
     }
     // bit 256: an upsampling convolution through the sub-pixel kernel (four parity-class F(4x4,2x2) convolutions on the low-res image); its
-    // weights go behind the F(4x4,3x3) copy.  Like bit 8 it ASKS: a geometry or scratch size the kernel cannot take is an error
-    if (a->force_direct & 256) {
-        int bh_, bw_, ni_;
-        if (L.w_wino4 && a->Cout % 128 == 0 && a->scratch_floats >= used + wino4sp_weight_floats(a->Cout, Cin_)) {
-            L.w_wino4sp = scratch_dev + used;
-            if (wino4sp_preferred(L, &bh_, &bw_, &ni_)) TRY(relayout_weight_wino4sp(a->weight, scratch_dev + used, a->Cout, Cin_, st));
-            else L.w_wino4sp = nullptr;
-        }
-        if (!L.w_wino4sp) {
-            set_error("dlpm_conv2d_f32: force_direct bit 256 asks for the sub-pixel upsampling kernel, which does not take this geometry / scratch size");
-            return DLPM_ERR_UNSUPPORTED;
-        }
+    // weights go behind the F(4x4,3x3) copy
+    if ((a->force_direct & 256) && L.w_wino4 && a->Cout % 128 == 0 && a->scratch_floats >= used + wino4sp_weight_floats(a->Cout, Cin_))
+        L.w_wino4sp = scratch_dev + used;
+    // the head kernels (Cout <= 4): bit 64 the one-pass kernel (head_fused.hip; in the UNet it also carries the sampler's update), W' fragments
+    // at the front of the scratch buffer; bit 32 the head as a 1x1 GEMM onto 9 Cout tap channels + gather, W' at the front, P behind it;
+    // no bit: k_conv3x3_head where it takes the shape, its [tap][cin][4] copy at the END of the scratch buffer (the front holds the layouts above)
+    const bool head_shape = a->ksize == 3 && a->C0 % 32 == 0 && a->C1 == 0;
+    const int ask_head = !head_shape || a->Cout > 3 ? 0 : (a->force_direct & 64) ? 64 : (a->force_direct & 32);
+    const int64_t taps_floats = (int64_t)head_taps_rows(a->Cout) * a->C0;
+    float *small_dev = nullptr;
+    if (ask_head == 64) {
+        L.gemm = (a->force_direct & 128) ? DLPM_GEMM_F32 : DLPM_GEMM_AUTO;   // bit 128: its fp32-MFMA form instead of the bf16 x 3 one
+        if (a->scratch_floats >= head_fused_weight_floats(a->C0)) L.w_hfused = scratch_dev;
+    } else if (ask_head == 32) {
+        if (a->scratch_floats >= taps_floats + head_gemm_scratch_floats(L)) L.w_taps = scratch_dev;
+    } else if (!(a->force_direct & 7) && head_shape && a->Cout <= 4) {
+        const int64_t front = (int64_t)a->Cout * a->C0 * 9 + frag_weight_floats(a->Cout, a->C0);
+        if (a->scratch_floats >= front + 9 * a->C0 * 4) L.w_small = small_dev = scratch_dev + (a->scratch_floats - 9 * a->C0 * 4);
     }
-    if (stats_out) {
-        // the direct kernel (force_direct bit 0, or a shape neither the MFMA kernels nor the stem kernels take) has no statistics epilogue
-        // (the head kernels dispatched below have none either, and are never reached with px > 0: they take Cout <= 4, which igemm_supported
-        //  admits only with NCHW output, where conv_stats_pixels is 0 on every route; with !ig only the stem has px > 0, and its 1 or 3 input
-        //  channels are not the C0 % 32 == 0 of a head kernel.  A head route that one day emits statistics has to be added to this gate.)
-        const bool stem = !ig && !(a->force_direct & 1) && conv_takes_stem(L);
-        const int px = (ig || L.w_wino4 || stem) ? conv_stats_pixels(L) : 0;
-        if (px <= 0) {
-            set_error("dlpm_conv2d_stats_f32: this launch emits no statistics (its kernel has no statistics epilogue, or its partials would not lie inside one image)");
+    // A bit ASKS for its kernel: a route that is not the family asked for (a geometry or scratch size the kernel cannot take, e.g. 16 one-tile
+    // 4x4 images on a 64- / 32-channel F(4x4) n-tile) is an error, not a silent drop to another kernel -- tests that compare "the F(4x4)
+    // kernel" with the default path must not pass for the wrong reason
+    const ConvRoute R = conv_route(L);
+    const bool f4 = R.family == CONV_WINO4 || R.family == CONV_WINO4SP;
+    const bool direct = (a->force_direct & 1) && !R.head() && !f4;    // bit 0: the direct kernel, whatever the route (it has no statistics epilogue)
+    const int px = direct ? 0 : R.stats_px;
+    const struct { bool asked, got; const char *msg; } asks[] = {
+        {ask_f4, f4, "dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry"},
+        {(a->force_direct & 256) != 0, R.family == CONV_WINO4SP,
+         "dlpm_conv2d_f32: force_direct bit 256 asks for the sub-pixel upsampling kernel, which does not take this geometry / scratch size"},
+        {stats_out != nullptr, px > 0,
+         "dlpm_conv2d_stats_f32: this launch emits no statistics (its kernel has no statistics epilogue, or its partials would not lie inside one image)"},
+        {ask_head == 64, R.family == CONV_HEAD_FUSED, "dlpm_conv2d_f32: the one-pass head kernel does not take this shape / scratch size"},
+        {ask_head == 32, R.family == CONV_HEAD_GEMM, "dlpm_conv2d_f32: the GEMM + gather head does not take this shape / scratch size"},
+    };
+    for (const auto &q : asks)
+        if (q.asked && !q.got) {
+            set_error("%s", q.msg);
             return DLPM_ERR_UNSUPPORTED;
         }
+    if (stats_out) {
         L.stats_out = reinterpret_cast<float2 *>(stats_out);
         *stats_px = px;
     }
-    if (L.w_wino4 && !ig) return L.w_wino4sp ? launch_conv_wino4sp(L, st) : launch_conv_wino4(L, st);   // (input channels a multiple of 8 but not of 32)
-    if ((a->force_direct & 64) && a->ksize == 3 && a->Cout <= 3 && a->C0 % 32 == 0 && a->C1 == 0) {
-        // bit 64: the one-pass head kernel (head_fused.hip; in the UNet it also carries the sampler's update): W' fragments in scratch
-        L.w_hfused = scratch_dev;
-        L.gemm = (a->force_direct & 128) ? DLPM_GEMM_F32 : DLPM_GEMM_AUTO;   // bit 128: its fp32-MFMA form instead of the bf16 x 3 one
-        if (a->scratch_floats >= head_fused_weight_floats(a->C0) && head_fused_ok(L)) {
-            TRY(relayout_weight_head_fused(a->weight, scratch_dev, a->Cout, a->C0, st));
-            return launch_conv_head_fused(L, nullptr, st);
-        }
-        set_error("dlpm_conv2d_f32: the one-pass head kernel does not take this shape / scratch size");
-        return DLPM_ERR_UNSUPPORTED;
-    }
-    if ((a->force_direct & 32) && a->ksize == 3 && a->Cout <= 3 && a->C0 % 32 == 0 && a->C1 == 0) {
-        // bit 32: the head as a 1x1 GEMM onto 9 Cout tap channels + gather: W' at the front of the scratch buffer, P behind it
-        const int64_t wsz = (int64_t)head_taps_rows(a->Cout) * a->C0;
-        L.w_taps = scratch_dev;   // (head_gemm_ok only looks at the pointer)
-        if (a->scratch_floats >= wsz + head_gemm_scratch_floats(L) && head_gemm_ok(L)) {
-            TRY(relayout_weight_head_taps(a->weight, scratch_dev, a->Cout, a->C0, st));
-            return launch_conv_head_gemm(L, nullptr, scratch_dev + wsz, st);
-        }
-        set_error("dlpm_conv2d_f32: the GEMM + gather head does not take this shape / scratch size");
-        return DLPM_ERR_UNSUPPORTED;
-    }
-    if (!(a->force_direct & 7) && a->ksize == 3 && a->Cout <= 4 && a->C0 % 32 == 0 && a->C1 == 0) {
-        // [tap][cin][4] copy at the END of the scratch buffer (the front holds the layouts built above)
-        const int64_t front = (int64_t)a->Cout * a->C0 * 9 + frag_weight_floats(a->Cout, a->C0);
-        const int64_t wsz = (int64_t)9 * a->C0 * 4;
-        if (a->scratch_floats >= front + wsz) {
-            float *ws = scratch_dev + (a->scratch_floats - wsz);
-            TRY(relayout_weight_head(a->weight, ws, a->Cout, a->C0, st));
-            L.w_small = ws;
-            if (head_conv_ok(L)) return launch_conv_head(L, nullptr, st);
-        }
-    }
-    if (ig) return launch_conv_igemm(L, st);
-    return (a->force_direct & 1) ? launch_conv_direct(L, st) : launch_conv_fallback(L, st);
+    if (R.family == CONV_WINO4SP) TRY(relayout_weight_wino4sp(a->weight, const_cast<float *>(L.w_wino4sp), a->Cout, Cin_, st));
+    if (R.family == CONV_HEAD_FUSED) TRY(relayout_weight_head_fused(a->weight, scratch_dev, a->Cout, a->C0, st));
+    if (R.family == CONV_HEAD_GEMM) TRY(relayout_weight_head_taps(a->weight, scratch_dev, a->Cout, a->C0, st));
+    if (R.family == CONV_HEAD) TRY(relayout_weight_head(a->weight, small_dev, a->Cout, a->C0, st));
+    if (direct) return launch_conv_direct(L, st);
+    return launch_conv(L, nullptr, scratch_dev + taps_floats, st);
 }
 
 extern "C" int dlpm_groupnorm_coeffs_f32(const float *src0, const float *src1, int32_t C0, int32_t C1, int32_t B, int32_t HW,
@@ -1529,7 +1504,9 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
         ConvLaunch s;
         s.src0 = a->x0; s.src1 = a->x1; s.C0 = a->C0; s.C1 = a->C1; s.B = a->B; s.Hin = s.Hout = a->H; s.Win = s.Wout = a->W;
         s.ks = 1; s.Cout = CO; s.w = a->skip_w; s.bias = a->skip_b; s.out = sk; s.gemm = DLPM_GEMM_F32;
-        TRY(launch_conv_igemm(s, st));
+        // (skip_w is in the reference's [O][I] layout, which is the implicit GEMM's: the direct kernel would misread it)
+        DLPM_CHECK_ARG(igemm_supported(s), "dlpm_resblock_img_f32: the skip convolution takes %d + %d input channels only in multiples of 32 per source", a->C0, a->C1);
+        TRY(launch_conv(s, nullptr, nullptr, st));
         r.res = sk;
     } else {
         r.res = a->x0;

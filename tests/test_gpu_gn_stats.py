@@ -326,7 +326,7 @@ REFUSALS = [
 
 @pytest.mark.parametrize('case', REFUSALS, ids=[c[0] for c in REFUSALS])
 def test_refusals(case):
-    """dlpm_conv2d_stats_f32 answers DLPM_ERR_UNSUPPORTED exactly where conv_stats_pixels is 0 -- the condition under which the plan
+    """dlpm_conv2d_stats_f32 answers DLPM_ERR_UNSUPPORTED exactly where conv_route gives stats_px = 0 -- the condition under which the plan
     falls back to reading the tensor -- and the same launch without statistics runs."""
     name, shape, Cout, ks, kw = case
     g = torch.Generator().manual_seed(sum(map(ord, name)))
