@@ -76,6 +76,14 @@ class ConvArgs(C.Structure):
                 ('out', vp), ('Cout', i32), ('in_nchw', i32), ('out_nchw', i32), ('force_direct', i32), ('scratch_floats', i64)]
 
 
+class ConvRoute(C.Structure):        # dlpm_conv_route, include/dlpm_amd_conv.h
+    _fields_ = [('family', i32), ('bh', i32), ('bw', i32), ('nimg', i32), ('nq', i32), ('stats_px', i32), ('ksplit', i32),
+                ('reserved', i32), ('grid', i64), ('scratch_floats', i64), ('partial_floats', i64)]
+
+
+CONV_FAMILIES = ('HEAD_FUSED', 'HEAD_GEMM', 'HEAD', 'SPLIT', 'WINO4SP', 'WINO4', 'WINO', 'IGEMM', 'STEM', 'DIRECT')   # dlpm_conv_family
+
+
 class ResBlockArgs(C.Structure):
     _fields_ = [('x0', vp), ('x1', vp), ('C0', i32), ('C1', i32), ('B', i32), ('H', i32), ('W', i32), ('gn1_w', vp), ('gn1_b', vp),
                 ('conv1_w', vp), ('conv1_b', vp), ('ss', vp), ('ss_stride', i64), ('gn2_w', vp), ('gn2_b', vp), ('conv2_w', vp),
@@ -225,6 +233,11 @@ SIGNATURES_CHAINS = {
     'dlpm_sampler_chains': (i32, [vp]),
     'dlpm_sampler_graph_captures': (i64, [vp]),
 }
+# the same for include/dlpm_amd_conv.h (one 3x3 launch under a declared conv policy)
+SIGNATURES_CONV = {
+    'dlpm_conv_policy_route': (C.c_int, [C.POINTER(ConvArgs), i32, i64, C.POINTER(ConvRoute)]),
+    'dlpm_conv_policy_f32': (C.c_int, [C.POINTER(ConvArgs), i32, i64, vp, vp, i64, vp, C.POINTER(i32), C.POINTER(ConvRoute), vp]),
+}
 
 _lib = None
 
@@ -242,7 +255,7 @@ def lib():
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
-                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()):
+                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -49,6 +49,7 @@ def build(force=False, verbose=True):
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_lim.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_toy.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_chains.h'))
+    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_conv.h'))
     jobs = []
     objs = []
     for src in SOURCES:

@@ -166,6 +166,21 @@ bool conv_split_ok(const ConvLaunch &c);
 int launch_conv_split(const ConvLaunch &c, hipStream_t st);
 int64_t split_weight_floats(int Cout, int Cin, int taps);
 int relayout_weight_split(const float *oihw_dev, void *dst_dev, int Cout, int Cin, int taps, hipStream_t st);
+// The weight layouts the UNet builds for a 3x3 layer besides the plain one (prep_conv, narrow_wino4_copies), as a function of the layer
+// and the declared batch: the ONE place that decides them.  Reads of `c`: C0, C1, Cout, ks, stride, in_nchw / out_nchw (a boundary or
+// stride-2 layer gets the fragment copy only), ups with Hin x Win (the low-res size of an Upsample convolution), dispatch_B.
+constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
+struct Conv3Layouts {
+    bool frag = false, wino = false, wino4 = false, wino4sp = false;
+    bool narrow = false;    // the 64- / 32-channel n-tile copies of the F(4x4) weights: Cout % 128 == 0 under a small declared batch
+};
+bool wino4_narrow_copies_wanted(int Cout, int64_t dispatch_B);
+Conv3Layouts conv3_layouts(const ConvLaunch &c);
+// A convolution launch as its route asks for it (conv_splitk.hip): launch_conv where r.ksplit <= 1; otherwise the split-K form -- the launch
+// stripped of bias / residual / statistics runs r.ksplit grid copies into part (splitk_partial_floats(c, r) floats, left holding the
+// partial outputs), then launch_splitk_reduce forms c.out.  r = conv_route(c).
+int64_t splitk_partial_floats(const ConvLaunch &c, const ConvRoute &r);
+int launch_conv_splitk(const ConvLaunch &c, const ConvRoute &r, float *part, hipStream_t st);
 // out = bias + sum_s part[s] (+ residual [res0 | res1]) over n = B Hout Wout pixels x Cout channels, partials summed in ascending s
 int launch_splitk_reduce(const float *part, int S, int64_t npix, int Cout, const float *bias, const float *res0, const float *res1, int R0,
                          float *out, hipStream_t st);

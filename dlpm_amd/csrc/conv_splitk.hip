@@ -1,4 +1,4 @@
-// conv_splitk.hip -- the reduction behind a split-K convolution launch (round 6).
+// conv_splitk.hip -- a split-K convolution launch (launch_conv_splitk) and the reduction behind it (round 6).
 //
 // At a small DECLARED batch the 8x8 / 4x4 levels of a UNet launch 16-128 workgroups that each walk a K loop of 32-64 serial phases
 // (the CIFAR net at B = 64: 14 F(2x2) launches of ~100 us on 16 workgroups).  conv_route (ConvRoute::ksplit) cuts that loop over 2 / 4 / 8 grid copies
@@ -48,6 +48,22 @@ int launch_splitk_reduce(const float *part, int S, int64_t npix, int Cout, const
     k_splitk_reduce<<<(unsigned)ceil_div(n4, 256), 256, 0, st>>>(part, S, n4, n4, Cout, bias, res0, res1, R0 ? R0 : Cout, out);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
+}
+
+int64_t splitk_partial_floats(const ConvLaunch &c, const ConvRoute &r) {
+    return r.ksplit > 1 ? (int64_t)r.ksplit * c.B * c.Hout * c.Wout * c.Cout : 0;
+}
+
+// The ONE definition of a split-K launch: the plan (unet.hip: run_conv3) and the kernel-level entry (dlpm_conv_policy_f32) both run this.
+int launch_conv_splitk(const ConvLaunch &c, const ConvRoute &r, float *part, hipStream_t st) {
+    const int S = r.ksplit;
+    if (S <= 1) return launch_conv(c, nullptr, nullptr, st);
+    DLPM_CHECK_ARG(part, "launch_conv_splitk: a split-K launch needs its partial buffer");
+    ConvLaunch P = c;
+    P.bias = nullptr; P.res0 = nullptr; P.res1 = nullptr; P.R0 = 0; P.stats_out = nullptr; P.out = part; P.ksplit = S;
+    const int rc = launch_conv(P, nullptr, nullptr, st);
+    if (rc != DLPM_OK) return rc;
+    return launch_splitk_reduce(part, S, (int64_t)c.B * c.Hout * c.Wout, c.Cout, c.bias, c.res0, c.res1, c.R0, c.out, st);
 }
 
 }  // namespace dlpm

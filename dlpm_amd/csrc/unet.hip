@@ -23,6 +23,7 @@
 
 #include "conv.h"
 #include "../../include/dlpm_amd_chains.h"
+#include "../../include/dlpm_amd_conv.h"
 
 using namespace dlpm;
 
@@ -290,6 +291,8 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  /
     ConvLaunch probe;
     probe.C0 = C0; probe.C1 = c.cin - C0; probe.Cout = c.cout; probe.ks = c.ks;
     probe.in_nchw = boundary == 1; probe.out_nchw = boundary == 2;
+    probe.stride = boundary == 4 ? 2 : 1; probe.ups = ups_lo > 0; probe.Hin = probe.Win = ups_lo;
+    const Conv3Layouts lay = conv3_layouts(probe);     // (the narrow F(4x4) copies come and go with the declared batch: narrow_wino4_copies)
     c.use_igemm = igemm_supported(probe);
     const float *src = u->params[c.p_w].dev;
     if (c.use_igemm && c.ks == 1) {  // [O][I] row-major is already the igemm layout
@@ -327,20 +330,20 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  /
         int r = relayout_weight_split(src, c.w_split, c.cout, c.cin, 9, nullptr);
         if (r != DLPM_OK) return r;
     }
-    if (c.use_igemm && c.ks == 3 && c.cin % 32 == 0) {
+    if (lay.frag) {     // which copies a 3x3 layer gets: conv3_layouts (conv.h)
         DLPM_HIP(hipMalloc(&c.w_frag, (size_t)frag_weight_floats(c.cout, c.cin) * sizeof(float)));
         int r = relayout_weight_frag(src, c.w_frag, c.cout, c.cin, nullptr);
         if (r != DLPM_OK) return r;
-        if (c.cout % 64 == 0 && c.cin % 16 == 0 && boundary == 0) {   // Winograd-domain copy (stride-1 launches pick it up)
+        if (lay.wino) {   // Winograd-domain copy (stride-1 launches pick it up)
             DLPM_HIP(hipMalloc(&c.w_wino, (size_t)wino_weight_floats(c.cout, c.cin) * sizeof(float)));
             r = relayout_weight_wino(src, c.w_wino, c.cout, c.cin, nullptr);
             if (r != DLPM_OK) return r;
         }
-        if (wino4_enabled() && c.cout % 32 == 0 && c.cin % 8 == 0 && boundary == 0) {   // F(4x4,3x3) copy (128-, 64- or 32-channel n-tiles)
+        if (lay.wino4) {   // F(4x4,3x3) copy (128-, 64- or 32-channel n-tiles)
             DLPM_HIP(hipMalloc(&c.w_wino4, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)));
             r = relayout_weight_wino4(src, c.w_wino4, c.cout, c.cin, nullptr);
             if (r != DLPM_OK) return r;
-            if (ups_lo > 0 && wino4sp_layer_ok(c.cout, c.cin, ups_lo, ups_lo)) {   // sub-pixel copy of an Upsample convolution (104 floats per filter)
+            if (lay.wino4sp) {   // sub-pixel copy of an Upsample convolution (104 floats per filter)
                 DLPM_HIP(hipMalloc(&c.w_wino4sp, (size_t)wino4sp_weight_floats(c.cout, c.cin) * sizeof(float)));
                 r = relayout_weight_wino4sp(src, c.w_wino4sp, c.cout, c.cin, nullptr);
                 if (r != DLPM_OK) return r;
@@ -470,16 +473,13 @@ int gn_any(Ctx &cx, Tensor4 x0, Tensor4 x1, int p_gamma, int p_beta, const float
 }
 
 // A 3x3 stride-1 convolution of the plan, cut over S = ConvRoute::ksplit grid copies where the layer and the declared batch ask for it
-// (conv_splitk.hip): the copies write their partial outputs into an arena buffer, launch_splitk_reduce adds bias / residual.
+// (conv_splitk.hip: launch_conv_splitk, the one definition of that launch): the copies write their partial outputs into an arena buffer,
+// launch_splitk_reduce adds bias / residual.  L comes from conv_io, layouts and policy attached.
 int run_conv3(Ctx &cx, const ConvW &c, const ConvLaunch &L) {
-    const int S = conv_route(L).ksplit;
-    if (S <= 1) return run_conv(cx, c, L);
-    const int64_t npix = (int64_t)L.B * L.Hout * L.Wout;
-    float *part = cx.ws.alloc((int64_t)S * npix * c.cout);
-    ConvLaunch P = L;
-    P.bias = nullptr; P.res0 = nullptr; P.res1 = nullptr; P.R0 = 0; P.stats_out = nullptr; P.out = part; P.ksplit = S;
-    int rc = run_conv(cx, c, P);
-    if (rc == DLPM_OK) rc = enqueue(cx, launch_splitk_reduce, part, S, npix, c.cout, L.bias, L.res0, L.res1, L.R0, L.out);
+    const ConvRoute r = conv_route(L);
+    if (r.ksplit <= 1) return run_conv(cx, c, L);
+    float *part = cx.ws.alloc(splitk_partial_floats(L, r));
+    const int rc = enqueue(cx, launch_conv_splitk, L, r, part);
     cx.ws.release(part);
     return rc;
 }
@@ -886,12 +886,12 @@ static void free_conv(ConvW &c) {
 // Round 6: under a small DECLARED batch (dlpm_unet_set_conv_policy's dispatch_batch) the 128-channel-multiple F(4x4) layers may run on 64- / 32-
 // channel n-tiles (conv_wino4.hip: wino4_nq_for), which read the same Winograd-domain weights in another fragment order.  The copies
 // exist only while such a batch is declared (3x the F(4x4) weight bytes of those layers); built from the parameters, on the null stream.
-constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
+// Which layers and which declarations: wino4_narrow_copies_wanted (conv.h: NARROW_COPIES_MAX_BATCH), the rule conv3_layouts states.
 static int narrow_wino4_copies(dlpm_unet *u) {
-    const bool want = u->dispatch_B > 0 && u->dispatch_B <= NARROW_COPIES_MAX_BATCH;
     int rc = DLPM_OK;
     for_each_conv(u, [&](ConvW &c) {
         if (!c.w_wino4 || c.cout % 128 != 0) return;      // (the ResBlock and Upsample convolutions that carry F(4x4) weights)
+        const bool want = wino4_narrow_copies_wanted(c.cout, u->dispatch_B);
         for (auto &n : NARROW_LAYOUTS) {
             float *&dst = c.*n.copy;
             if (!want) free_dev(dst);
@@ -1278,6 +1278,17 @@ extern "C" void dlpm_unet_destroy(dlpm_unet *u) {
 // ---------------------------------------------------------------------------------------------
 // building-block entry points (parity tests call each kernel through the C ABI)
 // ---------------------------------------------------------------------------------------------
+// the launch a dlpm_conv_args describes, no weights or policy attached yet
+static ConvLaunch launch_of_args(const dlpm_conv_args *a) {
+    ConvLaunch L;
+    L.src0 = a->src0; L.src1 = a->src1; L.C0 = a->C0; L.C1 = a->C1; L.B = a->B;
+    L.Hin = a->Hin; L.Win = a->Win; L.Hout = a->Hout; L.Wout = a->Wout;
+    L.ks = a->ksize; L.stride = a->stride; L.ups = a->upsample;
+    L.bias = a->bias; L.coefA = a->coefA; L.coefB = a->coefB; L.act_silu = a->act_silu;
+    L.res0 = a->res0; L.res1 = a->res1; L.R0 = a->R0; L.out = a->out; L.Cout = a->Cout;
+    L.in_nchw = a->in_nchw; L.out_nchw = a->out_nchw;
+    return L;
+}
 static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream);
 extern "C" int dlpm_conv2d_f32(const dlpm_conv_args *a, float *scratch_dev, dlpm_stream_t stream) {
     return conv2d_entry(a, scratch_dev, nullptr, nullptr, stream);
@@ -1292,13 +1303,7 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     DLPM_CHECK_ARG(a->ksize == 1 || a->ksize == 3, "dlpm_conv2d_f32: ksize must be 1 or 3");
     DLPM_CHECK_ARG(a->stride == 1 || a->stride == 2, "dlpm_conv2d_f32: stride must be 1 or 2");
     DLPM_CHECK_ARG((a->C1 == 0) == (a->src1 == nullptr), "dlpm_conv2d_f32: src1/C1 mismatch");
-    ConvLaunch L;
-    L.src0 = a->src0; L.src1 = a->src1; L.C0 = a->C0; L.C1 = a->C1; L.B = a->B;
-    L.Hin = a->Hin; L.Win = a->Win; L.Hout = a->Hout; L.Wout = a->Wout;
-    L.ks = a->ksize; L.stride = a->stride; L.ups = a->upsample;
-    L.bias = a->bias; L.coefA = a->coefA; L.coefB = a->coefB; L.act_silu = a->act_silu;
-    L.res0 = a->res0; L.res1 = a->res1; L.R0 = a->R0; L.out = a->out; L.Cout = a->Cout;
-    L.in_nchw = a->in_nchw; L.out_nchw = a->out_nchw;
+    ConvLaunch L = launch_of_args(a);
     const bool ig = !(a->force_direct & 1) && igemm_supported(L);
     if ((a->in_nchw || a->out_nchw) && a->C1 != 0) {
         set_error("dlpm_conv2d_f32: NCHW boundary layouts do not combine with a concat input");
@@ -1399,6 +1404,114 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     if (R.family == CONV_HEAD) TRY(relayout_weight_head(a->weight, small_dev, a->Cout, a->C0, st));
     if (direct) return launch_conv_direct(L, st);
     return launch_conv(L, nullptr, scratch_dev + taps_floats, st);
+}
+
+// ---- a 3x3 stride-1 launch under a declared policy (include/dlpm_amd_conv.h)
+// The launch of `a` under (generation, dispatch_batch) with the layouts conv3_layouts gives the layer, laid out one behind the other
+// from `base` (each at a multiple of 64 floats); *used = their floats together.  Nothing is read through a pointer.
+static int policy_launch(const dlpm_conv_args *a, int32_t generation, int64_t dispatch_batch, float *base, ConvLaunch *out,
+                         Conv3Layouts *lay_out, int64_t *used_out) {
+    DLPM_CHECK_ARG(a, "dlpm_conv_policy: null argument");
+    DLPM_CHECK_ARG(generation >= DLPM_CONV_AUTO && generation <= DLPM_CONV_IGEMM, "dlpm_conv_policy: unknown generation %d", generation);
+    DLPM_CHECK_ARG(dispatch_batch >= 0, "dlpm_conv_policy: negative dispatch batch");
+    if (a->ksize != 3 || a->stride != 1 || a->in_nchw || a->out_nchw || a->Cout <= 4 || a->force_direct != 0) {
+        set_error("dlpm_conv_policy: takes 3x3 stride-1 NHWC launches with Cout > 4 and force_direct = 0");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    const int up = a->upsample ? 2 : 1;
+    DLPM_CHECK_ARG(a->B > 0 && a->C0 > 0 && a->C1 >= 0 && a->Hin > 0 && a->Win > 0 && a->Hout == up * a->Hin && a->Wout == up * a->Win &&
+                   a->R0 >= 0 && a->R0 <= a->Cout,
+                   "dlpm_conv_policy: B %d, C0 %d, C1 %d, %dx%d -> %dx%d, R0 %d", a->B, a->C0, a->C1, a->Hin, a->Win, a->Hout, a->Wout, a->R0);
+    ConvLaunch L = launch_of_args(a);
+    L.ups = a->upsample ? 1 : 0;
+    L.gen = generation;
+    L.dispatch_B = dispatch_batch;
+    const Conv3Layouts lay = conv3_layouts(L);
+    const int Cin = a->C0 + a->C1;
+    int64_t used = 0;
+    auto take = [&](bool has, int64_t nfloats) -> const float * {
+        if (!has) return nullptr;
+        const float *p = base + used;
+        used += (nfloats + 63) / 64 * 64;
+        return p;
+    };
+    L.w = take(true, (int64_t)a->Cout * Cin * 9);
+    L.w_frag = take(lay.frag, lay.frag ? frag_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino = take(lay.wino, lay.wino ? wino_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino4 = take(lay.wino4, lay.wino4 ? wino4_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino4sp = take(lay.wino4sp, lay.wino4sp ? wino4sp_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino4_n64 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino4_n32 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
+    *out = L;
+    *lay_out = lay;
+    *used_out = used;
+    return DLPM_OK;
+}
+
+static void policy_route_out(const ConvLaunch &L, const ConvRoute &R, int64_t used, dlpm_conv_route *r) {
+    r->family = (int32_t)R.family;
+    r->bh = R.bh; r->bw = R.bw; r->nimg = R.nimg; r->nq = R.nq; r->stats_px = R.stats_px; r->ksplit = R.ksplit;
+    r->reserved = 0;
+    r->grid = R.grid;
+    r->scratch_floats = used;
+    r->partial_floats = splitk_partial_floats(L, R);
+}
+
+extern "C" int dlpm_conv_policy_route(const dlpm_conv_args *a, int32_t generation, int64_t dispatch_batch, dlpm_conv_route *route) {
+    DLPM_CHECK_ARG(route, "dlpm_conv_policy_route: null argument");
+    ConvLaunch L;
+    Conv3Layouts lay;
+    int64_t used = 0;
+    // (a base that is never dereferenced, as the plan's dry run: conv_route asks only which layouts a launch carries)
+    TRY(policy_launch(a, generation, dispatch_batch, reinterpret_cast<float *>(uintptr_t(1) << 20), &L, &lay, &used));
+    policy_route_out(L, conv_route(L), used, route);
+    return DLPM_OK;
+}
+
+extern "C" int dlpm_conv_policy_f32(const dlpm_conv_args *a, int32_t generation, int64_t dispatch_batch, float *scratch_dev,
+                                    float *partial_dev, int64_t partial_floats, float *stats_out, int32_t *stats_px, dlpm_conv_route *route,
+                                    dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(a && a->src0 && a->weight && a->out && scratch_dev, "dlpm_conv_policy_f32: null argument");
+    DLPM_CHECK_ARG((a->C1 == 0) == (a->src1 == nullptr), "dlpm_conv_policy_f32: src1/C1 mismatch");
+    DLPM_CHECK_ARG((stats_out == nullptr) == (stats_px == nullptr), "dlpm_conv_policy_f32: stats_out and stats_px go together");
+    ConvLaunch L;
+    Conv3Layouts lay;
+    int64_t used = 0;
+    TRY(policy_launch(a, generation, dispatch_batch, scratch_dev, &L, &lay, &used));
+    const ConvRoute R = conv_route(L);
+    const int64_t need = splitk_partial_floats(L, R);
+    if (a->scratch_floats < used) {
+        set_error("dlpm_conv_policy_f32: the weight layouts of this layer take %lld floats of scratch, %lld given", (long long)used,
+                  (long long)a->scratch_floats);
+        return DLPM_ERR_NOMEM;
+    }
+    if (need > 0 && (!partial_dev || partial_floats < need)) {
+        set_error("dlpm_conv_policy_f32: split-K over %d copies writes %lld floats of partial outputs, %lld given", R.ksplit, (long long)need,
+                  (long long)(partial_dev ? partial_floats : 0));
+        return DLPM_ERR_NOMEM;
+    }
+    if (stats_out && R.stats_px <= 0) {
+        set_error("dlpm_conv_policy_f32: this launch emits no statistics (a split-K launch, or a kernel whose partials would not lie inside one image)");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = as_stream(stream);
+    const int Cin = a->C0 + a->C1;
+    auto at = [](const float *p) { return const_cast<float *>(p); };     // the layouts are const in the launch; here they are written
+    TRY(relayout_weight(a->weight, at(L.w), a->Cout, Cin, 3, igemm_supported(L), st));
+    if (lay.frag) TRY(relayout_weight_frag(a->weight, at(L.w_frag), a->Cout, Cin, st));
+    if (lay.wino) TRY(relayout_weight_wino(a->weight, at(L.w_wino), a->Cout, Cin, st));
+    if (lay.wino4) TRY(relayout_weight_wino4(a->weight, at(L.w_wino4), a->Cout, Cin, st));
+    if (lay.wino4sp) TRY(relayout_weight_wino4sp(a->weight, at(L.w_wino4sp), a->Cout, Cin, st));
+    if (lay.narrow) {
+        TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n64), a->Cout, Cin, st, 64));
+        TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n32), a->Cout, Cin, st, 32));
+    }
+    if (stats_out) {
+        L.stats_out = reinterpret_cast<float2 *>(stats_out);
+        *stats_px = R.stats_px;
+    }
+    if (route) policy_route_out(L, R, used, route);
+    return launch_conv_splitk(L, R, partial_dev, st);
 }
 
 extern "C" int dlpm_groupnorm_coeffs_f32(const float *src0, const float *src1, int32_t C0, int32_t C1, int32_t B, int32_t HW,

@@ -177,6 +177,14 @@ def check_partials(name):
     args, kw = make(name)
     plain = run_conv(*args, **kw)
     assert torch.equal(out, plain), '%s: the launch with statistics wrote another output than the launch without' % name
+    return check_partials_of(name, out, buf, px, px_want, lay, PARTIALS_BOUND.get(name, (1e-5, 1e-5)))
+
+
+def check_partials_of(name, out, buf, px, px_want, lay, bounds):
+    """The statistics a launch left in the NaN-prefilled buffer `buf` beside its NCHW output `out`: px is the stated value, exactly the
+    first B (HW / px) Cout slots are written, every partial is the fp64 mean and centred sum of squares of its own pixels (layout
+    `lay`) within `bounds`.  (Any launch: tests/test_gpu_conv_policy.py brings one of its own.)"""
+    B, Cout = out.shape[:2]
     assert px == px_want, (name, px, px_want)
     HW = out.shape[2] * out.shape[3]
     n = 2 * B * (HW // px) * Cout
@@ -191,7 +199,7 @@ def check_partials(name):
     want_M2 = ((pix - want_m[..., None]) ** 2).sum(-1)
     e_m = (part[..., 0] - want_m).abs().max().item()
     e_M2 = ((part[..., 1] - want_M2).abs() / (1 + want_M2)).max().item()
-    tol_m, tol_M2 = PARTIALS_BOUND.get(name, (1e-5, 1e-5))
+    tol_m, tol_M2 = bounds
     print('%s: px %d, %d slots, max |mean - fp64| %.3g (bound %.3g), max |M2 - fp64| / (1 + M2) %.3g (bound %.3g)' % (
         name, px, n // 2, e_m, tol_m, e_M2, tol_M2))
     assert e_m < tol_m and e_M2 < tol_M2, (name, e_m, e_M2)
