@@ -1565,9 +1565,6 @@ extern "C" int dlpm_resblock_small_f32(const dlpm_resblock_args *a, float *scrat
                    (long long)(n1 + n2 + ns));
     DLPM_CHECK_ARG(small_weight_ok(64, Cin, 3), "dlpm_resblock_small_f32: %d input channels (64 or 128)", Cin);
     hipStream_t st = as_stream(stream);
-    TRY(relayout_weight_small(a->conv1_w, scratch_dev, 64, Cin, 3, st));
-    TRY(relayout_weight_small(a->conv2_w, scratch_dev + n1, 64, 64, 3, st));
-    if (a->skip_w) TRY(relayout_weight_small(a->skip_w, scratch_dev + n1 + n2, 64, Cin, 1, st));
     ResSmallLaunch r;
     r.x0 = a->x0; r.x1 = a->x1; r.C0 = a->C0; r.C1 = a->C1; r.B = a->B; r.H = a->H; r.W = a->W;
     r.gn1_w = a->gn1_w; r.gn1_b = a->gn1_b; r.gn2_w = a->gn2_w; r.gn2_b = a->gn2_b;
@@ -1575,6 +1572,18 @@ extern "C" int dlpm_resblock_small_f32(const dlpm_resblock_args *a, float *scrat
     r.wsf = a->skip_w ? scratch_dev + n1 + n2 : nullptr; r.bs = a->skip_b;
     r.emb = a->ss; r.emb_stride = a->ss_stride; r.emb_off = 0;
     r.out = a->out; r.stats_out = reinterpret_cast<float2 *>(a->stats_out);
+    // (asked before the first launch: a refused block leaves the scratch untouched)
+    if (!res_small_ok(r)) {
+        if (!small_blocks_enabled())
+            set_error("dlpm_resblock_small_f32: the fused blocks are switched off (DLPM_NO_FUSED_BLOCKS=1)");
+        else
+            set_error("dlpm_resblock_small_f32: %d + %d input channels %s skip_w (each source a multiple of 4; skip_w exactly when C0 + C1 = 128)",
+                      a->C0, a->C1, a->skip_w ? "with" : "without");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    TRY(relayout_weight_small(a->conv1_w, scratch_dev, 64, Cin, 3, st));
+    TRY(relayout_weight_small(a->conv2_w, scratch_dev + n1, 64, 64, 3, st));
+    if (a->skip_w) TRY(relayout_weight_small(a->skip_w, scratch_dev + n1 + n2, 64, Cin, 1, st));
     return launch_resblock_small(r, st);
 }
 
@@ -1603,9 +1612,6 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
     float *hb = cB + (int64_t)a->B * Cin, *sk = hb + (int64_t)a->B * HW * CO;
     hb += (64 - ((hb - scratch_dev) & 63)) & 63;          // (16-byte rows: float4 staging loads)
     sk = hb + (int64_t)a->B * HW * CO;
-    TRY(relayout_weight_wino4(a->conv1_w, w1, CO, Cin, st));
-    TRY(relayout_weight_wino4(a->conv2_w, w2, CO, CO, st));
-    TRY(launch_gn_coeffs(a->x0, a->x1, a->C0, a->C1, a->B, HW, 32, a->gn1_w, a->gn1_b, nullptr, 0, 0, cA, cB, st));
     ResImgLaunch r;
     r.x0 = a->x0; r.x1 = a->x1; r.C0 = a->C0; r.C1 = a->C1; r.B = a->B; r.H = a->H;
     r.coefA1 = cA; r.coefB1 = cB;
@@ -1613,17 +1619,15 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
     r.w1 = w1; r.b1 = a->conv1_b; r.w2 = w2; r.b2 = a->conv2_b;
     r.emb = a->ss; r.emb_stride = a->ss_stride; r.emb_off = 0;
     r.hbuf = hb; r.out = a->out; r.stats_out = reinterpret_cast<float2 *>(a->stats_out);
+    r.res = a->skip_w ? sk : a->x0;
+    ConvLaunch s;
     if (a->skip_w) {
-        ConvLaunch s;
         s.src0 = a->x0; s.src1 = a->x1; s.C0 = a->C0; s.C1 = a->C1; s.B = a->B; s.Hin = s.Hout = a->H; s.Win = s.Wout = a->W;
         s.ks = 1; s.Cout = CO; s.w = a->skip_w; s.bias = a->skip_b; s.out = sk; s.gemm = DLPM_GEMM_F32;
         // (skip_w is in the reference's [O][I] layout, which is the implicit GEMM's: the direct kernel would misread it)
         DLPM_CHECK_ARG(igemm_supported(s), "dlpm_resblock_img_f32: the skip convolution takes %d + %d input channels only in multiples of 32 per source", a->C0, a->C1);
-        TRY(launch_conv(s, nullptr, nullptr, st));
-        r.res = sk;
-    } else {
-        r.res = a->x0;
     }
+    // (every refusal before the first launch: a refused block leaves the scratch untouched)
     if (!res_img_ok(r)) {
         ResImgLaunch plain = r;      // 64 input channels from one source: refused only when the kernel is switched off
         plain.C0 = 64; plain.C1 = 0;
@@ -1633,6 +1637,10 @@ extern "C" int dlpm_resblock_img_f32(const dlpm_resblock_args *a, float *scratch
             set_error("dlpm_resblock_img_f32: the whole-image ResBlock kernel does not take %d + %d input channels on %d x %d images", a->C0, a->C1, a->H, a->W);
         return DLPM_ERR_UNSUPPORTED;
     }
+    TRY(relayout_weight_wino4(a->conv1_w, w1, CO, Cin, st));
+    TRY(relayout_weight_wino4(a->conv2_w, w2, CO, CO, st));
+    TRY(launch_gn_coeffs(a->x0, a->x1, a->C0, a->C1, a->B, HW, 32, a->gn1_w, a->gn1_b, nullptr, 0, 0, cA, cB, st));
+    if (a->skip_w) TRY(launch_conv(s, nullptr, nullptr, st));
     return launch_resblock_img(r, st);
 }
 

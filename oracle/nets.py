@@ -11,6 +11,11 @@ import torch
 import torch.nn.functional as F
 
 
+def _fp(x):
+    """fp32 as the reference computes -- except a float64 input, which keeps its type (the float64 references of the tests)."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def silu(x):
     # dlpm/models/nn.py:12-14
     return x * torch.sigmoid(x)
@@ -19,8 +24,8 @@ def silu(x):
 def timestep_embedding(t, dim, max_period=10000):
     """[cos | sin] sinusoidal features of (possibly fractional) t: dlpm/models/nn.py:103-121."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half)
-    ang = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=_fp(t).dtype) / half)
+    ang = _fp(t[:, None]) * freqs[None]
     out = torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1)
     if dim % 2:
         out = torch.cat([out, torch.zeros_like(out[:, :1])], dim=-1)
@@ -29,7 +34,7 @@ def timestep_embedding(t, dim, max_period=10000):
 
 def group_norm(x, w, b):
     # GroupNorm32 with min(32, C) groups, eps 1e-5: nn.py:17-19,93-100; unet.py:141
-    return F.group_norm(x.float(), min(32, x.shape[1]), w, b, 1e-5)
+    return F.group_norm(_fp(x), min(32, x.shape[1]), w, b, 1e-5)
 
 
 def qkv_attention(qkv):
@@ -38,7 +43,7 @@ def qkv_attention(qkv):
     q, k, v = qkv[:, :ch], qkv[:, ch:2 * ch], qkv[:, 2 * ch:]
     sc = 1 / math.sqrt(math.sqrt(ch))
     w = torch.einsum('bct,bcs->bts', q * sc, k * sc)
-    w = torch.softmax(w.float(), dim=-1)
+    w = torch.softmax(_fp(w), dim=-1)
     return torch.einsum('bts,bcs->bct', w, v)
 
 
@@ -95,7 +100,7 @@ def unet_forward(sd, x, t, heads, return_feats=False):
     n_in = 1 + max(int(k.split('.')[1]) for k in sd if k.startswith('input_blocks.'))
     n_out = 1 + max(int(k.split('.')[1]) for k in sd if k.startswith('output_blocks.'))
     feats = {'down': [], 'up': []}
-    hs, h = [], x.float()
+    hs, h = [], _fp(x)
     for i in range(n_in):
         h = _run_seq(sd, 'input_blocks.%d.' % i, h, emb, heads)
         hs.append(h)

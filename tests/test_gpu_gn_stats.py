@@ -22,7 +22,8 @@ Statistics-writing site -> cases that reach it (CASES below; `sel` is dlpm_conv_
   k_conv_stem_lds (in_nchw)                                         stem_c{1,3}_{32,128,512}_{32b2,64}; cancel_stem
   k_conv_stem_regw (in_nchw, DLPM_NO_STEM_LDS=1)                    stem cases in the child of test_variant_behind_switch[DLPM_NO_STEM_LDS=1]
   k_gn_coeffs_stats / gn_coeffs_from_stats_image (gn_stats.h)       test_chain_* (every case above), test_chain_concat_unequal_partials (nt0 != nt1)
-(The sub-pixel kernel's partials: test_gpu_upsample_subpixel.py.  The whole-block kernels' own statistics: test_gpu_kernels.py.)
+(The sub-pixel kernel's partials: test_gpu_upsample_subpixel.py.  The whole-block kernels' own statistics: test_gpu_fused_blocks.py,
+through check_partials_of.)
 
 Bounds.  Partials: |mean - want| < 1e-5 and |M2 - want| / (1 + want) < 1e-5 (the fused blocks' and the sub-pixel test's statistics
 tolerances).  Chain: 3e-6 plain, 4e-6 with scale-shift + SiLU (test_groupnorm_coeffs_against_reference_fixture's, O(1) GroupNorm

@@ -1040,17 +1040,13 @@ def test_conv3x3_bf16_split_implicit_gemm(case):
 
 
 # ---------------------------------------------------------------- round 4: whole blocks of small images in one launch (block_small.hip)
-def _dev(t):
-    return t.to(DEV).contiguous()
-
-
 @pytest.mark.parametrize('cin,hs', [(64, 8), (64, 4), (128, 8), (128, 4)])
 def test_fused_small_resblock_vs_reference(cin, hs):
     """k_resblock_small (GroupNorm + SiLU + conv3x3 + GroupNorm x (1 + scale) + shift + SiLU + conv3x3 + skip in ONE launch, one
     workgroup per image) against the reference's ResBlock (unet.py:105-196) on the F13 fixtures -- 64 -> 64 with the identity
     skip, 128 (= concat 64 | 64) -> 64 with the 1x1 skip convolution, 8x8 and 4x4 -- and bit-independence of the batch."""
-    import ctypes as C
     import small_block_weights as sbw
+    from test_gpu_fused_blocks import image, launch_res      # (the launch every whole-block test shares)
     from oracle import nets
     f = golden('f13_small_blocks')
     tag = 'res_c%d_h%d_' % (cin, hs)
@@ -1058,37 +1054,10 @@ def test_fused_small_resblock_vs_reference(cin, hs):
     assert sbw.digest(sd) == bytes(f[tag + 'digest']).hex()
     x, emb, want = torch.from_numpy(f[tag + 'x']), torch.from_numpy(f[tag + 'emb']), f[tag + 'y']
     ss = torch.nn.functional.linear(nets.silu(emb), sd['emb_layers.1.weight'], sd['emb_layers.1.bias'])   # the block's emb_layers (host)
-    L, st = _lib.lib(), _lib.stream_ptr()
 
     def run(xb, ssb):
-        B = xb.shape[0]
-        xh = _dev(nhwc(xb))
-        keep = [xh]
-        a = _lib.ResBlockArgs()
-        if cin == 128:       # the output blocks' virtual concat: two tensors of 64 channels
-            x0, x1 = _dev(xh[..., :64]), _dev(xh[..., 64:])
-            keep += [x0, x1]
-            a.x0, a.x1, a.C0, a.C1 = x0.data_ptr(), x1.data_ptr(), 64, 64
-        else:
-            a.x0, a.x1, a.C0, a.C1 = xh.data_ptr(), None, 64, 0
-        a.B, a.H, a.W = B, hs, hs
-        w = {k: _dev(v) for k, v in sd.items()}
-        a.gn1_w, a.gn1_b = w['in_layers.0.weight'].data_ptr(), w['in_layers.0.bias'].data_ptr()
-        a.conv1_w, a.conv1_b = w['in_layers.2.weight'].data_ptr(), w['in_layers.2.bias'].data_ptr()
-        ssd = _dev(ssb)
-        a.ss, a.ss_stride = ssd.data_ptr(), 128
-        a.gn2_w, a.gn2_b = w['out_layers.0.weight'].data_ptr(), w['out_layers.0.bias'].data_ptr()
-        a.conv2_w, a.conv2_b = w['out_layers.3.weight'].data_ptr(), w['out_layers.3.bias'].data_ptr()
-        if cin == 128:
-            a.skip_w, a.skip_b = w['skip_connection.weight'].data_ptr(), w['skip_connection.bias'].data_ptr()
-        out = torch.empty(B, hs, hs, 64, device=DEV)
-        stats = torch.empty(B, 64, 2, device=DEV)
-        a.out, a.stats_out = out.data_ptr(), stats.data_ptr()
-        n = 64 * cin * 9 + 64 * 64 * 9 + 64 * cin
-        scratch = torch.empty(n, device=DEV)
-        _lib.check(L.dlpm_resblock_small_f32(C.byref(a), scratch.data_ptr(), n, st))
-        torch.cuda.synchronize()
-        return nchw(out).cpu(), stats.cpu()
+        r = launch_res('res_small', sd, xb, ssb, 64, cin - 64)
+        return image(r), r['stats'].view(-1, 64, 2)
 
     got, stats = run(x, ss)
     err = (got.numpy() - want).__abs__().max()
@@ -1110,8 +1079,8 @@ def test_whole_image_resblock_16x16_vs_reference(cin):
     """Round 6: k_resblock_wino4_img16 (a whole 64-channel ResBlock of a 16x16 image in one launch: the intermediate stays in LDS, the K loop is
     split over wave pairs) against the reference's ResBlock (unet.py:105-196) on the F14 fixtures -- 64 -> 64 with the identity skip, 128
     (= 64 | 64) and 96 (= 64 | 32) -> 64 with the 1x1 skip convolution -- its per-image statistics, and bit-independence of the batch."""
-    import ctypes as C
     import small_block_weights as sbw
+    from test_gpu_fused_blocks import image, launch_res      # (the launch every whole-block test shares)
     from oracle import nets
     f = golden('f14_blocks16')
     tag = 'res_c%d_o64_h16_' % cin
@@ -1121,37 +1090,10 @@ def test_whole_image_resblock_16x16_vs_reference(cin):
     assert sbw.input_digest(x, emb) == bytes(f[tag + 'xdigest']).hex()
     want = f[tag + 'y']
     ss = torch.nn.functional.linear(nets.silu(emb), sd['emb_layers.1.weight'], sd['emb_layers.1.bias'])
-    L, st = _lib.lib(), _lib.stream_ptr()
 
     def run(xb, ssb):
-        B = xb.shape[0]
-        xh = _dev(nhwc(xb))
-        keep = [xh]
-        a = _lib.ResBlockArgs()
-        if cin > 64:
-            x0, x1 = _dev(xh[..., :64]), _dev(xh[..., 64:])
-            keep += [x0, x1]
-            a.x0, a.x1, a.C0, a.C1 = x0.data_ptr(), x1.data_ptr(), 64, cin - 64
-        else:
-            a.x0, a.x1, a.C0, a.C1 = xh.data_ptr(), None, 64, 0
-        a.B, a.H, a.W = B, 16, 16
-        w = {k: _dev(v) for k, v in sd.items()}
-        a.gn1_w, a.gn1_b = w['in_layers.0.weight'].data_ptr(), w['in_layers.0.bias'].data_ptr()
-        a.conv1_w, a.conv1_b = w['in_layers.2.weight'].data_ptr(), w['in_layers.2.bias'].data_ptr()
-        ssd = _dev(ssb)
-        a.ss, a.ss_stride = ssd.data_ptr(), 128
-        a.gn2_w, a.gn2_b = w['out_layers.0.weight'].data_ptr(), w['out_layers.0.bias'].data_ptr()
-        a.conv2_w, a.conv2_b = w['out_layers.3.weight'].data_ptr(), w['out_layers.3.bias'].data_ptr()
-        if cin > 64:
-            a.skip_w, a.skip_b = w['skip_connection.weight'].data_ptr(), w['skip_connection.bias'].data_ptr()
-        out = torch.empty(B, 16, 16, 64, device=DEV)
-        stats = torch.empty(B, 64, 2, device=DEV)
-        a.out, a.stats_out = out.data_ptr(), stats.data_ptr()
-        n = L.dlpm_resblock_img_scratch_floats(B, cin)
-        scratch = torch.empty(n, device=DEV)
-        _lib.check(L.dlpm_resblock_img_f32(C.byref(a), scratch.data_ptr(), n, st))
-        torch.cuda.synchronize()
-        return nchw(out).cpu(), stats.cpu()
+        r = launch_res('res_img16', sd, xb, ssb, 64, cin - 64)
+        return image(r), r['stats'].view(-1, 64, 2)
 
     got, stats = run(x, ss)
     err = np.abs(got.numpy() - want).max()
@@ -1171,8 +1113,8 @@ def test_whole_image_resblock_vs_reference(cin):
     """Round 6: k_resblock_wino4_img (a whole 32-channel ResBlock of a 32x32 image in one launch, Winograd F(4x4,3x3) inside) against the
     reference's ResBlock (unet.py:105-196) on the F14 fixtures -- 32 -> 32 with the identity skip, 64 (= concat 32 | 32) and 96 (= 64 | 32)
     -> 32 with the 1x1 skip convolution -- the quadrant statistics it emits, and bit-independence of the batch."""
-    import ctypes as C
     import small_block_weights as sbw
+    from test_gpu_fused_blocks import image, launch_res      # (the launch every whole-block test shares)
     from oracle import nets
     f = golden('f14_blocks16')
     tag = 'res_c%d_o32_h32_' % cin
@@ -1182,38 +1124,11 @@ def test_whole_image_resblock_vs_reference(cin):
     assert sbw.input_digest(x, emb) == bytes(f[tag + 'xdigest']).hex()
     want = f[tag + 'y']
     ss = torch.nn.functional.linear(nets.silu(emb), sd['emb_layers.1.weight'], sd['emb_layers.1.bias'])   # the block's emb_layers (host)
-    L, st = _lib.lib(), _lib.stream_ptr()
     c0 = {32: 32, 64: 32, 96: 64}[cin]
 
     def run(xb, ssb):
-        B = xb.shape[0]
-        xh = _dev(nhwc(xb))
-        keep = [xh]
-        a = _lib.ResBlockArgs()
-        if cin > 32:       # the output blocks' virtual concat
-            x0, x1 = _dev(xh[..., :c0]), _dev(xh[..., c0:])
-            keep += [x0, x1]
-            a.x0, a.x1, a.C0, a.C1 = x0.data_ptr(), x1.data_ptr(), c0, cin - c0
-        else:
-            a.x0, a.x1, a.C0, a.C1 = xh.data_ptr(), None, 32, 0
-        a.B, a.H, a.W = B, 32, 32
-        w = {k: _dev(v) for k, v in sd.items()}
-        a.gn1_w, a.gn1_b = w['in_layers.0.weight'].data_ptr(), w['in_layers.0.bias'].data_ptr()
-        a.conv1_w, a.conv1_b = w['in_layers.2.weight'].data_ptr(), w['in_layers.2.bias'].data_ptr()
-        ssd = _dev(ssb)
-        a.ss, a.ss_stride = ssd.data_ptr(), 64
-        a.gn2_w, a.gn2_b = w['out_layers.0.weight'].data_ptr(), w['out_layers.0.bias'].data_ptr()
-        a.conv2_w, a.conv2_b = w['out_layers.3.weight'].data_ptr(), w['out_layers.3.bias'].data_ptr()
-        if cin > 32:
-            a.skip_w, a.skip_b = w['skip_connection.weight'].data_ptr(), w['skip_connection.bias'].data_ptr()
-        out = torch.empty(B, 32, 32, 32, device=DEV)
-        stats = torch.empty(B, 4, 32, 2, device=DEV)
-        a.out, a.stats_out = out.data_ptr(), stats.data_ptr()
-        n = L.dlpm_resblock_img_scratch_floats(B, cin)
-        scratch = torch.empty(n, device=DEV)
-        _lib.check(L.dlpm_resblock_img_f32(C.byref(a), scratch.data_ptr(), n, st))
-        torch.cuda.synchronize()
-        return nchw(out).cpu(), stats.cpu()
+        r = launch_res('res_img32', sd, xb, ssb, c0, cin - c0)
+        return image(r), r['stats'].view(-1, 4, 32, 2)
 
     got, stats = run(x, ss)
     err = np.abs(got.numpy() - want).max()
@@ -1236,32 +1151,17 @@ def test_fused_attention_block_16x16_vs_reference():
     """Round 6: k_attnblock16 (GroupNorm -> per head: qkv, softmax(q k^T) v, proj accumulated in registers -> + x, ONE launch per 16x16
     image) against the reference's AttentionBlock (unet.py:199-250) at T = 256 (tests/golden/f14_blocks16.npz), its per-image output
     statistics, and bit-independence of the batch."""
-    import ctypes as C
     import small_block_weights as sbw
+    from test_gpu_fused_blocks import image, launch_attn     # (the launch every whole-block test shares)
     f = golden('f14_blocks16')
     sd = sbw.attn16_state()
     assert sbw.digest(sd) == bytes(f['attn_h16_digest']).hex()
     x, want = sbw.attn16_input(), f['attn_h16_y']
     assert sbw.input_digest(x) == bytes(f['attn_h16_xdigest']).hex()
-    L, st = _lib.lib(), _lib.stream_ptr()
 
     def run(xb, with_stats=True):
-        B = xb.shape[0]
-        xh = _dev(nhwc(xb))
-        w = {k: _dev(v) for k, v in sd.items()}
-        a = _lib.AttnBlockArgs()
-        a.x, a.C, a.heads, a.B, a.H, a.W = xh.data_ptr(), 64, 4, B, 16, 16
-        a.gn_w, a.gn_b = w['norm.weight'].data_ptr(), w['norm.bias'].data_ptr()
-        a.qkv_w, a.qkv_b = w['qkv.weight'].data_ptr(), w['qkv.bias'].data_ptr()
-        a.proj_w, a.proj_b = w['proj_out.weight'].data_ptr(), w['proj_out.bias'].data_ptr()
-        out = torch.empty(B, 16, 16, 64, device=DEV)
-        stats = torch.zeros(B, 64, 2, device=DEV)
-        a.out, a.stats_out = out.data_ptr(), stats.data_ptr() if with_stats else None
-        n = 192 * 64 + 64 * 64
-        scratch = torch.empty(n, device=DEV)
-        _lib.check(L.dlpm_attnblock_small_f32(C.byref(a), scratch.data_ptr(), n, st))
-        torch.cuda.synchronize()
-        return nchw(out).cpu(), stats.cpu()
+        r = launch_attn(sd, xb, with_stats=with_stats)
+        return image(r), r['stats'].view(-1, 64, 2)
 
     got, stats = run(x)
     err = np.abs(got.numpy() - want).max()
@@ -1279,31 +1179,16 @@ def test_fused_attention_block_16x16_vs_reference():
 def test_fused_small_attention_block_vs_reference(hs):
     """k_attnblock_small (GroupNorm -> qkv -> softmax(q k^T) v per head -> proj -> + x in one launch) against the reference's
     AttentionBlock (unet.py:199-250), 64 channels, 4 heads, T = 64 and 16."""
-    import ctypes as C
     import small_block_weights as sbw
+    from test_gpu_fused_blocks import image, launch_attn     # (the launch every whole-block test shares)
     f = golden('f13_small_blocks')
     tag = 'attn_h%d_' % hs
     sd = sbw.attn_state(hs)
     assert sbw.digest(sd) == bytes(f[tag + 'digest']).hex()
     x, want = torch.from_numpy(f[tag + 'x']), f[tag + 'y']
-    L, st = _lib.lib(), _lib.stream_ptr()
 
     def run(xb):
-        B = xb.shape[0]
-        xh = _dev(nhwc(xb))
-        w = {k: _dev(v) for k, v in sd.items()}
-        a = _lib.AttnBlockArgs()
-        a.x, a.C, a.heads, a.B, a.H, a.W = xh.data_ptr(), 64, 4, B, hs, hs
-        a.gn_w, a.gn_b = w['norm.weight'].data_ptr(), w['norm.bias'].data_ptr()
-        a.qkv_w, a.qkv_b = w['qkv.weight'].data_ptr(), w['qkv.bias'].data_ptr()
-        a.proj_w, a.proj_b = w['proj_out.weight'].data_ptr(), w['proj_out.bias'].data_ptr()
-        out = torch.empty(B, hs, hs, 64, device=DEV)
-        a.out, a.stats_out = out.data_ptr(), None
-        n = 192 * 64 + 64 * 64
-        scratch = torch.empty(n, device=DEV)
-        _lib.check(L.dlpm_attnblock_small_f32(C.byref(a), scratch.data_ptr(), n, st))
-        torch.cuda.synchronize()
-        return nchw(out).cpu()
+        return image(launch_attn(sd, xb, with_stats=False))
 
     got = run(x)
     err = np.abs(got.numpy() - want).max()
