@@ -18,6 +18,7 @@ MEAN_TYPES = {'EPSILON': 0, 'START_X': 1, 'Z': 2, 'PREVIOUS_X': 3}   # dlpm_mean
 PRED_TO_XSTART, PRED_CLIP, PRED_TO_EPS, PRED_ELEMENTWISE = 1, 2, 4, 16
 LOSS_RESCALE_T, LOSS_ELEMENTWISE = 1, 16    # dlpm_loss_flags
 AT_T_Q_SAMPLE, AT_T_PREDICT_EPS, AT_T_PREDICT_XSTART = 0, 1, 2    # dlpm_at_t_mode
+ANT_DLPM, ANT_DLIM = 0, 1    # dlpm_anterior_mode
 CONV_AUTO, CONV_F4, CONV_F2, CONV_IGEMM = 0, 1, 2, 3
 GEMM_AUTO, GEMM_F32, GEMM_BF16X3 = 0, 1, 2
 
@@ -61,6 +62,20 @@ class ToyDrawArgs(C.Structure):      # dlpm_toy_draw_args, include/dlpm_amd_toy.
     _fields_ = [('out_dev', vp), ('perm_out_dev', vp), ('weights_host', vp), ('cum_dev', vp), ('bounds_dev', vp), ('N', i64),
                 ('first_index', i64), ('kind', i32), ('n_mixture', i32), ('count', i32), ('isotropic', i32), ('std', f64), ('theta', f64),
                 ('data_alpha', f64), ('seed', u64), ('stream', u32), ('reserved', u32)]
+
+
+class AnteriorArgs(C.Structure):     # dlpm_anterior_args, include/dlpm_amd_step.h
+    _fields_ = [('x_dev', vp), ('eps_dev', vp), ('t_dev', vp), ('g_dev', vp), ('bs_dev', vp), ('Sigmas_dev', vp), ('A_dev', vp),
+                ('mean_dev', vp), ('var_dev', vp), ('B', i64), ('D', i64), ('T', i32), ('mode', i32), ('flags', i32), ('alpha', f32),
+                ('eta', f32)]
+
+
+class TwoRvArgs(C.Structure):        # dlpm_two_rv_args, include/dlpm_amd_step.h
+    _fields_ = [('x0_dev', vp), ('t_dev', vp), ('g_dev', vp), ('bg_dev', vp), ('s_dev', vp), ('bs_dev', vp), ('a0_dev', vp),
+                ('a1_dev', vp), ('z_dev', vp), ('x_t_dev', vp), ('eps_t_dev', vp), ('m_tilde_dev', vp), ('Sigma_tilde_dev', vp),
+                ('lambda_dev', vp), ('Sigma_prime_t_1_dev', vp), ('Sigma_prime_t_dev', vp), ('Gamma_prime_dev', vp),
+                ('a0_out_dev', vp), ('a1_out_dev', vp), ('B', i64), ('D', i64), ('T', i32), ('flags', i32), ('alpha', f64),
+                ('clamp_a', f64), ('seed', u64), ('sample_offset', i64)]
 
 
 class UNetConfig(C.Structure):
@@ -238,6 +253,11 @@ SIGNATURES_CONV = {
     'dlpm_conv_policy_route': (C.c_int, [C.POINTER(ConvArgs), i32, i64, C.POINTER(ConvRoute)]),
     'dlpm_conv_policy_f32': (C.c_int, [C.POINTER(ConvArgs), i32, i64, vp, vp, i64, vp, C.POINTER(i32), C.POINTER(ConvRoute), vp]),
 }
+# the same for include/dlpm_amd_step.h (the step-level API: anterior moments, Proposition-8 elements)
+SIGNATURES_STEP = {
+    'dlpm_anterior_f32': (C.c_int, [C.POINTER(AnteriorArgs), vp]),
+    'dlpm_two_rv_elements_f32': (C.c_int, [C.POINTER(TwoRvArgs), vp]),
+}
 
 _lib = None
 
@@ -255,7 +275,7 @@ def lib():
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
-                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()):
+                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

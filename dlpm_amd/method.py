@@ -16,6 +16,11 @@ estimator, three kernels of libdlpm_amd around one forward.  With LIM=True it is
 symmetric alpha-stable draw, a continuous time, x_t from the VPSDE coefficients, the net, and the mean smooth-L1 against -e / alpha
 -- one kernel of its own (k_lim_loss_elements) and the terms / estimator kernels of the DLPM loss.
 
+One step at a time: `p_mean_variance`, `p_sample`, `ddim_sample` and the progressive loops
+(`p_sample_loop_progressive`, `ddim_sample_loop_progressive`) with the reference's signatures.  A progressive loop takes the
+trajectory's Philox key and tables at its first item; the step methods use them from then on, so a loop written by hand around
+`p_sample` draws what `p_sample_loop` draws.
+
 Two RNG modes:
   rng='philox'     device Philox4x32-10 keyed by (seed, GLOBAL sample index, step, element): the
                    samples do not depend on how a batch is sharded over GPUs (default);
@@ -129,6 +134,8 @@ class GenerativeLevyProcess:
         self._samplers = {}
         self.calls = 0          # number of sample() calls so far: folded into the Philox key
         self._dataset = None    # see dataset_stream()
+        self._traj = None       # (seed, first global sample index) of the trajectory a progressive loop began: p_sample's Philox key
+        self._native_owner = None   # the progressive generator that currently drives the native sampler (see _progressive)
 
     # -------------------------------------------------------------------------------- helpers
     def _scale_timesteps(self, t):
@@ -173,6 +180,7 @@ class GenerativeLevyProcess:
 
     def _native_sampler(self, model, shape, flags, eta, clamp_a, clamp_eps, seed, offset=None):
         offset = self.sample_offset if offset is None else offset
+        self._native_owner = None       # whoever was stepping the native sampler has lost its state
         lim = bool(flags & _lib.SMP_LIM)
         from .unet import UNetModel
         B = shape[0]
@@ -525,6 +533,230 @@ class GenerativeLevyProcess:
         return self._loop(model, shape, _lib.UPD_DLIM | (_lib.UPD_CLIP if clip_denoised else 0), eta, noise, denoised_fn,
                           model_kwargs, get_sample_history, progress)
 
+    # -------------------------------------------------------------------------------- one step at a time
+    def _step_eps(self, model, x, t, clip, denoised_fn, model_kwargs, fold_clip):
+        """The model call and what p_mean_variance does to its output (GenerativeLevyProcess.py:170-207), exactly as the loop of
+        _run_callable does it: EPSILON without clipping bypasses everything, every other case goes model output -> x_0 ->
+        [denoised_fn] -> [clamp] -> eps through dlpm_predict_f32.  `fold_clip`: leave "EPSILON + clip, no denoised_fn" to the update
+        kernel's own flag, as the loop does.  Returns (x as contiguous fp32, eps, the int32 [1] device timestep, update flags)."""
+        d = self.dlpm
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise _lib.DlpmError('the step methods run on the MI355X only (x is on {}); there is no CPU fallback'.format(
+                x.device if torch.is_tensor(x) else type(x).__name__))
+        B = x.shape[0]
+        assert torch.is_tensor(t) and t.shape == (B,), 't must be a [B] tensor'
+        _, D, n = d._cols(x.shape)
+        T = self.reverse_steps
+        if d._Sigmas is None or tuple(d._Sigmas.shape) != (T, n) or d._table_shape != tuple(x.shape):
+            raise _lib.DlpmError('the step methods need the tables of a trajectory of shape {}: iterate p_sample_loop_progressive / '
+                                 'ddim_sample_loop_progressive, or call dlpm.sample_A(shape, reverse_steps) and '
+                                 'dlpm.compute_Sigmas()'.format(tuple(x.shape)))
+        L, st = _lib.lib(), _lib.stream_ptr()
+        x = x.contiguous().float()
+        t = t.to(x.device)
+        t_dev = d._t_scalar(x, t)
+        isc = self._input_scale_dev()
+        xin = x if isc is None else x * isc[t.long()].view(-1, *([1] * (x.dim() - 1)))
+        eps = model(xin, self._scale_timesteps(t), **(model_kwargs or {}))
+        eps = eps.contiguous().float()
+        assert eps.shape == x.shape, 'the model returned {}, expected {}'.format(tuple(eps.shape), tuple(x.shape))
+        mean_type = _lib.MEAN_TYPES[self.model_mean_type]
+        flags = 0 if self.isotropic else _lib.UPD_ELEMENTWISE
+        predict = (mean_type != 0) or (clip and (denoised_fn is not None or not fold_clip))
+        if clip and not predict:
+            flags |= _lib.UPD_CLIP
+        if predict:
+            if eps.data_ptr() == x.data_ptr():          # a model that returns its input: the conversion below writes in place
+                eps = eps.clone()
+            pa = _lib.PredictArgs()
+            pa.t_dev, pa.g_dev, pa.bg_dev, pa.bs_dev = t_dev.data_ptr(), _lib.ptr(d.gammas), _lib.ptr(d.bargammas), _lib.ptr(d.barsigmas)
+            pa.c_eps_dev, pa.A_dev = d._c_eps.data_ptr(), d._A.data_ptr()
+            pa.B, pa.D, pa.T, pa.mean_type = B, D, T, mean_type
+            el = _lib.PRED_ELEMENTWISE if not self.isotropic else 0
+            tail = (_lib.PRED_CLIP if clip else 0) | _lib.PRED_TO_EPS | el
+            pa.x_dev, pa.in_dev, pa.out_dev = x.data_ptr(), eps.data_ptr(), eps.data_ptr()
+            if denoised_fn is None:
+                pa.flags = _lib.PRED_TO_XSTART | tail
+                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+            else:
+                pa.flags = _lib.PRED_TO_XSTART | el
+                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+                eps = denoised_fn(eps.view(x.shape)).contiguous().float()
+                pa.in_dev, pa.out_dev, pa.flags = eps.data_ptr(), eps.data_ptr(), tail
+                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+        return x, eps, t_dev, flags
+
+    def p_mean_variance(self, model, x, t, clip_denoised=False, denoised_fn=None, model_kwargs=None):
+        """GenerativeLevyProcess.p_mean_variance (:154-219): {'eps', 'mean', 'variance'} of p(x_{t-1} | x_t).  The model is called
+        with the scaled timesteps (and the input scaling of a scale_exploding process), its output becomes the eps of the step
+        formulas per model_mean_type / clip_denoised / denoised_fn (dlpm_predict_f32), and the moments come from
+        dlpm_anterior_f32 on the process's Sigmas -- the tables of the trajectory a progressive loop began, or of the caller's
+        own dlpm.sample_A / compute_Sigmas.  `t`: a [B] tensor; the step formulas use its first entry, as the reference does
+        (t[0], :210).  'variance' is a stride-0 view of [B] when the noise is isotropic.  No host read."""
+        with torch.no_grad():
+            x, eps, _, _ = self._step_eps(model, x, t, clip_denoised, denoised_fn, model_kwargs, fold_clip=False)
+            mean, var = self.dlpm.anterior_mean_variance_dlpm(x, t, eps)
+        return {'eps': eps, 'mean': mean, 'variance': var}
+
+    def _step(self, model, x, t, clip, denoised_fn, model_kwargs, dlim, eta, noise):
+        """One reverse step as the loops take it: the eps of _step_eps, then ONE dlpm_update_f32 on a copy of x."""
+        d = self.dlpm
+        with torch.no_grad():
+            x, eps, t_dev, flags = self._step_eps(model, x, t, clip, denoised_fn, model_kwargs, fold_clip=True)
+            need_z = (not dlim) or eta != 0.0
+            z = None
+            if noise is not None:
+                z = noise.to(x.device, torch.float32).contiguous()
+                assert z.shape == x.shape, 'noise must have the shape of x'
+            elif need_z and self.rng == 'reference':
+                z = self._streams().randn(x.shape).to(x.device)
+            seed, offset = self._traj if self._traj is not None else self._philox_key()
+            out = x.clone()
+            a = _lib.UpdateArgs()
+            a.x_dev, a.eps_dev, a.z_dev, a.t_dev = out.data_ptr(), eps.data_ptr(), _lib.ptr(z), t_dev.data_ptr()
+            a.g_dev, a.bg_dev, a.bs_dev = _lib.ptr(d.gammas), _lib.ptr(d.bargammas), _lib.ptr(d.barsigmas)
+            a.c_eps_dev, a.c_noise_dev, a.A_dev = d._c_eps.data_ptr(), d._c_noise.data_ptr(), d._A.data_ptr()
+            a.B, a.D, a.T = x.shape[0], x[0].numel(), self.reverse_steps
+            a.flags, a.dlim_eta, a.alpha = flags | (_lib.UPD_DLIM if dlim else 0), float(eta), float(self.alpha)
+            a.seed, a.sample_offset = seed, offset
+            _lib.check(_lib.lib().dlpm_update_f32(C.byref(a), _lib.stream_ptr()))
+        return {'sample': out}
+
+    def p_sample(self, model, x, t, clip_denoised=False, denoised_fn=None, model_kwargs=None, noise=None):
+        """GenerativeLevyProcess.p_sample (:225-239): {'sample': x_{t-1}} = mean + 1[t != 1] sqrt(variance) z, one dlpm_update_f32
+        on a copy of x (x itself is left as it is).  z: `noise=` as given (this build's addition); else, rng='philox', the
+        sampler's own counters -- (key of the current trajectory, global sample, step t, element), the key being the one the last
+        progressive loop took, or the next sample() call's when none has begun -- so a hand-written loop over p_sample draws what
+        p_sample_loop draws; rng='reference': the next randn of the reference's torch stream."""
+        return self._step(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, 0.0, noise)
+
+    def ddim_sample(self, model, x, t, clip_denoised=False, denoised_fn=None, model_kwargs=None, eta=0.0, noise=None):
+        """GenerativeLevyProcess.ddim_sample (:332-363): the DLIM step, deterministic at eta = 0 (no z is drawn); z as p_sample."""
+        return self._step(model, x, t, clip_denoised, denoised_fn, model_kwargs, True, eta, noise)
+
+    def q_posterior_mean_variance(self, x_start, x_t, t, Sigmas):
+        """(mean, variance) of q(x_{t-1} | x_t, x_0, a_{1:T}) from a caller-given Sigmas table ([T,B] or [T, *shape]).  The
+        reference's method (:118-133) raises AttributeError: it calls dlpm.anterior_mean_dlpm / anterior_variance_dlpm, which do
+        not exist there.  Its evident meaning is built here: eps = predict_eps(x_t, t, x_start), then the DLPM moments of
+        anterior_mean_variance_dlpm on the given Sigmas instead of the process's own."""
+        assert x_start.shape == x_t.shape
+        eps = self.dlpm.predict_eps(x_t, t, x_start)
+        mean, var = self.dlpm.anterior_mean_variance_dlpm(x_t, t, eps, Sigmas=Sigmas)
+        assert mean.shape[0] == var.shape[0] == x_start.shape[0]
+        return mean, var
+
+    def _progressive(self, model, shape, flags, eta, noise, clip, denoised_fn, model_kwargs):
+        """The generator behind both progressive loops.  Prologue (at the first next()): take the Philox key of this trajectory,
+        keep it for the step methods, advance the call counter (or the dataset stream) at once -- a generator dropped half way
+        has still used its key -- fill dlpm.A / dlpm.Sigmas, draw x_T.  Then one fresh tensor per step.
+
+        A native net (UNetModel / MLPModel) with isotropic noise, device draws and no denoised_fn runs on the graph sampler: one
+        replay and one device copy per yield.  Everything else is the loop over p_sample / ddim_sample."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        assert self.device is not None
+        assert isinstance(shape, (tuple, list))
+        shape = [int(v) for v in shape]
+        if hasattr(model, 'eval'):
+            model.eval()
+        d = self.dlpm
+        T, dev = self.reverse_steps, torch.device(self.device)
+        if dev.type != 'cuda':
+            raise _lib.DlpmError('the progressive loops run on the MI355X only (device is {}); there is no CPU fallback'.format(dev))
+        clamp_a, clamp_eps = d.gen_a.kwargs.get('clamp_a'), d.gen_eps.kwargs.get('clamp_eps')
+        dlim = bool(flags & _lib.UPD_DLIM)
+        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and \
+            _native_kwargs(model, model_kwargs) and self.isotropic and self.rng == 'philox' and noise is None
+        seed, offset = self._philox_key()
+        self._traj = (seed, offset)
+        if self._dataset is not None:
+            self._dataset['next'] += shape[0]
+        else:
+            self.calls += 1
+        L, st = _lib.lib(), _lib.stream_ptr()
+        if self.rng == 'reference' or noise is not None:
+            with torch.no_grad():
+                A, xT = self._host_noise_prologue(shape, clamp_a, clamp_eps, noise)
+            d.sample_A(shape, T, A=A.to(dev))
+            x = xT.to(dev).reshape(shape).contiguous().clone()
+        else:
+            d.sample_A(shape, T, seed=seed, sample_offset=offset)
+            x = None
+        d.compute_Sigmas()
+        if native:
+            labels = (model_kwargs or {}).get('y')
+            if getattr(model, 'num_classes', None) is not None:
+                labels = model._check_labels(shape[0], labels)
+            h = self._native_sampler(model, shape, flags | (_lib.UPD_CLIP if clip else 0), eta, clamp_a, clamp_eps, seed, offset)
+            me = self._native_owner = object()
+            if labels is not None:
+                y_d = labels.to(dev, torch.int64).contiguous()
+                _lib.check(L.dlpm_sampler_set_labels(h, y_d.data_ptr(), st))
+            _lib.check(L.dlpm_sampler_set_history(h, None, st))
+            _lib.check(L.dlpm_sampler_begin(h, st))
+            for i in range(T):
+                if self._native_owner is not me:
+                    raise _lib.DlpmError('another loop ran on this method object since this progressive generator began; its '
+                                         'sampler state is gone')
+                st = _lib.stream_ptr()
+                if i:
+                    _lib.check(L.dlpm_sampler_steps(h, 1, st))
+                x = torch.empty(shape, dtype=torch.float32, device=dev)
+                _lib.check(L.dlpm_sampler_copy_state(h, x.data_ptr(), st))
+                yield {'sample': x}
+            return
+        if x is None:
+            x = torch.empty(shape, dtype=torch.float32, device=dev)
+            ce = -1.0 if clamp_eps is None else float(clamp_eps)
+            fn = L.dlpm_init_state_philox_f32 if self.isotropic else L.dlpm_init_state_elem_philox_f32
+            _lib.check(fn(x.data_ptr(), shape[0], int(np.prod(shape[1:])), float(self.alpha), ce,
+                          float(d.host_schedule[3][-1]), seed, offset, st))
+        yield {'sample': x}
+        for i in range(T - 1, 0, -1):
+            t = torch.full((shape[0],), i, dtype=torch.int64, device=dev)
+            out = self._step(model, x, t, clip, denoised_fn, model_kwargs, dlim, eta, None)
+            yield out
+            x = out['sample']
+
+    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=False, denoised_fn=None, model_kwargs=None):
+        """GenerativeLevyProcess.p_sample_loop_progressive (:291-330): a generator over {'sample': x} dicts, x_T first, then one
+        per reverse step (reverse_steps dicts in all); every yielded tensor is fresh.  The trajectory's key and tables are taken
+        when the first item is asked for, and the step methods (p_sample, ddim_sample, p_mean_variance) use them from then on, so
+        a caller may leave the generator at any step and go on by hand.  One native progressive loop per method object at a time."""
+        return self._progressive(model, shape, 0, 0.0, noise, clip_denoised, denoised_fn, model_kwargs)
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=False, denoised_fn=None, model_kwargs=None,
+                                     eta=0.0):
+        """GenerativeLevyProcess.ddim_sample_loop_progressive (:412-452): the DLIM loop as a generator; see
+        p_sample_loop_progressive."""
+        return self._progressive(model, shape, _lib.UPD_DLIM, eta, noise, clip_denoised, denoised_fn, model_kwargs)
+
+    def _lim_run(self, model, shape, ode, history, progress, clamp_eps):
+        """The LIM sampler on a native net (graph sampler) or a generic callable; `ode` selects the deterministic update."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        flags = _lib.SMP_LIM | (_lib.UPD_DLIM if ode else 0)
+        if isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps:
+            return self._run_native(model, shape, flags, 0.0, None, clamp_eps, None, history, progress)
+        return self._run_callable_lim(model, shape, flags, clamp_eps, history, progress)
+
+    def lim_sample(self, model, shape, ddim=False, get_sample_history=False, clip_denoised=False):
+        """GenerativeLevyProcess.lim_sample (:454-506): the LIM sampler by its own name, what sample() runs for a method built
+        with LIM=True; `ddim` selects the ODE, `clip_denoised` is accepted and ignored as in the reference.  x_0 is gen_eps's
+        noise under its current clamp_eps."""
+        assert self.LIM, 'lim_sample belongs to a method built with LIM=True'
+        if getattr(model, 'num_classes', None) is not None:
+            raise NotImplementedError('the LIM sampler does not take model_kwargs / class labels')
+        if hasattr(model, 'eval'):
+            model.eval()
+        with torch.inference_mode():
+            out = self._lim_run(model, list(shape), ddim, get_sample_history, False, self.dlpm.gen_eps.kwargs.get('clamp_eps'))
+        if self._dataset is not None:
+            self._dataset['next'] += shape[0]
+        else:
+            self.calls += 1
+        return out
+
     # -------------------------------------------------------------------------------- BEM: SAMPLING
     def sample(self, models, shape, reverse_steps, time_spacing=None, initial_data=None, clip_denoised=False,
                deterministic=False, dlim_eta=1.0, print_progression=False, get_sample_history=False, clamp_a=None,
@@ -556,11 +788,8 @@ class GenerativeLevyProcess:
             if self.LIM:
                 # lim_sample (GenerativeLevyProcess.py:454-507): `deterministic` selects the ODE; clip_denoised and
                 # initial_data are accepted and ignored, as in the reference
-                shape, flags = shape_arg, _lib.SMP_LIM | (_lib.UPD_DLIM if deterministic else 0)
-                if native:
-                    out = self._run_native(model, shape, flags, 0.0, None, clamp_eps, None, get_sample_history, print_progression)
-                else:
-                    out = self._run_callable_lim(model, shape, flags, clamp_eps, get_sample_history, print_progression)
+                shape = shape_arg
+                out = self._lim_run(model, shape, deterministic, get_sample_history, print_progression, clamp_eps)
             elif native:
                 out = self._run_native(model, shape, flags, eta, clamp_a, clamp_eps, noise, get_sample_history, print_progression,
                                        labels=labels)
