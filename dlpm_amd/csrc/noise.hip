@@ -594,6 +594,7 @@ extern "C" int dlpm_update_f32(const dlpm_update_args *a, dlpm_stream_t stream) 
     DLPM_CHECK_ARG(a && a->x_dev && a->eps_dev && a->t_dev && a->g_dev && a->bg_dev && a->bs_dev,
                    "dlpm_update_f32: null pointer");
     DLPM_CHECK_ARG(a->B > 0 && a->D > 0 && a->T >= 2, "dlpm_update_f32: bad shape");
+    DLPM_CHECK_ARG(a->T < (1 << 24), "dlpm_update_f32: T must fit 24 bits");   // the Philox counter holds purpose | t << 8
     if (!(a->flags & DLPM_UPD_DLIM))
         DLPM_CHECK_ARG(a->c_eps_dev && a->c_noise_dev, "dlpm_update_f32: DLPM step needs the coefficient tables");
     else if (a->dlim_eta != 0.0f)
@@ -653,6 +654,7 @@ extern "C" int dlpm_lim_update_f32(const dlpm_lim_update_args *a, dlpm_stream_t 
     DLPM_CHECK_ARG(a && a->x_dev && a->eps_dev && a->t_dev && a->tmp_dev && a->cx_dev && a->cs_dev && a->cn_dev,
                    "dlpm_lim_update_f32: null pointer");
     DLPM_CHECK_ARG(a->B > 0 && a->B < (1ll << 31) && a->D > 0 && a->D < (1ll << 31) && a->T >= 2, "dlpm_lim_update_f32: bad shape");
+    DLPM_CHECK_ARG(a->T < (1 << 24), "dlpm_lim_update_f32: T must fit 24 bits");   // the Philox counter holds purpose | t << 8
     const bool vec = (a->D % 4 == 0) && ((reinterpret_cast<uintptr_t>(a->x_dev) | reinterpret_cast<uintptr_t>(a->eps_dev) |
                                           reinterpret_cast<uintptr_t>(a->z_dev)) % 16 == 0);
     const bool ode = a->flags & DLPM_UPD_DLIM;

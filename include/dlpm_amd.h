@@ -167,7 +167,8 @@ typedef struct dlpm_update_args {
  * DLPM_UPD_ELEMENTWISE (non-isotropic noise, `--non_iso`, Distributions.py:47-48): the three tables are
  * [T,B,D] and indexed per element instead of per sample.
  * HBM-bound: 12 B/element with Philox noise, 16 B/element with injected z; +8 B/element for elementwise
- * tables, +4 B/element when a history row is written. */
+ * tables, +4 B/element when a history row is written.
+ * T >= 2^24 is refused (DLPM_ERR_ARG, nothing launched): the Philox counter holds purpose | t << 8. */
 int dlpm_update_f32(const dlpm_update_args *args, dlpm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -252,7 +253,8 @@ typedef struct dlpm_lim_update_args {
     float *const *hist_pp;    /* as in dlpm_update_args: row T - t of a [T,B,D] buffer                  */
 } dlpm_lim_update_args;
 
-/* x <- cx x + cs (eps tmp) [+ cn clamp(sqrt(a) z)]   -- sde_score_update / ode_score_update. */
+/* x <- cx x + cs (eps tmp) [+ cn clamp(sqrt(a) z)]   -- sde_score_update / ode_score_update.
+ * T >= 2^24 is refused like dlpm_update_f32's. */
 int dlpm_lim_update_f32(const dlpm_lim_update_args *args, dlpm_stream_t stream);
 
 /* tvec_dev[b] = ts_dev[(T-1) - *t_dev]: the continuous time the LIM loop feeds the net (sampler.py:233). */
