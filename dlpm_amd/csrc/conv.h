@@ -20,6 +20,8 @@ struct ConvLaunch {
                                    // n-tiles (round 6: at a small DECLARED batch the narrow shapes give 2-4x as many workgroups; same bits)
     const float *w_wino4sp = nullptr; // optional, ups launches with Cout % 128 == 0 only: the four parity classes' F(4x4,2x2) weights
                                    // (conv_wino4.hip: k_conv3x3_wino4sp); taken where wino4_route says so
+    const float *w_wino4_one = nullptr; // optional, 4x4-pixel tensors with Cout % 64 == 0, Cin % 16 == 0 only: the F(4x4,3x3) weights in the fragment
+                                   // order of 64-channel n-tiles (conv_wino4.hip: k_conv3x3_wino4_one); taken where wino4_route says so
     const void *w_split = nullptr; // optional: the weights as three bf16 planes in stage-tile order (conv_split.hip); a 3x3 launch
                                    // that carries it is a stride-2 downsampling convolution, or a test forcing the path
     const float *w_small = nullptr;// optional, 3x3 with Cout <= 4 (the head): [tap][Cin][4] for k_conv3x3_head
@@ -71,6 +73,7 @@ struct ConvRoute {
     ConvFamily family = CONV_DIRECT;
     int bh = 0, bw = 0, nimg = 0;   // Winograd families: tiles per block (rows, columns), images per block
     int nq = 0;                     // Winograd families: n-tile width in channels
+    int one = 0;                    // CONV_WINO4 only: 1 = the one-tile shape (16 whole 4x4 images x 64 channels, K split in-block: k_conv3x3_wino4_one)
     int64_t grid = 0;               // Winograd families under a declared batch: workgroups at dispatch_B (what AUTO and split-K weigh)
     int stats_px = 0;               // pixels behind one stats_out partial (0: the kernel that will run cannot emit statistics)
     int ksplit = 1;                 // split-K factor (1: none), see ConvLaunch::ksplit
@@ -131,6 +134,10 @@ bool wino4sp_layer_ok(int Cout, int Cin, int Hlo, int Wlo);               // wor
 int launch_conv_wino4sp(const ConvLaunch &c, const ConvRoute &r, hipStream_t st);
 int64_t wino4sp_weight_floats(int Cout, int Cin);
 int relayout_weight_wino4sp(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st);
+// 4x4-pixel tensors (one F(4x4) tile per image) on 16-image x 64-channel blocks with the K loop split over two groups of four waves
+// (conv_wino4.hip: k_conv3x3_wino4_one); weights: relayout_weight_wino4(.., nq = 64), wino4_weight_floats
+bool wino4_one_enabled();              // DLPM_WINO4_ONE
+bool wino4_one_layer_ok(int Cout, int C0, int C1, int H, int W);           // worth building the weights for
 // A WHOLE ResBlock with 32 output channels on 32x32 images in one launch (round 6, conv_wino4.hip: k_resblock_wino4_img): GroupNorm-1
 // coefficients from the producers' statistics (or given), conv1 as F(4x4,3x3), GroupNorm-2 with scale-shift inside the workgroup (an image
 // is one workgroup), conv2 over the activated intermediate (which makes one trip through L2, never a second launch), skip, output
@@ -172,6 +179,7 @@ int relayout_weight_split(const float *oihw_dev, void *dst_dev, int Cout, int Ci
 constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
 struct Conv3Layouts {
     bool frag = false, wino = false, wino4 = false, wino4sp = false;
+    bool wino4_one = false; // the one-tile copy of a layer on 4x4-pixel tensors (Hout x Wout of `c`; 0 x 0: unknown, none)
     bool narrow = false;    // the 64- / 32-channel n-tile copies of the F(4x4) weights: Cout % 128 == 0 under a small declared batch
 };
 bool wino4_narrow_copies_wanted(int Cout, int64_t dispatch_B);

@@ -1145,6 +1145,7 @@ Conv3Layouts conv3_layouts(const ConvLaunch &c) {
     y.wino = plain && c.Cout % 64 == 0 && Cin % 16 == 0;      // Winograd-domain copy (stride-1 launches pick it up)
     y.wino4 = plain && wino4_enabled() && c.Cout % 32 == 0 && Cin % 8 == 0;   // F(4x4,3x3) copy (128-, 64- or 32-channel n-tiles)
     y.wino4sp = y.wino4 && c.ups && wino4sp_layer_ok(c.Cout, Cin, c.Hin, c.Win);   // sub-pixel copy of an Upsample convolution
+    y.wino4_one = y.wino4 && !c.ups && wino4_one_layer_ok(c.Cout, c.C0, c.C1, c.Hout, c.Wout);   // one-tile copy of a layer on 4x4-pixel tensors
     y.narrow = y.wino4 && wino4_narrow_copies_wanted(c.Cout, c.dispatch_B);
     return y;
 }
@@ -1167,9 +1168,10 @@ ConvRoute conv_route(const ConvLaunch &c) {
         // per 128-pixel tile through the 4-wave row epilogue, or per whole 8x8 image from the registers of the 8-wave shape
         r.stats_px = (c.R0 & 3) ? 0 : hw % BM == 0 ? BM : hw == 64 ? 64 : 0;
     } else if (wino4_route(c, &r)) {
-        cls = r.family == CONV_WINO4SP ? "conv3x3_wino4sp" : "conv3x3_wino4";   // (a class of its own: 100 multiplies per 64 outputs, conv3x3_wino4 144)
-        // the 8-wave, sub-pixel and whole-image shapes carry no split
-        if (r.family == CONV_WINO4 && r.nq != 128 && !(c.Cout == 32 && c.Hout == 32 && c.Wout == 32)) r.ksplit = ksplit_for(c, r.grid);
+        cls = r.family == CONV_WINO4SP ? "conv3x3_wino4sp" : r.one ? "conv3x3_wino4_one" : "conv3x3_wino4";   // (classes of their own: 100 multiplies
+        // per 64 outputs, conv3x3_wino4 144; the one-tile shape on 4x4-pixel tensors)
+        // the 8-wave, sub-pixel, one-tile and whole-image shapes carry no split
+        if (r.family == CONV_WINO4 && !r.one && r.nq != 128 && !(c.Cout == 32 && c.Hout == 32 && c.Wout == 32)) r.ksplit = ksplit_for(c, r.grid);
     } else if (!igemm_supported(c)) {
         r.family = conv_takes_stem(c) ? CONV_STEM : CONV_DIRECT;
         if (r.family == CONV_STEM && stem_stats_ok(c)) r.stats_px = 1024;

@@ -1651,6 +1651,244 @@ __global__ void __launch_bounds__(FI_NT, 1) k_resblock_wino4_img16(ResImgLaunch 
 #endif
 }
 
+// =====================================================================================================================================
+// ONE-TILE shape: 3x3 stride-1 convolutions on 4x4-pixel tensors, where an image is exactly one F(4x4) tile.  k_conv3x3_wino4 takes them as
+// blocks of 16 images x 128 channels and loses to F(2x2) there (wino4_preferred) for two reasons that are not the arithmetic's: at batch
+// 1024 its grid is 128 workgroups, each walking the whole K loop on half of the chip, and 320 of the 576 halo pixels it stages per phase
+// are zero padding.  Here a workgroup is 16 whole images x 64 output channels, and its K loop is split over two groups of four waves
+// (k_resblock_wino4_img16's split): wave w owns channels 16 (w & 3) .. + 15 for all 36 positions (144 accumulator registers) and K half
+// w >> 2 -- waves 0..3 walk the chunks [0, nch), waves 4..7 [nch, 2 nch) -- so the grid is ceil(B / 16) x Cout / 64 workgroups of half the
+// K loop each.  Each half has its own V and raw double buffers and coefficient slots and runs the 8-wave kernel's pipeline on them (S(c+2)
+// raw stores, X(c+1) transform, G(c+3) global loads between the MFMAs of phase c, one barrier per phase for the whole workgroup).
+//   * The raw buffer holds the 16 REAL pixels of each image only (two staging items per thread); the border of the 6x6 patch is zero
+//     after the activation by construction, so the patch accessor returns the constant for it (F4PatchOne): 16 LDS reads per lane and row
+//     pair instead of 36.  An image is 16 pixels x 8 channels + 4 floats: the 16 tiles x 2
+//     channel pairs of an LDS pass of the transform then read 32 different 8-byte slots of the 64 banks.
+//   * The six row-pair jobs of a phase (three per half) go to waves 0, 1, 2 (half 0) and 7, 6, 5 (half 1): waves s and s + 4 share SIMD s,
+//     so the SIMDs carry 1, 2, 2, 1 jobs.
+//   * Behind the loop waves 4..7 hand their 144 accumulators to waves 0..3 through LDS (one round: the buffer aliases V and raw; the
+//     launch asks for its 144 KB), summed as half 0 + half 1, and waves 0..3 run the register epilogue of the 8-wave kernel.  A lane's four
+//     tiles are four images: GroupNorm statistics are one 16-pixel partial per image, [B][1][Cout].
+// Weights: the 64-channel fragment order, relayout_weight_wino4(.., nq = 64) (ConvLaunch::w_wino4_one).
+constexpr int F1_NQ = 64;                          // output channels per workgroup
+constexpr int F1_IP = 16 * F4_KC + 4;              // floats per staged image (bank spread, above)
+constexpr int F1_RAWBUF = F4_TILES * F1_IP;
+constexpr int F1_HALF = 2 * F4_VBUF + 2 * F1_RAWBUF + 2 * F4_CFS;   // floats of one K half: V, raw, coefficient slots, two of each
+constexpr int F1_XCH = 4 * 36 * 64 * 4;            // floats of the hand-over: [4 waves][36 accumulators][64 lanes][4]
+constexpr int F1_LDS = F1_XCH > 2 * F1_HALF ? F1_XCH : 2 * F1_HALF;
+static_assert(F1_LDS * sizeof(float) <= 160 * 1024, "one workgroup's LDS");
+// d(i, c) of a 4x4 image's 6x6 patch: the border is the zero padding, the interior pixel (i - 1, c - 1) lies at rb + 8 (4 (i - 1) + c - 1)
+struct F4PatchOne {
+    const float *rb;
+    __device__ __forceinline__ float2 operator()(int i, int c) const {
+        if (i == 0 || i == 5 || c == 0 || c == 5) return make_float2(0.f, 0.f);
+        return *reinterpret_cast<const float2 *>(rb + ((i - 1) * 4 + (c - 1)) * F4_KC);
+    }
+};
+
+__global__ void __launch_bounds__(F4_NT, 1) k_conv3x3_wino4_one(ConvLaunch p_in) {
+    ConvLaunch p = p_in;
+    extern __shared__ __attribute__((aligned(16))) float wsm[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nw = wave & 3, kh = wave >> 2;         // 16-channel output tile, K half
+    const int li = lane & 15, lk = lane >> 4;
+    float *V = wsm + kh * F1_HALF;                   // this half's [2][18][4][16][4]
+    float *raw = V + 2 * F4_VBUF;                    // [2][16 images][F1_IP]
+    float *Cf = raw + 2 * F1_RAWBUF;                 // [2][16][2][8]
+    const int Cin = p.C0 + p.C1;
+    const int nch = Cin / (2 * F4_KC), kb = kh * nch;         // phases per half, first chunk of this half
+    // n-tile-major grid, as k_conv3x3_wino4
+    const int ntn = p.Cout / F1_NQ, nmb = gridDim.x / ntn;
+    const int mb = blockIdx.x % nmb, n0 = (blockIdx.x / nmb) * F1_NQ;
+    const int img0 = mb * F4_TILES;
+
+    // ---- raw staging by the 256 threads of the half: item = (pixel it * 128 + (ht >> 1) of the block's 256, channel quad of the phase)
+    const int ht = tid & 255, squad = ht & 1;
+    int off[2], lo[2];     // lo: LDS float offset of the item (bits 0..15) | its image's coefficient offset (bits 16..)
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int pix = it * 128 + (ht >> 1);
+        const int img = pix >> 4, px = pix & 15;
+        off[it] = (img0 + img) >= p.B ? -1 : (img0 + img) * 16 + px;      // (an absent image of a ragged last block: zero, like padding)
+        lo[it] = (img * F1_IP + px * F4_KC + squad * 4) | ((img * 2 * F4_KC + squad * 4) << 16);
+    }
+    const bool has_coef = p.coefA != nullptr;
+    const int cf_img = ht >> 2, cf_isb = (ht >> 1) & 1;
+    const bool cf_mine = has_coef && ht < F4_TILES * 4;
+    const float *cf_base = has_coef ? ((cf_isb ? p.coefB : p.coefA) + (int64_t)min(img0 + cf_img, p.B - 1) * Cin + kb * F4_KC + squad * 4) : nullptr;
+    float4 xr[2], cfr = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto load_raw_into = [&](float4 (&dst)[2], int chunk) {
+        const int c = (kb + chunk) * F4_KC + squad * 4;
+        const bool first = c < p.C0;
+        const float *sb = first ? p.src0 + c : p.src1 + (c - p.C0);
+        const int ld = first ? p.C0 : p.C1;
+#pragma unroll
+        for (int it = 0; it < 2; it++) dst[it] = *reinterpret_cast<const float4 *>(sb + (int64_t)max(off[it], 0) * ld);
+    };
+    auto load_coef = [&](int chunk) {
+        if (cf_mine) cfr = *reinterpret_cast<const float4 *>(cf_base + chunk * F4_KC);
+    };
+    auto store_coef = [&](int slot) {
+        if (cf_mine) *reinterpret_cast<float4 *>(Cf + slot * F4_CFS + cf_img * 2 * F4_KC + cf_isb * F4_KC + squad * 4) = cfr;
+    };
+    auto store_raw_item = [&](int slot, int it) {
+        float4 x = xr[it];
+        if (has_coef) {
+            const float4 ca = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16));
+            const float4 cb = *reinterpret_cast<const float4 *>(Cf + slot * F4_CFS + (lo[it] >> 16) + F4_KC);
+            x = f4_affine4(x, ca, cb);
+        }
+        if (p.act_silu) x = f4_silu4(x);
+        if (off[it] < 0) x = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4 *>(raw + slot * F1_RAWBUF + (lo[it] & 0xffff)) = x;
+    };
+    auto store_raw = [&](int slot) {
+#pragma unroll
+        for (int it = 0; it < 2; it++) store_raw_item(slot, it);
+    };
+
+    // ---- input transform of this half: row pair xrp of B^T on waves 0, 1, 2 (half 0) and 7, 6, 5 (half 1); lane = (channel pair, tile)
+    const int xrp = kh == 0 ? wave : 7 - wave;
+    const int rbase = (lane & 15) * F1_IP + (lane >> 4) * 2, vofs = lane * 4;      // (V slot (pair * 16 + tile) * 4 = lane * 4)
+    auto transform = [&](int slot) {
+        if (xrp < 3) f4_transform_rp(xrp, F4PatchOne{raw + slot * F1_RAWBUF + rbase}, V + slot * F4_VBUF + vofs, 4 * F4_TILES * 4);
+    };
+
+    // ---- weight stream of this wave: Wf[ntile][wave nw][phase][18 position pairs][lane][4], from chunk kb on
+    const float4 *__restrict__ wp = reinterpret_cast<const float4 *>(p.w_wino4_one) + ((int64_t)((n0 / F1_NQ) * 4 + nw) * (Cin / F4_KC) + kb) * 18 * 64;
+    constexpr int AHEAD = F4_RING - 1;
+    float4 bq[F4_RING];
+    const float *asrc = V + lane * 4;
+
+    floatx4 acc[36];
+#pragma unroll
+    for (int q = 0; q < 36; q++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[q][r] = 0.f;
+
+    // ---- prologue and phase loop: k_conv3x3_wino4's, per half
+    const int last = nch - 1;
+    float4 xr1[2], cfr1 = make_float4(0.f, 0.f, 0.f, 0.f), cfr2 = cfr1;
+    load_raw_into(xr, 0);
+    load_raw_into(xr1, min(1, last));
+    load_coef(0);
+    if (cf_mine) {
+        cfr1 = *reinterpret_cast<const float4 *>(cf_base + min(1, last) * F4_KC);
+        cfr2 = *reinterpret_cast<const float4 *>(cf_base + min(2, last) * F4_KC);
+    }
+#pragma unroll
+    for (int a = 0; a < F4_RING - 1; a++) bq[a] = wp[a * 64 + lane];
+    store_coef(0);
+    cfr = cfr1;
+    store_coef(1);
+    __syncthreads();
+    store_raw(0);
+#pragma unroll
+    for (int it = 0; it < 2; it++) xr[it] = xr1[it];
+    store_raw(1);
+    load_raw_into(xr, min(2, last));
+    __syncthreads();
+    transform(0);
+    cfr = cfr2;
+    store_coef(0);
+    __syncthreads();
+
+#pragma unroll 1
+    for (int chunk = 0; chunk < nch; chunk++) {
+        const int cur = chunk & 1, nxt = cur ^ 1;
+        const float *ab = asrc + cur * F4_VBUF;
+        load_coef(min(chunk + 3, last));
+        float4 aq[F4_AAHEAD + 1];
+#pragma unroll
+        for (int a = 0; a < F4_AAHEAD; a++) aq[a] = *reinterpret_cast<const float4 *>(ab + a * (4 * F4_TILES * 4));
+#pragma unroll
+        for (int pp = 0; pp < 18; pp++) {
+            if (pp >= F4_S0 && pp < F4_S0 + 2) store_raw_item(cur, pp - F4_S0);    // S(chunk+2)
+            if (pp == F4_S0 + 2) load_raw_into(xr, min(chunk + 3, last));          // G(chunk+3)
+            if (pp == F4_X) transform(nxt);                                        // X(chunk+1)
+            bq[(pp + AHEAD) % F4_RING] = wp[AHEAD * 64 + lane];
+            wp += 64;
+            if (pp + F4_AAHEAD < 18)
+                aq[(pp + F4_AAHEAD) % (F4_AAHEAD + 1)] = *reinterpret_cast<const float4 *>(ab + (pp + F4_AAHEAD) * (4 * F4_TILES * 4));
+            if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
+            f4_mfma4(aq[pp % (F4_AAHEAD + 1)], bq[pp % F4_RING], acc[2 * pp], acc[2 * pp + 1]);
+            if (F4_PRIO) __builtin_amdgcn_s_setprio(1);
+        }
+        store_coef(nxt);
+        __syncthreads();
+    }
+    if (F4_PRIO) __builtin_amdgcn_s_setprio(0);
+
+    // ---- the two K halves meet (V, raw and the coefficient slots are dead behind the loop's last barrier): half 0 + half 1, in that order
+    float4 *xb = reinterpret_cast<float4 *>(wsm) + nw * 36 * 64 + lane;
+    if (kh == 1) {
+#pragma unroll
+        for (int q = 0; q < 36; q++) xb[q * 64] = make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
+    }
+    __syncthreads();
+    if (kh == 1) return;
+#pragma unroll
+    for (int q0 = 0; q0 < 36; q0 += 6) {      // six at a time (24 registers beside the accumulators)
+        float4 t[6];
+#pragma unroll
+        for (int q = 0; q < 6; q++) t[q] = xb[(q0 + q) * 64];
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            acc[q0 + q][0] += t[q].x;
+            acc[q0 + q][1] += t[q].y;
+            acc[q0 + q][2] += t[q].z;
+            acc[q0 + q][3] += t[q].w;
+            // the sum is formed HERE: left alone the compiler sinks the additions into the epilogue's branches and keeps all 36 loaded
+            // fragments alive until then (72 registers spilled)
+            asm volatile("" : "+v"(acc[q0 + q]) : : "memory");
+        }
+    }
+
+    // ---- epilogue from registers, as k_conv3x3_wino4: a lane holds the 16 pixels of images img0 + 4 lk + r, r = 0..3, of ONE channel
+    const int ch = n0 + 16 * nw + li;
+    const float bias_v = p.bias ? p.bias[ch] : 0.f;
+    const bool has_res = p.res0 != nullptr;
+    const bool res_first = __builtin_amdgcn_readfirstlane(n0 + 16 * nw) < p.R0;   // R0 % 16 == 0 (wino4_one_geometry)
+    const float *res_u = has_res ? (res_first ? p.res0 : p.res1 - p.R0) : nullptr;
+    const int res_ld = res_first ? p.R0 : p.Cout - p.R0;
+    const int64_t pix0 = (int64_t)img0 * 16;                                      // wave-uniform
+    float *__restrict__ out_blk = p.out + pix0 * p.Cout;
+    const float *__restrict__ res_blk = has_res ? res_u + pix0 * res_ld : nullptr;
+    const bool do_stats = p.stats_out != nullptr;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int tile = 4 * lk + r;
+        const bool ok = img0 + tile < p.B;
+        float rs[16];
+        const uint32_t bo_o = (uint32_t)(tile * 16 * p.Cout + ch) * 4u, bo_r = (uint32_t)(tile * 16 * res_ld + ch) * 4u;
+        if (has_res && ok) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) rs[k] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(res_blk + k * res_ld) + bo_r);
+        }
+        float Yt[16];
+        f4_out_tile(acc, r, Yt);
+        if (!ok) continue;
+        float K = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            float v = Yt[k] + bias_v;
+            if (has_res) v += rs[k];
+            if (do_stats) {
+                if (k == 0) K = v;
+                const float dd = v - K;
+                s1 += dd;
+                s2 = fmaf(dd, dd, s2);
+            }
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(out_blk + k * p.Cout) + bo_o) = v;
+        }
+        if (do_stats) {     // one partial per image: [B][1][Cout]
+            float mean, M2;
+            f4_stats_lane<16>(K, s1, s2, mean, M2);
+            p.stats_out[(int64_t)(img0 + tile) * p.Cout + ch] = make_float2(mean, M2);
+        }
+    }
+}
+
 // OIHW (3x3) -> U = G g G^T (6x6 per filter) in the kernel's fragment order Wf[ntile][wave][phase][18][lane][4]:
 // lane = lk*16 + li holds, for position pair pp and e = 0..3, U_pos[cin = phase*8 + 2 lk + (e & 1)][cout = ntile*128 + wave*16 + li]
 // with pos = 2 pp + (e >> 1).  Computed in double, rounded once.
@@ -1814,8 +2052,11 @@ static bool wino4_whole_image(const ConvLaunch &c) {
 
 static int launch_conv_wino4_nq(const ConvLaunch &c, int nq, int bh, int bw, int nimg, hipStream_t st);
 
+int launch_conv_wino4_one(const ConvLaunch &c, hipStream_t st);
+
 int launch_conv_wino4(const ConvLaunch &c, const ConvRoute &rt, hipStream_t st) {
     int bh, bw, nimg;
+    if (rt.family == CONV_WINO4 && rt.one) return launch_conv_wino4_one(c, st);
     if (rt.family != CONV_WINO4 || !wino4_geometry_nq(c, rt.nq, &bh, &bw, &nimg)) {
         set_error("launch_conv_wino4: unsupported shape");
         return DLPM_ERR_UNSUPPORTED;
@@ -1953,9 +2194,62 @@ static bool wino4sp_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
     return wino4sp_block(c.Cout, c.C0 + c.C1, c.Hin, c.Win, bh, bw, nimg);
 }
 
+// ---- the one-tile shape on 4x4-pixel tensors (k_conv3x3_wino4_one)
+// DLPM_WINO4_ONE=0 (A/B runs): those layers on the F(2x2) kernel as before; their one-tile weights are not built
+bool wino4_one_enabled() {
+    static const int v = env_switch("DLPM_WINO4_ONE", 1);
+    return v != 0 && wino4_enabled();
+}
+
+// a layer's geometry: one tile per image, 64-channel n-tiles, an even number of 8-channel chunks that do not straddle the input concat
+bool wino4_one_layer_ok(int Cout, int C0, int C1, int H, int W) {
+    return wino4_one_enabled() && H == 4 && W == 4 && Cout > 0 && Cout % F1_NQ == 0 && C0 > 0 && (C0 + C1) % (2 * F4_KC) == 0 && C0 % F4_KC == 0;
+}
+
+static bool wino4_one_geometry(const ConvLaunch &c) {
+    if (!c.w_wino4_one || c.ks != 3 || c.stride != 1 || c.ups || c.in_nchw || c.out_nchw || c.ksplit > 1) return false;
+    if ((c.R0 & 15) != 0) return false;   // a wave's 16 output channels stay on one side of a residual concat
+    return c.Hout == 4 && c.Wout == 4 && c.Cout % F1_NQ == 0 && c.C0 > 0 && (c.C0 + c.C1) % (2 * F4_KC) == 0 && c.C0 % F4_KC == 0;
+}
+
+// Taken when the launch carries the one-tile weights, the geometry qualifies, DLPM_WINO4_ONE is on and the declared policy says so -- a
+// function of the layer and the declared policy only, never of the batch a launch carries:
+//   DLPM_CONV_AUTO  under a DECLARED batch whose grid of 16-image x 64-channel blocks reaches the 256 CUs (dispatch_B = 1024 at 256 channels
+//                   is exactly 256).  The shape pays by filling the chip with half-K workgroups and carries no split over the grid: below
+//                   256 blocks the F(2x2) kernel's split-K copies (ksplit_for) do that, and WITHOUT a declaration nothing is known about
+//                   the grid, so the launch keeps the choice (and the bits) it had without the one-tile weights;
+//   DLPM_CONV_F4    also without a declaration (F(4x4) wherever the geometry qualifies); a declared batch is weighed as under AUTO.
+static bool wino4_one_taken(const ConvLaunch &c) {
+    if (c.gen != DLPM_CONV_AUTO && c.gen != DLPM_CONV_F4) return false;
+    if (!wino4_one_enabled() || !wino4_one_geometry(c)) return false;
+    if (c.dispatch_B <= 0) return c.gen == DLPM_CONV_F4;
+    return ceil_div(c.dispatch_B, (int64_t)F4_TILES) * (c.Cout / F1_NQ) >= 256;
+}
+
+int launch_conv_wino4_one(const ConvLaunch &c, hipStream_t st) {
+    if (!wino4_one_geometry(c)) {
+        set_error("launch_conv_wino4: the one-tile shape does not take this launch");
+        return DLPM_ERR_UNSUPPORTED;
+    }
+    const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(&k_conv3x3_wino4_one), 160 * 1024);
+    if (r != DLPM_OK) return r;
+    k_conv3x3_wino4_one<<<(unsigned)(ceil_div((int64_t)c.B, (int64_t)F4_TILES) * (c.Cout / F1_NQ)), F4_NT, (size_t)F1_LDS * sizeof(float), st>>>(c);
+    DLPM_LAUNCH_CHECK();
+    return DLPM_OK;
+}
+
 // The F(4x4) families' part of the route.  The sub-pixel kernel: a launch that the F(4x4) policy takes (generations AUTO and F4) on the
-// 128-channel n-tile, and that carries the sub-pixel weights -- a function of the layer and the declared policy only.
+// 128-channel n-tile, and that carries the sub-pixel weights -- a function of the layer and the declared policy only.  The one-tile
+// shape: wino4_one_taken.
 bool wino4_route(const ConvLaunch &c, ConvRoute *r) {
+    if (wino4_one_taken(c)) {
+        r->family = CONV_WINO4;
+        r->one = 1;
+        r->bh = r->bw = 1; r->nimg = F4_TILES; r->nq = F1_NQ;
+        if (c.dispatch_B > 0) r->grid = ceil_div(c.dispatch_B, (int64_t)F4_TILES) * (c.Cout / F1_NQ);
+        r->stats_px = 16;      // one partial per image
+        return true;
+    }
     const int nq = wino4_nq_for(c);
     int bh, bw, nimg;
     if (!wino4_preferred(c, nq, &bh, &bw, &nimg)) return false;

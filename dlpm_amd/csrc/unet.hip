@@ -49,6 +49,7 @@ struct ConvW {            // one convolution's weights
     float *w_wino4_n64 = nullptr, *w_wino4_n32 = nullptr;   // cout % 128 == 0, built while a SMALL dispatch batch is declared: the same weights in the
                              // fragment order of 64- / 32-channel n-tiles (narrow_wino4_copies)
     float *w_wino4sp = nullptr; // Upsample convolutions with cout % 128 == 0: the parity classes' F(4x4,2x2) weights (conv_wino4.hip: k_conv3x3_wino4sp)
+    float *w_wino4_one = nullptr; // layers on 4x4-pixel tensors with cout % 64 == 0: the F(4x4) weights in 64-channel fragment order (k_conv3x3_wino4_one)
     float *w_small = nullptr;// 3x3 with cout <= 4 (head): [tap][cin][4]
     float *w_taps = nullptr; // 3x3 with cout <= 3 (head): [9 cout -> 32][cin], the head as a 1x1 GEMM + gather (conv_direct.hip)
     float *w_split = nullptr;// 1x1 with cout % 128 == 0, cin % 32 == 0: three bf16 planes in stage-tile order (conv_split.hip)
@@ -57,7 +58,7 @@ struct ConvW {            // one convolution's weights
     bool owns = false;
 };
 // the layouts a ConvW always owns (w_dev only where `owns` says so); the copies that exist only under a small declared batch, by n-tile width
-constexpr float *ConvW::*OWNED_LAYOUTS[] = {&ConvW::w_frag, &ConvW::w_wino, &ConvW::w_wino4, &ConvW::w_wino4_n64, &ConvW::w_wino4_n32, &ConvW::w_wino4sp,
+constexpr float *ConvW::*OWNED_LAYOUTS[] = {&ConvW::w_frag, &ConvW::w_wino, &ConvW::w_wino4, &ConvW::w_wino4_n64, &ConvW::w_wino4_n32, &ConvW::w_wino4sp, &ConvW::w_wino4_one,
                                             &ConvW::w_small, &ConvW::w_taps, &ConvW::w_split, &ConvW::w_rs, &ConvW::w_hfused};
 constexpr struct { int nq; float *ConvW::*copy; } NARROW_LAYOUTS[] = {{64, &ConvW::w_wino4_n64}, {32, &ConvW::w_wino4_n32}};
 
@@ -286,12 +287,13 @@ void build_arch(dlpm_unet *u) {
     u->head = u->conv("out.2.", c.out_channels, mc, 3);
 }
 
-// ups_lo: low-res image size of an Upsample convolution (0: not one)
-int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
+// ups_lo: low-res image size of an Upsample convolution (0: not one); res: the image size a ResBlock convolution runs at (0: not one)
+int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0, int res = 0) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
     ConvLaunch probe;
     probe.C0 = C0; probe.C1 = c.cin - C0; probe.Cout = c.cout; probe.ks = c.ks;
     probe.in_nchw = boundary == 1; probe.out_nchw = boundary == 2;
     probe.stride = boundary == 4 ? 2 : 1; probe.ups = ups_lo > 0; probe.Hin = probe.Win = ups_lo;
+    probe.Hout = probe.Wout = ups_lo > 0 ? 2 * ups_lo : res;
     const Conv3Layouts lay = conv3_layouts(probe);     // (the narrow F(4x4) copies come and go with the declared batch: narrow_wino4_copies)
     c.use_igemm = igemm_supported(probe);
     const float *src = u->params[c.p_w].dev;
@@ -348,6 +350,11 @@ int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0) {  /
                 r = relayout_weight_wino4sp(src, c.w_wino4sp, c.cout, c.cin, nullptr);
                 if (r != DLPM_OK) return r;
             }
+            if (lay.wino4_one) {   // one-tile copy of a layer on 4x4-pixel tensors: the 64-channel fragment order
+                DLPM_HIP(hipMalloc(&c.w_wino4_one, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)));
+                r = relayout_weight_wino4(src, c.w_wino4_one, c.cout, c.cin, nullptr, 64);
+                if (r != DLPM_OK) return r;
+            }
         }
     }
     if (small_weight_ok(c.cout, c.cin, c.ks) && boundary == 0) {
@@ -368,6 +375,7 @@ void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
     L.w_wino4_n64 = c.w_wino4_n64;
     L.w_wino4_n32 = c.w_wino4_n32;
     L.w_wino4sp = c.w_wino4sp;
+    L.w_wino4_one = c.w_wino4_one;
     L.w_small = c.w_small;
     L.w_taps = c.w_taps;
     L.w_hfused = c.w_hfused;
@@ -907,10 +915,10 @@ static int narrow_wino4_copies(dlpm_unet *u) {
 // per-conv weight layouts of one layer; C0: channels of the first concat source (an output block's first layer), res: the image size
 // at the layer (as run_seq walks it)
 static int prep_layer(dlpm_unet *u, Layer &L, int C0, int &res) {
-    TRY(prep_conv(u, L.c1, C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0));
+    TRY(prep_conv(u, L.c1, C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0, L.kind == L_RES ? res : 0));
     if (L.kind == L_DOWN) res = (res - 1) / 2 + 1;
     if (L.kind == L_UP) res *= 2;
-    if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0));
+    if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0, 0, L.kind == L_RES ? res : 0));
     if (L.kind == L_RES && L.has_skip) TRY(prep_conv(u, L.skip, C0, 0));
     return DLPM_OK;
 }
@@ -1344,7 +1352,7 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     // bit 8: the F(4x4,3x3) kernel where the shape qualifies (128-, 64- or 32-channel n-tiles; its weights go behind the F(2x2) copy).  The
     // kernel takes input channels in multiples of 8, also where the implicit GEMM (multiples of 32) does not
     bool ask_f4 = false;
-    if (wino_shape && (a->force_direct & (8 | 256)) && a->Cout % 32 == 0 && Cin_ % 8 == 0 &&
+    if (wino_shape && (a->force_direct & (8 | 256 | 512)) && a->Cout % 32 == 0 && Cin_ % 8 == 0 &&
         a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
         float *w4 = scratch_dev + used;
         TRY(relayout_weight_wino4(a->weight, w4, a->Cout, Cin_, st));
@@ -1357,6 +1365,14 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     // weights go behind the F(4x4,3x3) copy
     if ((a->force_direct & 256) && L.w_wino4 && a->Cout % 128 == 0 && a->scratch_floats >= used + wino4sp_weight_floats(a->Cout, Cin_))
         L.w_wino4sp = scratch_dev + used;
+    // bit 512: a layer on 4x4-pixel tensors through the one-tile kernel (k_conv3x3_wino4_one); its weights (the 64-channel fragment order) go
+    // behind the F(4x4,3x3) copy
+    const bool ask_one = (a->force_direct & 512) != 0;
+    if (ask_one && L.w_wino4 && !L.w_wino4sp && !a->upsample && wino4_one_layer_ok(a->Cout, a->C0, a->C1, a->Hout, a->Wout) &&
+        a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
+        L.w_wino4_one = scratch_dev + used;
+        L.gen = DLPM_CONV_F4;     // (this entry declares no batch: the generation under which the shape is taken without one)
+    }
     // the head kernels (Cout <= 4): bit 64 the one-pass kernel (head_fused.hip; in the UNet it also carries the sampler's update), W' fragments
     // at the front of the scratch buffer; bit 32 the head as a 1x1 GEMM onto 9 Cout tap channels + gather, W' at the front, P behind it;
     // no bit: k_conv3x3_head where it takes the shape, its [tap][cin][4] copy at the END of the scratch buffer (the front holds the layouts above)
@@ -1384,6 +1400,8 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
         {ask_f4, f4, "dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry"},
         {(a->force_direct & 256) != 0, R.family == CONV_WINO4SP,
          "dlpm_conv2d_f32: force_direct bit 256 asks for the sub-pixel upsampling kernel, which does not take this geometry / scratch size"},
+        {ask_one, R.family == CONV_WINO4 && R.one,
+         "dlpm_conv2d_f32: force_direct bit 512 asks for the one-tile F(4x4) kernel, which does not take this geometry / scratch size"},
         {stats_out != nullptr, px > 0,
          "dlpm_conv2d_stats_f32: this launch emits no statistics (its kernel has no statistics epilogue, or its partials would not lie inside one image)"},
         {ask_head == 64, R.family == CONV_HEAD_FUSED, "dlpm_conv2d_f32: the one-pass head kernel does not take this shape / scratch size"},
@@ -1399,6 +1417,7 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
         *stats_px = px;
     }
     if (R.family == CONV_WINO4SP) TRY(relayout_weight_wino4sp(a->weight, const_cast<float *>(L.w_wino4sp), a->Cout, Cin_, st));
+    if (R.family == CONV_WINO4 && R.one) TRY(relayout_weight_wino4(a->weight, const_cast<float *>(L.w_wino4_one), a->Cout, Cin_, st, 64));
     if (R.family == CONV_HEAD_FUSED) TRY(relayout_weight_head_fused(a->weight, scratch_dev, a->Cout, a->C0, st));
     if (R.family == CONV_HEAD_GEMM) TRY(relayout_weight_head_taps(a->weight, scratch_dev, a->Cout, a->C0, st));
     if (R.family == CONV_HEAD) TRY(relayout_weight_head(a->weight, small_dev, a->Cout, a->C0, st));
@@ -1440,6 +1459,7 @@ static int policy_launch(const dlpm_conv_args *a, int32_t generation, int64_t di
     L.w_wino = take(lay.wino, lay.wino ? wino_weight_floats(a->Cout, Cin) : 0);
     L.w_wino4 = take(lay.wino4, lay.wino4 ? wino4_weight_floats(a->Cout, Cin) : 0);
     L.w_wino4sp = take(lay.wino4sp, lay.wino4sp ? wino4sp_weight_floats(a->Cout, Cin) : 0);
+    L.w_wino4_one = take(lay.wino4_one, lay.wino4_one ? wino4_weight_floats(a->Cout, Cin) : 0);
     L.w_wino4_n64 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
     L.w_wino4_n32 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
     *out = L;
@@ -1502,6 +1522,7 @@ extern "C" int dlpm_conv_policy_f32(const dlpm_conv_args *a, int32_t generation,
     if (lay.wino) TRY(relayout_weight_wino(a->weight, at(L.w_wino), a->Cout, Cin, st));
     if (lay.wino4) TRY(relayout_weight_wino4(a->weight, at(L.w_wino4), a->Cout, Cin, st));
     if (lay.wino4sp) TRY(relayout_weight_wino4sp(a->weight, at(L.w_wino4sp), a->Cout, Cin, st));
+    if (lay.wino4_one) TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_one), a->Cout, Cin, st, 64));
     if (lay.narrow) {
         TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n64), a->Cout, Cin, st, 64));
         TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n32), a->Cout, Cin, st, 32));

@@ -633,7 +633,11 @@ typedef struct dlpm_conv_args {
                                    fp32 MFMA; bit 8 (value 256): an upsampling 3x3 (Cout % 128 == 0, low-res size a multiple of 4 and
                                    not 4x4 itself) as four parity-class Winograd F(4x4,2x2) convolutions on the low-res image
                                    (scratch: + 36 + 104 floats per filter behind the other copies); a geometry or scratch size it
-                                   cannot take fails with DLPM_ERR_UNSUPPORTED */
+                                   cannot take fails with DLPM_ERR_UNSUPPORTED; bit 9 (value 512, with bit 3): a 3x3 stride-1
+                                   convolution on 4x4-pixel tensors (Cout % 64 == 0, C0 + C1 a multiple of 16, C0 of 8, no upsampling)
+                                   through the one-tile F(4x4,3x3) kernel: 16 whole images x 64 channels per workgroup, the input
+                                   channels split over two groups of four waves (scratch: + 36 + 36 floats per filter behind the
+                                   other copies); a geometry or scratch size it cannot take fails with DLPM_ERR_UNSUPPORTED */
     int64_t scratch_floats;     /* size of scratch_dev in floats; room for a second, fragment-ordered copy of a
                                    3x3 weight (+1 KB per 32 output channels) enables the weight-streaming kernel */
 } dlpm_conv_args;
@@ -650,7 +654,8 @@ int dlpm_conv2d_f32(const dlpm_conv_args *args, float *scratch_dev, dlpm_stream_
  * images, ...) fails with DLPM_ERR_UNSUPPORTED -- the condition under which the plan reads the tensor instead.
  * stats_out: [B][Hout*Wout / *stats_px][Cout][2] floats, (mean, centred sum of squares) of *stats_px output pixels each: 128 consecutive
  * NHWC pixels (implicit-GEMM family), 64 = one 8x8 image, 128 / 256 pixels of one F(2x2) block, 256 of one 16x16 F(4x4) block (with bit 8
- * (value 256): per block and parity class), 1024 consecutive pixels (stem); room for B * Hout*Wout/64 * Cout * 2 floats is always enough.
+ * (value 256): per block and parity class), 16 = one 4x4 image (bit 9), 1024 consecutive pixels (stem); room for
+ * B * max(1, Hout*Wout/64) * Cout * 2 floats is always enough.
  * k_gn_coeffs_stats merges an image's partials in index order. */
 int dlpm_conv2d_stats_f32(const dlpm_conv_args *args, float *scratch_dev, float *stats_out, int32_t *stats_px, dlpm_stream_t stream);
 

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Single-layer timing of the 3x3 stride-1 convolution kernels at the CIFAR step's launch shapes (developer tool).
 
-    python tools/bench_conv.py [--gen f4|sp|auto|f2|igemm] [--reps N] [--only I] [--pairs N]
+    python tools/bench_conv.py [--gen f4|sp|one|auto|f2|igemm] [--reps N] [--only I] [--pairs N] [--pairs-one N]
 
 --gen sp: the Upsample shapes through the sub-pixel kernel (force_direct 8 | 256), everything else as f4.  --pairs N: the Upsample
 shapes only, N times (f4, sp) alternating in one process -- the per-layer A/B table of the sub-pixel kernel.
+--gen one: the 4x4-pixel shapes through the one-tile kernel (force_direct 8 | 512), everything else as f4.  --pairs-one N: the two
+4x4-pixel shapes of the step only, N times (f2 = the kernel they ran on before, f4 = the 8-wave kernel on blocks of 16 one-tile images,
+one) alternating in one process -- the per-layer A/B table of the one-tile kernel.
 
 Prints ms per launch (HIP events around `reps` back-to-back launches, weights pre-transformed once through a throw-away
 dlpm_conv2d_f32 call is NOT possible -- that entry point re-lays the weights out on every call, so the relayout kernels are
@@ -34,6 +37,8 @@ SHAPES = [
 ]
 # the three Upsample convolutions of the CIFAR net (--pairs; index 6 above is the first)
 UPS_SHAPES = [SHAPES[6], ('H8->16 256->256 ups', 1024, 256, 0, 8, 256, 1, False, False), ('H4->8 256->256 ups', 1024, 256, 0, 4, 256, 1, False, False)]
+# the two 3x3 launch shapes of the step on 4x4-pixel tensors (--pairs-one): 11 and 3 launches per step
+ONE_SHAPES = [('H4  256->256 gn res', 1024, 256, 0, 4, 256, 0, True, True), ('H4  256+256->256 gn res', 1024, 256, 256, 4, 256, 0, True, True)]
 
 
 def run(name, B, C0, C1, H, Cout, ups, coef, res, gen, reps, zeros=False):
@@ -68,7 +73,8 @@ def run(name, B, C0, C1, H, Cout, ups, coef, res, gen, reps, zeros=False):
         keep.append(r)
         a.res0, a.R0 = r.data_ptr(), Cout
     a.out, a.Cout = out.data_ptr(), Cout
-    a.force_direct = {'auto': 0, 'f4': 8, 'f2': 0, 'igemm': 2, 'sp': (8 | 256) if ups and H > 4 else 8}[gen]
+    a.force_direct = {'auto': 0, 'f4': 8, 'f2': 0, 'igemm': 2, 'sp': (8 | 256) if ups and H > 4 else 8,
+                      'one': (8 | 512) if H == 4 and not ups else 8}[gen]
     scratch = torch.empty(90 * w.numel() + 64 * 1024 * (1 + Cout // 32), device=DEV)
     a.scratch_floats = scratch.numel()
     st = _lib.stream_ptr()
@@ -96,12 +102,20 @@ ap.add_argument('--gen', default='f4')
 ap.add_argument('--reps', type=int, default=10)
 ap.add_argument('--only', type=int, default=-1)
 ap.add_argument('--pairs', type=int, default=0)
+ap.add_argument('--pairs-one', type=int, default=0)
 ap.add_argument('--zeros', action='store_true', help='all-zero operands: the same instruction stream at the clock the chip holds without data toggling (DVFS check)')
 args = ap.parse_args()
 if args.pairs:
     for k in range(args.pairs):
         for s in UPS_SHAPES:
             for gen in ('f4', 'sp'):
+                print('pair %d %-3s' % (k, gen), end=' ')
+                run(*s, gen=gen, reps=args.reps)
+    sys.exit(0)
+if args.pairs_one:
+    for k in range(args.pairs_one):
+        for s in ONE_SHAPES:
+            for gen in ('f2', 'f4', 'one'):
                 print('pair %d %-3s' % (k, gen), end=' ')
                 run(*s, gen=gen, reps=args.reps)
     sys.exit(0)

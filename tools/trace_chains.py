@@ -9,7 +9,7 @@ import csv
 import sys
 from collections import defaultdict
 
-SUMS = ('k_conv3x3_wino4<', 'k_conv3x3_wino4sp', 'k_conv_split_pipe', 'k_gn_coeffs')
+SUMS = ('k_conv3x3_wino4<', 'k_conv3x3_wino4sp', 'k_conv3x3_wino4_one', 'k_conv_split_pipe', 'k_gn_coeffs')
 
 
 def short(name):
