@@ -57,7 +57,7 @@ struct ConvLaunch {
 #endif
 };
 
-// true when the MFMA implicit-GEMM kernel covers this shape (prep_conv chooses the weight layout by it)
+// true when the MFMA implicit-GEMM kernel covers this shape (conv_layouts chooses the plain weight layout by it)
 bool igemm_supported(const ConvLaunch &c);
 
 // The ONE routing decision of a convolution launch: which kernel family runs it, on what block geometry, and what follows from
@@ -173,17 +173,44 @@ bool conv_split_ok(const ConvLaunch &c);
 int launch_conv_split(const ConvLaunch &c, hipStream_t st);
 int64_t split_weight_floats(int Cout, int Cin, int taps);
 int relayout_weight_split(const float *oihw_dev, void *dst_dev, int Cout, int Cin, int taps, hipStream_t st);
-// The weight layouts the UNet builds for a 3x3 layer besides the plain one (prep_conv, narrow_wino4_copies), as a function of the layer
-// and the declared batch: the ONE place that decides them.  Reads of `c`: C0, C1, Cout, ks, stride, in_nchw / out_nchw (a boundary or
-// stride-2 layer gets the fragment copy only), ups with Hin x Win (the low-res size of an Upsample convolution), dispatch_B.
-constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
-struct Conv3Layouts {
-    bool frag = false, wino = false, wino4 = false, wino4sp = false;
-    bool wino4_one = false; // the one-tile copy of a layer on 4x4-pixel tensors (Hout x Wout of `c`; 0 x 0: unknown, none)
-    bool narrow = false;    // the 64- / 32-channel n-tile copies of the F(4x4) weights: Cout % 128 == 0 under a small declared batch
+// The weight layouts of a convolution layer: ONE table (conv_layouts.hip) with a row per layout -- its name, its size in floats for a
+// layer, the call that builds it from the OIHW parameter, the ConvLaunch field that receives it -- and ONE rule, conv_layouts, for which
+// layouts a layer gets.  The UNet's finalize / set_conv_policy, dlpm_conv_policy_f32 and dlpm_conv2d_f32 all place, build and attach
+// through it; the *_weight_floats and relayout_weight_* functions of the kernel files are what the rows call.  The order of the enum is
+// the order in which layouts are placed in a scratch buffer.
+enum ConvLayout {
+    LAY_PLAIN,          // [tap][Cout][Cin], the implicit GEMM's order (ConvLaunch::w)
+    LAY_PLAIN_DIRECT,   // [tap][Cin][Cout], the direct and stem kernels' order (ConvLaunch::w as well: a layer has one of the two, or, as a
+                        // 1x1 implicit GEMM, neither -- its [O][I] parameter is that layout already)
+    LAY_FRAG, LAY_WINO, LAY_WINO4, LAY_WINO4SP, LAY_WINO4_ONE, LAY_WINO4_N64, LAY_WINO4_N32, LAY_SPLIT, LAY_HEAD, LAY_HEAD_TAPS, LAY_HEAD_FUSED,
+    LAY_SMALL,          // fragment order of the fused small-image blocks: no ConvLaunch field, it feeds ResSmallLaunch / AttnSmallLaunch
+    CONV_LAYOUT_COUNT
 };
-bool wino4_narrow_copies_wanted(int Cout, int64_t dispatch_B);
-Conv3Layouts conv3_layouts(const ConvLaunch &c);
+constexpr unsigned lay_bit(ConvLayout l) { return 1u << l; }
+struct ConvLayoutRow {
+    const char *name;
+    int64_t (*floats)(const ConvLaunch &layer);
+    int (*build)(const ConvLaunch &layer, const float *oihw_dev, float *dst_dev, hipStream_t st);
+    void (*attach)(ConvLaunch &c, const float *p);      // null: see LAY_SMALL
+};
+const ConvLayoutRow &conv_layout(int l);              // the table, by ConvLayout
+// The layouts a layer gets, as a mask of lay_bit.  Reads of `layer`: C0, C1, Cout, ks, stride, in_nchw / out_nchw (a boundary or stride-2
+// layer gets the fragment copy only), ups with Hin x Win (the low-res size of an Upsample convolution), Hout x Wout (the one-tile copy of
+// a layer on 4x4-pixel tensors; 0 x 0: unknown, none), dispatch_B (the narrow F(4x4) copies exist for Cout % 128 == 0 under a declared
+// batch of at most NARROW_COPIES_MAX_BATCH), gemm (DLPM_GEMM_F32: the layer stays on the fp32 pipe -- the time MLP and the emb linears --
+// and gets neither the bf16x3 planes nor the fused blocks' order).
+constexpr int64_t NARROW_COPIES_MAX_BATCH = 512;
+unsigned conv_layouts(const ConvLaunch &layer);
+// Places the layouts of `mask` one behind the other from base + *used, in the order of the enum, each at a multiple of `align` floats
+// from base: at[l] = where layout l goes, *used = the floats from base to the end of the last one (a multiple of `align`).  A layout
+// that would end past `cap` floats is left out (at[l] stays as it was).  Returns the mask of the layouts placed.  Nothing is read
+// through a pointer.
+unsigned place_conv_layouts(const ConvLaunch &layer, unsigned mask, float *base, int64_t align, int64_t cap, float *at[CONV_LAYOUT_COUNT],
+                            int64_t *used);
+// Builds the layouts of `mask` from the OIHW weights into at[l], in the order of the enum, on `st`
+int build_conv_layouts(const ConvLaunch &layer, unsigned mask, const float *oihw_dev, float *const at[CONV_LAYOUT_COUNT], hipStream_t st);
+// Points the launch at every layout of at[] that is not null and has a ConvLaunch field
+void attach_conv_layouts(ConvLaunch &c, float *const at[CONV_LAYOUT_COUNT]);
 // A convolution launch as its route asks for it (conv_splitk.hip): launch_conv where r.ksplit <= 1; otherwise the split-K form -- the launch
 // stripped of bias / residual / statistics runs r.ksplit grid copies into part (splitk_partial_floats(c, r) floats, left holding the
 // partial outputs), then launch_splitk_reduce forms c.out.  r = conv_route(c).

@@ -1132,24 +1132,6 @@ static int ksplit_for(const ConvLaunch &c, int64_t grid) {
     return S;
 }
 
-bool wino4_narrow_copies_wanted(int Cout, int64_t dispatch_B) {
-    return Cout % 128 == 0 && dispatch_B > 0 && dispatch_B <= NARROW_COPIES_MAX_BATCH;
-}
-
-Conv3Layouts conv3_layouts(const ConvLaunch &c) {
-    Conv3Layouts y;
-    const int Cin = c.C0 + c.C1;
-    const bool plain = !c.in_nchw && !c.out_nchw && c.stride == 1;
-    if (!igemm_supported(c) || c.ks != 3 || Cin % 32 != 0) return y;
-    y.frag = true;
-    y.wino = plain && c.Cout % 64 == 0 && Cin % 16 == 0;      // Winograd-domain copy (stride-1 launches pick it up)
-    y.wino4 = plain && wino4_enabled() && c.Cout % 32 == 0 && Cin % 8 == 0;   // F(4x4,3x3) copy (128-, 64- or 32-channel n-tiles)
-    y.wino4sp = y.wino4 && c.ups && wino4sp_layer_ok(c.Cout, Cin, c.Hin, c.Win);   // sub-pixel copy of an Upsample convolution
-    y.wino4_one = y.wino4 && !c.ups && wino4_one_layer_ok(c.Cout, c.C0, c.C1, c.Hout, c.Wout);   // one-tile copy of a layer on 4x4-pixel tensors
-    y.narrow = y.wino4 && wino4_narrow_copies_wanted(c.Cout, c.dispatch_B);
-    return y;
-}
-
 ConvRoute conv_route(const ConvLaunch &c) {
     ConvRoute r;
     const int64_t hw = (int64_t)c.Hout * c.Wout;

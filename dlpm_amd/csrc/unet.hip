@@ -39,28 +39,11 @@ struct Param {
 enum LayerKind { L_STEM, L_RES, L_ATTN, L_DOWN, L_UP };
 
 struct ConvW {            // one convolution's weights
-    int p_w = -1, p_b = -1;  // param indices
+    int p_w = -1, p_b = -1;  // param indices (p_w < 0: the stacked emb linears, dlpm_unet::embcat_w)
     int cout = 0, cin = 0, ks = 1;
-    bool use_igemm = false;  // prep_conv: which layout w_dev holds (igemm_supported of the layer); the launch asks conv_route
-    float *w_dev = nullptr;  // re-laid-out copy (or the original for 1x1 igemm)
-    float *w_frag = nullptr; // 3x3 only: MFMA fragment order for the weight-streaming halo kernel
-    float *w_wino = nullptr; // 3x3 only: Winograd-domain weights in fragment order (conv_wino.hip)
-    float *w_wino4 = nullptr;// 3x3 only: F(4x4,3x3) Winograd-domain weights (conv_wino4.hip), when DLPM_WINO_F4 is on
-    float *w_wino4_n64 = nullptr, *w_wino4_n32 = nullptr;   // cout % 128 == 0, built while a SMALL dispatch batch is declared: the same weights in the
-                             // fragment order of 64- / 32-channel n-tiles (narrow_wino4_copies)
-    float *w_wino4sp = nullptr; // Upsample convolutions with cout % 128 == 0: the parity classes' F(4x4,2x2) weights (conv_wino4.hip: k_conv3x3_wino4sp)
-    float *w_wino4_one = nullptr; // layers on 4x4-pixel tensors with cout % 64 == 0: the F(4x4) weights in 64-channel fragment order (k_conv3x3_wino4_one)
-    float *w_small = nullptr;// 3x3 with cout <= 4 (head): [tap][cin][4]
-    float *w_taps = nullptr; // 3x3 with cout <= 3 (head): [9 cout -> 32][cin], the head as a 1x1 GEMM + gather (conv_direct.hip)
-    float *w_split = nullptr;// 1x1 with cout % 128 == 0, cin % 32 == 0: three bf16 planes in stage-tile order (conv_split.hip)
-    float *w_rs = nullptr;   // 64-channel layers: fragment order of the fused small-image blocks (block_small.hip)
-    float *w_hfused = nullptr;  // head: fragment order of the one-pass head + update kernel (head_fused.hip)
-    bool owns = false;
+    ConvLaunch layer;        // the layer as conv_layouts (conv.h) is asked about it: what dlpm_unet_finalize describes, under the declared batch
+    float *lay[CONV_LAYOUT_COUNT] = {};   // the device copies of the weights this convolution owns, by ConvLayout (sync_layouts)
 };
-// the layouts a ConvW always owns (w_dev only where `owns` says so); the copies that exist only under a small declared batch, by n-tile width
-constexpr float *ConvW::*OWNED_LAYOUTS[] = {&ConvW::w_frag, &ConvW::w_wino, &ConvW::w_wino4, &ConvW::w_wino4_n64, &ConvW::w_wino4_n32, &ConvW::w_wino4sp, &ConvW::w_wino4_one,
-                                            &ConvW::w_small, &ConvW::w_taps, &ConvW::w_split, &ConvW::w_rs, &ConvW::w_hfused};
-constexpr struct { int nq; float *ConvW::*copy; } NARROW_LAYOUTS[] = {{64, &ConvW::w_wino4_n64}, {32, &ConvW::w_wino4_n32}};
 
 struct Layer {
     LayerKind kind;
@@ -287,99 +270,13 @@ void build_arch(dlpm_unet *u) {
     u->head = u->conv("out.2.", c.out_channels, mc, 3);
 }
 
-// ups_lo: low-res image size of an Upsample convolution (0: not one); res: the image size a ResBlock convolution runs at (0: not one)
-int prep_conv(dlpm_unet *u, ConvW &c, int C0, int boundary, int ups_lo = 0, int res = 0) {  // boundary: 0 none, 1 NCHW input (stem), 2 NCHW output (head), 3 time MLP, 4 stride-2 downsampling
-    ConvLaunch probe;
-    probe.C0 = C0; probe.C1 = c.cin - C0; probe.Cout = c.cout; probe.ks = c.ks;
-    probe.in_nchw = boundary == 1; probe.out_nchw = boundary == 2;
-    probe.stride = boundary == 4 ? 2 : 1; probe.ups = ups_lo > 0; probe.Hin = probe.Win = ups_lo;
-    probe.Hout = probe.Wout = ups_lo > 0 ? 2 * ups_lo : res;
-    const Conv3Layouts lay = conv3_layouts(probe);     // (the narrow F(4x4) copies come and go with the declared batch: narrow_wino4_copies)
-    c.use_igemm = igemm_supported(probe);
-    const float *src = u->params[c.p_w].dev;
-    if (c.use_igemm && c.ks == 1) {  // [O][I] row-major is already the igemm layout
-        c.w_dev = const_cast<float *>(src);
-        if (small_weight_ok(c.cout, c.cin, 1) && boundary == 0) {
-            DLPM_HIP(hipMalloc(&c.w_rs, (size_t)small_weight_floats(c.cout, c.cin, 1) * sizeof(float)));
-            int r = relayout_weight_small(src, c.w_rs, c.cout, c.cin, 1, nullptr);
-            if (r != DLPM_OK) return r;
-        }
-        if (c.cout % 128 == 0 && c.cin % 32 == 0 && boundary == 0) {
-            DLPM_HIP(hipMalloc(&c.w_split, (size_t)split_weight_floats(c.cout, c.cin, 1) * sizeof(float)));
-            return relayout_weight_split(src, c.w_split, c.cout, c.cin, 1, nullptr);
-        }
-        return DLPM_OK;
-    }
-    DLPM_HIP(hipMalloc(&c.w_dev, (size_t)c.cout * c.cin * c.ks * c.ks * sizeof(float)));
-    c.owns = true;
-    if (c.ks == 3 && c.cout <= 4 && c.cin % 32 == 0) {
-        DLPM_HIP(hipMalloc(&c.w_small, (size_t)9 * c.cin * 4 * sizeof(float)));
-        int r = relayout_weight_head(src, c.w_small, c.cout, c.cin, nullptr);
-        if (r != DLPM_OK) return r;
-        if (c.cout <= 3) {
-            DLPM_HIP(hipMalloc(&c.w_taps, (size_t)head_taps_rows(c.cout) * c.cin * sizeof(float)));
-            r = relayout_weight_head_taps(src, c.w_taps, c.cout, c.cin, nullptr);
-            if (r != DLPM_OK) return r;
-            if (c.cin <= 128) {
-                DLPM_HIP(hipMalloc(&c.w_hfused, (size_t)head_fused_weight_floats(c.cin) * sizeof(float)));
-                r = relayout_weight_head_fused(src, c.w_hfused, c.cout, c.cin, nullptr);
-                if (r != DLPM_OK) return r;
-            }
-        }
-    }
-    if (c.use_igemm && c.ks == 3 && boundary == 4 && c.cout % 128 == 0 && c.cin % 32 == 0) {   // stride-2 downsampling convolution
-        DLPM_HIP(hipMalloc(&c.w_split, (size_t)split_weight_floats(c.cout, c.cin, 9) * sizeof(float)));
-        int r = relayout_weight_split(src, c.w_split, c.cout, c.cin, 9, nullptr);
-        if (r != DLPM_OK) return r;
-    }
-    if (lay.frag) {     // which copies a 3x3 layer gets: conv3_layouts (conv.h)
-        DLPM_HIP(hipMalloc(&c.w_frag, (size_t)frag_weight_floats(c.cout, c.cin) * sizeof(float)));
-        int r = relayout_weight_frag(src, c.w_frag, c.cout, c.cin, nullptr);
-        if (r != DLPM_OK) return r;
-        if (lay.wino) {   // Winograd-domain copy (stride-1 launches pick it up)
-            DLPM_HIP(hipMalloc(&c.w_wino, (size_t)wino_weight_floats(c.cout, c.cin) * sizeof(float)));
-            r = relayout_weight_wino(src, c.w_wino, c.cout, c.cin, nullptr);
-            if (r != DLPM_OK) return r;
-        }
-        if (lay.wino4) {   // F(4x4,3x3) copy (128-, 64- or 32-channel n-tiles)
-            DLPM_HIP(hipMalloc(&c.w_wino4, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)));
-            r = relayout_weight_wino4(src, c.w_wino4, c.cout, c.cin, nullptr);
-            if (r != DLPM_OK) return r;
-            if (lay.wino4sp) {   // sub-pixel copy of an Upsample convolution (104 floats per filter)
-                DLPM_HIP(hipMalloc(&c.w_wino4sp, (size_t)wino4sp_weight_floats(c.cout, c.cin) * sizeof(float)));
-                r = relayout_weight_wino4sp(src, c.w_wino4sp, c.cout, c.cin, nullptr);
-                if (r != DLPM_OK) return r;
-            }
-            if (lay.wino4_one) {   // one-tile copy of a layer on 4x4-pixel tensors: the 64-channel fragment order
-                DLPM_HIP(hipMalloc(&c.w_wino4_one, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)));
-                r = relayout_weight_wino4(src, c.w_wino4_one, c.cout, c.cin, nullptr, 64);
-                if (r != DLPM_OK) return r;
-            }
-        }
-    }
-    if (small_weight_ok(c.cout, c.cin, c.ks) && boundary == 0) {
-        DLPM_HIP(hipMalloc(&c.w_rs, (size_t)small_weight_floats(c.cout, c.cin, c.ks) * sizeof(float)));
-        int r = relayout_weight_small(src, c.w_rs, c.cout, c.cin, c.ks, nullptr);
-        if (r != DLPM_OK) return r;
-    }
-    return relayout_weight(src, c.w_dev, c.cout, c.cin, c.ks, c.use_igemm, nullptr);
-}
+const float *oihw_of(const dlpm_unet *u, const ConvW &c) { return c.p_w >= 0 ? u->params[c.p_w].dev : u->embcat_w; }
 
 // the launch descriptor with the net's policy and this convolution's weight layouts attached: the ONE place a ConvW is copied into a launch
 void attach_conv(const dlpm_unet *u, const ConvW &c, ConvLaunch &L) {
     policy_of(u, L);
-    L.w = c.w_dev;
-    L.w_frag = c.w_frag;
-    L.w_wino = c.w_wino;
-    L.w_wino4 = c.w_wino4;
-    L.w_wino4_n64 = c.w_wino4_n64;
-    L.w_wino4_n32 = c.w_wino4_n32;
-    L.w_wino4sp = c.w_wino4sp;
-    L.w_wino4_one = c.w_wino4_one;
-    L.w_small = c.w_small;
-    L.w_taps = c.w_taps;
-    L.w_hfused = c.w_hfused;
-    L.w_split = c.w_split;
+    L.w = oihw_of(u, c);       // (a 1x1 implicit GEMM owns no plain copy: its [O][I] parameter is that layout)
+    attach_conv_layouts(L, c.lay);
     L.ks = c.ks;
     L.Cout = c.cout;
 }
@@ -505,7 +402,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
         // policy only -- never of the batch -- like every other kernel choice (the fused block rounds differently).
         ResSmallLaunch r;
         r.x0 = x0.p; r.x1 = x1.p; r.C0 = C0; r.C1 = C1; r.B = B; r.H = H; r.W = W;
-        r.w1f = L.c1.w_rs; r.w2f = L.c2.w_rs; r.wsf = L.has_skip ? L.skip.w_rs : nullptr;
+        r.w1f = L.c1.lay[LAY_SMALL]; r.w2f = L.c2.lay[LAY_SMALL]; r.wsf = L.has_skip ? L.skip.lay[LAY_SMALL] : nullptr;
         if (u->gen == DLPM_CONV_AUTO && Co == 64 && (!L.has_skip || r.wsf) && res_small_ok(r)) {
             *out = new_tensor(cx, Co, H, W);
             out->stats = reinterpret_cast<float2 *>(cx.ws.alloc((int64_t)2 * B * Co));
@@ -519,7 +416,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
             return enqueue(cx, launch_resblock_small, r);
         }
     }
-    if (u->gen == DLPM_CONV_AUTO && ((Co == 32 && H == 32 && W == 32) || (Co == 64 && H == 16 && W == 16)) && L.c1.w_wino4 && L.c2.w_wino4) {
+    if (u->gen == DLPM_CONV_AUTO && ((Co == 32 && H == 32 && W == 32) || (Co == 64 && H == 16 && W == 16)) && L.c1.lay[LAY_WINO4] && L.c2.lay[LAY_WINO4]) {
         // 32 channels on 32x32 images: the whole block in ONE launch, one workgroup per image (conv_wino4.hip: k_resblock_wino4_img) -- the
         // bits of the separate launches below (a function of the layer and the policy only).  GroupNorm-1 runs inside the kernel when both
         // sources carry statistics; the 1x1 skip convolution of the concat blocks stays a launch of its own.
@@ -527,7 +424,7 @@ int run_res(Ctx &cx, const Layer &L, Tensor4 x0, Tensor4 x1, Tensor4 *out) {
         ResImgLaunch r;
         r.x0 = x0.p; r.x1 = x1.p; r.C0 = C0; r.C1 = C1; r.B = B; r.H = H;
         const bool from_stats = x0.stats && (C1 == 0 || x1.stats);
-        r.w1 = L.c1.w_wino4; r.w2 = L.c2.w_wino4;
+        r.w1 = L.c1.lay[LAY_WINO4]; r.w2 = L.c2.lay[LAY_WINO4];
         float *cA1 = from_stats ? nullptr : cx.ws.alloc((int64_t)B * Cin), *cB1 = from_stats ? nullptr : cx.ws.alloc((int64_t)B * Cin);
         Tensor4 sk = L.has_skip ? new_tensor(cx, Co, H, W) : Tensor4();
         Tensor4 hb = H == 32 ? new_tensor(cx, Co, H, W) : Tensor4();     // the activated intermediate (it stays in LDS at 16x16)
@@ -592,7 +489,7 @@ int run_attn(Ctx &cx, const Layer &L, Tensor4 x, Tensor4 *out) {
     // that do not take it: GroupNorm + qkv of one image in one launch
     AttnSmallLaunch a;
     a.x = x.p; a.C = C; a.heads = u->cfg.num_heads; a.B = B; a.H = x.H; a.W = x.W;
-    a.wqkv = L.c1.w_rs; a.wproj = L.c2.w_rs;
+    a.wqkv = L.c1.lay[LAY_SMALL]; a.wproj = L.c2.lay[LAY_SMALL];
     a.gn_w = u->params[L.p_gn1_w].dev; a.gn_b = u->params[L.p_gn1_b].dev;
     a.bqkv = u->params[L.c1.p_b].dev; a.bproj = u->params[L.c2.p_b].dev;
     const bool whole16 = attn16_ok(a);
@@ -788,7 +685,7 @@ void for_each_layer(dlpm_unet *u, F fn) {
         for (size_t i = 0; i < s.size(); i++) fn(s[i], i == 0);
 }
 
-// ... and every convolution, the time MLP's and the head included
+// ... and every convolution, the time MLP's, the stacked emb linears and the head included
 template <class F>
 void for_each_conv(dlpm_unet *u, F fn) {
     for_each_layer(u, [&](Layer &L, bool) {
@@ -798,6 +695,7 @@ void for_each_conv(dlpm_unet *u, F fn) {
     });
     fn(u->te0);
     fn(u->te2);
+    fn(u->embcat);
     fn(u->head);
 }
 
@@ -885,42 +783,48 @@ static void free_dev(float *&p) {
 }
 
 static void free_conv(ConvW &c) {
-    if (!c.owns) c.w_dev = nullptr;      // (the parameter itself, or the stacked emb weights)
-    free_dev(c.w_dev);
-    for (auto layout : OWNED_LAYOUTS) free_dev(c.*layout);
-    c.owns = false;
+    for (float *&p : c.lay) free_dev(p);
 }
 
-// Round 6: under a small DECLARED batch (dlpm_unet_set_conv_policy's dispatch_batch) the 128-channel-multiple F(4x4) layers may run on 64- / 32-
-// channel n-tiles (conv_wino4.hip: wino4_nq_for), which read the same Winograd-domain weights in another fragment order.  The copies
-// exist only while such a batch is declared (3x the F(4x4) weight bytes of those layers); built from the parameters, on the null stream.
-// Which layers and which declarations: wino4_narrow_copies_wanted (conv.h: NARROW_COPIES_MAX_BATCH), the rule conv3_layouts states.
-static int narrow_wino4_copies(dlpm_unet *u) {
+// Brings every convolution's device copies in line with conv_layouts (conv.h) of its layer under the declared batch: frees what is present
+// and not wanted, allocates and builds what is wanted and absent (after free_conv: everything).  So the 64- / 32-channel n-tile copies of
+// the F(4x4) weights come and go with dlpm_unet_set_conv_policy's dispatch_batch.  Built from the parameters, on the null stream.
+static int sync_layouts(dlpm_unet *u) {
     int rc = DLPM_OK;
     for_each_conv(u, [&](ConvW &c) {
-        if (!c.w_wino4 || c.cout % 128 != 0) return;      // (the ResBlock and Upsample convolutions that carry F(4x4) weights)
-        const bool want = wino4_narrow_copies_wanted(c.cout, u->dispatch_B);
-        for (auto &n : NARROW_LAYOUTS) {
-            float *&dst = c.*n.copy;
-            if (!want) free_dev(dst);
-            if (!want || dst || rc != DLPM_OK) continue;
-            if (hipMalloc(&dst, (size_t)wino4_weight_floats(c.cout, c.cin) * sizeof(float)) != hipSuccess) { dst = nullptr; rc = DLPM_ERR_HIP; set_error("narrow_wino4_copies: hipMalloc failed"); continue; }
-            rc = relayout_weight_wino4(u->params[c.p_w].dev, dst, c.cout, c.cin, nullptr, n.nq);
+        c.layer.dispatch_B = u->dispatch_B;
+        const unsigned want = conv_layouts(c.layer);
+        unsigned absent = 0;
+        for (int l = 0; l < CONV_LAYOUT_COUNT && rc == DLPM_OK; l++) {
+            if (!(want >> l & 1)) free_dev(c.lay[l]);
+            if (!(want >> l & 1) || c.lay[l]) continue;
+            if (hipMalloc(&c.lay[l], (size_t)conv_layout(l).floats(c.layer) * sizeof(float)) != hipSuccess) { c.lay[l] = nullptr; rc = DLPM_ERR_HIP; set_error("sync_layouts: hipMalloc failed"); continue; }
+            absent |= 1u << l;
         }
+        if (rc == DLPM_OK) rc = build_conv_layouts(c.layer, absent, oihw_of(u, c), c.lay, nullptr);
     });
-    if (rc == DLPM_OK && hipDeviceSynchronize() != hipSuccess) { set_error("narrow_wino4_copies: synchronize failed"); rc = DLPM_ERR_HIP; }
+    if (rc == DLPM_OK && hipDeviceSynchronize() != hipSuccess) { set_error("sync_layouts: synchronize failed"); rc = DLPM_ERR_HIP; }
     return rc;
 }
 
-// per-conv weight layouts of one layer; C0: channels of the first concat source (an output block's first layer), res: the image size
-// at the layer (as run_seq walks it)
-static int prep_layer(dlpm_unet *u, Layer &L, int C0, int &res) {
-    TRY(prep_conv(u, L.c1, C0, L.kind == L_STEM ? 1 : L.kind == L_DOWN ? 4 : 0, L.kind == L_UP ? res : 0, L.kind == L_RES ? res : 0));
+// the layer of convolution `c` as conv_layouts is asked about it: C0 channels from the first concat source, images of `in` -> `out` pixels a side
+static ConvLaunch layer_of(const ConvW &c, int C0, int in, int out) {
+    ConvLaunch d;
+    d.C0 = C0; d.C1 = c.cin - C0; d.Cout = c.cout; d.ks = c.ks;
+    d.Hin = d.Win = in; d.Hout = d.Wout = out;
+    return d;
+}
+
+// ... of the convolutions of one layer of the plan; C0: channels of the first concat source (an output block's first layer), res: the
+// image size at the layer (as run_seq walks it)
+static void describe_layer(Layer &L, int C0, int &res) {
+    const int in = res;
     if (L.kind == L_DOWN) res = (res - 1) / 2 + 1;
     if (L.kind == L_UP) res *= 2;
-    if (L.kind == L_RES || L.kind == L_ATTN) TRY(prep_conv(u, L.c2, L.c2.cin, 0, 0, L.kind == L_RES ? res : 0));
-    if (L.kind == L_RES && L.has_skip) TRY(prep_conv(u, L.skip, C0, 0));
-    return DLPM_OK;
+    L.c1.layer = layer_of(L.c1, C0, in, res);
+    L.c1.layer.in_nchw = L.kind == L_STEM; L.c1.layer.stride = L.kind == L_DOWN ? 2 : 1; L.c1.layer.ups = L.kind == L_UP;
+    if (L.kind == L_RES || L.kind == L_ATTN) L.c2.layer = layer_of(L.c2, L.c2.cin, res, res);
+    if (L.kind == L_RES && L.has_skip) L.skip.layer = layer_of(L.skip, C0, res, res);
 }
 
 // fused emb GEMM: this ResBlock's emb_layers.1 rows into the stacked weights
@@ -945,29 +849,19 @@ extern "C" int dlpm_unet_finalize(dlpm_unet *u) {
     DLPM_HIP(hipMalloc(&u->embcat_b, (size_t)u->emb_total * sizeof(float)));
     int rc = DLPM_OK, res = u->cfg.image_size, ch = 0;      // ch: channels of h entering the layer = the previous layer's cout
     for_each_layer(u, [&](Layer &L, bool cat) {
-        if (rc == DLPM_OK) rc = prep_layer(u, L, cat ? ch : L.c1.cin, res);
+        describe_layer(L, cat ? ch : L.c1.cin, res);
         if (rc == DLPM_OK && L.kind == L_RES) rc = stack_emb(u, L);
         ch = L.cout;
     });
     TRY(rc);
-    TRY(prep_conv(u, u->te0, u->te0.cin, 3));   // 3: the time path stays on the fp32 pipe whatever its row count
-    TRY(prep_conv(u, u->te2, u->te2.cin, 3));
-    TRY(prep_conv(u, u->head, u->head.cin, 2));
     u->embcat.cout = u->emb_total; u->embcat.cin = u->ted; u->embcat.ks = 1;
-    {
-        ConvLaunch probe;
-        probe.C0 = u->ted; probe.Cout = u->emb_total; probe.ks = 1;
-        u->embcat.use_igemm = igemm_supported(probe);
-        if (u->embcat.use_igemm) {
-            u->embcat.w_dev = u->embcat_w;
-        } else {
-            DLPM_HIP(hipMalloc(&u->embcat.w_dev, (size_t)u->emb_total * u->ted * sizeof(float)));
-            u->embcat.owns = true;
-            TRY(relayout_weight(u->embcat_w, u->embcat.w_dev, u->emb_total, u->ted, 1, false, nullptr));
-        }
+    for (ConvW *c : {&u->te0, &u->te2, &u->embcat}) {
+        c->layer = layer_of(*c, c->cin, 1, 1);
+        c->layer.gemm = DLPM_GEMM_F32;     // the time path stays on the fp32 pipe whatever its row count
     }
-    TRY(narrow_wino4_copies(u));     // (a dispatch batch declared before finalize, or weights re-uploaded under one)
-    DLPM_HIP(hipDeviceSynchronize());
+    u->head.layer = layer_of(u->head, u->head.cin, res, res);
+    u->head.layer.out_nchw = 1;
+    TRY(sync_layouts(u));     // (under the dispatch batch declared before finalize, if any)
     u->flops = count_flops(u);
     u->finalized = true;
     u->plan_version++;
@@ -983,7 +877,7 @@ extern "C" int dlpm_unet_set_conv_policy(dlpm_unet *u, int32_t generation, int64
     u->gen = generation;
     u->dispatch_B = dispatch_batch;
     u->plan_version++;
-    if (u->finalized) TRY(narrow_wino4_copies(u));
+    if (u->finalized) TRY(sync_layouts(u));
     return DLPM_OK;
 }
 
@@ -1275,7 +1169,6 @@ extern "C" int64_t dlpm_unet_flops_per_sample(const dlpm_unet *net) { return net
 extern "C" void dlpm_unet_destroy(dlpm_unet *u) {
     if (!u) return;
     for_each_conv(u, free_conv);
-    if (u->embcat.owns && u->embcat.w_dev) (void)hipFree(u->embcat.w_dev);
     if (u->embcat_w) (void)hipFree(u->embcat_w);
     if (u->embcat_b) (void)hipFree(u->embcat_b);
     for (auto &p : u->params)
@@ -1312,93 +1205,79 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
     DLPM_CHECK_ARG(a->stride == 1 || a->stride == 2, "dlpm_conv2d_f32: stride must be 1 or 2");
     DLPM_CHECK_ARG((a->C1 == 0) == (a->src1 == nullptr), "dlpm_conv2d_f32: src1/C1 mismatch");
     ConvLaunch L = launch_of_args(a);
-    const bool ig = !(a->force_direct & 1) && igemm_supported(L);
+    const int fd = a->force_direct, Cin_ = a->C0 + a->C1;
+    const bool ig = !(fd & 1) && igemm_supported(L);
     if ((a->in_nchw || a->out_nchw) && a->C1 != 0) {
         set_error("dlpm_conv2d_f32: NCHW boundary layouts do not combine with a concat input");
         return DLPM_ERR_UNSUPPORTED;
     }
-    if (a->force_direct & 4) {
+    if (fd & 4) {
         set_error("dlpm_conv2d_f32: force_direct bit 2 (value 4) asked for 1x1 convolutions on the weight-streaming kernel, which was removed");
         return DLPM_ERR_UNSUPPORTED;
     }
-    hipStream_t st = as_stream(stream);
-    TRY(relayout_weight(a->weight, scratch_dev, a->Cout, a->C0 + a->C1, a->ksize, ig, st));
-    L.w = scratch_dev;
     L.gemm = DLPM_GEMM_F32;
-    const int taps = a->ksize * a->ksize;
-    if (ig && (a->force_direct & 16) && a->Cout % 128 == 0 && (a->C0 + a->C1) % 32 == 0 &&
-        a->scratch_floats >= (int64_t)a->Cout * (a->C0 + a->C1) * taps + split_weight_floats(a->Cout, a->C0 + a->C1, taps)) {
-        float *wsp = scratch_dev + (int64_t)a->Cout * (a->C0 + a->C1) * taps;
-        TRY(relayout_weight_split(a->weight, wsp, a->Cout, a->C0 + a->C1, taps, st));
-        L.w_split = wsp;
+    // The force_direct bits as masks of layouts asked for (sizes, relayout calls and ConvLaunch fields: the table of conv.h), placed in the
+    // scratch buffer front to back.  A layout that does not fit is left out, and the launch takes what its route makes of the rest.
+    const int64_t cap = a->scratch_floats;
+    float *at[CONV_LAYOUT_COUNT] = {};
+    int64_t used = 0;      // floats of the front of the scratch taken so far
+    auto place = [&](unsigned mask, int64_t &from, int64_t room) { return place_conv_layouts(L, mask, scratch_dev, 1, room, at, &from); };
+    auto floats = [&](ConvLayout l) { return conv_layout(l).floats(L); };
+    unsigned have = place(lay_bit(ig ? LAY_PLAIN : LAY_PLAIN_DIRECT), used, INT64_MAX);       // the plain copy: whatever the size says
+    // bit 16: the bf16x3 planes, behind the plain copy
+    if (ig && (fd & 16) && a->Cout % 128 == 0 && Cin_ % 32 == 0 && place(lay_bit(LAY_SPLIT), used, cap)) {
+        have |= lay_bit(LAY_SPLIT);
         L.gemm = DLPM_GEMM_BF16X3;
     }
-    const int Cin_ = a->C0 + a->C1;
-    int64_t used = (int64_t)a->Cout * Cin_ * taps;
-    const bool wino_shape = a->ksize == 3 && !L.w_split && !(a->force_direct & 2) && a->stride == 1 && !a->in_nchw && !a->out_nchw;
-    if (ig && a->ksize == 3 && !L.w_split && Cin_ % 32 == 0 &&   // (the split copy sits where these would go)
-        a->scratch_floats >= used + frag_weight_floats(a->Cout, Cin_)) {
-        float *wf = scratch_dev + used;
-        TRY(relayout_weight_frag(a->weight, wf, a->Cout, Cin_, st));
-        L.w_frag = wf;
-        used += frag_weight_floats(a->Cout, Cin_);
-        if (wino_shape && a->Cout % 64 == 0 && a->scratch_floats >= used + wino_weight_floats(a->Cout, Cin_)) {
-            float *ww = scratch_dev + used;
-            TRY(relayout_weight_wino(a->weight, ww, a->Cout, Cin_, st));
-            L.w_wino = ww;
-            used += wino_weight_floats(a->Cout, Cin_);
-        }
+    const bool split = (have & lay_bit(LAY_SPLIT)) != 0;
+    // no split copy (it sits where these would go): the fragment copy, the F(2x2) copy unless bit 2 says no, and under bit 8 (or 256 / 512, which
+    // need it) the F(4x4,3x3) copy behind them (128-, 64- or 32-channel n-tiles).  That kernel takes input channels in multiples of 8, also where
+    // the implicit GEMM (multiples of 32) does not
+    const bool wino_shape = a->ksize == 3 && !split && !(fd & 2) && a->stride == 1 && !a->in_nchw && !a->out_nchw;
+    unsigned ask = 0;
+    if (ig && a->ksize == 3 && !split && Cin_ % 32 == 0) ask |= lay_bit(LAY_FRAG) | (wino_shape && a->Cout % 64 == 0 ? lay_bit(LAY_WINO) : 0);
+    if (wino_shape && (fd & (8 | 256 | 512)) && a->Cout % 32 == 0 && Cin_ % 8 == 0) ask |= lay_bit(LAY_WINO4);
+    have |= place(ask, used, cap);
+    const bool ask_f4 = (have & lay_bit(LAY_WINO4)) != 0;
+    if (ask_f4) {          // no F(2x2) alternative: the launch takes the F(4x4) kernel (whose copy stays behind the F(2x2) copy's place)
+        have &= ~lay_bit(LAY_WINO);
+        at[LAY_WINO] = nullptr;
     }
-    // bit 8: the F(4x4,3x3) kernel where the shape qualifies (128-, 64- or 32-channel n-tiles; its weights go behind the F(2x2) copy).  The
-    // kernel takes input channels in multiples of 8, also where the implicit GEMM (multiples of 32) does not
-    bool ask_f4 = false;
-    if (wino_shape && (a->force_direct & (8 | 256 | 512)) && a->Cout % 32 == 0 && Cin_ % 8 == 0 &&
-        a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
-        float *w4 = scratch_dev + used;
-        TRY(relayout_weight_wino4(a->weight, w4, a->Cout, Cin_, st));
-        L.w_wino4 = w4;
-        L.w_wino = nullptr;   // no F(2x2) alternative: the launch takes the F(4x4) kernel
-        used += wino4_weight_floats(a->Cout, Cin_);
-        ask_f4 = true;
-    }
-    // bit 256: an upsampling convolution through the sub-pixel kernel (four parity-class F(4x4,2x2) convolutions on the low-res image); its
-    // weights go behind the F(4x4,3x3) copy
-    if ((a->force_direct & 256) && L.w_wino4 && a->Cout % 128 == 0 && a->scratch_floats >= used + wino4sp_weight_floats(a->Cout, Cin_))
-        L.w_wino4sp = scratch_dev + used;
-    // bit 512: a layer on 4x4-pixel tensors through the one-tile kernel (k_conv3x3_wino4_one); its weights (the 64-channel fragment order) go
-    // behind the F(4x4,3x3) copy
-    const bool ask_one = (a->force_direct & 512) != 0;
-    if (ask_one && L.w_wino4 && !L.w_wino4sp && !a->upsample && wino4_one_layer_ok(a->Cout, a->C0, a->C1, a->Hout, a->Wout) &&
-        a->scratch_floats >= used + wino4_weight_floats(a->Cout, Cin_)) {
-        L.w_wino4_one = scratch_dev + used;
+    // bit 256: an upsampling convolution through the sub-pixel kernel (four parity-class F(4x4,2x2) convolutions on the low-res image); bit 512: a
+    // layer on 4x4-pixel tensors through the one-tile kernel (k_conv3x3_wino4_one).  Either copy goes behind the F(4x4,3x3) copy
+    if ((fd & 256) && ask_f4 && a->Cout % 128 == 0) have |= place(lay_bit(LAY_WINO4SP), used, cap);
+    const bool ask_one = (fd & 512) != 0;
+    if (ask_one && ask_f4 && !at[LAY_WINO4SP] && !a->upsample && wino4_one_layer_ok(a->Cout, a->C0, a->C1, a->Hout, a->Wout) &&
+        place(lay_bit(LAY_WINO4_ONE), used, cap)) {
+        have |= lay_bit(LAY_WINO4_ONE);
         L.gen = DLPM_CONV_F4;     // (this entry declares no batch: the generation under which the shape is taken without one)
     }
     // the head kernels (Cout <= 4): bit 64 the one-pass kernel (head_fused.hip; in the UNet it also carries the sampler's update), W' fragments
     // at the front of the scratch buffer; bit 32 the head as a 1x1 GEMM onto 9 Cout tap channels + gather, W' at the front, P behind it;
     // no bit: k_conv3x3_head where it takes the shape, its [tap][cin][4] copy at the END of the scratch buffer (the front holds the layouts above)
     const bool head_shape = a->ksize == 3 && a->C0 % 32 == 0 && a->C1 == 0;
-    const int ask_head = !head_shape || a->Cout > 3 ? 0 : (a->force_direct & 64) ? 64 : (a->force_direct & 32);
-    const int64_t taps_floats = (int64_t)head_taps_rows(a->Cout) * a->C0;
-    float *small_dev = nullptr;
+    const int ask_head = !head_shape || a->Cout > 3 ? 0 : (fd & 64) ? 64 : (fd & 32);
+    int64_t front = 0;
     if (ask_head == 64) {
-        L.gemm = (a->force_direct & 128) ? DLPM_GEMM_F32 : DLPM_GEMM_AUTO;   // bit 128: its fp32-MFMA form instead of the bf16 x 3 one
-        if (a->scratch_floats >= head_fused_weight_floats(a->C0)) L.w_hfused = scratch_dev;
+        L.gemm = (fd & 128) ? DLPM_GEMM_F32 : DLPM_GEMM_AUTO;   // bit 128: its fp32-MFMA form instead of the bf16 x 3 one
+        have |= place(lay_bit(LAY_HEAD_FUSED), front, cap);
     } else if (ask_head == 32) {
-        if (a->scratch_floats >= taps_floats + head_gemm_scratch_floats(L)) L.w_taps = scratch_dev;
-    } else if (!(a->force_direct & 7) && head_shape && a->Cout <= 4) {
-        const int64_t front = (int64_t)a->Cout * a->C0 * 9 + frag_weight_floats(a->Cout, a->C0);
-        if (a->scratch_floats >= front + 9 * a->C0 * 4) L.w_small = small_dev = scratch_dev + (a->scratch_floats - 9 * a->C0 * 4);
+        have |= place(lay_bit(LAY_HEAD_TAPS), front, cap - head_gemm_scratch_floats(L));
+    } else if (!(fd & 7) && head_shape && a->Cout <= 4) {
+        front = cap - floats(LAY_HEAD);
+        if (front >= floats(LAY_PLAIN) + floats(LAY_FRAG)) have |= place(lay_bit(LAY_HEAD), front, cap);
     }
+    attach_conv_layouts(L, at);
     // A bit ASKS for its kernel: a route that is not the family asked for (a geometry or scratch size the kernel cannot take, e.g. 16 one-tile
     // 4x4 images on a 64- / 32-channel F(4x4) n-tile) is an error, not a silent drop to another kernel -- tests that compare "the F(4x4)
     // kernel" with the default path must not pass for the wrong reason
     const ConvRoute R = conv_route(L);
     const bool f4 = R.family == CONV_WINO4 || R.family == CONV_WINO4SP;
-    const bool direct = (a->force_direct & 1) && !R.head() && !f4;    // bit 0: the direct kernel, whatever the route (it has no statistics epilogue)
+    const bool direct = (fd & 1) && !R.head() && !f4;    // bit 0: the direct kernel, whatever the route (it has no statistics epilogue)
     const int px = direct ? 0 : R.stats_px;
     const struct { bool asked, got; const char *msg; } asks[] = {
         {ask_f4, f4, "dlpm_conv2d_f32: force_direct bit 8 asks for the F(4x4,3x3) kernel, which does not take this geometry"},
-        {(a->force_direct & 256) != 0, R.family == CONV_WINO4SP,
+        {(fd & 256) != 0, R.family == CONV_WINO4SP,
          "dlpm_conv2d_f32: force_direct bit 256 asks for the sub-pixel upsampling kernel, which does not take this geometry / scratch size"},
         {ask_one, R.family == CONV_WINO4 && R.one,
          "dlpm_conv2d_f32: force_direct bit 512 asks for the one-tile F(4x4) kernel, which does not take this geometry / scratch size"},
@@ -1416,20 +1295,18 @@ static int conv2d_entry(const dlpm_conv_args *a, float *scratch_dev, float *stat
         L.stats_out = reinterpret_cast<float2 *>(stats_out);
         *stats_px = px;
     }
-    if (R.family == CONV_WINO4SP) TRY(relayout_weight_wino4sp(a->weight, const_cast<float *>(L.w_wino4sp), a->Cout, Cin_, st));
-    if (R.family == CONV_WINO4 && R.one) TRY(relayout_weight_wino4(a->weight, const_cast<float *>(L.w_wino4_one), a->Cout, Cin_, st, 64));
-    if (R.family == CONV_HEAD_FUSED) TRY(relayout_weight_head_fused(a->weight, scratch_dev, a->Cout, a->C0, st));
-    if (R.family == CONV_HEAD_GEMM) TRY(relayout_weight_head_taps(a->weight, scratch_dev, a->Cout, a->C0, st));
-    if (R.family == CONV_HEAD) TRY(relayout_weight_head(a->weight, small_dev, a->Cout, a->C0, st));
+    hipStream_t st = as_stream(stream);
+    if (R.family != CONV_HEAD) have &= ~lay_bit(LAY_HEAD);      // (k_conv3x3_head's copy is offered unasked: built where the route takes it)
+    TRY(build_conv_layouts(L, have, a->weight, at, st));         // in the order of the enum: a head copy at the front overwrites the plain one
     if (direct) return launch_conv_direct(L, st);
-    return launch_conv(L, nullptr, scratch_dev + taps_floats, st);
+    return launch_conv(L, nullptr, scratch_dev + floats(LAY_HEAD_TAPS), st);
 }
 
 // ---- a 3x3 stride-1 launch under a declared policy (include/dlpm_amd_conv.h)
-// The launch of `a` under (generation, dispatch_batch) with the layouts conv3_layouts gives the layer, laid out one behind the other
-// from `base` (each at a multiple of 64 floats); *used = their floats together.  Nothing is read through a pointer.
+// The launch of `a` under (generation, dispatch_batch) with the layouts conv_layouts gives the layer (*mask), laid out one behind the other
+// from `base` in the order of the enum (each at a multiple of 64 floats: at[]); *used = their floats together.  Nothing is read through a pointer.
 static int policy_launch(const dlpm_conv_args *a, int32_t generation, int64_t dispatch_batch, float *base, ConvLaunch *out,
-                         Conv3Layouts *lay_out, int64_t *used_out) {
+                         float *at[CONV_LAYOUT_COUNT], unsigned *mask, int64_t *used) {
     DLPM_CHECK_ARG(a, "dlpm_conv_policy: null argument");
     DLPM_CHECK_ARG(generation >= DLPM_CONV_AUTO && generation <= DLPM_CONV_IGEMM, "dlpm_conv_policy: unknown generation %d", generation);
     DLPM_CHECK_ARG(dispatch_batch >= 0, "dlpm_conv_policy: negative dispatch batch");
@@ -1445,26 +1322,11 @@ static int policy_launch(const dlpm_conv_args *a, int32_t generation, int64_t di
     L.ups = a->upsample ? 1 : 0;
     L.gen = generation;
     L.dispatch_B = dispatch_batch;
-    const Conv3Layouts lay = conv3_layouts(L);
-    const int Cin = a->C0 + a->C1;
-    int64_t used = 0;
-    auto take = [&](bool has, int64_t nfloats) -> const float * {
-        if (!has) return nullptr;
-        const float *p = base + used;
-        used += (nfloats + 63) / 64 * 64;
-        return p;
-    };
-    L.w = take(true, (int64_t)a->Cout * Cin * 9);
-    L.w_frag = take(lay.frag, lay.frag ? frag_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino = take(lay.wino, lay.wino ? wino_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino4 = take(lay.wino4, lay.wino4 ? wino4_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino4sp = take(lay.wino4sp, lay.wino4sp ? wino4sp_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino4_one = take(lay.wino4_one, lay.wino4_one ? wino4_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino4_n64 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
-    L.w_wino4_n32 = take(lay.narrow, lay.narrow ? wino4_weight_floats(a->Cout, Cin) : 0);
+    *mask = conv_layouts(L) & ~lay_bit(LAY_SMALL);     // (the fused blocks' order belongs to no launch)
+    *used = 0;
+    place_conv_layouts(L, *mask, base, 64, INT64_MAX, at, used);
+    attach_conv_layouts(L, at);
     *out = L;
-    *lay_out = lay;
-    *used_out = used;
     return DLPM_OK;
 }
 
@@ -1480,10 +1342,11 @@ static void policy_route_out(const ConvLaunch &L, const ConvRoute &R, int64_t us
 extern "C" int dlpm_conv_policy_route(const dlpm_conv_args *a, int32_t generation, int64_t dispatch_batch, dlpm_conv_route *route) {
     DLPM_CHECK_ARG(route, "dlpm_conv_policy_route: null argument");
     ConvLaunch L;
-    Conv3Layouts lay;
+    float *at[CONV_LAYOUT_COUNT] = {};
+    unsigned mask = 0;
     int64_t used = 0;
     // (a base that is never dereferenced, as the plan's dry run: conv_route asks only which layouts a launch carries)
-    TRY(policy_launch(a, generation, dispatch_batch, reinterpret_cast<float *>(uintptr_t(1) << 20), &L, &lay, &used));
+    TRY(policy_launch(a, generation, dispatch_batch, reinterpret_cast<float *>(uintptr_t(1) << 20), &L, at, &mask, &used));
     policy_route_out(L, conv_route(L), used, route);
     return DLPM_OK;
 }
@@ -1495,9 +1358,10 @@ extern "C" int dlpm_conv_policy_f32(const dlpm_conv_args *a, int32_t generation,
     DLPM_CHECK_ARG((a->C1 == 0) == (a->src1 == nullptr), "dlpm_conv_policy_f32: src1/C1 mismatch");
     DLPM_CHECK_ARG((stats_out == nullptr) == (stats_px == nullptr), "dlpm_conv_policy_f32: stats_out and stats_px go together");
     ConvLaunch L;
-    Conv3Layouts lay;
+    float *at[CONV_LAYOUT_COUNT] = {};
+    unsigned mask = 0;
     int64_t used = 0;
-    TRY(policy_launch(a, generation, dispatch_batch, scratch_dev, &L, &lay, &used));
+    TRY(policy_launch(a, generation, dispatch_batch, scratch_dev, &L, at, &mask, &used));
     const ConvRoute R = conv_route(L);
     const int64_t need = splitk_partial_floats(L, R);
     if (a->scratch_floats < used) {
@@ -1515,18 +1379,7 @@ extern "C" int dlpm_conv_policy_f32(const dlpm_conv_args *a, int32_t generation,
         return DLPM_ERR_UNSUPPORTED;
     }
     hipStream_t st = as_stream(stream);
-    const int Cin = a->C0 + a->C1;
-    auto at = [](const float *p) { return const_cast<float *>(p); };     // the layouts are const in the launch; here they are written
-    TRY(relayout_weight(a->weight, at(L.w), a->Cout, Cin, 3, igemm_supported(L), st));
-    if (lay.frag) TRY(relayout_weight_frag(a->weight, at(L.w_frag), a->Cout, Cin, st));
-    if (lay.wino) TRY(relayout_weight_wino(a->weight, at(L.w_wino), a->Cout, Cin, st));
-    if (lay.wino4) TRY(relayout_weight_wino4(a->weight, at(L.w_wino4), a->Cout, Cin, st));
-    if (lay.wino4sp) TRY(relayout_weight_wino4sp(a->weight, at(L.w_wino4sp), a->Cout, Cin, st));
-    if (lay.wino4_one) TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_one), a->Cout, Cin, st, 64));
-    if (lay.narrow) {
-        TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n64), a->Cout, Cin, st, 64));
-        TRY(relayout_weight_wino4(a->weight, at(L.w_wino4_n32), a->Cout, Cin, st, 32));
-    }
+    TRY(build_conv_layouts(L, mask, a->weight, at, st));
     if (stats_out) {
         L.stats_out = reinterpret_cast<float2 *>(stats_out);
         *stats_px = R.stats_px;

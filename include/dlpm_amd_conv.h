@@ -5,7 +5,7 @@
  * of the F(2x2) kernel and of the narrow F(4x4) shapes (ConvRoute::ksplit = 2, 4, 8, conv_splitk.hip) and the 64- / 32-channel n-tiles
  * of a Cout % 128 == 0 layer.  These two entry points carry the policy of dlpm_unet_set_conv_policy -- a generation and a dispatch
  * batch -- down to ONE launch: the layer gets the weight layouts the UNet would build for it under that declaration (conv.h:
- * conv3_layouts, which prep_conv and narrow_wino4_copies ask too), conv_route decides, and the launch runs through the function the
+ * conv_layouts and its table, which dlpm_unet_finalize and dlpm_unet_set_conv_policy ask too), conv_route decides, and the launch runs through the function the
  * plan runs (conv_splitk.hip: launch_conv_splitk).  Test / bring-up entry points, like dlpm_conv2d_f32.
  *
  * Both take launches with ksize = 3, stride = 1, NHWC on both sides, Cout > 4, force_direct = 0 (upsampling included); anything else
