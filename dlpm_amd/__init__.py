@@ -24,3 +24,5 @@ from .config import load_config, is_image_dataset, init_model_by_parameter  # no
 from . import checkpoint  # noqa: F401
 from . import datasets  # noqa: F401
 from .datasets import Generator, get_dataset, ToyLoader  # noqa: F401
+from . import training  # noqa: F401
+from .training import MLPTrainer, TrainingManager  # noqa: F401

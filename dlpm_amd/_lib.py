@@ -78,6 +78,12 @@ class TwoRvArgs(C.Structure):        # dlpm_two_rv_args, include/dlpm_amd_step.h
                 ('clamp_a', f64), ('seed', u64), ('sample_offset', i64)]
 
 
+class AdamwArgs(C.Structure):        # dlpm_adamw_args, include/dlpm_amd_train.h
+    _fields_ = [('theta_dev', vp), ('grad_dev', vp), ('exp_avg_dev', vp), ('exp_avg_sq_dev', vp), ('n', i64), ('lr', f64),
+                ('beta1', f64), ('beta2', f64), ('eps', f64), ('weight_decay', f64), ('step', i64), ('coef_dev', vp), ('n_ema', i32),
+                ('reserved', i32), ('ema_dev', vp * 8), ('ema_mu', f64 * 8)]
+
+
 class UNetConfig(C.Structure):
     _fields_ = [('in_channels', i32), ('model_channels', i32), ('out_channels', i32), ('num_res_blocks', i32),
                 ('num_heads', i32), ('image_size', i32), ('n_mult', i32), ('channel_mult', i32 * 8), ('n_attn', i32),
@@ -258,6 +264,17 @@ SIGNATURES_STEP = {
     'dlpm_anterior_f32': (C.c_int, [C.POINTER(AnteriorArgs), vp]),
     'dlpm_two_rv_elements_f32': (C.c_int, [C.POINTER(TwoRvArgs), vp]),
 }
+# the same for include/dlpm_amd_train.h (training of the toy net: backward, loss gradient, clip, AdamW + EMA, parameter layout)
+SIGNATURES_TRAIN = {
+    'dlpm_mlp_param_floats': (i64, [vp]),
+    'dlpm_mlp_export_params_f32': (C.c_int, [vp, vp, i64, vp]),
+    'dlpm_mlp_import_params_f32': (C.c_int, [vp, vp, i64, vp]),
+    'dlpm_mlp_backward_workspace_bytes': (i64, [vp, i64]),
+    'dlpm_mlp_backward_f32': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+    'dlpm_loss_grad_f32': (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, i64, i32, vp]),
+    'dlpm_grad_clip_coef_f32': (C.c_int, [vp, i64, f64, vp, vp, vp]),
+    'dlpm_adamw_step_f32': (C.c_int, [C.POINTER(AdamwArgs), vp]),
+}
 
 _lib = None
 
@@ -275,7 +292,7 @@ def lib():
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
-                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()):
+                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

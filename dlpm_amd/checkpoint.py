@@ -147,17 +147,18 @@ def load_into(model, path_or_ckpt, name='default', ema=None):
     return ckpt.get('epoch'), ckpt.get('steps')
 
 
-def save_checkpoint(path, models, epoch=0, steps=0, ema_shadows=None):
-    """Write a file `TrainingManager.load` accepts (no optimizer / schedule state: `safe_load_state_dict`
-    skips `None` destinations, bem/TrainingManager.py:242-244, so such a file loads when the manager was
-    built for evaluation only).  `ema_shadows`: {name: [shadow_dict, ...]}."""
+def save_checkpoint(path, models, epoch=0, steps=0, ema_shadows=None, optimizers=None, learning_schedules=None):
+    """Write a file `TrainingManager.load` accepts.  Without `optimizers` / `learning_schedules` it carries no optimizer / schedule
+    state: `safe_load_state_dict` skips `None` destinations, bem/TrainingManager.py:242-244, so such a file loads when the manager
+    was built for evaluation only.  `ema_shadows`: {name: [shadow_dict, ...]}.  `optimizers`, `learning_schedules`: {name: the
+    state_dict to store (torch.optim.AdamW.state_dict()'s form, dlpm_amd.training) or None}."""
     ck = {'epoch': epoch, 'steps': steps}
     for name, model in models.items():
         k_model, k_ema = _names(name)
         sfx = '' if name == 'default' else '_' + name
         ck[k_model] = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-        ck['optimizer' + sfx] = None
-        ck[('learning_schedule' if name == 'default' else 'learnin_schedule') + sfx] = None
+        ck['optimizer' + sfx] = (optimizers or {}).get(name)
+        ck[('learning_schedule' if name == 'default' else 'learnin_schedule') + sfx] = (learning_schedules or {}).get(name)
         if ema_shadows and name in ema_shadows:
             ck[k_ema] = [{k: v.detach().cpu() for k, v in s.items()} for s in ema_shadows[name]]
     torch.save(ck, path)

@@ -35,6 +35,11 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   config's own `data:` description (dlpm_amd/datasets.py; the draw is keyed by --set_seed), so no data file is needed.  --dataset
   overrides data.dataset (gmm_2, gmm_grid, swiss_roll, sas_grid; gmm_2 gets equal weights when the config's weights are another
   mixture's); --dump_dataset writes the N real samples ([N, 1, dim] float32).
+  --train EPOCHS [--save OUT.pt] [--ema_rates MU ...] [--max_batch_per_epoch N] [--grad_clip C]: on a 2-D config, first train the net on
+  the device (dlpm_amd.TrainingManager: AdamW at optim.lr, the loss settings of training.<method>, batches of training.batch_size from
+  the train split drawn from the config's own `data:` description, keyed by --set_seed) and print `epoch <e> loss <mean loss>` per epoch;
+  --save writes a checkpoint in the reference's format, which --checkpoint loads.  With --generate N (and --eval_2d ...) the trained
+  net -- with --ema_eval the --ema_index-th EMA -- is then evaluated in the same run; without it the run ends after training.
 """
 import argparse
 import os
@@ -144,7 +149,14 @@ def main(argv=None):
     ap.add_argument('--dataset', default=None, metavar='NAME', help='override data.dataset')
     ap.add_argument('--dump_dataset', default=None, metavar='OUT.npy',
                     help='on a 2-D config: write the --generate N real samples drawn from the config\'s data distribution to this file')
+    ap.add_argument('--train', type=int, default=None, metavar='EPOCHS', help='train the 2-D toy net for this many epochs first')
+    ap.add_argument('--save', default=None, metavar='OUT.pt', help='with --train: write the checkpoint (reference format) to this file')
+    ap.add_argument('--ema_rates', type=float, nargs='+', default=None, help='with --train: EMA rates (default: training.<method>.ema_rates)')
+    ap.add_argument('--max_batch_per_epoch', type=int, default=None, help='with --train: stop every epoch after this many batches')
+    ap.add_argument('--grad_clip', type=float, default=None, help='with --train: gradient-norm clip (default: training.<method>.grad_clip)')
     a = ap.parse_args(argv)
+    if a.train is None and (a.save or a.ema_rates or a.max_batch_per_epoch is not None or a.grad_clip is not None):
+        raise SystemExit('--save / --ema_rates / --max_batch_per_epoch / --grad_clip belong to --train EPOCHS')
     if a.save_fid_stats and not (a.eval_fid and not a.eval_fid.endswith('.npz')):
         raise SystemExit('--save_fid_stats needs --eval_fid REAL.npy')
     for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc),
@@ -212,6 +224,33 @@ def main(argv=None):
             raise SystemExit('--gemm applies to the UNet score networks')
         model.set_gemm_policy(a.gemm)
     method = dlpm_amd.init_method_by_parameter(p, rng=a.rng, seed=seed or 0)
+    if a.train is not None:
+        if dlpm_amd.is_image_dataset(p['data']['dataset']):
+            raise SystemExit('--train trains the 2-D toy net; training of the UNets is out of scope')
+        tr = dict((p.get('training') or {}).get(m) or {})
+        ema_rates = a.ema_rates if a.ema_rates else tr.get('ema_rates')
+        keys = ('clamp_a', 'clamp_eps') if m == 'lim' else ('lploss', 'loss_monte_carlo', 'monte_carlo_outer', 'monte_carlo_inner',
+                                                          'clamp_a', 'clamp_eps')
+        kw = {k: tr[k] for k in keys if k in tr}
+        train_data = dlpm_amd.get_dataset(p, 'cuda', seed or 0)[0]
+        tm = dlpm_amd.TrainingManager({'default': model}, dlpm_amd.ToyLoader(train_data, p['training']['batch_size']), method, None,
+                                      (p.get('optim') or {}).get('schedule'), None, ema_rates=ema_rates, p=p, seed=seed or 0)
+        done = len(tm.epoch_losses)
+        tm.train(a.train, max_batch_per_epoch=a.max_batch_per_epoch, grad_clip=a.grad_clip if a.grad_clip is not None else tr.get('grad_clip'),
+                 **kw)
+        for e, loss in enumerate(tm.epoch_losses[done:]):
+            print('epoch %d loss %.9g' % (e + 1, loss))
+        if a.save:
+            tm.save(a.save)
+            print('saved %s (epoch %d, %d steps)' % (a.save, tm.epochs, tm.total_steps), file=sys.stderr)
+        if a.ema_eval:
+            if not ema_rates:
+                raise SystemExit('--ema_eval after --train needs EMA rates (--ema_rates or training.<method>.ema_rates)')
+            model = tm.ema_model(a.ema_index)
+        else:
+            tm.sync()
+        if a.generate is None:
+            return tm.epoch_losses
     if a.eval_loss:
         data = np.load(a.eval_loss)
         tr = dict((p.get('training') or {}).get(m) or {})      # a reference-schema YAML carries the loss settings of its training run

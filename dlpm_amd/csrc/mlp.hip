@@ -11,56 +11,12 @@
 // LayerNorm is a wave butterfly, a Linear is a k-loop of {coalesced weight row load, one 16-byte
 // LDS broadcast of the 4 samples' activations, 4 FMAs}, and no workgroup barrier is ever needed.
 // Weights (220 kB, transposed to [k][unit]) stay L2-resident across the whole sampling loop.
-#include <map>
-#include <string>
-#include <vector>
-
-#include "common.h"
+#include "mlp.h"
 #include "philox.h"
 
 using namespace dlpm;
 
 namespace {
-
-constexpr int NU = 64;   // hidden units == wavefront width
-constexpr int SPW = 4;   // samples per wave
-
-struct MlpOffsets {      // offsets (floats) into the packed parameter blob
-    int te_w, te_b, tm_w, tm_b, in_w, in_b, in_g, in_be, blk0, blk_stride, out_w, out_b;
-    // per block: w1T[64*64] b1 g1 be1 twT[TE*64] tb w2T[64*64] b2 g2 be2
-    int b_w1, b_b1, b_g1, b_be1, b_tw, b_tb, b_w2, b_b2, b_g2, b_be2;
-};
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + __expf(-v)); }
-
-// acc[s] += sum_k WT[k][lane] * act[k][s]
-__device__ __forceinline__ void matvec(const float *__restrict__ WT, int K, const float *actT, int lane, float acc[SPW]) {
-#pragma unroll 8
-    for (int k = 0; k < K; k++) {
-        const float w = WT[k * NU + lane];
-        const float4 h = *reinterpret_cast<const float4 *>(actT + k * SPW);
-        acc[0] = fmaf(w, h.x, acc[0]);
-        acc[1] = fmaf(w, h.y, acc[1]);
-        acc[2] = fmaf(w, h.z, acc[2]);
-        acc[3] = fmaf(w, h.w, acc[3]);
-    }
-}
-
-__device__ __forceinline__ void layer_norm(float v[SPW], float gam, float bet) {
-#pragma unroll
-    for (int s = 0; s < SPW; s++) {
-        const float mean = wave_sum(v[s]) * (1.0f / NU);
-        const float d = v[s] - mean;
-        const float var = wave_sum(d * d) * (1.0f / NU);
-        v[s] = d * (1.0f / sqrtf(var + 1e-5f)) * gam + bet;
-    }
-}
 
 __global__ void __launch_bounds__(64) k_mlp_forward(const float *__restrict__ P, MlpOffsets o, const float *__restrict__ x,
                                                     const float *__restrict__ t, float *__restrict__ out, int64_t B, int F,
@@ -276,18 +232,6 @@ __global__ void __launch_bounds__(256) k_mlp_sample(MlpLoopArgs a, MlpOffsets o)
 
 }  // namespace
 
-struct dlpm_mlp {
-    int F, nunits, nblocks, TE;
-    std::vector<float> host;       // packed blob, filled by set_param
-    std::map<std::string, bool> seen;
-    MlpOffsets off;
-    float *dev = nullptr;
-    float4 *q4 = nullptr;      // float4-interleaved copies of the 64x64 matrices (k_mlp_sample)
-    float *tp = nullptr;       // [T][nblocks+1][64] step-only terms
-    int tp_T = 0;
-    bool finalized = false;
-};
-
 extern "C" int dlpm_mlp_create(int32_t nfeatures, int32_t nunits, int32_t nblocks, int32_t time_emb_size, dlpm_mlp **out) {
     DLPM_CHECK_ARG(out, "dlpm_mlp_create: null out");
     DLPM_CHECK_ARG(nfeatures > 0 && nblocks >= 0, "dlpm_mlp_create: bad nfeatures / nblocks");
@@ -419,6 +363,7 @@ extern "C" int dlpm_mlp_finalize(dlpm_mlp *m) {
         DLPM_HIP(hipMemcpy(m->q4, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     m->tp_T = 0;
+    m->flat_valid = false;
     m->finalized = true;
     return DLPM_OK;
 }
@@ -474,5 +419,7 @@ extern "C" void dlpm_mlp_destroy(dlpm_mlp *m) {
     if (m->dev) (void)hipFree(m->dev);
     if (m->q4) (void)hipFree(m->q4);
     if (m->tp) (void)hipFree(m->tp);
+    if (m->flat) (void)hipFree(m->flat);
+    if (m->flat_map) (void)hipFree(m->flat_map);
     delete m;
 }

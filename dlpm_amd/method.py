@@ -833,7 +833,7 @@ class GenerativeLevyProcess:
                     out_offset=0, t_out=None, keep=False):
         """The launches before the estimator: k_loss_elements, the net on the extended batch, k_loss_terms.  Terms go to
         `out[r * out_stride + out_offset + b]` (default: a fresh [outer * inner * B] buffer, the reference's layout).  Returns a dict
-        with 'losses', 't' (int32 [B]) and, with `keep`, 'x_t', 'eps_t', 'x_in', 'model_eps'.  No synchronisation, no host read."""
+        with 'losses', 't' (int32 [B]) and, with `keep`, 'x_t', 'eps_t', 'x_in', 'model_eps', 'tvec' (the times the net was given).  No synchronisation, no host read."""
         from .unet import UNetModel
         from .mlp import MLPModel
         L, st = _lib.lib(), _lib.stream_ptr()
@@ -903,13 +903,15 @@ class GenerativeLevyProcess:
             self.calls += 1
         res = {'losses': out, 't': t_out}
         if keep:
-            res.update(x_t=x_t, eps_t=eps_t, x_in=x_in, model_eps=model_eps)
+            res.update(x_t=x_t, eps_t=eps_t, x_in=x_in, model_eps=model_eps, tvec=tvec)
         return res
 
-    def _loss_reduce(self, terms, N, outer, inner, loss_monte_carlo, check_finite, median_index=None):
-        """k_loss_reduce on terms[outer * inner * N] -> 0-dim fp32 loss on the device; `check_finite` reads the 4-byte flag."""
+    def _loss_reduce(self, terms, N, outer, inner, loss_monte_carlo, check_finite, median_index=None, flag=None):
+        """k_loss_reduce on terms[outer * inner * N] -> 0-dim fp32 loss on the device; `check_finite` reads the 4-byte flag
+        (`flag`: an int32 [1] device tensor of the caller's to receive it instead of a fresh one)."""
         res = torch.empty(1, dtype=torch.float32, device=terms.device)
-        flag = torch.empty(1, dtype=torch.int32, device=terms.device)
+        if flag is None:
+            flag = torch.empty(1, dtype=torch.int32, device=terms.device)
         _lib.check(_lib.lib().dlpm_loss_reduce_f32(terms.data_ptr(), N, outer, inner, int(loss_monte_carlo == 'median'),
                                                    res.data_ptr(), flag.data_ptr(), _lib.ptr(median_index), _lib.stream_ptr()))
         if check_finite:
