@@ -448,7 +448,7 @@ static bool wino_disabled() {
 // 32-tile x 64-channel shape is used instead: twice the workgroups, two per CU.  Per (tile, channel) the arithmetic is the
 // same in both shapes (same position split, same fixed-order exchange), and multi-image blocks emit no GroupNorm
 // statistics in either, so the choice may follow the batch of the call without changing a bit
-// (test_conv_winograd_f2_small_launch_shape_is_bit_identical).
+// (test_conv_winograd_f2_small_launch_shape_is_bit_identical).  wino_geometry gives a large batch the 64-tile shape only where the 32-tile shape takes the layer's images too.
 static bool wino_small_launch(const ConvLaunch &c) {
     if (c.Cout % 128 == 0) return false;                       // those layers already run 32-tile blocks
     const int tpi = (c.Hout / 2) * (c.Wout / 2);               // tiles per image
@@ -471,13 +471,9 @@ static int64_t f2_mblocks(const ConvLaunch &c, int64_t B, int mt, int nimg) {
     return nimg == 1 ? B * (c.Hout / 2) * (c.Wout / 2) / mt : ceil_div(B, (int64_t)nimg);
 }
 
-static bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
-    if (wino_disabled() || c.gen == DLPM_CONV_IGEMM || !c.w_wino || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
-    if ((c.Hout & 1) || (c.Wout & 1) || c.Cout % WN != 0 || (c.C0 + c.C1) % WKC != 0 || c.C0 % WKC != 0) return false;
-    if ((c.R0 & 3) != 0) return false;
-    if (c.ups && ((c.Hout & 3) || (c.Wout & 3))) return false;
+// the block of T tiles on this launch's images: h x w tiles inside one image, or n whole small images
+static bool wino_block(const ConvLaunch &c, int T, int *bh, int *bw, int *nimg) {
     const int TH = c.Hout / 2, TW = c.Wout / 2;
-    const int T = wino_tiles(c);
     int h, w, n;
     if (TH * TW >= T) {            // a block inside one image
         w = TW < 8 ? TW : 8;
@@ -493,6 +489,26 @@ static bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
     const int RH = c.ups ? h + 2 : 2 * h + 2, RW = c.ups ? w + 2 : 2 * w + 2;
     if (c.ups && ((h & 1) || (w & 1))) return false;   // source-resolution halo needs even block origins
     if (n * RH * RW > (T == 64 ? RAW_MAXPIX : RAW_MAXPIX / 2)) return false;
+    *bh = h; *bw = w; *nimg = n;
+    return true;
+}
+
+static bool wino_geometry(const ConvLaunch &c, int *bh, int *bw, int *nimg) {
+    if (wino_disabled() || c.gen == DLPM_CONV_IGEMM || !c.w_wino || c.ks != 3 || c.stride != 1 || c.in_nchw || c.out_nchw) return false;
+    if ((c.Hout & 1) || (c.Wout & 1) || c.Cout % WN != 0 || (c.C0 + c.C1) % WKC != 0 || c.C0 % WKC != 0) return false;
+    if ((c.R0 & 3) != 0) return false;
+    if (c.ups && ((c.Hout & 3) || (c.Wout & 3))) return false;
+    const int T = wino_tiles(c);
+    int h, w, n;
+    if (!wino_block(c, T, &h, &w, &n)) return false;
+    // Where the batch of the call chose the 64-tile shape over the small launch's 32 tiles, the 32-tile shape must take the images too:
+    // otherwise (images of 1 x 32 or 2 x 16 tiles, which it cannot cut into 4 x 8-tile blocks) small batches of the same layer would run
+    // on the implicit GEMM and an image's bits would follow the batch it came in (conv.h: the route is a function of the layer)
+    const int tpi = (c.Hout / 2) * (c.Wout / 2);
+    if (T == 64 && tpi < 64 && 64 % tpi == 0) {
+        int h2, w2, n2;
+        if (!wino_block(c, 32, &h2, &w2, &n2)) return false;
+    }
     *bh = h; *bw = w; *nimg = n;
     return true;
 }

@@ -118,7 +118,9 @@ def _plan(size, mult, attn, mc=32, heads=4, B=8):
 @pytest.mark.parametrize('size,mult,attn', [(28, [1, 2, 2], [2, 4]),          # mnist28.yml: attention at T = 196 / 49
                                             (28, [1, 2, 2], [1, 2, 4]),       # attention at T = 784 (head dim 8)
                                             (32, [1, 2, 2, 2], [1, 2, 4]),    # T = 1024
-                                            (32, [1, 2, 2, 2, 2], [16])])     # 5 levels: attention at 2x2 (T = 4)
+                                            (32, [1, 2, 2, 2, 2], [16]),      # 5 levels: attention at 2x2 (T = 4)
+                                            (48, [1, 2, 2, 2], [2, 4]),       # 48 / 24 / 12 / 6: attention at T = 576 / 144
+                                            (20, [1, 2, 2], [2, 4])])         # 20 / 10 / 5: attention at T = 100 / 25
 def test_planner_takes_the_new_geometries(size, mult, attn):
     a, b = _plan(size, mult, attn)
     assert 0 < a < b < 2.2 * a, (a, b)

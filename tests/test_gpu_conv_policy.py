@@ -45,7 +45,12 @@ SENTINEL = -12345.0
 
 def make(name, B=None):
     """Seeded cpu inputs of a case (NCHW), optionally at another batch"""
-    c = BY_NAME[name]
+    return make_of(BY_NAME[name], B)
+
+
+def make_of(c, B=None):
+    """... of any Case (tests/test_gpu_conv_geometry.py brings its own table)"""
+    name = c.name
     B = B or c.B
     g = torch.Generator().manual_seed(sum(map(ord, name)))
     Cin = c.C0 + c.C1
@@ -101,7 +106,9 @@ def launch(c, inp, gen=_lib.CONV_AUTO, d=None, stats=False, want_route=None, sho
     _lib.check(L().dlpm_conv_policy_route(C.byref(a), gen, d, C.byref(need)))
     if want_route is None:
         want_route = (c.family, c.nq, c.nimg, c.ksplit)
-    assert route_tuple(need) == want_route, (c.name, route_tuple(need), want_route)
+    # (family, nq, nimg, ksplit), or those and (bh, bw, stats_px) behind them
+    route_of = lambda r: (route_tuple(r) + (r.bh, r.bw, r.stats_px))[:max(4, len(want_route))]
+    assert route_of(need) == want_route, (c.name, route_of(need), want_route)
     S, n_out = need.ksplit, B * Ho * Wo * c.Cout
     assert need.partial_floats == (S * n_out if S > 1 else 0)
     scratch = torch.empty(need.scratch_floats, device=DEV)
@@ -124,7 +131,7 @@ def launch(c, inp, gen=_lib.CONV_AUTO, d=None, stats=False, want_route=None, sho
     if rc != 0:
         return dict(rc=rc, untouched=bool(torch.isnan(out[:n_out]).all()) and bool(torch.isnan(part[:need.partial_floats]).all()) and
                     (sbuf is None or bool(torch.isnan(sbuf).all())) and px.value == -1)
-    assert route_tuple(took) == want_route and (took.bh, took.bw, took.stats_px, took.grid) == (need.bh, need.bw, need.stats_px, need.grid)
+    assert route_of(took) == want_route and (took.bh, took.bw, took.stats_px, took.grid) == (need.bh, need.bw, need.stats_px, need.grid)
     intact = bool((out[n_out:] == SENTINEL).all()) and bool((part[need.partial_floats:] == SENTINEL).all())
     return dict(rc=0, out=nchw(out[:n_out].view(B, Ho, Wo, c.Cout)).cpu(),
                 part=part[:need.partial_floats].view(S, B, Ho, Wo, c.Cout).cpu() if S > 1 else None,

@@ -1,6 +1,7 @@
 """Geometries beyond the four shipped configs on the MI355X: the general attention kernel (any token count 1..4096, any head dim
 1..256) through dlpm_attention_f32 / dlpm_attention_general_f32, and the 28x28 MNIST UNet of dlpm_amd/configs/mnist28.yml (attention
 at 14x14 / 7x7, stride-2 downsample 14 -> 7, upsample 7 -> 14) end to end: forward, sampler, GenerationManager and the CLI's PNG dump."""
+import functools
 import math
 import os
 import struct
@@ -184,6 +185,47 @@ def test_32x32_nets_with_new_attention_shapes_against_oracle(mult, attn):
         err = float(np.abs(got - want).max())
         print('32x32 net %s attn %s (%s): max |hip - oracle| = %.3g' % (mult, attn, gen, err))
         assert err < 1e-4
+
+
+ODD_NETS = {
+    # 48x48: F(4x4) with 3 blocks per row, the 24 -> 48 upsample on the UPS instantiation, 24x24 / 12x12 / 6x6 on the generic implicit GEMM;
+    # attention at T = 576 and 144
+    '48x48': (48, [1, 2, 2, 2]),
+    # 20x20: a 5x5 level, stride-2 10 -> 5 and upsample 5 -> 10; attention at T = 100 and 25
+    '20x20': (20, [1, 2, 2]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def odd_net(name):
+    """(net, x, t, the oracle's forward on the CPU), computed once and shared by every generation and GEMM policy"""
+    size, mult = ODD_NETS[name]
+    torch.manual_seed(1234)
+    net = dlpm_amd.UNetModel(1, 32, 1, 2, [2, 4], channel_mult=mult, num_heads=4, use_scale_shift_norm=True)
+    dlpm_amd.rerandomize_(net, 4321)
+    sd = {k: v.detach() for k, v in net.state_dict().items()}
+    g = torch.Generator().manual_seed(77)
+    x = torch.randn(3, 1, size, size, generator=g)
+    t = torch.rand(3, generator=g)
+    with torch.no_grad():
+        want = nets.unet_forward(sd, x, t, 4).numpy()
+    return net, x, t, want
+
+
+@pytest.mark.parametrize('gemm', ['bf16x3', 'f32'])
+@pytest.mark.parametrize('gen', GENERATIONS)
+@pytest.mark.parametrize('name', list(ODD_NETS))
+def test_48x48_and_20x20_nets_against_oracle(name, gen, gemm):
+    """image_size is a free value of the reference's configs: two nets whose levels are no power of two, B = 3, under every
+    generation and both GEMM policies, against the oracle (the bound of test_32x32_nets_with_new_attention_shapes_against_oracle)."""
+    net, x, t, want = odd_net(name)
+    net.set_conv_policy(gen)
+    net.set_gemm_policy(gemm)
+    got = net(x.to(DEV), t.to(DEV)).cpu().numpy()
+    assert np.isfinite(got).all()
+    err = float(np.abs(got - want).max())
+    print('%s net (%s, %s): max |hip - oracle| = %.3g' % (name, gen, gemm, err))
+    assert err < 1e-4
 
 
 @pytest.mark.parametrize('gemm', ['bf16x3', 'f32'])

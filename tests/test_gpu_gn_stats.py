@@ -53,6 +53,10 @@ def BLK(bh, bw):     # blocks of bh x bw output pixels, row-major inside the ima
     return (bh, bw)
 
 
+def SUBPIX(bh, bw):  # blocks of bh x bw output pixels, row-major; inside a block the four parity classes 2 a + b = pixels (2 i + a, 2 j + b)
+    return ('subpix', bh, bw)
+
+
 # name, sel, ks, stride, ups, B, C0, C1, H (input), Cout, coef + SiLU, residual, px, slot layout
 CASES = [
     # implicit GEMM, default selector: MODE 2 (1x1, full tiles), MODE 0 (Cout % bn != 0), MODE 1 (full tiles, not 1x1 stride 1)
@@ -166,6 +170,11 @@ def partial_pixels(out, px, lay):
     o = out.double()
     if lay == ROWS:
         return o.permute(0, 2, 3, 1).reshape(B, H * W // px, px, Cc).permute(0, 1, 3, 2)
+    if lay[0] == 'subpix':       # the sub-pixel upsample kernel (test_gpu_upsample_subpixel.py): slot = 4 block + class
+        _, bh, bw = lay
+        assert bh * bw == 4 * px
+        o = o.reshape(B, Cc, H // bh, bh // 2, 2, W // bw, bw // 2, 2)       # [B][C][block row][i][a][block column][j][b]
+        return o.permute(0, 2, 5, 4, 7, 1, 3, 6).reshape(B, (H // bh) * (W // bw) * 4, Cc, px)
     bh, bw = lay
     assert bh * bw == px
     return o.reshape(B, Cc, H // bh, bh, W // bw, bw).permute(0, 2, 4, 1, 3, 5).reshape(B, (H // bh) * (W // bw), Cc, px)

@@ -150,6 +150,8 @@ def test_unet_uniform_t_forward_is_bit_identical(name):
     ('tiny2', 16, 5, None),     # the fused small-image ResBlocks and attention blocks
     ('mnist', 32, 2, None),     # the whole-image ResBlocks at 32x32 and 16x16
     ('wide', 16, 2, 2),         # a declared batch of 2: narrow n-tiles, split-K partial buffers, the general path
+    ('mnist', 48, 3, None),     # levels of 48, 24, 12 and 6 pixels: F(4x4) with 3 blocks per row, the generic implicit GEMM
+    ('tiny2', 20, 3, None),     # levels of 20, 10 and 5 pixels
 ])
 def test_unet_forward_stays_inside_the_planned_workspace(name, size, B, declared):
     """The sized plan is the launched plan: dlpm_unet_workspace_bytes is a dry run of the very walk that launches, so a forward handed
