@@ -275,6 +275,13 @@ SIGNATURES_TRAIN = {
     'dlpm_grad_clip_coef_f32': (C.c_int, [vp, i64, f64, vp, vp, vp]),
     'dlpm_adamw_step_f32': (C.c_int, [C.POINTER(AdamwArgs), vp]),
 }
+# the same for include/dlpm_amd_mlp.h (the toy net at any architecture: the general MFMA forward)
+MLP_NO_LAYERNORM, MLP_NO_SKIP, MLP_FORCE_GENERAL, MLP_TILE_16, MLP_TILE_32 = 1, 2, 4, 8, 16
+SIGNATURES_MLP = {
+    'dlpm_mlp_create_ex': (C.c_int, [i32, i32, i32, i32, i32, C.POINTER(vp)]),
+    'dlpm_mlp_tile_rows': (i32, [vp]),
+    'dlpm_mlp_lds_bytes': (i64, [vp]),
+}
 
 _lib = None
 
@@ -292,7 +299,8 @@ def lib():
                             '(or __graft_entry__.build()); there is no CPU fallback' % LIB_PATH)
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
-                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()):
+                list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()) + \
+                list(SIGNATURES_MLP.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

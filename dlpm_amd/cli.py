@@ -40,6 +40,9 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   the train split drawn from the config's own `data:` description, keyed by --set_seed) and print `epoch <e> loss <mean loss>` per epoch;
   --save writes a checkpoint in the reference's format, which --checkpoint loads.  With --generate N (and --eval_2d ...) the trained
   net -- with --ema_eval the --ema_index-th EMA -- is then evaluated in the same run; without it the run ends after training.
+  --units N / --blocks N / --t_embedding_size N: the 2-D toy net's width, depth and time embedding size, as the reference's flags of
+  the same names (script_utils.py:92-102); anything but the shipped 64 units runs on the general MFMA forward, which samples and
+  evaluates a checkpoint but does not --train.
 """
 import argparse
 import os
@@ -68,7 +71,18 @@ def class_labels(spec, num_classes, n):
     return torch.full((n,), k, dtype=torch.int64)
 
 
-def main(argv=None):
+def apply_model_arguments(p, a):
+    """--blocks / --units / --t_embedding_size into p['model'], as the reference's script_utils.py:92-102 does."""
+    if a.blocks is not None:
+        p['model']['nblocks'] = a.blocks
+    if a.units is not None:
+        p['model']['nunits'] = a.units
+    if a.t_embedding_size is not None:
+        p['model']['time_emb_size'] = a.t_embedding_size
+    return p
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--config', required=True, help='config name (dlpm_amd/configs) or path to a reference-schema YAML')
     ap.add_argument('--method', default=None, choices=['dlpm', 'lim'], help='generative method (script_utils.py:6-7)')
@@ -154,6 +168,15 @@ def main(argv=None):
     ap.add_argument('--ema_rates', type=float, nargs='+', default=None, help='with --train: EMA rates (default: training.<method>.ema_rates)')
     ap.add_argument('--max_batch_per_epoch', type=int, default=None, help='with --train: stop every epoch after this many batches')
     ap.add_argument('--grad_clip', type=float, default=None, help='with --train: gradient-norm clip (default: training.<method>.grad_clip)')
+    ap.add_argument('--blocks', type=int, default=None, help='2-D toy net: number of blocks (model.nblocks; script_utils.py:92-93,200)')
+    ap.add_argument('--units', type=int, default=None, help='2-D toy net: hidden units (model.nunits, up to 1024; script_utils.py:95-96,201)')
+    ap.add_argument('--t_embedding_size', type=int, default=None,
+                    help='2-D toy net: time embedding size (model.time_emb_size, up to 1024; script_utils.py:101-102,206)')
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.train is None and (a.save or a.ema_rates or a.max_batch_per_epoch is not None or a.grad_clip is not None):
         raise SystemExit('--save / --ema_rates / --max_batch_per_epoch / --grad_clip belong to --train EPOCHS')
@@ -178,6 +201,7 @@ def main(argv=None):
             p['data']['weights'] = None
     if a.method is not None:
         p['method'] = a.method
+    apply_model_arguments(p, a)
     m = p['method']
     if a.eval_loss and m == 'lim' and (a.lploss is not None or a.median is not None):
         ap.error('--lploss / --median belong to the DLPM loss; --method lim evaluates training_losses_lim, which has neither')

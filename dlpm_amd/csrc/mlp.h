@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mlp_pack.h"
 
 namespace dlpm {
 
@@ -70,4 +71,32 @@ struct dlpm_mlp {
     float *flat = nullptr;
     int32_t *flat_map = nullptr;
     bool flat_valid = false;
+    // the general forward (mlp_general.hip): every net the lane kernels do not take.  Such a handle uses none of the fields above
+    // but `finalized`: set_param keeps the tensors as given, finalize packs them into the MFMA blob.
+    int flags = 0;                 // DLPM_MLP_* of dlpm_mlp_create_ex
+    bool ln = true, skip = true;   // LayerNorm / skip connection
+    bool general = false;
+    dlpm::MlpGenLayout gen{};
+    int gen_M = 0;                 // rows of the tallest tile a workgroup may own: 32 where the LDS holds them, else 16
+    std::map<std::string, std::vector<float>> raw;
+    float *gen_dev = nullptr;
 };
+
+namespace dlpm {
+// mlp_general.hip
+int mlp_general_init(dlpm_mlp *m);
+int mlp_general_set_param(dlpm_mlp *m, const char *key, const float *w, int64_t numel);
+int mlp_general_finalize(dlpm_mlp *m);
+int mlp_general_forward(dlpm_mlp *m, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, hipStream_t st);
+}  // namespace dlpm
+
+// the training entry points and the one-launch sampling loop run the lane kernels' net only
+#define DLPM_MLP_REFUSE_GENERAL(m, name, what)                                                                                  \
+    do {                                                                                                                        \
+        if ((m)->general) {                                                                                                     \
+            ::dlpm::set_error(name ": " what " runs at the shipped 64-unit architecture (nunits 64, time_emb_size <= 64, "       \
+                              "LayerNorm, skip connections); this net (nunits %d, time_emb_size %d) takes the general forward", \
+                              (m)->nunits, (m)->TE);                                                                            \
+            return DLPM_ERR_UNSUPPORTED;                                                                                        \
+        }                                                                                                                       \
+    } while (0)

@@ -13,6 +13,7 @@
 // Weights (220 kB, transposed to [k][unit]) stay L2-resident across the whole sampling loop.
 #include "mlp.h"
 #include "philox.h"
+#include "../../include/dlpm_amd_mlp.h"
 
 using namespace dlpm;
 
@@ -233,15 +234,38 @@ __global__ void __launch_bounds__(256) k_mlp_sample(MlpLoopArgs a, MlpOffsets o)
 }  // namespace
 
 extern "C" int dlpm_mlp_create(int32_t nfeatures, int32_t nunits, int32_t nblocks, int32_t time_emb_size, dlpm_mlp **out) {
+    return dlpm_mlp_create_ex(nfeatures, nunits, nblocks, time_emb_size, 0, out);
+}
+
+extern "C" int dlpm_mlp_create_ex(int32_t nfeatures, int32_t nunits, int32_t nblocks, int32_t time_emb_size, int32_t flags,
+                                  dlpm_mlp **out) {
     DLPM_CHECK_ARG(out, "dlpm_mlp_create: null out");
     DLPM_CHECK_ARG(nfeatures > 0 && nblocks >= 0, "dlpm_mlp_create: bad nfeatures / nblocks");
-    if (nunits != NU || time_emb_size <= 0 || time_emb_size > NU) {
-        set_error("dlpm_mlp_create: this build maps hidden units onto the 64-lane wavefront: nunits must be 64 "
-                  "(got %d) and time_emb_size <= 64 (got %d)", nunits, time_emb_size);
+    DLPM_CHECK_ARG(nunits > 0 && time_emb_size > 0, "dlpm_mlp_create: nunits (%d) and time_emb_size (%d) must be positive", nunits,
+                   time_emb_size);
+    DLPM_CHECK_ARG(!(flags & ~(DLPM_MLP_NO_LAYERNORM | DLPM_MLP_NO_SKIP | DLPM_MLP_FORCE_GENERAL | DLPM_MLP_TILE_16 | DLPM_MLP_TILE_32)),
+                   "dlpm_mlp_create: unknown flag in %d", flags);
+    DLPM_CHECK_ARG(!((flags & DLPM_MLP_TILE_16) && (flags & DLPM_MLP_TILE_32)), "dlpm_mlp_create: DLPM_MLP_TILE_16 and DLPM_MLP_TILE_32 exclude each other");
+    if (nunits > GEN_MAX_UNITS || time_emb_size > GEN_MAX_TE || nfeatures > GEN_MAX_FEATURES) {
+        set_error("dlpm_mlp_create: the toy net runs at nunits <= %d (got %d), time_emb_size <= %d (got %d) and nfeatures <= %d "
+                  "(got %d)", GEN_MAX_UNITS, nunits, GEN_MAX_TE, time_emb_size, GEN_MAX_FEATURES, nfeatures);
         return DLPM_ERR_UNSUPPORTED;
     }
     dlpm_mlp *m = new dlpm_mlp();
     m->F = nfeatures; m->nunits = nunits; m->nblocks = nblocks; m->TE = time_emb_size;
+    m->flags = flags;
+    m->ln = !(flags & DLPM_MLP_NO_LAYERNORM);
+    m->skip = !(flags & DLPM_MLP_NO_SKIP);
+    // the lane kernels map the hidden units onto the 64-lane wavefront: the shipped architecture and nothing else
+    if (!(nunits == NU && time_emb_size <= NU && m->ln && m->skip && !(flags & DLPM_MLP_FORCE_GENERAL))) {
+        const int rc = mlp_general_init(m);
+        if (rc != DLPM_OK) {
+            delete m;
+            return rc;
+        }
+        *out = m;
+        return DLPM_OK;
+    }
     MlpOffsets &o = m->off;
     int p = 0;
     auto take = [&](int n) { int r = p; p += (n + 3) / 4 * 4; return r; };
@@ -271,6 +295,7 @@ void put_T(std::vector<float> &h, int off, const float *w, int N, int K, int ld)
 
 extern "C" int dlpm_mlp_set_param(dlpm_mlp *m, const char *key_c, const float *w, int64_t numel) {
     DLPM_CHECK_ARG(m && key_c && w, "dlpm_mlp_set_param: null argument");
+    if (m->general) return mlp_general_set_param(m, key_c, w, numel);
     const std::string key = key_c;
     const MlpOffsets &o = m->off;
     const int TE = m->TE, F = m->F;
@@ -341,6 +366,7 @@ extern "C" int dlpm_mlp_set_param(dlpm_mlp *m, const char *key_c, const float *w
 
 extern "C" int dlpm_mlp_finalize(dlpm_mlp *m) {
     DLPM_CHECK_ARG(m, "dlpm_mlp_finalize: null handle");
+    if (m->general) return mlp_general_finalize(m);
     const size_t expected = 8 + 10 * (size_t)(m->nblocks + 1) + 2;
     if (m->seen.size() != expected) {
         set_error("dlpm_mlp_finalize: %zu of %zu parameter tensors were set", m->seen.size(), expected);
@@ -373,6 +399,7 @@ extern "C" int dlpm_mlp_sample_steps_f32(dlpm_mlp *m, float *x_dev, const float 
                                          uint64_t seed, int64_t sample_offset, const uint64_t *key_dev, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && x_dev && c_eps_dev && c_noise_dev && g_dev, "dlpm_mlp_sample_steps_f32: null argument");
     DLPM_CHECK_ARG(T >= 2 && B > 0 && nsteps >= 0 && t_start < T && t_start - nsteps >= 0, "dlpm_mlp_sample_steps_f32: bad step range");
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_sample_steps_f32", "the one-launch sampling loop");
     if (!m->finalized) {
         set_error("dlpm_mlp_sample_steps_f32: call dlpm_mlp_finalize first");
         return DLPM_ERR_STATE;
@@ -408,6 +435,7 @@ extern "C" int dlpm_mlp_forward(dlpm_mlp *m, const float *x_dev, const float *t_
         set_error("dlpm_mlp_forward: call dlpm_mlp_finalize first");
         return DLPM_ERR_STATE;
     }
+    if (m->general) return mlp_general_forward(m, x_dev, t_dev, eps_dev, B, as_stream(stream));
     k_mlp_forward<<<(unsigned)ceil_div(B, SPW), 64, 0, as_stream(stream)>>>(m->dev, m->off, x_dev, t_dev, eps_dev, B, m->F,
                                                                           m->TE, m->nblocks + 1);
     DLPM_LAUNCH_CHECK();
@@ -421,5 +449,6 @@ extern "C" void dlpm_mlp_destroy(dlpm_mlp *m) {
     if (m->tp) (void)hipFree(m->tp);
     if (m->flat) (void)hipFree(m->flat);
     if (m->flat_map) (void)hipFree(m->flat_map);
+    if (m->gen_dev) (void)hipFree(m->gen_dev);
     delete m;
 }

@@ -510,6 +510,7 @@ int64_t backward_floats(const dlpm_mlp *m, int64_t rows, int64_t *rec_floats, in
 
 extern "C" int64_t dlpm_mlp_param_floats(const dlpm_mlp *m) {
     if (!m) return -1;
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_param_floats", "training");
     MlpOffsets f;
     return flat_offsets(m, f);
 }
@@ -524,6 +525,7 @@ extern "C" int64_t dlpm_mlp_param_floats(const dlpm_mlp *m) {
 
 extern "C" int dlpm_mlp_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t n, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_export_params_f32: null argument");
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_export_params_f32", "training");
     DLPM_CHECK_ARG(n == dlpm_mlp_param_floats(m), "dlpm_mlp_export_params_f32: n = %lld, the net has %lld parameters", (long long)n,
                    (long long)dlpm_mlp_param_floats(m));
     TRAIN_NEED_FINALIZED(m, "dlpm_mlp_export_params_f32");
@@ -535,6 +537,7 @@ extern "C" int dlpm_mlp_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t 
 
 extern "C" int dlpm_mlp_import_params_f32(dlpm_mlp *m, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_import_params_f32: null argument");
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_import_params_f32", "training");
     DLPM_CHECK_ARG(n == dlpm_mlp_param_floats(m), "dlpm_mlp_import_params_f32: n = %lld, the net has %lld parameters", (long long)n,
                    (long long)dlpm_mlp_param_floats(m));
     TRAIN_NEED_FINALIZED(m, "dlpm_mlp_import_params_f32");
@@ -551,6 +554,7 @@ extern "C" int dlpm_mlp_import_params_f32(dlpm_mlp *m, const float *flat_dev, in
 
 extern "C" int64_t dlpm_mlp_backward_workspace_bytes(const dlpm_mlp *m, int64_t rows) {
     if (!m || rows <= 0) return -1;
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_backward_workspace_bytes", "training");
     return backward_floats(m, rows, nullptr, nullptr) * (int64_t)sizeof(float);
 }
 
@@ -559,6 +563,7 @@ extern "C" int dlpm_mlp_backward_f32(dlpm_mlp *m, const float *x_dev, const floa
                                      dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && x_dev && t_dev && dout_dev && grad_flat_dev && workspace_dev, "dlpm_mlp_backward_f32: null argument");
     DLPM_CHECK_ARG(rows > 0, "dlpm_mlp_backward_f32: rows must be positive (got %lld)", (long long)rows);
+    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_backward_f32", "training");
     DLPM_CHECK_ARG(ceil_div(rows, SPW) < (1ll << 31) && ceil_div(rows, RC) <= 65535, "dlpm_mlp_backward_f32: rows = %lld is beyond "
                    "the grid of one call (at most %d)", (long long)rows, 65535 * RC);
     int64_t rec_floats, sc_floats;

@@ -13,6 +13,7 @@
 using namespace dlpm;
 
 extern "C" int dlpm_mlp_forward(dlpm_mlp *, const float *, const float *, float *, int64_t, dlpm_stream_t);
+extern "C" int32_t dlpm_mlp_tile_rows(const dlpm_mlp *);   // > 0: the net takes the general forward (include/dlpm_amd_mlp.h)
 
 struct dlpm_sampler {
     dlpm_sampler_config cfg;
@@ -587,7 +588,8 @@ extern "C" int dlpm_sampler_steps(dlpm_sampler *s, int32_t nsteps, dlpm_stream_t
     // toy net, plain stochastic DLPM steps: the whole run of steps is one launch (state in registers)
     // (one wave per sample: best while the batch is latency-bound; beyond ~16k samples the 4-samples-per-wave
     //  forward kernel + update kernel reuse the weights better)
-    if (s->cfg.mlp && !(s->cfg.flags & (DLPM_UPD_DLIM | DLPM_UPD_CLIP | DLPM_SMP_NO_FUSED_MLP | DLPM_SMP_LIM)) && s->D <= 4 && s->cfg.mean_type == DLPM_MEAN_EPSILON &&
+    // (a net on the general forward has no such loop: it takes the per-step path below)
+    if (s->cfg.mlp && dlpm_mlp_tile_rows(s->cfg.mlp) == 0 && !(s->cfg.flags & (DLPM_UPD_DLIM | DLPM_UPD_CLIP | DLPM_SMP_NO_FUSED_MLP | DLPM_SMP_LIM)) && s->D <= 4 && s->cfg.mean_type == DLPM_MEAN_EPSILON &&
         s->cfg.B <= 16384 && !s->hist && !s->in_scale && !prof_enabled()) {
         TRY(dlpm_mlp_sample_steps_f32(s->cfg.mlp, s->x, s->c_eps, s->c_noise, s->g, s->cfg.T, s->cfg.B, s->t_host, nsteps,
                                       s->cfg.seed, s->cfg.sample_offset, s->key_dev, st));

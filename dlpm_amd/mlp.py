@@ -2,6 +2,11 @@
 forward runs in libdlpm_amd.  Same `state_dict` keys (including the aliases the reference's
 nn.Sequential re-registrations create) and the same construction order, hence the same default
 initialisation under a given torch.manual_seed.
+
+Any nunits / time_emb_size up to 1024, nfeatures up to 64, nblocks >= 0, group_norm and skip_connection on or
+off, as the reference takes them.  The shipped architecture (64 units, time_emb_size <= 64, LayerNorm, skip)
+runs on the lane kernels; every other one, or any with kernel='general', on the general MFMA forward
+(include/dlpm_amd_mlp.h), which samples and evaluates but does not train.
 """
 import ctypes as C
 import weakref
@@ -12,11 +17,14 @@ import torch.nn as nn
 from . import _lib
 
 
-def _cond_block(nunits, temb):
-    """Parameters of DiffusionBlockConditioned (time-conditioned, LayerNorm): DiffusionBlocks.py:88-123."""
+MAX_UNITS, MAX_TIME_EMB, MAX_FEATURES = 1024, 1024, 64     # GEN_MAX_* of dlpm_amd/csrc/mlp_pack.h
+
+
+def _cond_block(nunits, temb, group_norm=True):
+    """Parameters of DiffusionBlockConditioned (time-conditioned): DiffusionBlocks.py:88-123."""
     blk = nn.Module()
-    blk.group_norm1 = nn.LayerNorm([nunits])
-    blk.group_norm2 = nn.LayerNorm([nunits])
+    blk.group_norm1 = nn.LayerNorm([nunits]) if group_norm else nn.Identity()
+    blk.group_norm2 = nn.LayerNorm([nunits]) if group_norm else nn.Identity()
     drop = nn.Dropout(p=0.0)
     act = nn.SiLU()
     blk.mlp_1 = nn.Sequential(drop, nn.Linear(nunits, nunits), blk.group_norm1)
@@ -26,35 +34,63 @@ def _cond_block(nunits, temb):
 
 
 class MLPModel(nn.Module):
-    def __init__(self, p):
+    def __init__(self, p, kernel='auto', tile_rows=None):
+        """kernel: 'auto' (the lane kernels for the shipped architecture, the general forward otherwise) or 'general' (the general
+        forward whatever the architecture).  tile_rows: None (the general forward takes 32-row tiles where they fit the LDS and
+        fill the chip, 16-row tiles otherwise), or 16 / 32 for that height whatever the batch (the results are the same bits)."""
         super().__init__()
         m = p['model']
-        self.nfeatures = p['data']['nfeatures']
-        self.nunits, self.nblocks, self.time_emb_size = m['nunits'], m['nblocks'], m['time_emb_size']
+        self.nfeatures = int(p['data']['nfeatures'])
+        self.nunits, self.nblocks, self.time_emb_size = int(m['nunits']), int(m['nblocks']), int(m['time_emb_size'])
+        self.group_norm, self.skip_connection = bool(m['group_norm']), bool(m['skip_connection'])
+        if kernel not in ('auto', 'general'):
+            raise ValueError("kernel must be 'auto' or 'general', got {!r}".format(kernel))
+        if tile_rows not in (None, 16, 32):
+            raise ValueError('tile_rows must be None, 16 or 32, got {!r}'.format(tile_rows))
+        self.kernel, self.tile_rows = kernel, tile_rows
         unsupported = []
         if not (m['no_a'] and p[p['method']]['isotropic']):
             unsupported.append('a_t inputs / non-isotropic (the reference asserts the same, Model.py:44)')
         if m['time_emb_type'] != 'learnable':
-            unsupported.append("time_emb_type != 'learnable'")
+            unsupported.append("time_emb_type != 'learnable' (the reference's other two types do not run: Model.py:59 reads an "
+                               'undefined attribute, :188 appends to an undefined list)')
         if m.get('a_pos_emb') or m.get('learn_variance'):
             unsupported.append('a_pos_emb / learn_variance')
-        if not m['group_norm'] or not m['skip_connection'] or m.get('dropout_rate', 0.0):
-            unsupported.append('group_norm=False / skip_connection=False / dropout')
+        if m.get('dropout_rate', 0.0):
+            unsupported.append('dropout (the forward is an inference path)')
+        if self.nunits < 1 or self.time_emb_size < 1 or self.nfeatures < 1 or self.nblocks < 0:
+            raise ValueError('nunits, time_emb_size and nfeatures must be positive and nblocks >= 0')
+        if self.nunits > MAX_UNITS:
+            unsupported.append('nunits {} > {} (a 16-row tile of activations must fit the LDS)'.format(self.nunits, MAX_UNITS))
+        if self.time_emb_size > MAX_TIME_EMB:
+            unsupported.append('time_emb_size {} > {}'.format(self.time_emb_size, MAX_TIME_EMB))
+        if self.nfeatures > MAX_FEATURES:
+            unsupported.append('nfeatures {} > {} (the input and output layers run on the VALU)'.format(self.nfeatures, MAX_FEATURES))
         if unsupported:
-            raise NotImplementedError('dlpm_amd.MLPModel implements the shipped 2d_data.yml architecture; got: '
-                                      + '; '.join(unsupported))
+            raise NotImplementedError('dlpm_amd.MLPModel does not implement: ' + '; '.join(unsupported))
         act = nn.SiLU()
-        self.group_norm_in = nn.LayerNorm([self.nunits])
+        self.group_norm_in = nn.LayerNorm([self.nunits]) if self.group_norm else nn.Identity()
         self.time_emb = nn.Linear(1, self.time_emb_size)
         self.time_mlp = nn.Sequential(self.time_emb, act, nn.Linear(self.time_emb_size, self.time_emb_size), act)
         self.linear_in = nn.Linear(self.nfeatures, self.nunits)
         self.inblock = nn.Sequential(self.linear_in, self.group_norm_in, act)
-        self.midblocks = nn.ModuleList([_cond_block(self.nunits, self.time_emb_size) for _ in range(self.nblocks)])
-        self.outblocks_mean = nn.ModuleList([_cond_block(self.nunits, self.time_emb_size),
+        self.midblocks = nn.ModuleList([_cond_block(self.nunits, self.time_emb_size, self.group_norm) for _ in range(self.nblocks)])
+        self.outblocks_mean = nn.ModuleList([_cond_block(self.nunits, self.time_emb_size, self.group_norm),
                                              nn.Linear(self.nunits, self.nfeatures)])
         self._handle = None
         self.handle_generation = 0          # bumped whenever the native handle is destroyed (sampler cache keys carry it)
         self._dependents = weakref.WeakSet()  # method objects holding native samplers built on this handle
+
+    @property
+    def general(self):
+        """True when the forward is the general MFMA kernel (the routing of dlpm_mlp_create_ex): such a net samples and evaluates
+        but has no backward and no one-launch sampling loop."""
+        return not (self.nunits == 64 and self.time_emb_size <= 64 and self.group_norm and self.skip_connection
+                    and self.kernel == 'auto')
+
+    def native_flags(self):
+        return ((0 if self.group_norm else _lib.MLP_NO_LAYERNORM) | (0 if self.skip_connection else _lib.MLP_NO_SKIP)
+                | (_lib.MLP_FORCE_GENERAL if self.kernel == 'general' else 0) | {None: 0, 16: _lib.MLP_TILE_16, 32: _lib.MLP_TILE_32}[self.tile_rows])
 
     def invalidate(self):
         for m in list(self._dependents):
@@ -80,11 +116,16 @@ class MLPModel(nn.Module):
             return self._handle
         L = _lib.lib()
         h = C.c_void_p()
-        _lib.check(L.dlpm_mlp_create(self.nfeatures, self.nunits, self.nblocks, self.time_emb_size, C.byref(h)))
-        for k, v in self.state_dict().items():
-            w = v.detach().to('cpu', torch.float32).contiguous()
-            _lib.check(L.dlpm_mlp_set_param(h, k.encode(), w.data_ptr(), w.numel()))
-        _lib.check(L.dlpm_mlp_finalize(h))
+        _lib.check(L.dlpm_mlp_create_ex(self.nfeatures, self.nunits, self.nblocks, self.time_emb_size, self.native_flags(), C.byref(h)))
+        try:
+            assert (L.dlpm_mlp_tile_rows(h) > 0) == self.general, 'the library routes this net differently from MLPModel.general'
+            for k, v in self.state_dict().items():
+                w = v.detach().to('cpu', torch.float32).contiguous()
+                _lib.check(L.dlpm_mlp_set_param(h, k.encode(), w.data_ptr(), w.numel()))
+            _lib.check(L.dlpm_mlp_finalize(h))
+        except Exception:
+            L.dlpm_mlp_destroy(h)
+            raise
         self._handle = h
         return h
 

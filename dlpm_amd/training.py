@@ -27,6 +27,12 @@ def _refuse_model(model):
     if not isinstance(model, MLPModel):
         raise NotImplementedError('training runs for the 2-D toy net (MLPModel) only, got {}: training of the UNets is out of scope '
                                   '(DESIGN.md section 8)'.format(type(model).__name__))
+    if model.general:
+        raise NotImplementedError('training runs at the shipped 64-unit architecture (nunits 64, time_emb_size <= 64, LayerNorm, skip '
+                                  "connections, kernel='auto'); this net (nunits {}, time_emb_size {}, group_norm {}, skip_connection {}, "
+                                  'kernel {!r}) takes the general forward, which has no backward: training of the wide toy nets is a '
+                                  'follow-up (DESIGN.md section 9)'.format(model.nunits, model.time_emb_size, model.group_norm,
+                                                                           model.skip_connection, model.kernel))
 
 
 class MLPTrainer:
