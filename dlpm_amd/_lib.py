@@ -282,6 +282,14 @@ SIGNATURES_MLP = {
     'dlpm_mlp_tile_rows': (i32, [vp]),
     'dlpm_mlp_lds_bytes': (i64, [vp]),
 }
+# the same for include/dlpm_amd_mlp_grad.h (gradients of the toy net at any architecture: what the autograd bridge calls)
+SIGNATURES_MLP_GRAD = {
+    'dlpm_mlp_grad_param_floats': (i64, [vp]),
+    'dlpm_mlp_grad_export_params_f32': (C.c_int, [vp, vp, i64, vp]),
+    'dlpm_mlp_grad_import_params_f32': (C.c_int, [vp, vp, i64, vp]),
+    'dlpm_mlp_grad_workspace_bytes': (i64, [vp, i64]),
+    'dlpm_mlp_grad_backward_f32': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+}
 
 _lib = None
 
@@ -300,7 +308,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
                 list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()) + \
-                list(SIGNATURES_MLP.items()):
+                list(SIGNATURES_MLP.items()) + list(SIGNATURES_MLP_GRAD.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

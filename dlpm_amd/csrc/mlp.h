@@ -79,7 +79,8 @@ struct dlpm_mlp {
     dlpm::MlpGenLayout gen{};
     int gen_M = 0;                 // rows of the tallest tile a workgroup may own: 32 where the LDS holds them, else 16
     std::map<std::string, std::vector<float>> raw;
-    float *gen_dev = nullptr;
+    float *gen_dev = nullptr;      // the forward's blob, then the transposed operands of the backward (MlpGenGradLayout)
+    int64_t *gen_map = nullptr;    // [2][P]: the flat vector's map into both regions (mlp_general_grad.hip), built on first use
 };
 
 namespace dlpm {
@@ -90,12 +91,14 @@ int mlp_general_finalize(dlpm_mlp *m);
 int mlp_general_forward(dlpm_mlp *m, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B, hipStream_t st);
 }  // namespace dlpm
 
-// the training entry points and the one-launch sampling loop run the lane kernels' net only
+// the fused trainer's entry points and the one-launch sampling loop run the lane kernels' net only (any net's gradients:
+// mlp_general_grad.hip)
 #define DLPM_MLP_REFUSE_GENERAL(m, name, what)                                                                                  \
     do {                                                                                                                        \
         if ((m)->general) {                                                                                                     \
             ::dlpm::set_error(name ": " what " runs at the shipped 64-unit architecture (nunits 64, time_emb_size <= 64, "       \
-                              "LayerNorm, skip connections); this net (nunits %d, time_emb_size %d) takes the general forward", \
+                              "LayerNorm, skip connections); this net (nunits %d, time_emb_size %d) takes the general forward, " \
+                              "whose gradients come through dlpm_amd_mlp_grad.h (MLPModel(differentiable=True))",               \
                               (m)->nunits, (m)->TE);                                                                            \
             return DLPM_ERR_UNSUPPORTED;                                                                                        \
         }                                                                                                                       \

@@ -450,5 +450,6 @@ extern "C" void dlpm_mlp_destroy(dlpm_mlp *m) {
     if (m->flat) (void)hipFree(m->flat);
     if (m->flat_map) (void)hipFree(m->flat_map);
     if (m->gen_dev) (void)hipFree(m->gen_dev);
+    if (m->gen_map) (void)hipFree(m->gen_map);
     delete m;
 }

@@ -15,131 +15,12 @@
 // row go over the thread's tiles, a 16-lane butterfly and the waves in order, and neither M nor the row's place in the tile enters.
 #include <cstring>
 
-#include "mlp.h"
+#include "mlp_general.h"
 #include "../../include/dlpm_amd_mlp.h"
 
 using namespace dlpm;
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-struct GenArgs {
-    const float *P;
-    MlpGenLayout L;
-    const float *x, *t;
-    float *out;
-    int64_t B;
-    int ln, skip;
-};
-
-// acc[m][n] += A[16 m .. 16 m + 15][0 .. 16 KG) * (column tile n of the packed operand Wp); Wp points at this wave's first tile
-template <int MT, int NT>
-__device__ __forceinline__ void gemm_tiles(const float4 *__restrict__ Wp, int KG, const float *A, int ld, int lane,
-                                           floatx4 (&acc)[MT][NT]) {
-    const float *arow = A + (lane & 15) * ld + 4 * (lane >> 4);
-    const float4 *wl = Wp + lane;
-    for (int g = 0; g < KG; g++) {
-        float4 b[NT], a[MT];
-#pragma unroll
-        for (int n = 0; n < NT; n++) b[n] = wl[((int64_t)n * KG + g) * 64];
-#pragma unroll
-        for (int m = 0; m < MT; m++) a[m] = *reinterpret_cast<const float4 *>(arow + m * 16 * ld + 16 * g);
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int n = 0; n < NT; n++) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].x, b[n].x, acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int n = 0; n < NT; n++) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].y, b[n].y, acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int n = 0; n < NT; n++) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].z, b[n].z, acc[m][n], 0, 0, 0);
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int n = 0; n < NT; n++) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m].w, b[n].w, acc[m][n], 0, 0, 0);
-    }
-}
-
-// the sum over the 16 lanes that hold one row of a column tile; every one of them gets the same bits
-__device__ __forceinline__ float row16_sum(float v) {
-#pragma unroll
-    for (int m = 1; m <= 8; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-// torch's LayerNorm over the NU real columns of every row (mlp.h::layer_norm: mean, centred variance, eps 1e-5), the row sums
-// taken over this thread's tiles, its 16 lanes and then the waves in order through part[2][W][M]
-template <int MT, int NT>
-__device__ __forceinline__ void layer_norm_rows(floatx4 (&v)[MT][NT], const float *__restrict__ gam, const float *__restrict__ bet,
-                                                const int (&col)[NT], int NU, float *part, int W, int w, int lane) {
-    constexpr int M = 16 * MT;
-    const float inv = 1.0f / (float)NU;
-    const int q4 = 4 * (lane >> 4);
-    float mean[MT][4];
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float s = 0.f;
-#pragma unroll
-            for (int n = 0; n < NT; n++) s += v[m][n][r];       // padded columns hold exactly 0
-            s = row16_sum(s);
-            if ((lane & 15) == 0) part[w * M + 16 * m + q4 + r] = s;
-        }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float s = 0.f;
-            for (int ww = 0; ww < W; ww++) s += part[ww * M + 16 * m + q4 + r];
-            mean[m][r] = s * inv;
-        }
-    float *part2 = part + W * M;
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float s = 0.f;
-#pragma unroll
-            for (int n = 0; n < NT; n++) {
-                const float d = col[n] < NU ? v[m][n][r] - mean[m][r] : 0.f;   // a padded column is no part of the variance
-                v[m][n][r] = d;
-                s += d * d;
-            }
-            s = row16_sum(s);
-            if ((lane & 15) == 0) part2[w * M + 16 * m + q4 + r] = s;
-        }
-    __syncthreads();
-    float g[NT], be[NT];
-#pragma unroll
-    for (int n = 0; n < NT; n++) { g[n] = gam[col[n]]; be[n] = bet[col[n]]; }
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float s = 0.f;
-            for (int ww = 0; ww < W; ww++) s += part2[ww * M + 16 * m + q4 + r];
-            const float rstd = 1.0f / sqrtf(s * inv + 1e-5f);
-#pragma unroll
-            for (int n = 0; n < NT; n++) v[m][n][r] = v[m][n][r] * rstd * g[n] + be[n];
-        }
-}
-
-// this thread's elements into the activation image: rows 16 m + 4 (lane >> 4) + r, columns col[n]
-template <int MT, int NT>
-__device__ __forceinline__ void store_tiles(float *A, int ld, const floatx4 (&v)[MT][NT], const int (&col)[NT], int lane) {
-#pragma unroll
-    for (int m = 0; m < MT; m++)
-#pragma unroll
-        for (int n = 0; n < NT; n++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) A[(16 * m + 4 * (lane >> 4) + r) * ld + col[n]] = v[m][n][r];
-}
 
 template <int MT, int NT>
 __global__ void __launch_bounds__(64 * GEN_MAX_WAVES) k_mlp_general(GenArgs a) {
@@ -394,7 +275,8 @@ int mlp_general_set_param(dlpm_mlp *m, const char *key_c, const float *w, int64_
 int mlp_general_finalize(dlpm_mlp *m) {
     const MlpGenLayout &L = m->gen;
     const int F = m->F, NU = m->nunits, TE = m->TE;
-    std::vector<float> blob((size_t)L.total, 0.f);
+    const MlpGenGradLayout G = mlp_gen_grad_layout(L);
+    std::vector<float> blob((size_t)(L.total + G.total), 0.f);
     const std::string *missing = nullptr;
     std::string name;
     auto get = [&](const std::string &key) -> const float * {
@@ -406,20 +288,24 @@ int mlp_general_finalize(dlpm_mlp *m) {
         return it->second.data();
     };
     auto vec = [&](int64_t off, const std::string &key, int n, int npad) { if (const float *v = get(key)) mlp_pack_vector(&blob[off], v, n, npad); };
-    auto op = [&](int64_t off, const std::string &key, int N, int K, int NPad, int KPad) {
-        if (const float *v = get(key)) mlp_pack_operand(&blob[off], v, N, K, NPad, KPad);
+    // a hidden Linear: the forward's operand and, in the second region, its transpose for the backward's dX = dY W
+    auto op = [&](int64_t off, int64_t offT, const std::string &key, int N, int K, int NPad, int KPad) {
+        if (const float *v = get(key)) {
+            mlp_pack_operand(&blob[off], v, N, K, NPad, KPad);
+            mlp_pack_operand_t(&blob[G.base + offT], v, N, K, NPad, KPad);
+        }
     };
     vec(L.te_w, "time_emb.weight", TE, L.TEP); vec(L.te_b, "time_emb.bias", TE, L.TEP);
-    op(L.tm_w, "time_mlp.2.weight", TE, TE, L.TEP, L.TEP); vec(L.tm_b, "time_mlp.2.bias", TE, L.TEP);
+    op(L.tm_w, G.tm_wT, "time_mlp.2.weight", TE, TE, L.TEP, L.TEP); vec(L.tm_b, "time_mlp.2.bias", TE, L.TEP);
     if (const float *v = get("linear_in.weight")) mlp_pack_transposed(&blob[L.in_w], v, NU, F, L.NP);
     vec(L.in_b, "linear_in.bias", NU, L.NP);
     if (m->ln) { vec(L.in_g, "group_norm_in.weight", NU, L.NP); vec(L.in_be, "group_norm_in.bias", NU, L.NP); }
     for (int bi = 0; bi <= m->nblocks; bi++) {
         const std::string pre = bi < m->nblocks ? "midblocks." + std::to_string(bi) + "." : std::string("outblocks_mean.0.");
-        const int64_t b = L.blk0 + (int64_t)bi * L.blk_stride;
-        op(b + L.b_w1, pre + "mlp_1.1.weight", NU, NU, L.NP, L.NP); vec(b + L.b_b1, pre + "mlp_1.1.bias", NU, L.NP);
-        op(b + L.b_tw, pre + "t_proj.1.weight", NU, TE, L.NP, L.TEP); vec(b + L.b_tb, pre + "t_proj.1.bias", NU, L.NP);
-        op(b + L.b_w2, pre + "mlp_2.1.weight", NU, NU, L.NP, L.NP); vec(b + L.b_b2, pre + "mlp_2.1.bias", NU, L.NP);
+        const int64_t b = L.blk0 + (int64_t)bi * L.blk_stride, bT = G.blk0 + (int64_t)bi * G.blk_stride;
+        op(b + L.b_w1, bT + G.b_w1T, pre + "mlp_1.1.weight", NU, NU, L.NP, L.NP); vec(b + L.b_b1, pre + "mlp_1.1.bias", NU, L.NP);
+        op(b + L.b_tw, bT + G.b_twT, pre + "t_proj.1.weight", NU, TE, L.NP, L.TEP); vec(b + L.b_tb, pre + "t_proj.1.bias", NU, L.NP);
+        op(b + L.b_w2, bT + G.b_w2T, pre + "mlp_2.1.weight", NU, NU, L.NP, L.NP); vec(b + L.b_b2, pre + "mlp_2.1.bias", NU, L.NP);
         if (m->ln) {
             vec(b + L.b_g1, pre + "group_norm1.weight", NU, L.NP); vec(b + L.b_be1, pre + "group_norm1.bias", NU, L.NP);
             vec(b + L.b_g2, pre + "group_norm2.weight", NU, L.NP); vec(b + L.b_be2, pre + "group_norm2.bias", NU, L.NP);

@@ -103,6 +103,51 @@ class ReferenceStreams:
         return torch.from_numpy(out).reshape(list(shape))
 
 
+class _TrainingLoss(torch.autograd.Function):
+    """training_losses with a graph, for a differentiable MLPModel: the forward is the launches the forward-only call makes (the
+    same bits), kept; the backward is dlpm_loss_grad_f32 times the incoming gradient and one backward of the net -- the pieces
+    MLPTrainer.step composes.  Returns (loss, terms, t); only the loss is differentiable, with respect to the net's parameters."""
+
+    @staticmethod
+    def forward(ctx, method, model, spec, x_start, *params):
+        B = int(x_start.shape[0])
+        if spec['lim']:
+            r = method._lim_loss_terms(model, x_start, spec['clamp_eps'], spec['noise'], keep=True)
+            out, target, x_in, tvec = r['output'], r['score'], r['x_t'], r['t']
+            lp, outer, inner, median = 1, 1, 1, None
+        else:
+            lp, outer, inner = spec['lploss'], spec['outer'], spec['inner']
+            r = method._loss_terms(model, x_start, lp, outer, inner, None, spec['clamp_a'], spec['noise'], keep=True)
+            out, target, x_in, tvec = r['model_eps'], r['eps_t'], r['x_in'], r['tvec']
+            median = torch.empty(B, dtype=torch.int32, device=x_start.device) if spec['median'] else None
+        loss = method._loss_reduce(r['losses'], B, outer, inner, 'median' if median is not None else 'mean', False, median_index=median)
+        ctx.model, ctx.key, ctx.dims, ctx.median = model, model._imported, (B, outer, inner, lp), median
+        ctx.save_for_backward(out, target, r['losses'], x_in, tvec)
+        ctx.mark_non_differentiable(r['losses'], r['t'])
+        return loss.clone(), r['losses'], r['t']
+
+    @staticmethod
+    def backward(ctx, gloss, _glosses, _gt):
+        out, target, terms, x_in, tvec = ctx.saved_tensors
+        model, (B, outer, inner, lp) = ctx.model, ctx.dims
+        if model._imported != ctx.key:
+            raise RuntimeError('a parameter of the MLPModel was modified between training_losses and this backward; the native '
+                               'handle holds the newer values')
+        with torch.cuda.device(out.device):
+            dmodel = torch.empty_like(out)
+            _lib.check(_lib.lib().dlpm_loss_grad_f32(out.data_ptr(), target.data_ptr(), terms.data_ptr(), _lib.ptr(ctx.median),
+                                                     dmodel.data_ptr(), B, outer, inner, int(x_in[0].numel()), lp, _lib.stream_ptr()))
+            dmodel.mul_(gloss.to(dmodel.dtype))
+            flat, _ = model.native_backward(x_in, tvec, dmodel)
+        return (None, None, None, None) + tuple(g if ctx.needs_input_grad[4 + i] else None for i, g in enumerate(model.split_flat(flat)))
+
+
+def _wants_graph(model):
+    from .mlp import MLPModel
+    return (isinstance(model, MLPModel) and model.differentiable and torch.is_grad_enabled()
+            and any(p.requires_grad for p in model.parameters()))
+
+
 class GenerativeLevyProcess:
     def __init__(self, alpha, device, reverse_steps, model_mean_type=ModelMeanType.EPSILON,
                  model_var_type=ModelVarType.FIXED, time_spacing='linear', rescale_timesteps=False, isotropic=True,
@@ -969,6 +1014,12 @@ class GenerativeLevyProcess:
         self.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
         if hasattr(model, 'eval'):
             model.eval()
+        if _wants_graph(model) and not model_kwargs:
+            # a differentiable MLPModel under grad mode: the same launches with a graph behind the loss.  No host read here
+            # (`check_finite` is not consulted): a non-finite loss shows in the caller's own loss.item()
+            spec = dict(lim=False, lploss=lploss, outer=outer, inner=inner, clamp_a=clamp_a, noise=noise, median=loss_monte_carlo == 'median')
+            loss, terms, t = _TrainingLoss.apply(self, model, spec, x_start, *model.parameters())
+            return (loss, terms, t) if return_terms else loss
         with torch.inference_mode():
             r = self._loss_terms(model, x_start, lploss, outer, inner, model_kwargs, clamp_a, noise)
             loss = self._loss_reduce(r['losses'], x_start.shape[0], outer, inner, loss_monte_carlo, check_finite)
@@ -1115,14 +1166,20 @@ class GenerativeLevyProcess:
         self.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
         if hasattr(model, 'eval'):
             model.eval()
+        if _wants_graph(model):       # as in training_losses_dlpm
+            spec = dict(lim=True, clamp_eps=clamp_eps, noise=noise)
+            loss, terms, t = _TrainingLoss.apply(self, model, spec, x_start, *model.parameters())
+            return (loss, terms, t) if return_terms else loss
         with torch.inference_mode():
             r = self._lim_loss_terms(model, x_start, clamp_eps, noise)
             loss = self._loss_reduce(r['losses'], x_start.shape[0], 1, 1, 'mean', check_finite)
         return (loss, r['losses'], r['t']) if return_terms else loss
 
     def training_losses(self, models, x_start, model_kwargs=None, **kwargs):
-        """Forward-only, under torch.inference_mode(): the result carries no autograd graph.  GenerativeLevyProcess.training_losses
-        (:581-609) as a held-out metric: {'loss': 0-dim fp32 tensor on the device, 'losses': the per-extended-sample terms
+        """GenerativeLevyProcess.training_losses (:581-609).  For a differentiable MLPModel (MLPModel(p, differentiable=True)) under
+        grad mode 'loss' carries a graph -- one autograd.Function around the whole loss, the same launches and bits, nothing read on
+        the host -- so the reference's loop (loss.backward(), optimizer.step()) trains it.  Otherwise forward-only, under
+        torch.inference_mode(), as a held-out metric: {'loss': 0-dim fp32 tensor on the device, 'losses': the per-extended-sample terms
         [outer * inner * B] (this build's addition), 't': the timesteps [B]}.  `model_kwargs={'y': labels}` reaches a
         class-conditional net with the labels following their sample into every replica; the nested form
         {'model_kwargs': {'y': labels}} (the only one the reference's own splat lets through) is accepted too.  Other keywords

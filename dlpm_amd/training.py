@@ -30,8 +30,10 @@ def _refuse_model(model):
     if model.general:
         raise NotImplementedError('training runs at the shipped 64-unit architecture (nunits 64, time_emb_size <= 64, LayerNorm, skip '
                                   "connections, kernel='auto'); this net (nunits {}, time_emb_size {}, group_norm {}, skip_connection {}, "
-                                  'kernel {!r}) takes the general forward, which has no backward: training of the wide toy nets is a '
-                                  'follow-up (DESIGN.md section 9)'.format(model.nunits, model.time_emb_size, model.group_norm,
+                                  'kernel {!r}) takes the general forward.  Its gradients come through torch.autograd -- '
+                                  'MLPModel(p, differentiable=True), then the reference\'s own loop: training_losses(...)[\'loss\'].backward() '
+                                  'and a torch.optim optimizer (DESIGN.md section 3.21); the fused trainer for wide nets is a follow-up '
+                                  '(DESIGN.md section 9)'.format(model.nunits, model.time_emb_size, model.group_norm,
                                                                            model.skip_connection, model.kernel))
 
 

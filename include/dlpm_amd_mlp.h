@@ -13,8 +13,8 @@
  *
  * dlpm_mlp_forward routes by handle.  For a handle on the general forward, dlpm_mlp_sample_steps_f32 (the one-launch loop) and
  * the training entry points of dlpm_amd_train.h (dlpm_mlp_param_floats, dlpm_mlp_backward_workspace_bytes, dlpm_mlp_backward_f32,
- * dlpm_mlp_export_params_f32, dlpm_mlp_import_params_f32) return DLPM_ERR_UNSUPPORTED with a message; a sampler on such a handle
- * takes the per-step path (forward + update kernel in the captured graph). */
+ * dlpm_mlp_export_params_f32, dlpm_mlp_import_params_f32) return DLPM_ERR_UNSUPPORTED with a message (the gradients of such a
+ * net: dlpm_amd_mlp_grad.h); a sampler on such a handle takes the per-step path (forward + update kernel in the captured graph). */
 #ifndef DLPM_AMD_MLP_H
 #define DLPM_AMD_MLP_H
 #include "dlpm_amd.h"
