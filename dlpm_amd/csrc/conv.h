@@ -11,8 +11,8 @@ struct ConvLaunch {
     int B = 0, Hin = 0, Win = 0, Hout = 0, Wout = 0;
     int ks = 1, stride = 1, ups = 0;
     const float *w = nullptr;      // igemm: [ks*ks][Cout][Cin]   direct: [ks*ks][Cin][Cout]
-    const float *w_frag = nullptr; // optional, 3x3 only: MFMA B-fragment order [Cout/32][Cin/32][9][4][64 lanes][4]
-                                   // (see k_conv3x3_halo_ws): each wave streams it straight into registers
+    const float *w_frag = nullptr; // optional, 3x3 only: MFMA B-fragment order [n-blocks of 32][Cin/32][9][4][64 lanes][4], padded with zero
+                                   // n-blocks to whole BN tiles (see k_conv3x3_halo_ws, frag_weight_floats): each wave streams it straight into registers
     const float *w_wino = nullptr; // optional, 3x3 s1 only: Winograd-domain weights U = G g G^T in fragment order
                                    // (see conv_wino.hip); when the shape qualifies the F(2x2,3x3) kernel runs
     const float *w_wino4 = nullptr;// optional, 3x3 s1 only: F(4x4,3x3) Winograd-domain weights (conv_wino4.hip); preferred over w_wino

@@ -759,8 +759,8 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_halo_ws(ConvLaunch p, int th
 
 // OIHW (3x3) -> Wf[nb][chunk][tap][kk][lane][4]:  lane = kh*32 + l31 holds
 // W[cout = nb*32 + l31][cin = chunk*32 + kk*8 + kh*4 + e][tap], zero beyond Cout.
-__global__ void k_relayout_weight_frag(const float *oihw, float *dst, int Cout, int Cin) {
-    const int nbk = (Cout + 31) / 32, nch = Cin / 32;
+__global__ void k_relayout_weight_frag(const float *oihw, float *dst, int Cout, int Cin, int nbk) {
+    const int nch = Cin / 32;
     const int64_t n = (int64_t)nbk * nch * 9 * 4 * 64 * 4;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1259,15 +1259,21 @@ static int launch_igemm(const ConvLaunch &c, hipStream_t st) {
     return DLPM_OK;
 }
 
+// n-blocks of 32 output channels in the fragment copy: whole tiles of the BN launch_igemm picks for Cout -- every wave of
+// k_conv3x3_halo_ws streams its RN n-blocks whether or not the layer has those channels (Cout = 96: 4 n-blocks, 160 and 192: 8); the
+// n-blocks beyond Cout hold zeros
+static int frag_nblocks(int Cout) { return Cout > 64 ? (Cout + 127) / 128 * 4 : Cout > 32 ? 2 : 1; }
+
 int64_t frag_weight_floats(int Cout, int Cin) {
     // + 2 groups of padding at the end: the 2-ahead prefetch of the last groups reads past the data
-    return ((int64_t)((Cout + 31) / 32) * (Cin / 32) * 9 * 4 + 2) * 256;
+    return ((int64_t)frag_nblocks(Cout) * (Cin / 32) * 9 * 4 + 2) * 256;
 }
 
 int relayout_weight_frag(const float *oihw_dev, float *dst_dev, int Cout, int Cin, hipStream_t st) {
-    const int64_t n = (int64_t)((Cout + 31) / 32) * (Cin / 32) * 9 * 4 * 256;
+    const int nbk = frag_nblocks(Cout);
+    const int64_t n = (int64_t)nbk * (Cin / 32) * 9 * 4 * 256;
     DLPM_HIP(hipMemsetAsync(dst_dev + n, 0, 2 * 256 * sizeof(float), st));
-    k_relayout_weight_frag<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin);
+    k_relayout_weight_frag<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(oihw_dev, dst_dev, Cout, Cin, nbk);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }

@@ -35,6 +35,8 @@ BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
 # dlpm_conv_policy_route(..).scratch_floats of each case (AUTO, the case's declared batch), recorded from the commit before the weight
 # layouts moved into one table (conv.h: ConvLayout): the floats the layouts of the layer take, one behind the other at multiples of 64
+# (the three Cout = 96 cases: those values + one n-block of Cin / 32 * 36 * 256 floats, since the fragment copy is padded to whole
+# 128-channel tiles -- frag_weight_floats, csrc/conv_igemm.hip; tests/test_conv_tile_cases_cpu.py holds that size against the kernel's reads)
 SCRATCH_FLOATS = {
     'f2_4x4_32_32to64_d256': 440832,
     'f2_ups2to4_128_128to64_d2': 1151488,
@@ -44,9 +46,9 @@ SCRATCH_FLOATS = {
     'f2_ups4x8to8x16_256_128to128_d64': 6988288,
     'f4_16x16_32_32to32_d64_coef_res': 113152,
     'f4_8x16_128_128to32_d64': 444928,
-    'f4_8x16_128_128to96_d2': 1329664,
-    'f4_ups2to4_256_128to96_d256': 1993216,
-    'f4_ups4to8_32_32to96_d64_coef': 334336,
+    'f4_8x16_128_128to96_d2': 1403392,
+    'f4_ups2to4_256_128to96_d256': 2103808,
+    'f4_ups4to8_32_32to96_d64_coef': 352768,
     'f4_ups8to16_128_128to32_d2_rescat': 444928,
     'nq32_16x16_32to128_d64': 590336,
     'nq64_16x16_32to128_d128': 590336,
