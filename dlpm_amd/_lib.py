@@ -290,6 +290,12 @@ SIGNATURES_MLP_GRAD = {
     'dlpm_mlp_grad_workspace_bytes': (i64, [vp, i64]),
     'dlpm_mlp_grad_backward_f32': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
 }
+# the same for include/dlpm_amd_w1.h (the exact W1 between two point sets: integer auction)
+W1_L1_MEAN, W1_EUCLIDEAN = 0, 1
+SIGNATURES_W1 = {
+    'dlpm_w1_workspace_bytes': (i64, [i64, i64]),
+    'dlpm_w1_f32': (C.c_int, [vp, vp, i64, i64, i32, i64, i64, vp, i64, vp, vp, vp, vp]),
+}
 
 _lib = None
 
@@ -308,7 +314,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
                 list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()) + \
-                list(SIGNATURES_MLP.items()) + list(SIGNATURES_MLP_GRAD.items()):
+                list(SIGNATURES_MLP.items()) + list(SIGNATURES_MLP_GRAD.items()) + list(SIGNATURES_W1.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -20,7 +20,9 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   --eval_wass REAL.npy --generate N [--wass_bins K]: generate N samples and print the reference's `wass` figure between the first N
   float32 samples of REAL.npy and them (EvaluationManager.evaluate_wass: the earth mover's distance between the histograms of the
   flattened sets, the last sample of each left out as the reference does; 250 bins from 512 samples on, else numpy's 'auto').  With
-  more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc / --eval_fid the samples are generated once and every figure is printed.
+  more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc / --eval_fid / --eval_w1 the samples are generated once and every figure is printed.
+  --eval_w1 REAL.npy|dataset --generate N [--w1_ground l1_mean|euclidean]: the exact W1 between the N generated samples and the
+  first N real ones as points (`dataset`: N samples of the config's own 2-D distribution); prints `w1 <value> ground <g> over ...`.
   --eval_prdc REAL.npy --generate N [--nearest_k K]: generate N samples and print the k-nearest-neighbour precision, recall, density
   and coverage (the `prdc` package's compute_prdc) between the first N float32 samples of REAL.npy and them, with f_1_pr and f_1_dc
   (EvaluationManager.evaluate_prdc on the flattened samples; K = 5 neighbours by default).  A feature network is plugged in through
@@ -144,6 +146,13 @@ def build_parser():
                          'prints `wass <value> over <N> generated vs <N> real samples`')
     ap.add_argument('--wass_bins', type=int, default=None, help='with --eval_wass: number of bins (default: 250 from 512 samples on, '
                                                                 'else numpy\'s auto rule)')
+    ap.add_argument('--eval_w1', default=None, metavar='REAL.npy|dataset',
+                    help='with --generate N: the exact Wasserstein-1 distance between the N generated samples and the first N float32 '
+                         'samples of this file, as points (optimal transport, one bin per point); `dataset` draws the N real samples '
+                         'from the config\'s own 2-D data distribution; prints `w1 <value> ground <g> over <N> generated vs <N> real samples`')
+    ap.add_argument('--w1_ground', default='l1_mean', choices=('l1_mean', 'euclidean'),
+                    help='with --eval_w1: the distance between two points: the mean absolute difference (the reference\'s manual_compute '
+                         'cost, default) or the Euclidean norm')
     ap.add_argument('--eval_prdc', default=None, metavar='REAL.npy',
                     help='with --generate N: k-nearest-neighbour precision / recall / density / coverage (compute_prdc of the prdc '
                          'package) between the first N float32 samples of this file and the N generated samples, flattened; prints '
@@ -183,7 +192,7 @@ def main(argv=None):
     if a.save_fid_stats and not (a.eval_fid and not a.eval_fid.endswith('.npz')):
         raise SystemExit('--save_fid_stats needs --eval_fid REAL.npy')
     for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc),
-                        ('--eval_fid', a.eval_fid), ('--eval_2d', a.eval_2d), ('--dump_dataset', a.dump_dataset)):
+                        ('--eval_fid', a.eval_fid), ('--eval_2d', a.eval_2d), ('--dump_dataset', a.dump_dataset), ('--eval_w1', a.eval_w1)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -293,9 +302,9 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     loader = dlpm_amd.ShapeProbe(sample_shape(p))
-    if a.eval_2d or a.dump_dataset:
+    if a.eval_2d or a.dump_dataset or a.eval_w1 == 'dataset':
         if is_image:
-            raise SystemExit('--eval_2d / --dump_dataset draw the 2-D toy distributions; %s is an image dataset' % p['data']['dataset'])
+            raise SystemExit('--eval_2d / --dump_dataset / --eval_w1 dataset draw the 2-D toy distributions; %s is an image dataset' % p['data']['dataset'])
         loader = dlpm_amd.ToyLoader(dlpm_amd.get_dataset(p, 'cuda', seed or 0)[0], p['eval']['batch_size'])
     gm = dlpm_amd.GenerationManager(method, loader, is_image, **p['eval'][m])
     if a.dump_dataset:
@@ -309,7 +318,7 @@ def main(argv=None):
         if a.out:
             np.save(a.out, res['samples'].cpu().numpy())
         return res
-    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid:
+    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid or a.eval_w1:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
         value = samples = None
@@ -373,6 +382,16 @@ def main(argv=None):
                 value = f
             else:
                 value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass': value}, fid=f)
+        if a.eval_w1:
+            if samples is None:
+                samples = generated()
+            real = None if a.eval_w1 == 'dataset' else real_of(a.eval_w1)
+            w = ev.evaluate_w1({'default': model}, real, N, p['eval']['batch_size'], ground=a.w1_ground, samples=samples)
+            print('w1 %.9g ground %s over %d generated vs %d real samples' % (w, a.w1_ground, N, N))
+            if value is None:
+                value = w
+            else:
+                value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass' if a.eval_wass else 'fid': value}, w1=w)
         if a.out:
             np.save(a.out, samples.cpu().numpy())
         return value

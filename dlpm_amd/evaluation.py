@@ -156,6 +156,8 @@ class EvaluationManager:
         for k in ('wass', 'mmd', 'precision', 'recall', 'density', 'coverage', 'f_1_pr', 'f_1_dc', 'fid', 'fig'):
             e[k] = old[k] if keep_evals else []
         e['grad_norm'] = old['grad_norm'] if keep_evals else np.array([], dtype=np.float32)
+        if keep_evals and 'w1' in old:                                              # evaluate_w1's own key: there only once filled
+            e['w1'] = old['w1']
         self.evals = e
 
     def evaluate_loss(self, models, data, batch_size, per_timestep=False, class_labels=None, **loss_kwargs):
@@ -380,6 +382,22 @@ class EvaluationManager:
             bins = 250 if len(gen) >= 512 else 'auto'                               # EvaluationManager.py:149
         value = metrics.compute_wasserstein_distance(real, gen, bins=bins)
         self.evals['wass'].append(value)
+        return value
+
+    def evaluate_w1(self, models, real_data, data_to_generate, batch_size, class_labels=None, ground='l1_mean', samples=None, **kwargs):
+        """The exact W1 between `real_data[:data_to_generate]` and `data_to_generate` generated samples as points (metrics.w1: optimal
+        transport with one bin of mass 1 / N per point), as a Python float appended to `evals['w1']` -- a key of this package, created
+        on first use.  ground='l1_mean' is the figure the reference's commented-out manual_compute branch (EvaluationManager.py:144-146)
+        was meant to put into `wass`; 'euclidean' the textbook W1.  `real_data=None`: samples of the config's own distribution.
+
+        The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`."""
+        from . import metrics
+        if ground not in metrics.W1_GROUNDS:
+            raise ValueError('evaluate_w1: ground must be one of %s, got %r' % (sorted(metrics.W1_GROUNDS), ground))
+        real, gen, _ = self._real_and_samples('evaluate_w1', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                              kwargs)
+        value = metrics.w1(real, gen, ground=ground)
+        self.evals.setdefault('w1', []).append(value)
         return value
 
     def evaluate_prdc(self, models, real_data, data_to_generate, batch_size, class_labels=None, nearest_k=5, features=None, samples=None,

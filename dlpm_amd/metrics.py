@@ -24,8 +24,12 @@ Inputs are float32 tensors or arrays [N, ...] (rows are flattened), on the host 
 Unequal counts are allowed (the reference's broadcast raises on them): sum XX / n1^2 + sum YY / n2^2 - 2 sum XY / (n1 n2).
 Not built: any Inception forward -- the network needs weights nobody can ship; bring the features (`prdc`, `fd`,
 `EvaluationManager.evaluate_prdc(features=...)`, `evaluate_fid(features=...)`).  Neither are the reference's
-unused get_MMD / MMDStatistic / MMD helpers, nor the `manual_compute` branch of compute_wasserstein_distance (a general 2N x 2N
-transport problem)."""
+unused get_MMD / MMDStatistic / MMD helpers.  The `manual_compute` branch of compute_wasserstein_distance stays refused under that name; its
+figure is `compute_w1_distance`:
+
+    w1(first, second, ground='l1_mean') -> float      dlpm_w1_f32: exact optimal transport between equal-count point sets by an
+                                                      integer auction
+    compute_w1_distance(data, gen_samples, num_samples)   the manual_compute branch's figure"""
 import numpy as np
 import torch
 
@@ -378,12 +382,100 @@ def compute_wasserstein_distance(data, gen_samples, manual_compute=False, num_sa
     callable or other `distance`, normalized=False."""
     if manual_compute:
         raise NotImplementedError('compute_wasserstein_distance: manual_compute=True is a general 2N x 2N transport problem; only the '
-                                  'histogram form is built (DESIGN 8)')
+                                  'histogram form is built here (DESIGN 8) -- metrics.compute_w1_distance gives that branch\'s figure')
     if distance != 'euclidean':
         raise NotImplementedError('compute_wasserstein_distance: only distance=\'euclidean\' between bin centres is built (DESIGN 8)')
     if not normalized:
         raise NotImplementedError('compute_wasserstein_distance: normalized=False is not built (DESIGN 8)')
     return wass(gen_samples[:num_samples], data[:num_samples], bins=bins, range=_range)
+
+
+# ---------------------------------------------------------------------------------------------- exact W1 (integer auction)
+W1_MAX_POINTS = 32768
+W1_MAX_WIDTH = 4096
+W1_GROUNDS = {'l1_mean': _lib.W1_L1_MEAN, 'euclidean': _lib.W1_EUCLIDEAN}
+W1_TAIL_THRESHOLD = 4              # rounds with at most this many bidders run in the one-workgroup kernel: the best of {0, 4, 16, 64}
+#                                    at N = 1024 and 4096 in every configuration of profiles/w1
+W1_ROUNDS_COEF, W1_ROUNDS_POWER = 15, 1.25   # the most rounds seen at n points stay below 15 n^1.25 for n = 256 ... 8192 (profiles/w1)
+
+
+def w1_default_max_rounds(n):
+    """The cap on the auction's rounds when none is given: 16 x the largest round count measured at that n, which over n = 256 ...
+    8192 grows like n^1.25 (15 153 rounds at 256, 1 165 974 at 8192; at most 15 n^1.25 everywhere in profiles/w1), so
+    16 * 15 * max(n, 64)^1.25.  A guard against a spin, not a tuning value; nothing beyond 8192 points has been measured."""
+    return int(16 * W1_ROUNDS_COEF * max(int(n), 64) ** W1_ROUNDS_POWER)
+
+
+def _w1_check(first, second, ground, max_rounds, tail_threshold):
+    x, y = _row_pair('w1', first, 'first', second, 'second')
+    assert x.shape[0] == y.shape[0], 'w1: equal counts needed, got %d and %d points (compute_w1_distance cuts both to the shorter)' % (
+        x.shape[0], y.shape[0])
+    assert x.shape[0] <= W1_MAX_POINTS, 'w1: at most %d points, got %d' % (W1_MAX_POINTS, x.shape[0])
+    assert x.shape[1] <= W1_MAX_WIDTH, 'w1: rows of at most %d values, got %d' % (W1_MAX_WIDTH, x.shape[1])
+    if ground not in W1_GROUNDS:
+        raise ValueError('w1: ground must be one of %s, got %r' % (sorted(W1_GROUNDS), ground))
+    n = x.shape[0]
+    max_rounds = w1_default_max_rounds(n) if max_rounds is None else max_rounds
+    tail_threshold = W1_TAIL_THRESHOLD if tail_threshold is None else tail_threshold
+    assert int(max_rounds) == max_rounds and max_rounds >= 1, 'w1: max_rounds must be a positive integer, got %r' % (max_rounds,)
+    assert int(tail_threshold) == tail_threshold and tail_threshold >= 0, 'w1: tail_threshold must be a non-negative integer, got %r' % (
+        tail_threshold,)
+    return x, y, W1_GROUNDS[ground], int(max_rounds), int(tail_threshold)
+
+
+def _w1_run(first, second, ground, max_rounds, tail_threshold):
+    """w1_device and the cap on the rounds that the call ran under."""
+    x, y, g, max_rounds, tail_threshold = _w1_check(first, second, ground, max_rounds, tail_threshold)
+    x, y, dev = _on_device(x, y)
+    L = _lib.lib()
+    n, D = x.shape
+    ws = _workspace(L.dlpm_w1_workspace_bytes(n, D), dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        perm = torch.empty(n, dtype=torch.int32, device=dev)
+        prices = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(L.dlpm_w1_f32(x.data_ptr(), y.data_ptr(), n, D, g, max_rounds, tail_threshold, ws.data_ptr(), ws.numel(),
+                                 perm.data_ptr(), prices.data_ptr(), out.data_ptr(), _lib.stream_ptr()))
+    return out, perm, prices, max_rounds
+
+
+def w1_device(first, second, ground='l1_mean', max_rounds=None, tail_threshold=None):
+    """The call itself: (out, perm, prices) on the GPU -- out float64 [8] = W, the integer optimum, the scale exponent e, rounds,
+    phases, cmax, status, rounds run by the one-workgroup kernel; perm int32 [n] (row perm[i] of `second` is matched with row i of
+    `first`); prices int64 [n].  status 1 (a non-finite input value) and 2 (max_rounds reached) leave W NaN.  No synchronisation
+    beyond the call's own: it is enqueued on the current stream but NOT graph-capturable, since the host reads the device's header
+    once per batch of rounds."""
+    return _w1_run(first, second, ground, max_rounds, tail_threshold)[:3]
+
+
+def w1(first, second, ground='l1_mean', return_parts=False):
+    """The exact Wasserstein-1 distance between two sets of n float32 points (rows flattened), every point of mass 1 / n, as a Python
+    float: (1 / n) min over permutations s of sum_i c(first_i, second_s(i)) with c = mean_d |a_d - b_d| (ground='l1_mean', the cost
+    of the reference's manual_compute branch) or the Euclidean distance (ground='euclidean').  The assignment is exactly optimal for
+    the costs rounded to 24-bit integers; the figure is the fp64 cost of that assignment, so 0 <= w1 - optimum <= 2^-e.
+    ValueError on a non-finite input value, RuntimeError if the round cap is reached.
+    `return_parts=True` returns (w1, parts) with parts = {'perm' int32 [n], 'prices' int64 [n], 'rounds', 'phases', 'scale_exponent',
+    'cmax', 'integer_cost'}."""
+    out, perm, prices, max_rounds = _w1_run(first, second, ground, None, None)
+    o = out.cpu().numpy()
+    if int(o[6]) == 1:
+        raise ValueError('w1: a non-finite value in the input')
+    if int(o[6]) == 2:
+        raise RuntimeError('w1: the auction has not ended within the cap of max_rounds = %d rounds' % max_rounds)
+    if not return_parts:
+        return float(o[0])
+    return float(o[0]), {'perm': perm.cpu().numpy(), 'prices': prices.cpu().numpy(), 'rounds': int(o[3]), 'phases': int(o[4]),
+                         'scale_exponent': int(o[2]), 'cmax': float(o[5]), 'integer_cost': int(o[1])}
+
+
+def compute_w1_distance(data, gen_samples, num_samples=-1):
+    """The figure of the reference's compute_wasserstein_distance(data, gen_samples, manual_compute=True, num_samples=...)
+    (bem/evaluate/wasserstein.py:23-46): N = min of the two counts, or num_samples when it is not -1; the first N rows of each set;
+    one bin of mass 1 / N per point and the mean absolute difference as ground distance -- `w1(..., ground='l1_mean')`."""
+    n = min(len(data), len(gen_samples)) if num_samples == -1 else int(num_samples)
+    assert 1 <= n <= min(len(data), len(gen_samples)), 'compute_w1_distance: num_samples = %r with %d and %d points' % (
+        num_samples, len(data), len(gen_samples))
+    return w1(data[:n], gen_samples[:n], ground='l1_mean')
 
 
 # ---------------------------------------------------------------------------------------------- PRDC (k-NN precision / recall / density / coverage)
