@@ -399,6 +399,7 @@ extern "C" int dlpm_mlp_sample_steps_f32(dlpm_mlp *m, float *x_dev, const float 
                                          uint64_t seed, int64_t sample_offset, const uint64_t *key_dev, dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && x_dev && c_eps_dev && c_noise_dev && g_dev, "dlpm_mlp_sample_steps_f32: null argument");
     DLPM_CHECK_ARG(T >= 2 && B > 0 && nsteps >= 0 && t_start < T && t_start - nsteps >= 0, "dlpm_mlp_sample_steps_f32: bad step range");
+    DLPM_CHECK_ARG(T < (1 << 24), "dlpm_mlp_sample_steps_f32: T must fit 24 bits");   // the Philox counter holds purpose | t << 8
     DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_sample_steps_f32", "the one-launch sampling loop");
     if (!m->finalized) {
         set_error("dlpm_mlp_sample_steps_f32: call dlpm_mlp_finalize first");

@@ -593,7 +593,9 @@ int dlpm_mlp_forward(dlpm_mlp *net, const float *x_dev, const float *t_dev, floa
 /* `nsteps` whole reverse steps t = t_start, t_start-1, ... for the toy net in ONE launch: model forward
  * + DLPM update (Philox noise) with the state held in registers (nfeatures <= 4).  x_dev[B,1,F] is
  * updated in place; tables as produced by dlpm_coeff_tables_f32.  key_dev (nullable) overrides
- * {seed, sample_offset} from device memory.  Replaces the loop body of p_sample_loop_progressive
+ * {seed, sample_offset} from device memory.  t_start < T, t_start - nsteps >= 0 and T < 2^24 (the step
+ * shares a Philox counter word with the purpose, and T sizes a per-step table), else DLPM_ERR_ARG before
+ * anything is allocated or launched.  Replaces the loop body of p_sample_loop_progressive
  * (GenerativeLevyProcess.py:317-330) for BASELINE configs[0], which is otherwise launch-bound. */
 int dlpm_mlp_sample_steps_f32(dlpm_mlp *net, float *x_dev, const float *c_eps_dev, const float *c_noise_dev,
                               const float *g_dev, int32_t T, int64_t B, int32_t t_start, int32_t nsteps,
