@@ -91,7 +91,7 @@ int launch_conv_stem(const ConvLaunch &c, hipStream_t st);
 // its epilogue: x <- (x - c_eps[t,b] eps) / g[t] + c_noise[t,b] z on the NCHW state the eps would have been subtracted from
 struct HeadUpdate {
     float *x = nullptr;                 // [B, Cout*H*W] state, updated in place (null: plain convolution, eps -> ConvLaunch::out)
-    const float *z = nullptr;           // injected normals, or null = in-kernel Philox (same counters as k_update_rows)
+    const float *z = nullptr;           // injected normals, or null = in-kernel Philox (update_step.h)
     const int32_t *t = nullptr;         // device step counter
     const float *g = nullptr, *c_eps = nullptr, *c_noise = nullptr;   // [T], [T,B], [T,B]
     const uint64_t *key = nullptr;      // optional device {seed, sample_offset}

@@ -6,7 +6,7 @@
 #include <algorithm>
 
 #include "conv.h"
-#include "philox.h"
+#include "update_step.h"
 
 namespace dlpm {
 namespace {
@@ -66,8 +66,8 @@ __global__ void __launch_bounds__(256) k_conv_direct(ConvLaunch p) {
 // a row and all <= 4 output channels (16 accumulators): per (input row, channel quad) it reads 6 activated input pixels
 // and 12 weight quads from LDS for 192 FMAs, so the loop is VALU-bound (the one-pixel-per-thread generation of this
 // kernel issued 360 LDS reads per pixel and 32-channel chunk).  Four consecutive pixels of one channel are
-// also exactly one Philox counter of the update (element quad), so the fused epilogue draws the same normals as
-// k_update_rows and reproduces it bit for bit.  A workgroup owns TH whole rows of one image (512 pixels, 128 threads);
+// also exactly one Philox counter of the update (element quad), so the fused epilogue is update_step.h's rows form on
+// the quads the update kernel would take.  A workgroup owns TH whole rows of one image (512 pixels, 128 threads);
 // per 8-channel chunk the activated halo goes through LDS once (12 floats per pixel, odd row pitch: lanes walk down
 // the rows, 16 rows = 16 distinct bank groups), weights [tap][cin][4] with uniform (broadcast) reads.  What bounds it
 // now is VALU work: 36 FMAs (a quarter of them on the padding channel when Cout = 3) and one SiLU per input element.
@@ -170,31 +170,23 @@ __global__ void __launch_bounds__(128) k_conv3x3_head(ConvLaunch p, HeadUpdate u
     const int64_t HW = (int64_t)H * W;
     const int64_t pix = (int64_t)(y0 + ty) * W + 4 * tx4;
     if (u.x) {
-        // the reverse update on this thread's element quads: same arithmetic, same Philox counters as k_update_rows (noise.hip)
+        // the reverse update on this thread's element quads (update_step.h)
         const int t = *u.t;
-        const float g = u.g[t], rg = 1.0f / g;
-        const float ce = u.c_eps[(int64_t)t * u.B + b], cn = u.c_noise[(int64_t)t * u.B + b];
-        const uint64_t seed = u.key ? u.key[0] : u.seed;
-        const uint64_t gidx = (uint64_t)((u.key ? (int64_t)u.key[1] : u.sample_offset) + b);
-        float *hr = u.hist_pp ? *u.hist_pp : nullptr;
+        const RowCoeffs c = row_coeffs(u.g, u.c_eps, u.c_noise, t, u.B, b);
+        const StepKey key = step_key(u.key, u.seed, u.sample_offset, b);
         const int64_t D = (int64_t)p.Cout * HW;
-        if (hr) hr += ((int64_t)(u.T - t) * u.B + b) * D;
+        float *hr = history_row(u.hist_pp, u.T, t, u.B, b, D);
 #pragma unroll
         for (int co = 0; co < 4; co++)
             if (co < p.Cout) {
                 const int64_t e0 = (int64_t)co * HW + pix;       // element index inside the sample (NCHW); e0 % 4 == 0
+                const float4 eps = make_float4(acc[0][co], acc[1][co], acc[2][co], acc[3][co]);
                 const float4 x = *reinterpret_cast<const float4 *>(u.x + (int64_t)b * D + e0);
-                float4 z;
-                if (u.z) z = *reinterpret_cast<const float4 *>(u.z + (int64_t)b * D + e0);
-                else z = (cn != 0.0f) ? philox_normal4(seed, gidx, (uint32_t)(e0 >> 2), kPurposeStepZ, (uint32_t)t) : make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 o;
-                o.x = fmaf(cn, z.x, div_by(x.x - ce * acc[0][co], g, rg));
-                o.y = fmaf(cn, z.y, div_by(x.y - ce * acc[1][co], g, rg));
-                o.z = fmaf(cn, z.z, div_by(x.z - ce * acc[2][co], g, rg));
-                o.w = fmaf(cn, z.w, div_by(x.w - ce * acc[3][co], g, rg));
+                const float4 z = step_normals(u.z, (int64_t)b * D + e0, key, (uint32_t)(e0 >> 2), t, c.cn);
+                const float4 o = row_update4(x, eps, z, c);
                 *reinterpret_cast<float4 *>(u.x + (int64_t)b * D + e0) = o;
                 if (hr) *reinterpret_cast<float4 *>(hr + e0) = o;
-                if (u.eps_out) *reinterpret_cast<float4 *>(u.eps_out + (int64_t)b * D + e0) = make_float4(acc[0][co], acc[1][co], acc[2][co], acc[3][co]);
+                if (u.eps_out) *reinterpret_cast<float4 *>(u.eps_out + (int64_t)b * D + e0) = eps;
             }
         return;
     }
@@ -222,7 +214,7 @@ __global__ void __launch_bounds__(128) k_conv3x3_head(ConvLaunch p, HeadUpdate u
 // pixel lies outside the image are simply absent from the sum.
 //
 // The gather kernel is the sampler's fused update kernel: it reads P (4 * 9 Cout B per pixel) and x, applies
-// x <- (x - c_eps eps) / gamma + c_noise z with the Philox counters of k_update_rows (a thread owns four consecutive pixels of
+// x <- (x - c_eps eps) / gamma + c_noise z as update_step.h defines it (a thread owns four consecutive pixels of
 // one row = element quads of the NCHW state), and writes x: eps never reaches HBM.  HBM-bound.
 // ---------------------------------------------------------------------------------------------
 constexpr int HG_LD = 29;   // LDS words per halo pixel (odd: the 9 Cout values of neighbouring pixels fall into different banks; >= 4 ceil(27 / 4) = 28)
@@ -302,26 +294,18 @@ __global__ void __launch_bounds__(256, HG_MINBLOCKS) k_head_gather(const float *
             const int64_t pix = (int64_t)(y0 + r) * W + 4 * q;
             const int64_t e0 = (int64_t)co * HW + pix;       // element index inside the sample (NCHW); e0 % 4 == 0
             if (u.x) {
-                // the reverse update on this thread's element quad: same arithmetic, same Philox counters as k_update_rows (noise.hip)
+                // the reverse update on this thread's element quad (update_step.h)
                 const int tt = *u.t;
-                const float g = u.g[tt], rg = 1.0f / g;
-                const float ce = u.c_eps[(int64_t)tt * u.B + b], cn = u.c_noise[(int64_t)tt * u.B + b];
-                const uint64_t seed = u.key ? u.key[0] : u.seed;
-                const uint64_t gidx = (uint64_t)((u.key ? (int64_t)u.key[1] : u.sample_offset) + b);
-                float *hr = u.hist_pp ? *u.hist_pp : nullptr;
-                if (hr) hr += ((int64_t)(u.T - tt) * u.B + b) * D;
+                const RowCoeffs c = row_coeffs(u.g, u.c_eps, u.c_noise, tt, u.B, b);
+                const StepKey key = step_key(u.key, u.seed, u.sample_offset, b);
+                float *hr = history_row(u.hist_pp, u.T, tt, u.B, b, D);
+                const float4 eps = make_float4(acc[0], acc[1], acc[2], acc[3]);
                 const float4 x = *reinterpret_cast<const float4 *>(u.x + (int64_t)b * D + e0);
-                float4 z;
-                if (u.z) z = *reinterpret_cast<const float4 *>(u.z + (int64_t)b * D + e0);
-                else z = (cn != 0.0f) ? philox_normal4(seed, gidx, (uint32_t)(e0 >> 2), kPurposeStepZ, (uint32_t)tt) : make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 o;
-                o.x = fmaf(cn, z.x, div_by(x.x - ce * acc[0], g, rg));
-                o.y = fmaf(cn, z.y, div_by(x.y - ce * acc[1], g, rg));
-                o.z = fmaf(cn, z.z, div_by(x.z - ce * acc[2], g, rg));
-                o.w = fmaf(cn, z.w, div_by(x.w - ce * acc[3], g, rg));
+                const float4 z = step_normals(u.z, (int64_t)b * D + e0, key, (uint32_t)(e0 >> 2), tt, c.cn);
+                const float4 o = row_update4(x, eps, z, c);
                 *reinterpret_cast<float4 *>(u.x + (int64_t)b * D + e0) = o;
                 if (hr) *reinterpret_cast<float4 *>(hr + e0) = o;
-                if (u.eps_out) *reinterpret_cast<float4 *>(u.eps_out + (int64_t)b * D + e0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                if (u.eps_out) *reinterpret_cast<float4 *>(u.eps_out + (int64_t)b * D + e0) = eps;
             } else if (out_nchw) {
                 *reinterpret_cast<float4 *>(out + (int64_t)b * D + e0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             } else {

@@ -31,7 +31,7 @@
 // All loads are unconditional (past the last image they read the L2-resident weight buffer) and the update's stores are hidden from
 // the compiler (hf_store4), so every wait of the loop is an exact vmcnt count.
 #include "conv.h"
-#include "philox.h"
+#include "update_step.h"
 
 namespace dlpm {
 namespace {
@@ -222,16 +222,14 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
     // the update's launch constants (t -> g is a DEPENDENT pair of loads: once, here)
     int tt = 0;
     float g = 1.f, rg = 1.f;
-    uint64_t seed = 0;
-    int64_t soff = 0;
+    StepKey key0{0, 0};                                // (of sample 0: gidx + b per image)
     float *hist = nullptr;
     if (u.x) {
         tt = *u.t;
         g = u.g[tt];
         rg = 1.0f / g;
-        seed = u.key ? u.key[0] : u.seed;
-        soff = u.key ? (int64_t)u.key[1] : u.sample_offset;
-        hist = u.hist_pp ? *u.hist_pp : nullptr;
+        key0 = step_key(u.key, u.seed, u.sample_offset, 0);
+        hist = history_base(u.hist_pp);
     }
     // ---- the walk: position (image b, phase ph); n = the image's index in this workgroup's sequence (its coefficient slot is n & 1)
     int b = blockIdx.x, ph = 0, n = 0;
@@ -334,8 +332,8 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
 #endif
         asm volatile("" :: "v"(xq.x), "v"(xq.y), "v"(xq.z), "v"(xq.w), "v"(bv), "v"(ce), "v"(cn));   // (every path consumes what it requested)
         if (carry) put_coefs(ncf, (n + 1) & 1);
-        const uint64_t gidx = (uint64_t)(soff + b);
-        float *hr = hist ? hist + ((int64_t)(u.T - tt) * u.B + b) * D : nullptr;
+        const StepKey key{key0.seed, key0.gidx + (uint64_t)(int64_t)b};
+        float *hr = history_row_of(hist, u.T, tt, u.B, b, D);
         const HfItem it = hf_item(tid, g_lo, g_hi - g_lo, nq);
         const int co = it.co, y = it.y, q = it.q;
         const bool item = co < COUT;
@@ -369,17 +367,12 @@ __global__ void __launch_bounds__(HF_NT) __attribute__((amdgpu_waves_per_eu(2, 2
                 }
             }
             if (u.x) {
-                float4 z;
-                if (u.z) z = *reinterpret_cast<const float4 *>(u.z + (int64_t)b * D + e0);
-                else z = (cn != 0.0f) ? philox_normal4(seed, gidx, (uint32_t)(e0 >> 2), kPurposeStepZ, (uint32_t)tt) : make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 o;
-                o.x = fmaf(cn, z.x, div_by(xq.x - ce * acc[0], g, rg));
-                o.y = fmaf(cn, z.y, div_by(xq.y - ce * acc[1], g, rg));
-                o.z = fmaf(cn, z.z, div_by(xq.z - ce * acc[2], g, rg));
-                o.w = fmaf(cn, z.w, div_by(xq.w - ce * acc[3], g, rg));
+                const float4 eps = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                const float4 z = step_normals(u.z, (int64_t)b * D + e0, key, (uint32_t)(e0 >> 2), tt, cn);
+                const float4 o = row_update4(xq, eps, z, RowCoeffs{g, rg, ce, cn});
                 hf_store4(u.x + (int64_t)b * D + e0, o);
                 if (hr) hf_store4(hr + e0, o);
-                if (u.eps_out) hf_store4(u.eps_out + (int64_t)b * D + e0, make_float4(acc[0], acc[1], acc[2], acc[3]));
+                if (u.eps_out) hf_store4(u.eps_out + (int64_t)b * D + e0, eps);
             } else if (p.out_nchw) {
                 hf_store4(p.out + (int64_t)b * D + e0, make_float4(acc[0], acc[1], acc[2], acc[3]));
             } else {

@@ -12,7 +12,7 @@
 // LDS broadcast of the 4 samples' activations, 4 FMAs}, and no workgroup barrier is ever needed.
 // Weights (220 kB, transposed to [k][unit]) stay L2-resident across the whole sampling loop.
 #include "mlp.h"
-#include "philox.h"
+#include "update_step.h"
 #include "../../include/dlpm_amd_mlp.h"
 
 using namespace dlpm;
@@ -182,8 +182,7 @@ __global__ void __launch_bounds__(256) k_mlp_sample(MlpLoopArgs a, MlpOffsets o)
     const int64_t bb = live ? b : a.B - 1;            // dead waves shadow the last sample (barriers stay uniform)
     float *act = acts[wv];
     const float *P = a.P;
-    const uint64_t seed = a.key_dev ? a.key_dev[0] : a.seed;
-    const uint64_t gidx = (uint64_t)((a.key_dev ? (int64_t)a.key_dev[1] : a.sample_offset) + bb);
+    const StepKey key = step_key(a.key_dev, a.seed, a.sample_offset, bb);
     float x[4] = {0.f, 0.f, 0.f, 0.f};
     for (int f = 0; f < a.F; f++) x[f] = a.x[bb * a.F + f];
     const float in_b = P[o.in_b + lane], in_g = P[o.in_g + lane], in_be = P[o.in_be + lane];
@@ -214,17 +213,13 @@ __global__ void __launch_bounds__(256) k_mlp_sample(MlpLoopArgs a, MlpOffsets o)
             __syncthreads();
         }
         // ---- eps, then the DLPM update (dlpm.py:272-278, GenerativeLevyProcess.py:236-238)
-        const float g = a.g[t];
+        const StepScalars c{a.g[t], 0.f, 0.f, 0.f};     // (no clipping, no DLIM: only gamma_t is read)
         const float ce = a.c_eps[(int64_t)t * a.B + bb], cn = a.c_noise[(int64_t)t * a.B + bb];
-        float zz[4] = {0.f, 0.f, 0.f, 0.f};
-        if (cn != 0.0f) {
-            const float4 z4 = philox_normal4(seed, gidx, 0u, 4u /* kPurposeStepZ */, (uint32_t)t);
-            zz[0] = z4.x; zz[1] = z4.y; zz[2] = z4.z; zz[3] = z4.w;
-        }
+        const float4 z4 = step_draw4(key, 0u, t, cn);
+        const float zz[4] = {z4.x, z4.y, z4.z, z4.w};
         for (int f = 0; f < a.F; f++) {
             const float eps = wave_sum(out_w[f] * h) + P[o.out_b + f];
-            const float m = __fdiv_rn(x[f] - __fmul_rn(ce, eps), g);
-            x[f] = __fadd_rn(m, __fmul_rn(cn, zz[f]));
+            x[f] = step_exact(x[f], eps, zz[f], ce, cn, c, false, false, 0.f);
         }
     }
     if (live && lane == 0)

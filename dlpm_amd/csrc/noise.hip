@@ -8,6 +8,7 @@
 // one coefficient pair per sample fetched through the scalar/L1 path.
 #include "common.h"
 #include "philox.h"
+#include "update_step.h"
 
 using namespace dlpm;
 
@@ -156,17 +157,6 @@ __global__ void k_coeff_tables(const float *A, const float *g, const float *s, c
     }
 }
 
-struct StepScalars {
-    float g, bg, bs, bs_prev;
-};
-
-__device__ inline float clip_eps(float x, float e, const StepScalars &c) {
-    // predict_xstart -> clamp -> predict_eps (dlpm.py:191-202)
-    float xs = __fdiv_rn(x - __fmul_rn(e, c.bs), c.bg);
-    xs = fminf(fmaxf(xs, -1.0f), 1.0f);
-    return __fdiv_rn(x - __fmul_rn(xs, c.bg), c.bs);
-}
-
 // One reverse step, fused.  VEC: D % 4 == 0 -> each thread owns UNROLL float4 quads spaced a whole
 // grid apart, issues all of their loads (x, eps, coefficients, optional z) before any arithmetic,
 // then computes (Philox normals in registers) and stores: enough bytes in flight per CU to stream
@@ -174,23 +164,17 @@ __device__ inline float clip_eps(float x, float e, const StepScalars &c) {
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_update(dlpm_update_args p) {
     constexpr int UNROLL = 4;
-    if (p.key_dev) { p.seed = p.key_dev[0]; p.sample_offset = (int64_t)p.key_dev[1]; }
+    const StepKey key0 = step_key(p.key_dev, p.seed, p.sample_offset, 0);   // (sample 0: gidx + b below)
     const int t = *p.t_dev;
-    StepScalars c{p.g_dev[t], p.bg_dev[t], p.bs_dev[t], p.bs_dev[t > 0 ? t - 1 : 0]};
+    const StepScalars c = step_scalars(p.g_dev, p.bg_dev, p.bs_dev, t);
     const bool dlim = p.flags & DLPM_UPD_DLIM, clip = p.flags & DLPM_UPD_CLIP;
     const int64_t D = p.D;
     const int64_t nq = VEC ? D / 4 : D;          // work items per sample
     const int64_t total = p.B * nq;
-    // DLIM eta > 0 extra mean coefficient: (bs_{t-1}^alpha - (eta bs_{t-1})^alpha)^(1/alpha)
-    float dl_mean = c.bs_prev, dl_sig = 0.f;
-    if (dlim && p.dlim_eta != 0.0f) {
-        dl_sig = p.dlim_eta * c.bs_prev;
-        dl_mean = powf(powf(c.bs_prev, p.alpha) - powf(dl_sig, p.alpha), 1.0f / p.alpha);
-    }
+    const DlimCoeffs dl = dlim_coeffs(dlim, p.dlim_eta, p.alpha, c.bs_prev);
     const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    float *hist = p.hist_pp ? *p.hist_pp : nullptr;
-    if (hist) hist += (int64_t)(p.T - t) * p.B * D;
+    float *hist = history_row(p.hist_pp, p.T, t, p.B, 0, D);
     if (VEC) {
         for (int64_t base_i = tid0; base_i < total; base_i += nthreads * UNROLL) {
             float4 x[UNROLL], e[UNROLL], z[UNROLL];
@@ -213,24 +197,16 @@ __global__ void __launch_bounds__(256) k_update(dlpm_update_args p) {
                     cn[u] = p.c_noise_dev[(int64_t)t * p.B + b[u]];
                 } else {
                     ce[u] = c.bs;
-                    cn[u] = (p.dlim_eta != 0.0f && t != 1) ? dl_sig * sqrtf(p.A_dev[(int64_t)t * p.B + b[u]]) : 0.0f;
+                    cn[u] = (p.dlim_eta != 0.0f && t != 1) ? dl.sig * sqrtf(p.A_dev[(int64_t)t * p.B + b[u]]) : 0.0f;
                 }
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; u++) {
-                if (!p.z_dev)
-                    z[u] = (cn[u] != 0.0f) ? philox_normal4(p.seed, (uint64_t)(p.sample_offset + b[u]), (uint32_t)q[u],
-                                                            kPurposeStepZ, (uint32_t)t)
-                                           : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!p.z_dev) z[u] = step_draw4(StepKey{key0.seed, key0.gidx + (uint64_t)b[u]}, (uint32_t)q[u], t, cn[u]);
                 float xv[4] = {x[u].x, x[u].y, x[u].z, x[u].w}, ev[4] = {e[u].x, e[u].y, e[u].z, e[u].w};
                 float zv[4] = {z[u].x, z[u].y, z[u].z, z[u].w}, o[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float ee = clip ? clip_eps(xv[j], ev[j], c) : ev[j];
-                    float m = __fdiv_rn(xv[j] - __fmul_rn(ce[u], ee), c.g);
-                    if (dlim) m = __fadd_rn(m, __fmul_rn(dl_mean, ee));
-                    o[j] = __fadd_rn(m, __fmul_rn(cn[u], zv[j]));
-                }
+                for (int j = 0; j < 4; j++) o[j] = step_exact(xv[j], ev[j], zv[j], ce[u], cn[u], c, clip, dlim, dl.mean);
                 if (ok[u]) {
                     *reinterpret_cast<float4 *>(p.x_dev + b[u] * D + q[u] * 4) = make_float4(o[0], o[1], o[2], o[3]);
                     if (hist) *reinterpret_cast<float4 *>(hist + b[u] * D + q[u] * 4) = make_float4(o[0], o[1], o[2], o[3]);
@@ -246,21 +222,17 @@ __global__ void __launch_bounds__(256) k_update(dlpm_update_args p) {
                 cn = p.c_noise_dev[(int64_t)t * p.B + b];
             } else {
                 ce = c.bs;
-                cn = (p.dlim_eta != 0.0f && t != 1) ? dl_sig * sqrtf(p.A_dev[(int64_t)t * p.B + b]) : 0.0f;
+                cn = (p.dlim_eta != 0.0f && t != 1) ? dl.sig * sqrtf(p.A_dev[(int64_t)t * p.B + b]) : 0.0f;
             }
             const int64_t idx = b * D + q;
             float xv = p.x_dev[idx], ev = p.eps_dev[idx], zv;
             if (p.z_dev) zv = p.z_dev[idx];
-            else if (cn == 0.0f) zv = 0.0f;
             else {
-                float4 z = philox_normal4(p.seed, (uint64_t)(p.sample_offset + b), (uint32_t)(q >> 2), kPurposeStepZ, (uint32_t)t);
+                const float4 z = step_draw4(StepKey{key0.seed, key0.gidx + (uint64_t)b}, (uint32_t)(q >> 2), t, cn);
                 float zz[4] = {z.x, z.y, z.z, z.w};
                 zv = zz[q & 3];
             }
-            float ee = clip ? clip_eps(xv, ev, c) : ev;
-            float m = __fdiv_rn(xv - __fmul_rn(ce, ee), c.g);
-            if (dlim) m = __fadd_rn(m, __fmul_rn(dl_mean, ee));
-            const float o = __fadd_rn(m, __fmul_rn(cn, zv));
+            const float o = step_exact(xv, ev, zv, ce, cn, c, clip, dlim, dl.mean);
             p.x_dev[idx] = o;
             if (hist) hist[idx] = o;
         }
@@ -268,22 +240,17 @@ __global__ void __launch_bounds__(256) k_update(dlpm_update_args p) {
 }
 
 // Non-isotropic variant (DLPM_UPD_ELEMENTWISE): c_eps / c_noise / A are [T,B,D] and are streamed like x and eps
-// (20 B/element with Philox noise).  Same arithmetic as k_update, element by element.
+// (20 B/element with Philox noise).
 template <bool VEC>
 __global__ void __launch_bounds__(256) k_update_elem(dlpm_update_args p) {
     constexpr int W = VEC ? 4 : 1;
-    if (p.key_dev) { p.seed = p.key_dev[0]; p.sample_offset = (int64_t)p.key_dev[1]; }
+    const StepKey key0 = step_key(p.key_dev, p.seed, p.sample_offset, 0);   // (sample 0: gidx + b below)
     const int t = *p.t_dev;
-    StepScalars c{p.g_dev[t], p.bg_dev[t], p.bs_dev[t], p.bs_dev[t > 0 ? t - 1 : 0]};
+    const StepScalars c = step_scalars(p.g_dev, p.bg_dev, p.bs_dev, t);
     const bool dlim = p.flags & DLPM_UPD_DLIM, clip = p.flags & DLPM_UPD_CLIP;
     const int64_t D = p.D, BD = p.B * D;
-    float dl_mean = c.bs_prev, dl_sig = 0.f;
-    if (dlim && p.dlim_eta != 0.0f) {
-        dl_sig = p.dlim_eta * c.bs_prev;
-        dl_mean = powf(powf(c.bs_prev, p.alpha) - powf(dl_sig, p.alpha), 1.0f / p.alpha);
-    }
-    float *hist = p.hist_pp ? *p.hist_pp : nullptr;
-    if (hist) hist += (int64_t)(p.T - t) * BD;
+    const DlimCoeffs dl = dlim_coeffs(dlim, p.dlim_eta, p.alpha, c.bs_prev);
+    float *hist = history_row(p.hist_pp, p.T, t, p.B, 0, D);
     const float *ce_t = dlim ? nullptr : p.c_eps_dev + (int64_t)t * BD;
     const float *cn_t = dlim ? nullptr : p.c_noise_dev + (int64_t)t * BD;
     const float *a_t = (dlim && p.dlim_eta != 0.0f) ? p.A_dev + (int64_t)t * BD : nullptr;
@@ -313,25 +280,20 @@ __global__ void __launch_bounds__(256) k_update_elem(dlpm_update_args p) {
 #pragma unroll
             for (int j = 0; j < W; j++) {
                 ce[j] = c.bs;
-                cn[j] = (a_t && t != 1) ? dl_sig * sqrtf(cn[j]) : 0.0f;
+                cn[j] = (a_t && t != 1) ? dl.sig * sqrtf(cn[j]) : 0.0f;
             }
         }
         if (!p.z_dev) {
             const bool need = dlim ? (a_t && t != 1) : (t != 1);
-            float4 z = need ? philox_normal4(p.seed, (uint64_t)(p.sample_offset + b), (uint32_t)(e0 >> 2), kPurposeStepZ, (uint32_t)t)
-                            : make_float4(0.f, 0.f, 0.f, 0.f);
+            // (per-element coefficients: the draw is skipped by the step, t == 1 adds no noise, not by a coefficient's value)
+            float4 z = need ? step_philox4(StepKey{key0.seed, key0.gidx + (uint64_t)b}, (uint32_t)(e0 >> 2), t) : make_float4(0.f, 0.f, 0.f, 0.f);
             float zz[4] = {z.x, z.y, z.z, z.w};
 #pragma unroll
             for (int j = 0; j < W; j++) zv[j] = zz[VEC ? j : (int)(e0 & 3)];
         }
         float o[W];
 #pragma unroll
-        for (int j = 0; j < W; j++) {
-            float ee = clip ? clip_eps(xv[j], ev[j], c) : ev[j];
-            float m = __fdiv_rn(xv[j] - __fmul_rn(ce[j], ee), c.g);
-            if (dlim) m = __fadd_rn(m, __fmul_rn(dl_mean, ee));
-            o[j] = __fadd_rn(m, __fmul_rn(cn[j], zv[j]));
-        }
+        for (int j = 0; j < W; j++) o[j] = step_exact(xv[j], ev[j], zv[j], ce[j], cn[j], c, clip, dlim, dl.mean);
         if (VEC) {
             *reinterpret_cast<float4 *>(p.x_dev + off) = *reinterpret_cast<float4 *>(o);
             if (hist) *reinterpret_cast<float4 *>(hist + off) = *reinterpret_cast<float4 *>(o);
@@ -350,17 +312,14 @@ __global__ void __launch_bounds__(256) k_update_elem(dlpm_update_args p) {
 
 __global__ void __launch_bounds__(256) k_update_rows(dlpm_update_args p) {
     const int t = *p.t_dev;
-    const float g = p.g_dev[t], rg = 1.0f / g;
     const int64_t b = blockIdx.x;
-    const float ce = p.c_eps_dev[(int64_t)t * p.B + b], cn = p.c_noise_dev[(int64_t)t * p.B + b];
+    const RowCoeffs c = row_coeffs(p.g_dev, p.c_eps_dev, p.c_noise_dev, t, p.B, b);
     const int nq = (int)(p.D >> 2);
     float *xr = p.x_dev + b * p.D;
     const float *er = p.eps_dev + b * p.D;
     const float *zr = p.z_dev ? p.z_dev + b * p.D : nullptr;
-    const uint64_t seed = p.key_dev ? p.key_dev[0] : p.seed;
-    const uint64_t gidx = (uint64_t)((p.key_dev ? (int64_t)p.key_dev[1] : p.sample_offset) + b);
-    float *hr = p.hist_pp ? *p.hist_pp : nullptr;
-    if (hr) hr += ((int64_t)(p.T - t) * p.B + b) * p.D;
+    const StepKey key = step_key(p.key_dev, p.seed, p.sample_offset, b);
+    float *hr = history_row(p.hist_pp, p.T, t, p.B, b, p.D);
     for (int q0 = threadIdx.x; q0 < nq; q0 += 3 * 256) {
         float4 x[3], e[3], z[3];
         int q[3];
@@ -376,13 +335,8 @@ __global__ void __launch_bounds__(256) k_update_rows(dlpm_update_args p) {
         }
 #pragma unroll
         for (int u = 0; u < 3; u++) {
-            if (!zr) z[u] = (cn != 0.0f) ? philox_normal4(seed, gidx, (uint32_t)q[u], kPurposeStepZ, (uint32_t)t)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 o;
-            o.x = fmaf(cn, z[u].x, div_by(x[u].x - ce * e[u].x, g, rg));
-            o.y = fmaf(cn, z[u].y, div_by(x[u].y - ce * e[u].y, g, rg));
-            o.z = fmaf(cn, z[u].z, div_by(x[u].z - ce * e[u].z, g, rg));
-            o.w = fmaf(cn, z[u].w, div_by(x[u].w - ce * e[u].w, g, rg));
+            if (!zr) z[u] = step_draw4(key, (uint32_t)q[u], t, c.cn);
+            const float4 o = row_update4(x[u], e[u], z[u], c);
             if (ok[u]) {
                 reinterpret_cast<float4 *>(xr)[q[u]] = o;
                 if (hr) reinterpret_cast<float4 *>(hr)[q[u]] = o;
@@ -430,13 +384,11 @@ __global__ void __launch_bounds__(256) k_update_lim(dlpm_lim_update_args p) {
     const int64_t b = blockIdx.x;
     const float sa = p.A_dev ? sqrtf(p.A_dev[(int64_t)i * p.B + b]) : 1.0f;
     const bool clamp = p.A_dev && p.clamp_eps >= 0.0f;
-    const uint64_t seed = p.key_dev ? p.key_dev[0] : p.seed;
-    const uint64_t gidx = (uint64_t)((p.key_dev ? (int64_t)p.key_dev[1] : p.sample_offset) + b);
+    const StepKey key = step_key(p.key_dev, p.seed, p.sample_offset, b);
     float *xr = p.x_dev + b * p.D;
     const float *er = p.eps_dev + b * p.D;
     const float *zr = p.z_dev ? p.z_dev + b * p.D : nullptr;
-    float *hr = p.hist_pp ? *p.hist_pp : nullptr;
-    if (hr) hr += ((int64_t)(p.T - t) * p.B + b) * p.D;
+    float *hr = history_row(p.hist_pp, p.T, t, p.B, b, p.D);
     constexpr int W = VEC ? 4 : 1;
     const int n = (int)(p.D / W);
     for (int q = threadIdx.x; q < n; q += blockDim.x) {
@@ -451,7 +403,7 @@ __global__ void __launch_bounds__(256) k_update_lim(dlpm_lim_update_args p) {
             if (zr) zv[0] = zr[q];
         }
         if (!ode && !zr) {
-            float4 z = philox_normal4(seed, gidx, (uint32_t)(VEC ? q : q >> 2), kPurposeStepZ, (uint32_t)t);
+            float4 z = step_philox4(key, (uint32_t)(VEC ? q : q >> 2), t);
             float zz[4] = {z.x, z.y, z.z, z.w};
 #pragma unroll
             for (int j = 0; j < W; j++) zv[j] = zz[VEC ? j : (q & 3)];

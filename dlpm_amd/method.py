@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .process import DLPM
+from .process import DLPM, clamp_arg
 
 
 class ModelMeanType:
@@ -93,7 +93,7 @@ class ReferenceStreams:
     def skewed_levy(self, alpha, n, clamp_a=None):
         out = np.empty(n, np.float32)
         _lib.check(_lib.lib().dlpm_skewed_levy_host_f32(C.byref(self.N), float(alpha), n,
-                                                       -1.0 if clamp_a is None else float(clamp_a), out.ctypes.data))
+                                                       clamp_arg(clamp_a), out.ctypes.data))
         return torch.from_numpy(out)
 
     def randn(self, shape):
@@ -196,6 +196,21 @@ class GenerativeLevyProcess:
         calls, first = (self._dataset['calls'], self._dataset['next']) if self._dataset else (self.calls, 0)
         return (self.seed + 0x9E3779B97F4A7C15 * calls) & 0xFFFFFFFFFFFFFFFF, self.sample_offset + first
 
+    def _advance_key(self, n):
+        """n samples were drawn under _philox_key(): the dataset stream moves on by n, or the call counter by one."""
+        if self._dataset is not None:
+            self._dataset['next'] += n
+        else:
+            self.calls += 1
+
+    def _takes_native(self, model, model_kwargs, denoised_fn=None):
+        """Whether the native (graph) sampler takes this call: one of the package's nets, scaled timesteps, no Python hook on
+        the x_0 prediction, and model_kwargs it carries."""
+        from .unet import UNetModel
+        from .mlp import MLPModel
+        return isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and \
+            _native_kwargs(model, model_kwargs)
+
     @contextlib.contextmanager
     def dataset_stream(self, first_index=0):
         """Inside this context every sample() call continues ONE Philox stream indexed by the running sample
@@ -255,8 +270,7 @@ class GenerativeLevyProcess:
         cfg.unet, cfg.mlp = handles['unet'], handles['mlp']
         cfg.B, (cfg.C, cfg.H, cfg.W), cfg.T = B, dims, self.reverse_steps + (1 if lim else 0)
         cfg.alpha = float(self.alpha)
-        cfg.clamp_a = -1.0 if clamp_a is None else float(clamp_a)
-        cfg.clamp_eps = -1.0 if clamp_eps is None else float(clamp_eps)
+        cfg.clamp_a, cfg.clamp_eps = clamp_arg(clamp_a), clamp_arg(clamp_eps)
         cfg.flags = flags | (0 if self.fused_mlp else _lib.SMP_NO_FUSED_MLP)
         cfg.dlim_eta, cfg.seed = float(eta), seed
         cfg.mean_type = _lib.MEAN_TYPES[self.model_mean_type]
@@ -348,10 +362,7 @@ class GenerativeLevyProcess:
         hist = torch.empty([T] + list(shape), dtype=torch.float32, device=dev) if history else None
         _lib.check(L.dlpm_sampler_set_history(h, hist.data_ptr() if history else None, st))
 
-        pbar = None
-        if progress:
-            from tqdm import tqdm
-            pbar = tqdm(total=T)
+        pbar = _progress_bar(progress, T)
         if lim and self.rng == 'reference':
             # stream N interleaves with the model calls in the reference but is independent of stream P, so all the
             # per-step a's can be drawn up front
@@ -399,86 +410,45 @@ class GenerativeLevyProcess:
         Also the loop for a `denoised_fn` (a Python function applied to the x_0 prediction, p_mean_variance :162-167)."""
         model_kwargs = model_kwargs or {}
         L, st = _lib.lib(), _lib.stream_ptr()
+        d = self.dlpm
         T, B = self.reverse_steps, shape[0]
         D = int(np.prod(shape[1:]))
         dev = torch.device(self.device)
         seed, offset = self._philox_key()
-        g, bg, s, bs = (v.to(dev) for v in self.dlpm.host_schedule)
-        ca = -1.0 if clamp_a is None else float(clamp_a)
-        ce = -1.0 if clamp_eps is None else float(clamp_eps)
+        g, bg, s, bs = (v.to(dev) for v in d.host_schedule)
         host = self.rng == 'reference' or noise is not None
         if host:
             A, xT = self._host_noise_prologue(shape, clamp_a, clamp_eps, noise)
             A, x = A.to(dev), xT.to(dev).reshape(shape).contiguous()
-        elif self.isotropic:
-            A = torch.empty((T, B), dtype=torch.float32, device=dev)
-            x = torch.empty(shape, dtype=torch.float32, device=dev)
-            _lib.check(L.dlpm_skewed_levy_philox_f32(A.data_ptr(), T, B, float(self.alpha), ca, seed, offset, st))
-            _lib.check(L.dlpm_init_state_philox_f32(x.data_ptr(), B, D, float(self.alpha), ce,
-                                                   float(self.dlpm.host_schedule[3][-1]), seed, offset, st))
         else:
-            A = torch.empty((T, B * D), dtype=torch.float32, device=dev)
-            x = torch.empty(shape, dtype=torch.float32, device=dev)
-            _lib.check(L.dlpm_skewed_levy_elem_philox_f32(A.data_ptr(), T, B, D, float(self.alpha), ca, seed, offset, st))
-            _lib.check(L.dlpm_init_state_elem_philox_f32(x.data_ptr(), B, D, float(self.alpha), ce,
-                                                        float(self.dlpm.host_schedule[3][-1]), seed, offset, st))
-        if not self.isotropic:
-            flags |= _lib.UPD_ELEMENTWISE
+            # the loop's own tables: dlpm.A / dlpm.Sigmas stay what the caller's step methods hold
+            A = d._draw_A(T, shape, clamp_a, seed, offset)
+            x = d._draw_state(shape, clamp_eps, d.host_schedule[3][-1], seed, offset)
         c_eps, c_noise = torch.empty_like(A), torch.empty_like(A)
         _lib.check(L.dlpm_coeff_tables_f32(A.data_ptr(), g.data_ptr(), s.data_ptr(), bs.data_ptr(), T, A.shape[1],
                                           c_eps.data_ptr(), c_noise.data_ptr(), None, st))
+        tab = dict(g=g, bg=bg, bs=bs, c_eps=c_eps, c_noise=c_noise, A=A)
         t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         tvec = torch.empty(B, dtype=torch.float32, device=dev)
         isc = self._input_scale()
         isc = None if isc is None else isc.to(dev)
         hist = [x.clone()] if history else []
         need_z = not (flags & _lib.UPD_DLIM) or eta != 0.0
-        # p_mean_variance (:182-207): EPSILON without clipping bypasses everything (a denoised_fn is then never called, as in
-        # the reference); EPSILON + clip without a denoised_fn is a flag of the update kernel; every other case goes
-        # model output -> x_0 -> [denoised_fn] -> [clamp] -> eps through dlpm_predict_f32
         clip = bool(flags & _lib.UPD_CLIP)
-        mean_type = _lib.MEAN_TYPES[self.model_mean_type]
-        predict = (mean_type != 0) or (clip and denoised_fn is not None)
-        pa = None
-        if predict:
-            flags &= ~_lib.UPD_CLIP
-            pa = _lib.PredictArgs()
-            pa.t_dev, pa.g_dev, pa.bg_dev, pa.bs_dev = t_dev.data_ptr(), g.data_ptr(), bg.data_ptr(), bs.data_ptr()
-            pa.c_eps_dev, pa.A_dev = c_eps.data_ptr(), A.data_ptr()
-            pa.B, pa.D, pa.T, pa.mean_type = B, D, T, mean_type
-            el = _lib.PRED_ELEMENTWISE if not self.isotropic else 0
-            tail = (_lib.PRED_CLIP if clip else 0) | _lib.PRED_TO_EPS | el
-        args = _lib.UpdateArgs()
-        args.t_dev, args.g_dev, args.bg_dev, args.bs_dev = t_dev.data_ptr(), g.data_ptr(), bg.data_ptr(), bs.data_ptr()
-        args.c_eps_dev, args.c_noise_dev, args.A_dev = c_eps.data_ptr(), c_noise.data_ptr(), A.data_ptr()
-        args.B, args.D, args.T, args.flags, args.dlim_eta, args.alpha = B, D, T, flags, float(eta), float(self.alpha)
-        args.seed, args.sample_offset = seed, offset
-        pbar = None
-        if progress:
-            from tqdm import tqdm
-            pbar = tqdm(total=T)
+        flags = (flags & ~_lib.UPD_CLIP) | (0 if self.isotropic else _lib.UPD_ELEMENTWISE)
+        args = self._update_args(tab, t_dev, B, D, flags, eta, seed, offset)
+        pbar = _progress_bar(progress, T)
         for i in range(T - 1, 0, -1):
             t_dev.fill_(i)
             _lib.check(L.dlpm_fill_scaled_t_f32(tvec.data_ptr(), t_dev.data_ptr(), T, B, st))
             xin = x if isc is None else x * isc[i]
-            eps = model(xin, tvec if self.rescale_timesteps else torch.full((B,), i, device=dev), **model_kwargs)
-            eps = eps.contiguous().float()
-            if predict:
-                pa.x_dev, pa.in_dev, pa.out_dev = x.data_ptr(), eps.data_ptr(), eps.data_ptr()
-                if denoised_fn is None:
-                    pa.flags = _lib.PRED_TO_XSTART | tail
-                    _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
-                else:
-                    pa.flags = _lib.PRED_TO_XSTART | el
-                    _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
-                    eps = denoised_fn(eps.view(shape)).contiguous().float()
-                    pa.in_dev, pa.out_dev, pa.flags = eps.data_ptr(), eps.data_ptr(), tail
-                    _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+            out = model(xin, tvec if self.rescale_timesteps else torch.full((B,), i, device=dev), **model_kwargs)
+            eps, clip_flag = self._eps_of_output(out, x, t_dev, tab, clip, denoised_fn, fold_clip=True)
             z = None
             if host and need_z:
                 z = (self._streams().randn(shape) if self.rng == 'reference' else torch.randn(shape)).to(dev)
-            args.x_dev, args.eps_dev = x.data_ptr(), eps.data_ptr()
-            args.z_dev = z.data_ptr() if z is not None else None
+            args.x_dev, args.eps_dev, args.z_dev = x.data_ptr(), eps.data_ptr(), _lib.ptr(z)
+            args.flags = flags | clip_flag
             _lib.check(L.dlpm_update_f32(C.byref(args), st))
             if history:
                 hist.append(x.clone())
@@ -499,7 +469,6 @@ class GenerativeLevyProcess:
         ode = bool(flags & _lib.UPD_DLIM)
         seed, offset = self._philox_key()
         ts, tmp, cx, cs, cn = (v.to(dev) for v in lim_tables(self.sde, steps, ode))
-        ce = -1.0 if clamp_eps is None else float(clamp_eps)
         host = self.rng == 'reference'
         gauss = self.alpha == 2.0
         A = None
@@ -509,22 +478,17 @@ class GenerativeLevyProcess:
             if not (ode or gauss):
                 A = torch.stack([self._streams().skewed_levy(self.alpha, B, None) for _ in range(steps)]).contiguous().to(dev)
         else:
-            x = torch.empty(shape, dtype=torch.float32, device=dev)
-            _lib.check(L.dlpm_init_state_philox_f32(x.data_ptr(), B, D, float(self.alpha), ce, 1.0, seed, offset, st))
+            x = self.dlpm._draw_state(shape, clamp_eps, 1.0, seed, offset)
             if not (ode or gauss):
-                A = torch.empty((steps, B), dtype=torch.float32, device=dev)
-                _lib.check(L.dlpm_skewed_levy_philox_f32(A.data_ptr(), steps, B, float(self.alpha), -1.0, seed, offset, st))
+                A = self.dlpm._draw_A(steps, shape, None, seed, offset)      # (unclamped; LIM is isotropic: [steps,B])
         t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         a = _lib.LimUpdateArgs()
         a.t_dev, a.tmp_dev, a.cx_dev, a.cs_dev, a.cn_dev = t_dev.data_ptr(), tmp.data_ptr(), cx.data_ptr(), cs.data_ptr(), cn.data_ptr()
         a.A_dev = A.data_ptr() if A is not None else None
-        a.B, a.D, a.T, a.flags, a.clamp_eps = B, D, T, (_lib.UPD_DLIM if ode else 0), ce
+        a.B, a.D, a.T, a.flags, a.clamp_eps = B, D, T, (_lib.UPD_DLIM if ode else 0), clamp_arg(clamp_eps)
         a.seed, a.sample_offset = seed, offset
         hist = [x.clone()] if history else []
-        pbar = None
-        if progress:
-            from tqdm import tqdm
-            pbar = tqdm(total=steps)
+        pbar = _progress_bar(progress, steps)
         for i in range(steps):
             t_dev.fill_(T - 1 - i)
             eps = model(x, torch.ones(B, device=dev) * ts[i]).contiguous().float()      # sampler.py:233
@@ -540,25 +504,18 @@ class GenerativeLevyProcess:
         return (x, torch.stack(hist)) if history else x
 
     def _loop(self, model, shape, flags, eta, noise, denoised_fn, model_kwargs, history, progress):
-        from .unet import UNetModel
-        from .mlp import MLPModel
         if hasattr(model, 'eval'):
             model.eval()
         clamp_a = self.dlpm.gen_a.kwargs.get('clamp_a')
         clamp_eps = self.dlpm.gen_eps.kwargs.get('clamp_eps')
-        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and \
-            _native_kwargs(model, model_kwargs)
         with torch.inference_mode():
-            if native:
+            if self._takes_native(model, model_kwargs, denoised_fn):
                 out = self._run_native(model, list(shape), flags, eta, clamp_a, clamp_eps, noise, history, progress,
                                        labels=(model_kwargs or {}).get('y'))
             else:
                 out = self._run_callable(model, list(shape), flags, eta, clamp_a, clamp_eps, noise, history, progress,
                                          denoised_fn=denoised_fn, model_kwargs=model_kwargs)
-        if self._dataset is not None:
-            self._dataset['next'] += shape[0]
-        else:
-            self.calls += 1
+        self._advance_key(shape[0])
         return out
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=False, denoised_fn=None, model_kwargs=None, progress=False,
@@ -579,11 +536,55 @@ class GenerativeLevyProcess:
                           model_kwargs, get_sample_history, progress)
 
     # -------------------------------------------------------------------------------- one step at a time
+    def _eps_of_output(self, out, x, t_dev, tab, clip, denoised_fn, fold_clip):
+        """What p_mean_variance does to the model's output (GenerativeLevyProcess.py:182-207), for the loop of _run_callable and
+        the step methods alike: EPSILON without clipping bypasses everything (a denoised_fn is then never called, as in the
+        reference); `fold_clip` leaves "EPSILON + clip, no denoised_fn" to the update kernel's own flag; every other case goes
+        model output -> x_0 -> [denoised_fn] -> [clamp] -> eps through dlpm_predict_f32.  `tab`: the trajectory's tables (see
+        _tables).  Returns (eps, UPD_CLIP where the update kernel still has to clip, else 0)."""
+        eps = out.contiguous().float()
+        mean_type = _lib.MEAN_TYPES[self.model_mean_type]
+        predict = (mean_type != 0) or (clip and (denoised_fn is not None or not fold_clip))
+        if not predict:
+            return eps, (_lib.UPD_CLIP if clip else 0)
+        if eps.data_ptr() == x.data_ptr():          # a model that returns its input: the conversion below writes in place
+            eps = eps.clone()
+        L, st = _lib.lib(), _lib.stream_ptr()
+        pa = _lib.PredictArgs()
+        pa.t_dev, pa.g_dev, pa.bg_dev, pa.bs_dev = t_dev.data_ptr(), _lib.ptr(tab['g']), _lib.ptr(tab['bg']), _lib.ptr(tab['bs'])
+        pa.c_eps_dev, pa.A_dev = tab['c_eps'].data_ptr(), tab['A'].data_ptr()
+        pa.B, pa.D, pa.T, pa.mean_type = x.shape[0], x[0].numel(), self.reverse_steps, mean_type
+        el = _lib.PRED_ELEMENTWISE if not self.isotropic else 0
+        tail = (_lib.PRED_CLIP if clip else 0) | _lib.PRED_TO_EPS | el
+        pa.x_dev, pa.in_dev, pa.out_dev = x.data_ptr(), eps.data_ptr(), eps.data_ptr()
+        if denoised_fn is None:
+            pa.flags = _lib.PRED_TO_XSTART | tail
+            _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+        else:
+            pa.flags = _lib.PRED_TO_XSTART | el
+            _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+            eps = denoised_fn(eps.view(x.shape)).contiguous().float()
+            pa.in_dev, pa.out_dev, pa.flags = eps.data_ptr(), eps.data_ptr(), tail
+            _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
+        return eps, 0
+
+    def _update_args(self, tab, t_dev, B, D, flags, eta, seed, offset):
+        """dlpm_update_args of one trajectory (tables `tab`, Philox key); the caller sets x_dev / eps_dev / z_dev per step."""
+        a = _lib.UpdateArgs()
+        a.t_dev, a.g_dev, a.bg_dev, a.bs_dev = t_dev.data_ptr(), _lib.ptr(tab['g']), _lib.ptr(tab['bg']), _lib.ptr(tab['bs'])
+        a.c_eps_dev, a.c_noise_dev, a.A_dev = tab['c_eps'].data_ptr(), tab['c_noise'].data_ptr(), tab['A'].data_ptr()
+        a.B, a.D, a.T, a.flags, a.dlim_eta, a.alpha = B, D, self.reverse_steps, flags, float(eta), float(self.alpha)
+        a.seed, a.sample_offset = seed, offset
+        return a
+
+    def _tables(self):
+        """The tables the step methods read: the process's schedule and the A / coefficient tables of its current trajectory."""
+        d = self.dlpm
+        return dict(g=d.gammas, bg=d.bargammas, bs=d.barsigmas, c_eps=d._c_eps, c_noise=d._c_noise, A=d._A)
+
     def _step_eps(self, model, x, t, clip, denoised_fn, model_kwargs, fold_clip):
-        """The model call and what p_mean_variance does to its output (GenerativeLevyProcess.py:170-207), exactly as the loop of
-        _run_callable does it: EPSILON without clipping bypasses everything, every other case goes model output -> x_0 ->
-        [denoised_fn] -> [clamp] -> eps through dlpm_predict_f32.  `fold_clip`: leave "EPSILON + clip, no denoised_fn" to the update
-        kernel's own flag, as the loop does.  Returns (x as contiguous fp32, eps, the int32 [1] device timestep, update flags)."""
+        """The model call of a step method and the eps of its output (_eps_of_output) on the process's own tables.  Returns (x as
+        contiguous fp32, eps, the int32 [1] device timestep, update flags)."""
         d = self.dlpm
         if not (torch.is_tensor(x) and x.is_cuda):
             raise _lib.DlpmError('the step methods run on the MI355X only (x is on {}); there is no CPU fallback'.format(
@@ -596,40 +597,15 @@ class GenerativeLevyProcess:
             raise _lib.DlpmError('the step methods need the tables of a trajectory of shape {}: iterate p_sample_loop_progressive / '
                                  'ddim_sample_loop_progressive, or call dlpm.sample_A(shape, reverse_steps) and '
                                  'dlpm.compute_Sigmas()'.format(tuple(x.shape)))
-        L, st = _lib.lib(), _lib.stream_ptr()
         x = x.contiguous().float()
         t = t.to(x.device)
         t_dev = d._t_scalar(x, t)
         isc = self._input_scale_dev()
         xin = x if isc is None else x * isc[t.long()].view(-1, *([1] * (x.dim() - 1)))
-        eps = model(xin, self._scale_timesteps(t), **(model_kwargs or {}))
-        eps = eps.contiguous().float()
-        assert eps.shape == x.shape, 'the model returned {}, expected {}'.format(tuple(eps.shape), tuple(x.shape))
-        mean_type = _lib.MEAN_TYPES[self.model_mean_type]
-        flags = 0 if self.isotropic else _lib.UPD_ELEMENTWISE
-        predict = (mean_type != 0) or (clip and (denoised_fn is not None or not fold_clip))
-        if clip and not predict:
-            flags |= _lib.UPD_CLIP
-        if predict:
-            if eps.data_ptr() == x.data_ptr():          # a model that returns its input: the conversion below writes in place
-                eps = eps.clone()
-            pa = _lib.PredictArgs()
-            pa.t_dev, pa.g_dev, pa.bg_dev, pa.bs_dev = t_dev.data_ptr(), _lib.ptr(d.gammas), _lib.ptr(d.bargammas), _lib.ptr(d.barsigmas)
-            pa.c_eps_dev, pa.A_dev = d._c_eps.data_ptr(), d._A.data_ptr()
-            pa.B, pa.D, pa.T, pa.mean_type = B, D, T, mean_type
-            el = _lib.PRED_ELEMENTWISE if not self.isotropic else 0
-            tail = (_lib.PRED_CLIP if clip else 0) | _lib.PRED_TO_EPS | el
-            pa.x_dev, pa.in_dev, pa.out_dev = x.data_ptr(), eps.data_ptr(), eps.data_ptr()
-            if denoised_fn is None:
-                pa.flags = _lib.PRED_TO_XSTART | tail
-                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
-            else:
-                pa.flags = _lib.PRED_TO_XSTART | el
-                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
-                eps = denoised_fn(eps.view(x.shape)).contiguous().float()
-                pa.in_dev, pa.out_dev, pa.flags = eps.data_ptr(), eps.data_ptr(), tail
-                _lib.check(L.dlpm_predict_f32(C.byref(pa), st))
-        return x, eps, t_dev, flags
+        out = model(xin, self._scale_timesteps(t), **(model_kwargs or {}))
+        assert out.shape == x.shape, 'the model returned {}, expected {}'.format(tuple(out.shape), tuple(x.shape))
+        eps, clip_flag = self._eps_of_output(out, x, t_dev, self._tables(), clip, denoised_fn, fold_clip)
+        return x, eps, t_dev, clip_flag | (0 if self.isotropic else _lib.UPD_ELEMENTWISE)
 
     def p_mean_variance(self, model, x, t, clip_denoised=False, denoised_fn=None, model_kwargs=None):
         """GenerativeLevyProcess.p_mean_variance (:154-219): {'eps', 'mean', 'variance'} of p(x_{t-1} | x_t).  The model is called
@@ -645,7 +621,6 @@ class GenerativeLevyProcess:
 
     def _step(self, model, x, t, clip, denoised_fn, model_kwargs, dlim, eta, noise):
         """One reverse step as the loops take it: the eps of _step_eps, then ONE dlpm_update_f32 on a copy of x."""
-        d = self.dlpm
         with torch.no_grad():
             x, eps, t_dev, flags = self._step_eps(model, x, t, clip, denoised_fn, model_kwargs, fold_clip=True)
             need_z = (not dlim) or eta != 0.0
@@ -657,13 +632,9 @@ class GenerativeLevyProcess:
                 z = self._streams().randn(x.shape).to(x.device)
             seed, offset = self._traj if self._traj is not None else self._philox_key()
             out = x.clone()
-            a = _lib.UpdateArgs()
-            a.x_dev, a.eps_dev, a.z_dev, a.t_dev = out.data_ptr(), eps.data_ptr(), _lib.ptr(z), t_dev.data_ptr()
-            a.g_dev, a.bg_dev, a.bs_dev = _lib.ptr(d.gammas), _lib.ptr(d.bargammas), _lib.ptr(d.barsigmas)
-            a.c_eps_dev, a.c_noise_dev, a.A_dev = d._c_eps.data_ptr(), d._c_noise.data_ptr(), d._A.data_ptr()
-            a.B, a.D, a.T = x.shape[0], x[0].numel(), self.reverse_steps
-            a.flags, a.dlim_eta, a.alpha = flags | (_lib.UPD_DLIM if dlim else 0), float(eta), float(self.alpha)
-            a.seed, a.sample_offset = seed, offset
+            a = self._update_args(self._tables(), t_dev, x.shape[0], x[0].numel(), flags | (_lib.UPD_DLIM if dlim else 0), eta,
+                                  seed, offset)
+            a.x_dev, a.eps_dev, a.z_dev = out.data_ptr(), eps.data_ptr(), _lib.ptr(z)
             _lib.check(_lib.lib().dlpm_update_f32(C.byref(a), _lib.stream_ptr()))
         return {'sample': out}
 
@@ -697,8 +668,6 @@ class GenerativeLevyProcess:
 
         A native net (UNetModel / MLPModel) with isotropic noise, device draws and no denoised_fn runs on the graph sampler: one
         replay and one device copy per yield.  Everything else is the loop over p_sample / ddim_sample."""
-        from .unet import UNetModel
-        from .mlp import MLPModel
         assert self.device is not None
         assert isinstance(shape, (tuple, list))
         shape = [int(v) for v in shape]
@@ -710,14 +679,10 @@ class GenerativeLevyProcess:
             raise _lib.DlpmError('the progressive loops run on the MI355X only (device is {}); there is no CPU fallback'.format(dev))
         clamp_a, clamp_eps = d.gen_a.kwargs.get('clamp_a'), d.gen_eps.kwargs.get('clamp_eps')
         dlim = bool(flags & _lib.UPD_DLIM)
-        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and denoised_fn is None and \
-            _native_kwargs(model, model_kwargs) and self.isotropic and self.rng == 'philox' and noise is None
+        native = self._takes_native(model, model_kwargs, denoised_fn) and self.isotropic and self.rng == 'philox' and noise is None
         seed, offset = self._philox_key()
         self._traj = (seed, offset)
-        if self._dataset is not None:
-            self._dataset['next'] += shape[0]
-        else:
-            self.calls += 1
+        self._advance_key(shape[0])
         L, st = _lib.lib(), _lib.stream_ptr()
         if self.rng == 'reference' or noise is not None:
             with torch.no_grad():
@@ -751,11 +716,7 @@ class GenerativeLevyProcess:
                 yield {'sample': x}
             return
         if x is None:
-            x = torch.empty(shape, dtype=torch.float32, device=dev)
-            ce = -1.0 if clamp_eps is None else float(clamp_eps)
-            fn = L.dlpm_init_state_philox_f32 if self.isotropic else L.dlpm_init_state_elem_philox_f32
-            _lib.check(fn(x.data_ptr(), shape[0], int(np.prod(shape[1:])), float(self.alpha), ce,
-                          float(d.host_schedule[3][-1]), seed, offset, st))
+            x = d._draw_state(shape, clamp_eps, d.host_schedule[3][-1], seed, offset)
         yield {'sample': x}
         for i in range(T - 1, 0, -1):
             t = torch.full((shape[0],), i, dtype=torch.int64, device=dev)
@@ -796,10 +757,7 @@ class GenerativeLevyProcess:
             model.eval()
         with torch.inference_mode():
             out = self._lim_run(model, list(shape), ddim, get_sample_history, False, self.dlpm.gen_eps.kwargs.get('clamp_eps'))
-        if self._dataset is not None:
-            self._dataset['next'] += shape[0]
-        else:
-            self.calls += 1
+        self._advance_key(shape[0])
         return out
 
     # -------------------------------------------------------------------------------- BEM: SAMPLING
@@ -808,8 +766,6 @@ class GenerativeLevyProcess:
                clamp_eps=None, model_kwargs=None):
         """GenerativeLevyProcess.sample: dlpm/methods/GenerativeLevyProcess.py:512-569.  `model_kwargs` (this build's addition, passed on
         to the model as the reference's loops do, :601): {'y': labels} for a class-conditional UNetModel."""
-        from .unet import UNetModel
-        from .mlp import MLPModel
         self.dlpm.gen_a.setParams(clamp_a=clamp_a)          # stateful, as in the reference (:526-527)
         self.dlpm.gen_eps.setParams(clamp_eps=clamp_eps)
         model = models['default']
@@ -825,7 +781,7 @@ class GenerativeLevyProcess:
         noise = initial_data if deterministic else None
         flags = (_lib.UPD_DLIM if deterministic else 0) | (_lib.UPD_CLIP if clip_denoised else 0)
         eta = dlim_eta if deterministic else 0.0
-        native = isinstance(model, (UNetModel, MLPModel)) and self.rescale_timesteps and _native_kwargs(model, model_kwargs)
+        native = self._takes_native(model, model_kwargs)
         labels = (model_kwargs or {}).get('y')
         with torch.inference_mode():
             if self.LIM and (model_kwargs or getattr(model, 'num_classes', None) is not None):
@@ -841,10 +797,7 @@ class GenerativeLevyProcess:
             else:
                 out = self._run_callable(model, shape, flags, eta, clamp_a, clamp_eps, noise, get_sample_history, print_progression,
                                          model_kwargs=model_kwargs)
-        if self._dataset is not None:
-            self._dataset['next'] += shape[0]
-        else:
-            self.calls += 1
+        self._advance_key(shape[0])
         return out
 
     # -------------------------------------------------------------------------------- BEM: held-out loss
@@ -921,7 +874,7 @@ class GenerativeLevyProcess:
         a.tvec_out_dev, a.t_out_dev, a.a_out_dev = tvec.data_ptr(), t_out.data_ptr(), None
         a.B, a.D, a.T, a.outer, a.inner = B, D, T, outer, inner
         a.flags = (_lib.LOSS_RESCALE_T if self.rescale_timesteps else 0) | (0 if self.isotropic else _lib.LOSS_ELEMENTWISE)
-        a.alpha, a.clamp_a = float(self.alpha), -1.0 if clamp_a is None else float(clamp_a)
+        a.alpha, a.clamp_a = float(self.alpha), clamp_arg(clamp_a)
         a.seed, a.sample_offset = seed, offset
         _lib.check(L.dlpm_loss_elements_f32(C.byref(a), st))
 
@@ -942,10 +895,7 @@ class GenerativeLevyProcess:
             out, out_stride = torch.empty(R * B, dtype=torch.float32, device=dev), B
         _lib.check(L.dlpm_loss_terms_f32(model_eps.data_ptr(), eps_t.data_ptr(), out.data_ptr(), B, R, D, int(lploss), out_stride,
                                          out_offset, st))
-        if self._dataset is not None:
-            self._dataset['next'] += B
-        else:
-            self.calls += 1
+        self._advance_key(B)
         res = {'losses': out, 't': t_out}
         if keep:
             res.update(x_t=x_t, eps_t=eps_t, x_in=x_in, model_eps=model_eps, tvec=tvec)
@@ -1110,7 +1060,7 @@ class GenerativeLevyProcess:
         a.a_out_dev, a.e_out_dev = _lib.ptr(kept.get('a')), _lib.ptr(kept.get('e'))
         a.x_coeff_out_dev, a.sigma_out_dev = _lib.ptr(kept.get('x_coeff')), _lib.ptr(kept.get('sigma'))
         a.B, a.D, a.alpha, a.t_max = B, D, float(self.alpha), float(self.sde.T)
-        a.clamp_eps = -1.0 if clamp_eps is None else float(clamp_eps)
+        a.clamp_eps = clamp_arg(clamp_eps)
         a.seed, a.sample_offset = seed, offset
         _lib.check(L.dlpm_lim_loss_elements_f32(C.byref(a), st))
 
@@ -1127,10 +1077,7 @@ class GenerativeLevyProcess:
         # F.smooth_l1_loss(output, score, beta=1, reduction='mean') (loss.py:39) is the mean of the per-sample means: every row has D
         # elements
         _lib.check(L.dlpm_loss_terms_f32(output.data_ptr(), score.data_ptr(), out.data_ptr(), B, 1, D, 1, out.numel(), out_offset, st))
-        if self._dataset is not None:
-            self._dataset['next'] += B
-        else:
-            self.calls += 1
+        self._advance_key(B)
         res = {'losses': out, 't': t_out}
         if keep:
             res.update(kept, x_t=x_t, score=score, output=output)
@@ -1197,6 +1144,14 @@ class GenerativeLevyProcess:
         assert 'model_kwargs' not in kwargs and 'return_terms' not in kwargs
         loss, losses, t = self.training_losses_dlpm(model, x_start, model_kwargs=mk, return_terms=True, **kwargs)
         return {'loss': loss, 'losses': losses, 't': t}
+
+
+def _progress_bar(progress, total):
+    """A tqdm bar of `total` steps, or None when no progress display is asked for."""
+    if not progress:
+        return None
+    from tqdm import tqdm
+    return tqdm(total=total)
 
 
 def _native_kwargs(model, model_kwargs):

@@ -24,6 +24,11 @@ import torch
 from . import _lib
 
 
+def clamp_arg(clamp):
+    """A clamp as libdlpm_amd takes it: the bound, or -1.0 for None (no clamping)."""
+    return -1.0 if clamp is None else float(clamp)
+
+
 class NoiseParams:
     """The kwargs store of bem.datasets.Data.Generator (setParams mutates defaults: Data.py:60-65)."""
 
@@ -172,12 +177,7 @@ class DLPM:
         an unclamped skewed-Levy a per sample (per element when non-isotropic) -- from the device Philox stream (seed, sample_offset)."""
         if eps is None:
             self._t_dev(xstart, 0)
-            B = xstart.shape[0]
-            eps = torch.empty(xstart.shape, dtype=torch.float32, device=xstart.device)
-            ce = self.gen_eps.kwargs.get('clamp_eps')
-            fn = _lib.lib().dlpm_init_state_philox_f32 if self.isotropic else _lib.lib().dlpm_init_state_elem_philox_f32
-            _lib.check(fn(eps.data_ptr(), B, eps.numel() // B, float(self.alpha), -1.0 if ce is None else float(ce), 1.0, seed,
-                          sample_offset, _lib.stream_ptr()))
+            eps = self._draw_state(xstart.shape, self.gen_eps.kwargs.get('clamp_eps'), 1.0, seed, sample_offset, device=xstart.device)
         return self._at_t(_lib.AT_T_Q_SAMPLE, xstart, eps, t), eps
 
     def get_one_rv_loss_elements(self, t, x_0, a_t=None, z_t=None, seed=0, sample_offset=0):
@@ -196,14 +196,13 @@ class DLPM:
         if z_t is not None:
             z_t = z_t.to(x0.device, torch.float32).contiguous()
             assert z_t.shape == x0.shape
-        ca = self.gen_a.kwargs.get('clamp_a')
         a = _lib.LossArgs()
         a.x0_dev, a.t_dev, a.a_dev, a.z_dev = x0.data_ptr(), t.data_ptr(), _lib.ptr(a_t), _lib.ptr(z_t)
         a.bg_dev, a.bs_dev = _lib.ptr(self.bargammas), _lib.ptr(self.barsigmas)
         a.x_in_dev, a.eps_dev, a.x_t_dev = x_in.data_ptr(), eps_t.data_ptr(), x_t.data_ptr()
         a.B, a.D, a.T, a.outer, a.inner = B, D, self.diffusion_steps, 1, 1
         a.flags = 0 if self.isotropic else _lib.LOSS_ELEMENTWISE
-        a.alpha, a.clamp_a, a.seed, a.sample_offset = float(self.alpha), -1.0 if ca is None else float(ca), seed, sample_offset
+        a.alpha, a.clamp_a, a.seed, a.sample_offset = float(self.alpha), clamp_arg(self.gen_a.kwargs.get('clamp_a')), seed, sample_offset
         _lib.check(_lib.lib().dlpm_loss_elements_f32(C.byref(a), _lib.stream_ptr()))
         return x_t, eps_t
 
@@ -220,6 +219,29 @@ class DLPM:
         """(B, D, n): n table entries per timestep for samples of this shape."""
         B, D = int(shape[0]), int(np.prod(shape[1:]))
         return B, D, (B if self.isotropic else B * D)
+
+    def _draw_A(self, T, shape, clamp_a, seed, sample_offset):
+        """A table of T rows for this shape: [T,n] skewed-Levy draws, one per (row, sample) -- per (row, element) when
+        non-isotropic -- clamped at clamp_a (None: not at all), from the device Philox stream (seed, sample_offset)."""
+        B, D, n = self._cols(shape)
+        A = torch.empty((T, n), dtype=torch.float32, device=self.device)
+        L, dims = _lib.lib(), ((B,) if self.isotropic else (B, D))
+        fn = L.dlpm_skewed_levy_philox_f32 if self.isotropic else L.dlpm_skewed_levy_elem_philox_f32
+        with torch.cuda.device(A.device):
+            _lib.check(fn(A.data_ptr(), T, *dims, float(self.alpha), clamp_arg(clamp_a), seed, sample_offset, _lib.stream_ptr()))
+        return A
+
+    def _draw_state(self, shape, clamp_eps, scale, seed, sample_offset, device=None):
+        """Noise state for this shape: scale * clamp(sqrt(a) z, clamp_eps) with an unclamped skewed-Levy a per sample (per element
+        when non-isotropic), gen_eps's draw, from the device Philox stream (seed, sample_offset)."""
+        B, D, n = self._cols(shape)
+        x = torch.empty(tuple(shape), dtype=torch.float32, device=self.device if device is None else device)
+        L = _lib.lib()
+        fn = L.dlpm_init_state_philox_f32 if self.isotropic else L.dlpm_init_state_elem_philox_f32
+        with torch.cuda.device(x.device):
+            _lib.check(fn(x.data_ptr(), B, D, float(self.alpha), clamp_arg(clamp_eps), float(scale), seed, sample_offset,
+                          _lib.stream_ptr()))
+        return x
 
     def _as_table(self, v, shape):
         """A caller's [T,B], [T,n] or (expanded) [T, *shape] table as the contiguous fp32 [T,n] the kernels read."""
@@ -266,22 +288,12 @@ class DLPM:
         as given ([T,B], or the reference's [T, *shape])."""
         self._need_gpu()
         shape = tuple(int(v) for v in shape)
-        B, D, n = self._cols(shape)
         T = int(diffusion_steps)
         if A is not None:
             A = self._as_table(A, shape)
             assert A.shape[0] == T, 'A holds {} timesteps, diffusion_steps is {}'.format(A.shape[0], T)
         else:
-            ca = self.gen_a.kwargs.get('clamp_a')
-            ca = -1.0 if ca is None else float(ca)
-            A = torch.empty((T, n), dtype=torch.float32, device=self.device)
-            with torch.cuda.device(A.device):
-                if self.isotropic:
-                    _lib.check(_lib.lib().dlpm_skewed_levy_philox_f32(A.data_ptr(), T, B, float(self.alpha), ca, seed, sample_offset,
-                                                                      _lib.stream_ptr()))
-                else:
-                    _lib.check(_lib.lib().dlpm_skewed_levy_elem_philox_f32(A.data_ptr(), T, B, D, float(self.alpha), ca, seed,
-                                                                           sample_offset, _lib.stream_ptr()))
+            A = self._draw_A(T, shape, self.gen_a.kwargs.get('clamp_a'), seed, sample_offset)
         self._A, self._table_shape = A, shape
         self._Sigmas = self._c_eps = self._c_noise = None
 
@@ -436,17 +448,7 @@ class DLPM:
         expanded to `shape`, from the device Philox stream (seed, sample_offset)."""
         self._need_gpu()
         shape = tuple(int(v) for v in shape)
-        B, D, n = self._cols(shape)
-        ca = self.gen_a.kwargs.get('clamp_a')
-        ca = -1.0 if ca is None else float(ca)
-        a = torch.empty((1, n), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(a.device):
-            if self.isotropic:
-                _lib.check(_lib.lib().dlpm_skewed_levy_philox_f32(a.data_ptr(), 1, B, float(self.alpha), ca, seed, sample_offset,
-                                                                  _lib.stream_ptr()))
-            else:
-                _lib.check(_lib.lib().dlpm_skewed_levy_elem_philox_f32(a.data_ptr(), 1, B, D, float(self.alpha), ca, seed, sample_offset,
-                                                                       _lib.stream_ptr()))
+        a = self._draw_A(1, shape, self.gen_a.kwargs.get('clamp_a'), seed, sample_offset)
         return self._expanded(a[0], shape)
 
     def _two_rv(self, t, x_0, a_t_0, a_t_1, z_t, seed, sample_offset, want):
@@ -462,7 +464,6 @@ class DLPM:
             assert z_t.shape == x0.shape
         rows = ('x_t', 'eps_t', 'm_tilde')
         out = {k: (torch.empty_like(x0) if k in rows else torch.empty(n, dtype=torch.float32, device=x0.device)) for k in want}
-        ca = self.gen_a.kwargs.get('clamp_a')
         a = _lib.TwoRvArgs()
         a.x0_dev, a.t_dev = x0.data_ptr(), t.data_ptr()
         a.g_dev, a.bg_dev, a.s_dev, a.bs_dev = (_lib.ptr(v) for v in (self.gammas, self.bargammas, self.sigmas, self.barsigmas))
@@ -471,7 +472,7 @@ class DLPM:
             setattr(a, k + '_dev', out[k].data_ptr())
         a.B, a.D, a.T = B, D, self.diffusion_steps
         a.flags = 0 if self.isotropic else _lib.LOSS_ELEMENTWISE
-        a.alpha, a.clamp_a, a.seed, a.sample_offset = float(self.alpha), -1.0 if ca is None else float(ca), seed, sample_offset
+        a.alpha, a.clamp_a, a.seed, a.sample_offset = float(self.alpha), clamp_arg(self.gen_a.kwargs.get('clamp_a')), seed, sample_offset
         with torch.cuda.device(x0.device):
             _lib.check(_lib.lib().dlpm_two_rv_elements_f32(C.byref(a), _lib.stream_ptr()))
         return {k: (v if k in rows else self._expanded(v, x0.shape)) for k, v in out.items()}

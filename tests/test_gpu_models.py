@@ -254,17 +254,33 @@ def test_celeba64_unet_at_its_own_width_against_oracle():
     assert err < 1e-4
 
 
-@pytest.mark.parametrize('name', ['tiny2', 'cifar'])
+# The three head kernels that carry the update in their epilogue, by the profiler class of the launch, and a net that reaches each:
+# the one-pass head wants 32- or 64-pixel rows (cifar), the GEMM + gather takes the 16-pixel ones (tiny2), and k_conv3x3_head is
+# left with what neither MFMA head takes -- four output channels (tiny2's architecture on 4-channel images).
+HEAD_OF = {'cifar': 'head_fused+update', 'tiny2': 'head_gather+update', 'tiny2_4ch': 'conv3x3_head+update'}
+
+
+def _net_and_state(name):
+    if name == 'tiny2_4ch':
+        c = UNETS['tiny2']
+        torch.manual_seed(1234)
+        net = dlpm_amd.UNetModel(4, c['mc'], 4, c['res'], c['attn'], channel_mult=c['mult'], num_heads=c['heads'],
+                                 use_scale_shift_norm=True)
+        dlpm_amd.rerandomize_(net, 4321)
+        return net, torch.randn(3, 4, 16, 16, generator=torch.Generator().manual_seed(5)).to(DEV)
+    return build_unet(name)[0], torch.from_numpy(golden('f6_unet_' + name)['x']).to(DEV)
+
+
+@pytest.mark.parametrize('name', ['tiny2', 'cifar', 'tiny2_4ch'])
 @pytest.mark.parametrize('variant', ['philox', 'injected_z', 'history', 'dlim_unfused'])
 def test_unet_forward_with_fused_update_is_bit_identical_to_the_pair(name, variant):
     """dlpm_unet_forward_update (the head convolution applies x <- (x - c_eps eps)/g + c_noise z in its epilogue,
     GenerativeLevyProcess.py:225-239) against dlpm_unet_forward_uniform_t followed by dlpm_update_f32: same bits, with
-    in-kernel Philox noise, with injected normals, with a history row, and for a variant that takes the unfused pair."""
+    in-kernel Philox noise, with injected normals, with a history row, and for a variant that takes the unfused pair.  One net
+    per head kernel that carries the update (HEAD_OF); the fused call must have run that kernel."""
     import ctypes as C
     from dlpm_amd import _lib
-    f = golden('f6_unet_' + name)
-    net, _ = build_unet(name)
-    x0 = torch.from_numpy(f['x']).to(DEV)
+    net, x0 = _net_and_state(name)
     x0 = torch.cat([x0, x0.flip(0) * 0.5, x0 * 0.25])[:3].contiguous()
     B, D, T, t = 3, x0[0].numel(), 7, 4
     g = torch.Generator(device='cpu').manual_seed(11)
@@ -300,8 +316,14 @@ def test_unet_forward_with_fused_update_is_bit_identical_to_the_pair(name, varia
         cell = torch.tensor([hist.data_ptr()], dtype=torch.int64, device=DEV) if hist is not None else None
         a = args(x, t_dev, eps, cell)
         if fused:
+            _lib.check(L.dlpm_prof_enable(1))
             _lib.check(L.dlpm_unet_forward_update(h, x.data_ptr(), tvec.data_ptr(), C.byref(a), eps.data_ptr(), B, ws.data_ptr(),
                                                   ws.numel(), st))
+            buf = C.create_string_buffer(1 << 16)
+            _lib.check(L.dlpm_prof_report(buf, len(buf)))
+            _lib.check(L.dlpm_prof_enable(0))
+            ran = {line.split()[0] for line in buf.value.decode().strip().splitlines()}
+            assert any(k.startswith(HEAD_OF[name]) for k in ran) == (variant != 'dlim_unfused'), sorted(ran)
         else:
             _lib.check(L.dlpm_unet_forward_uniform_t(h, x.data_ptr(), tvec.data_ptr(), eps.data_ptr(), B, ws.data_ptr(), ws.numel(), st))
             _lib.check(L.dlpm_update_f32(C.byref(a), st))
