@@ -18,6 +18,7 @@ from .metrics import mmd, MMD_loss, kmeans, prd  # noqa: F401
 from .metrics import compute_prd_from_embedding, compute_precision_recall_curve, prd_to_max_f_beta_pair, compute_f_beta  # noqa: F401
 from .metrics import wass, wass_device, compute_wasserstein_distance  # noqa: F401
 from .metrics import w1, w1_device, compute_w1_distance  # noqa: F401
+from .metrics import tail, tail_device, msle, hill_index  # noqa: F401
 from .metrics import prdc, prdc_device, compute_prdc  # noqa: F401
 from .metrics import fd, fd_device, feature_statistics, calculate_frechet_distance  # noqa: F401
 from .weights import rerandomize_  # noqa: F401

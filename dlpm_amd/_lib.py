@@ -296,6 +296,12 @@ SIGNATURES_W1 = {
     'dlpm_w1_workspace_bytes': (i64, [i64, i64]),
     'dlpm_w1_f32': (C.c_int, [vp, vp, i64, i64, i32, i64, i64, vp, i64, vp, vp, vp, vp]),
 }
+# the same for include/dlpm_amd_tail.h (the tail figures: upper-quantile MSLE and Hill tail index)
+TAIL_NORM, TAIL_ABS = 0, 1
+SIGNATURES_TAIL = {
+    'dlpm_tail_workspace_bytes': (i64, [i64, i64, i64, i32, f64, i32]),
+    'dlpm_tail_f32': (C.c_int, [vp, i64, vp, i64, i64, i32, f64, i32, vp, i64, vp, vp, vp]),
+}
 
 _lib = None
 
@@ -314,7 +320,7 @@ def lib():
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_FD.items()) + list(SIGNATURES_LIM.items()) + \
                 list(SIGNATURES_TOY.items()) + list(SIGNATURES_CHAINS.items()) + list(SIGNATURES_CONV.items()) + list(SIGNATURES_STEP.items()) + list(SIGNATURES_TRAIN.items()) + \
-                list(SIGNATURES_MLP.items()) + list(SIGNATURES_MLP_GRAD.items()) + list(SIGNATURES_W1.items()):
+                list(SIGNATURES_MLP.items()) + list(SIGNATURES_MLP_GRAD.items()) + list(SIGNATURES_W1.items()) + list(SIGNATURES_TAIL.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

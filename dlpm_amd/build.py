@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, '_obj')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIB_DIR, 'libdlpm_amd.so')
-SOURCES = ['host.cpp', 'png.cpp', 'images.hip', 'noise.hip', 'loss.hip', 'lim_loss.hip', 'mmd.hip', 'prd.hip', 'wass.hip', 'prdc.hip', 'fd.hip', 'w1.hip', 'toy.hip', 'step.hip', 'conv_igemm.hip', 'conv_split.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_splitk.hip', 'conv_layouts.hip', 'conv_direct.hip', 'head_fused.hip', 'groupnorm.hip', 'attention.hip', 'block_small.hip',
+SOURCES = ['host.cpp', 'png.cpp', 'images.hip', 'noise.hip', 'loss.hip', 'lim_loss.hip', 'mmd.hip', 'prd.hip', 'wass.hip', 'prdc.hip', 'fd.hip', 'w1.hip', 'tail.hip', 'toy.hip', 'step.hip', 'conv_igemm.hip', 'conv_split.hip', 'conv_wino.hip', 'conv_wino4.hip', 'conv_splitk.hip', 'conv_layouts.hip', 'conv_direct.hip', 'head_fused.hip', 'groupnorm.hip', 'attention.hip', 'block_small.hip',
            'embed.hip', 'unet.hip', 'mlp.hip', 'mlp_general.hip', 'mlp_general_grad.hip', 'mlp_train.hip', 'sampler.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off', '-Wall', '-Wno-unused-function']
@@ -55,6 +55,7 @@ def build(force=False, verbose=True):
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_mlp.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_mlp_grad.h'))
     headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_w1.h'))
+    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_tail.h'))
     jobs = []
     objs = []
     for src in SOURCES:

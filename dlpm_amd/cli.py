@@ -23,6 +23,12 @@ Samples are produced in chunks of eval.batch_size like EvaluationManager (:181-1
   more than one of --eval_wass / --eval_mmd / --eval_prd / --eval_prdc / --eval_fid / --eval_w1 the samples are generated once and every figure is printed.
   --eval_w1 REAL.npy|dataset --generate N [--w1_ground l1_mean|euclidean]: the exact W1 between the N generated samples and the
   first N real ones as points (`dataset`: N samples of the config's own 2-D distribution); prints `w1 <value> ground <g> over ...`.
+  --eval_tail REAL.npy|dataset --generate N [--tail_xi X] [--tail_levels K] [--tail_marginal norm|abs]: the tail figures between the
+  first N real samples (`dataset` as for --eval_w1) and the N generated ones (EvaluationManager.evaluate_tail: the mean squared
+  logarithmic error between their K upper quantiles above the level X, default 0.95 and 100, and the Hill tail index of each set, on
+  the norms of the samples or on every scalar); prints `tail msle <v> index real <a> generated <b> xi <x> over <N> generated vs <M>
+  real samples`.  Generated 2-D samples are clamped to +-6: keep X below the clamped fraction.  It shares the one generation with the
+  other --eval_* flags.
   --eval_prdc REAL.npy --generate N [--nearest_k K]: generate N samples and print the k-nearest-neighbour precision, recall, density
   and coverage (the `prdc` package's compute_prdc) between the first N float32 samples of REAL.npy and them, with f_1_pr and f_1_dc
   (EvaluationManager.evaluate_prdc on the flattened samples; K = 5 neighbours by default).  A feature network is plugged in through
@@ -153,6 +159,15 @@ def build_parser():
     ap.add_argument('--w1_ground', default='l1_mean', choices=('l1_mean', 'euclidean'),
                     help='with --eval_w1: the distance between two points: the mean absolute difference (the reference\'s manual_compute '
                          'cost, default) or the Euclidean norm')
+    ap.add_argument('--eval_tail', default=None, metavar='REAL.npy|dataset',
+                    help='with --generate N: the tail figures between the first N float32 samples of this file (`dataset`: N samples of '
+                         'the config\'s own 2-D data distribution) and the N generated samples: the mean squared logarithmic error '
+                         'between their upper quantiles and the Hill tail index of each set; prints `tail msle <v> index real <a> '
+                         'generated <b> xi <x> over <N> generated vs <M> real samples`')
+    ap.add_argument('--tail_xi', type=float, default=0.95, help='with --eval_tail: the level in [0.5, 1) the tail starts at (default 0.95)')
+    ap.add_argument('--tail_levels', type=int, default=100, help='with --eval_tail: the number of quantile levels (default 100)')
+    ap.add_argument('--tail_marginal', default='norm', choices=('norm', 'abs'),
+                    help='with --eval_tail: the norm of every sample (default) or the absolute value of every scalar')
     ap.add_argument('--eval_prdc', default=None, metavar='REAL.npy',
                     help='with --generate N: k-nearest-neighbour precision / recall / density / coverage (compute_prdc of the prdc '
                          'package) between the first N float32 samples of this file and the N generated samples, flattened; prints '
@@ -192,7 +207,8 @@ def main(argv=None):
     if a.save_fid_stats and not (a.eval_fid and not a.eval_fid.endswith('.npz')):
         raise SystemExit('--save_fid_stats needs --eval_fid REAL.npy')
     for flag, value in (('--eval_mmd', a.eval_mmd), ('--eval_prd', a.eval_prd), ('--eval_wass', a.eval_wass), ('--eval_prdc', a.eval_prdc),
-                        ('--eval_fid', a.eval_fid), ('--eval_2d', a.eval_2d), ('--dump_dataset', a.dump_dataset), ('--eval_w1', a.eval_w1)):
+                        ('--eval_fid', a.eval_fid), ('--eval_2d', a.eval_2d), ('--dump_dataset', a.dump_dataset), ('--eval_w1', a.eval_w1),
+                        ('--eval_tail', a.eval_tail)):
         if value and a.gen_data_path:
             raise SystemExit('%s cannot be combined with --gen_data_path' % flag)
         if value and a.generate is None:
@@ -302,9 +318,9 @@ def main(argv=None):
     is_image = dlpm_amd.is_image_dataset(p['data']['dataset'])
     labels = class_labels(a.class_labels, getattr(model, 'num_classes', None), p['eval']['data_to_generate'])
     loader = dlpm_amd.ShapeProbe(sample_shape(p))
-    if a.eval_2d or a.dump_dataset or a.eval_w1 == 'dataset':
+    if a.eval_2d or a.dump_dataset or a.eval_w1 == 'dataset' or a.eval_tail == 'dataset':
         if is_image:
-            raise SystemExit('--eval_2d / --dump_dataset / --eval_w1 dataset draw the 2-D toy distributions; %s is an image dataset' % p['data']['dataset'])
+            raise SystemExit('--eval_2d / --dump_dataset / --eval_w1 dataset / --eval_tail dataset draw the 2-D toy distributions; %s is an image dataset' % p['data']['dataset'])
         loader = dlpm_amd.ToyLoader(dlpm_amd.get_dataset(p, 'cuda', seed or 0)[0], p['eval']['batch_size'])
     gm = dlpm_amd.GenerationManager(method, loader, is_image, **p['eval'][m])
     if a.dump_dataset:
@@ -318,7 +334,7 @@ def main(argv=None):
         if a.out:
             np.save(a.out, res['samples'].cpu().numpy())
         return res
-    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid or a.eval_w1:
+    if a.eval_mmd or a.eval_prd or a.eval_wass or a.eval_prdc or a.eval_fid or a.eval_w1 or a.eval_tail:
         N = p['eval']['data_to_generate']
         ev = dlpm_amd.EvaluationManager(method, gm, None, verbose=False, is_image=is_image)
         value = samples = None
@@ -392,6 +408,19 @@ def main(argv=None):
                 value = w
             else:
                 value = dict(value if isinstance(value, dict) else {'mmd' if a.eval_mmd else 'wass' if a.eval_wass else 'fid': value}, w1=w)
+        if a.eval_tail:
+            if samples is None:
+                samples = generated()
+            real = None if a.eval_tail == 'dataset' else real_of(a.eval_tail)
+            res = ev.evaluate_tail({'default': model}, real, N, p['eval']['batch_size'], xi=a.tail_xi, levels=a.tail_levels,
+                                   marginal=a.tail_marginal, samples=samples)
+            print('tail msle %.9g index real %.9g generated %.9g xi %.9g over %d generated vs %d real samples' % (
+                res['msle'], res['tail_index_real'], res['tail_index_gen'], a.tail_xi, N, N))
+            if value is None:
+                value = res
+            else:                                       # beside other figures the three go under 'tail'
+                value = dict(value if isinstance(value, dict) else
+                             {'mmd' if a.eval_mmd else 'wass' if a.eval_wass else 'fid' if a.eval_fid else 'w1': value}, tail=res)
         if a.out:
             np.save(a.out, samples.cpu().numpy())
         return value

@@ -400,6 +400,27 @@ class EvaluationManager:
         self.evals.setdefault('w1', []).append(value)
         return value
 
+    def evaluate_tail(self, models, real_data, data_to_generate, batch_size, class_labels=None, xi=0.95, levels=100, marginal='norm',
+                      samples=None, **kwargs):
+        """The tail figures (metrics.tail) between `real_data[:data_to_generate]` and `data_to_generate` generated
+        samples: the mean squared logarithmic error between their upper quantiles above the level `xi` and the Hill tail index of
+        each set, appended to `evals['msle']`, `evals['tail_index_real']` and `evals['tail_index_gen']` -- keys of this package,
+        created on first use -- and returned as a dict under those names.  marginal='norm' takes the norm of every sample, 'abs' every
+        scalar.  `real_data=None`: samples of the config's own distribution.
+
+        The samples are generated as `evaluate_mmd` generates them, or taken from `samples=`; with rng='philox' the figures do not
+        depend on `batch_size`.  GenerationManager._post clamps 2-D samples to +-6 and data.quantile_cutoff < 1 clamps the real set: a
+        clamp shows up as ties at the top, and a tail that lies wholly on the clamp has index +inf -- choose `xi` below it."""
+        from . import metrics
+        metrics._tail_check(torch.zeros(2, 1), torch.zeros(2, 1), xi, levels, marginal)     # the refusals, before the generation
+        real, gen, _ = self._real_and_samples('evaluate_tail', models, real_data, data_to_generate, batch_size, class_labels, samples,
+                                              kwargs)
+        t = metrics.tail(real, gen, xi=xi, levels=levels, marginal=marginal)
+        res = {'msle': t['msle'], 'tail_index_real': t['tail_index_first'], 'tail_index_gen': t['tail_index_second']}
+        for k, v in res.items():
+            self.evals.setdefault(k, []).append(v)
+        return res
+
     def evaluate_prdc(self, models, real_data, data_to_generate, batch_size, class_labels=None, nearest_k=5, features=None, samples=None,
                       **kwargs):
         """k-nearest-neighbour precision, recall, density and coverage (the `prdc` package's compute_prdc, the last step of

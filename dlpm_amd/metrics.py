@@ -29,7 +29,13 @@ figure is `compute_w1_distance`:
 
     w1(first, second, ground='l1_mean') -> float      dlpm_w1_f32: exact optimal transport between equal-count point sets by an
                                                       integer auction
-    compute_w1_distance(data, gen_samples, num_samples)   the manual_compute branch's figure"""
+    compute_w1_distance(data, gen_samples, num_samples)   the manual_compute branch's figure
+
+The reference has no figure that sees a tail; for the alpha-stable models this package is about there are two:
+
+    tail(first, second, xi=0.95, levels=100, marginal='norm') -> dict   dlpm_tail_f32: MSLE between upper quantiles and the Hill
+                                                      tail index of each set, on exact order statistics
+    msle(real, gen, ...) -> float, hill_index(x, xi=0.95, marginal='norm') -> float"""
 import numpy as np
 import torch
 
@@ -476,6 +482,75 @@ def compute_w1_distance(data, gen_samples, num_samples=-1):
     assert 1 <= n <= min(len(data), len(gen_samples)), 'compute_w1_distance: num_samples = %r with %d and %d points' % (
         num_samples, len(data), len(gen_samples))
     return w1(data[:n], gen_samples[:n], ground='l1_mean')
+
+
+# ---------------------------------------------------------------------------------------------- tail figures (upper-quantile MSLE, Hill index)
+TAIL_MARGINALS = {'norm': _lib.TAIL_NORM, 'abs': _lib.TAIL_ABS}
+TAIL_MAX_LEVELS = 65536
+
+
+def _tail_check(first, second, xi, levels, marginal):
+    x, y = _row_pair('tail', first, 'first', second, 'second')
+    if marginal not in TAIL_MARGINALS:
+        raise ValueError('tail: marginal must be one of %s, got %r' % (sorted(TAIL_MARGINALS), marginal))
+    assert x.shape[0] >= 2 and y.shape[0] >= 2, 'tail: at least 2 samples a set, got %d and %d' % (x.shape[0], y.shape[0])
+    assert 0.5 <= xi < 1.0, 'tail: xi must be in [0.5, 1), got %r' % (xi,)
+    assert int(levels) == levels and 1 <= levels <= TAIL_MAX_LEVELS, 'tail: levels must be in [1, %d], got %r' % (TAIL_MAX_LEVELS, levels)
+    return x, y, float(xi), int(levels), TAIL_MARGINALS[marginal]
+
+
+def _tail_run(first, second, xi, levels, marginal, parts):
+    x, y, xi, K, m = _tail_check(first, second, xi, levels, marginal)
+    x, y, dev = _on_device(x, y)
+    L = _lib.lib()
+    n1, n2, D = x.shape[0], y.shape[0], x.shape[1]
+    ws = _workspace(L.dlpm_tail_workspace_bytes(n1, n2, D, m, xi, K), dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(8, dtype=torch.float64, device=dev)
+        q = torch.empty((2, K), dtype=torch.float64, device=dev) if parts else None
+        _lib.check(L.dlpm_tail_f32(x.data_ptr(), n1, y.data_ptr(), n2, D, m, xi, K, ws.data_ptr(), ws.numel(),
+                                   q.data_ptr() if parts else None, out.data_ptr(), _lib.stream_ptr()))
+    return out, q
+
+
+def tail_device(first, second, xi=0.95, levels=100, marginal='norm'):
+    """The call itself, without a host synchronisation: a float64 [8] tensor on the GPU holding (msle, Hill index of `first`, Hill
+    index of `second`, k and the threshold s[r0] of `first`, k and s[r0] of `second`, status).  status 1 (a non-finite value) leaves
+    the figures NaN, status 2 (a quantile or a threshold <= 0) the affected ones.  Enqueued on the current stream; it can be captured
+    in a torch.cuda.graph."""
+    return _tail_run(first, second, xi, levels, marginal, False)[0]
+
+
+def tail(first, second, xi=0.95, levels=100, marginal='norm', return_parts=False):
+    """The tail figures of two float32 sample sets (rows flattened, unequal counts allowed) as a dict {'msle', 'tail_index_first',
+    'tail_index_second'}.  Each set becomes a vector of non-negative values: marginal='norm' the Euclidean norm of every
+    sample, 'abs' |x| of every scalar, as `wass` flattens.  `msle` is the mean squared difference of the logarithms of their quantiles
+    at the `levels` levels xi + (1 - xi) j / levels, j = 0 .. levels - 1 (numpy's 'linear' quantiles; the maximum itself is left out);
+    `tail_index_*` the Hill estimate k / sum_{i > r0} log(s[i] / s[r0]) on the k = N - 1 - r0 largest values of a set, r0 = min(floor(xi
+    (N - 1)), N - 2).  The order statistics are exact (radix select, exact sort), every sum runs in a fixed order: same inputs, same bits.
+
+    Ties are handled: a tail that is one repeated value has index +inf.  That is what a CLAMP looks like -- GenerationManager._post
+    clamps 2-D samples to +-6 and data.quantile_cutoff < 1 clamps the real set -- so choose xi below the clamped fraction.
+    ValueError on a non-finite value.  Where a quantile or a threshold is <= 0 (no logarithm) the affected figures are NaN.
+    `return_parts=True` adds 'k' (2 ints), 'thresholds' (the two s[r0]) and 'quantiles' (float64 [2, levels])."""
+    out, q = _tail_run(first, second, xi, levels, marginal, return_parts)
+    o = out.cpu().numpy()
+    if int(o[7]) == 1:
+        raise ValueError('tail: a non-finite value in the input')
+    res = {'msle': float(o[0]), 'tail_index_first': float(o[1]), 'tail_index_second': float(o[2])}
+    if return_parts:
+        res.update(k=(int(o[3]), int(o[5])), thresholds=(float(o[4]), float(o[6])), quantiles=q.cpu().numpy())
+    return res
+
+
+def msle(real, gen, xi=0.95, levels=100, marginal='norm'):
+    """The upper-quantile mean squared logarithmic error of `tail` alone, as a Python float."""
+    return tail(real, gen, xi, levels, marginal)['msle']
+
+
+def hill_index(x, xi=0.95, marginal='norm'):
+    """The Hill tail index of one set (`tail`'s tail_index_first), as a Python float."""
+    return tail(x, x, xi, 1, marginal)['tail_index_first']
 
 
 # ---------------------------------------------------------------------------------------------- PRDC (k-NN precision / recall / density / coverage)
