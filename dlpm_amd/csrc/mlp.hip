@@ -26,77 +26,9 @@ __global__ void __launch_bounds__(64) k_mlp_forward(const float *__restrict__ P,
     __shared__ __attribute__((aligned(16))) float tembT[NU * SPW];  // [k][sample] time embedding
     const int lane = threadIdx.x;
     const int64_t s0 = (int64_t)blockIdx.x * SPW;
-
-    // ---- time embedding (Model.py:64,68-72,191): Linear(1,TE) -> SiLU -> Linear(TE,TE) -> SiLU
-    float tv[SPW];
-#pragma unroll
-    for (int s = 0; s < SPW; s++) tv[s] = (s0 + s < B) ? t[s0 + s] : 0.f;
-    if (lane < TE) {
-        const float w = P[o.te_w + lane], b = P[o.te_b + lane];
-#pragma unroll
-        for (int s = 0; s < SPW; s++) actT[lane * SPW + s] = silu(fmaf(w, tv[s], b));
-    }
-    __syncthreads();
-    if (lane < TE) {
-        float acc[SPW];
-        const float b = P[o.tm_b + lane];
-#pragma unroll
-        for (int s = 0; s < SPW; s++) acc[s] = b;
-        for (int k = 0; k < TE; k++) {
-            const float w = P[o.tm_w + k * TE + lane];
-#pragma unroll
-            for (int s = 0; s < SPW; s++) acc[s] = fmaf(w, actT[k * SPW + s], acc[s]);
-        }
-#pragma unroll
-        for (int s = 0; s < SPW; s++) tembT[lane * SPW + s] = silu(acc[s]);
-    }
-    __syncthreads();
-
-    // ---- input layer (Model.py:93-97): Linear(F,64) -> LayerNorm -> SiLU
     float h[SPW];
-    {
-        const float b = P[o.in_b + lane];
-#pragma unroll
-        for (int s = 0; s < SPW; s++) h[s] = b;
-        for (int f = 0; f < F; f++) {
-            const float w = P[o.in_w + f * NU + lane];
-#pragma unroll
-            for (int s = 0; s < SPW; s++) h[s] = fmaf(w, (s0 + s < B) ? x[(s0 + s) * F + f] : 0.f, h[s]);
-        }
-        layer_norm(h, P[o.in_g + lane], P[o.in_be + lane]);
-#pragma unroll
-        for (int s = 0; s < SPW; s++) h[s] = silu(h[s]);
-    }
-
-    // ---- conditioned residual blocks (DiffusionBlocks.py:125-136)
-    for (int bi = 0; bi < nblk; bi++) {
-        const float *Q = P + o.blk0 + (int64_t)bi * o.blk_stride;
-#pragma unroll
-        for (int s = 0; s < SPW; s++) actT[lane * SPW + s] = h[s];
-        __syncthreads();
-        float y[SPW], tp[SPW];
-        const float b1 = Q[o.b_b1 + lane], tb = Q[o.b_tb + lane];
-#pragma unroll
-        for (int s = 0; s < SPW; s++) { y[s] = b1; tp[s] = tb; }
-        matvec(Q + o.b_w1, NU, actT, lane, y);
-        layer_norm(y, Q[o.b_g1 + lane], Q[o.b_be1 + lane]);
-        matvec(Q + o.b_tw, TE, tembT, lane, tp);
-#pragma unroll
-        for (int s = 0; s < SPW; s++) y[s] = silu(y[s]) + silu(tp[s]);
-        __syncthreads();  // everyone is done reading actT
-#pragma unroll
-        for (int s = 0; s < SPW; s++) actT[lane * SPW + s] = y[s];
-        __syncthreads();
-        float z[SPW];
-        const float b2 = Q[o.b_b2 + lane];
-#pragma unroll
-        for (int s = 0; s < SPW; s++) z[s] = b2;
-        matvec(Q + o.b_w2, NU, actT, lane, z);
-        layer_norm(z, Q[o.b_g2 + lane], Q[o.b_be2 + lane]);
-#pragma unroll
-        for (int s = 0; s < SPW; s++) h[s] = silu(z[s] + h[s]);
-        __syncthreads();
-    }
+    LaneNoTap tap;
+    lane_forward(P, o, x, t, B, F, TE, nblk, lane, s0, actT, tembT, h, tap);
 
     // ---- output layer Linear(64,F) (Model.py:129): a wave reduction per feature
     for (int f = 0; f < F; f++) {
@@ -261,21 +193,8 @@ extern "C" int dlpm_mlp_create_ex(int32_t nfeatures, int32_t nunits, int32_t nbl
         *out = m;
         return DLPM_OK;
     }
-    MlpOffsets &o = m->off;
-    int p = 0;
-    auto take = [&](int n) { int r = p; p += (n + 3) / 4 * 4; return r; };
-    const int TE = m->TE, F = m->F;
-    o.te_w = take(TE); o.te_b = take(TE); o.tm_w = take(TE * TE); o.tm_b = take(TE);
-    o.in_w = take(F * NU); o.in_b = take(NU); o.in_g = take(NU); o.in_be = take(NU);
-    int q = 0;
-    auto takeb = [&](int n) { int r = q; q += (n + 3) / 4 * 4; return r; };
-    o.b_w1 = takeb(NU * NU); o.b_b1 = takeb(NU); o.b_g1 = takeb(NU); o.b_be1 = takeb(NU);
-    o.b_tw = takeb(TE * NU); o.b_tb = takeb(NU);
-    o.b_w2 = takeb(NU * NU); o.b_b2 = takeb(NU); o.b_g2 = takeb(NU); o.b_be2 = takeb(NU);
-    o.blk_stride = q;
-    o.blk0 = take(q * (nblocks + 1));
-    o.out_w = take(F * NU); o.out_b = take(F);
-    m->host.assign(p, 0.f);
+    m->off = mlp_lane_offsets(m->F, m->TE, nblocks, &m->blob_floats);
+    m->host.assign(m->blob_floats, 0.f);
     *out = m;
     return DLPM_OK;
 }
@@ -396,10 +315,7 @@ extern "C" int dlpm_mlp_sample_steps_f32(dlpm_mlp *m, float *x_dev, const float 
     DLPM_CHECK_ARG(T >= 2 && B > 0 && nsteps >= 0 && t_start < T && t_start - nsteps >= 0, "dlpm_mlp_sample_steps_f32: bad step range");
     DLPM_CHECK_ARG(T < (1 << 24), "dlpm_mlp_sample_steps_f32: T must fit 24 bits");   // the Philox counter holds purpose | t << 8
     DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_sample_steps_f32", "the one-launch sampling loop");
-    if (!m->finalized) {
-        set_error("dlpm_mlp_sample_steps_f32: call dlpm_mlp_finalize first");
-        return DLPM_ERR_STATE;
-    }
+    DLPM_MLP_NEED_FINALIZED(m, "dlpm_mlp_sample_steps_f32");
     if (m->F > 4) {
         set_error("dlpm_mlp_sample_steps_f32: the fused loop keeps the state in registers: nfeatures <= 4 (got %d)", m->F);
         return DLPM_ERR_UNSUPPORTED;
@@ -427,10 +343,7 @@ extern "C" int dlpm_mlp_sample_steps_f32(dlpm_mlp *m, float *x_dev, const float 
 extern "C" int dlpm_mlp_forward(dlpm_mlp *m, const float *x_dev, const float *t_dev, float *eps_dev, int64_t B,
                                 dlpm_stream_t stream) {
     DLPM_CHECK_ARG(m && x_dev && t_dev && eps_dev && B > 0, "dlpm_mlp_forward: bad argument");
-    if (!m->finalized) {
-        set_error("dlpm_mlp_forward: call dlpm_mlp_finalize first");
-        return DLPM_ERR_STATE;
-    }
+    DLPM_MLP_NEED_FINALIZED(m, "dlpm_mlp_forward");
     if (m->general) return mlp_general_forward(m, x_dev, t_dev, eps_dev, B, as_stream(stream));
     k_mlp_forward<<<(unsigned)ceil_div(B, SPW), 64, 0, as_stream(stream)>>>(m->dev, m->off, x_dev, t_dev, eps_dev, B, m->F,
                                                                           m->TE, m->nblocks + 1);

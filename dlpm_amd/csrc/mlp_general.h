@@ -1,6 +1,9 @@
 // mlp_general.h -- what the general toy-net forward (mlp_general.hip) and its backward (mlp_general_grad.hip) share: the kernel
-// arguments, the MFMA tile loop, the row sums and the LayerNorm over a row tile.  One definition, so the backward's recomputed
-// forward rounds exactly as k_mlp_general does.
+// arguments, the MFMA tile loop, the row sums and the LayerNorm over a row tile.  These building blocks have one definition; the
+// SEQUENCE of the forward is written out in both kernels (k_mlp_general and the first half of k_mlp_general_backward) and has to
+// be kept the same by hand, operation for operation: the build does not contract, so the source order is the rounding order.
+// (Running one shared body in both kernels gives the same bits, but hipcc allocates the backward's registers differently from
+// the same IR and its smallest row passes measured 0.7 % slower: profiles/mlp_forward_body/README.md.)
 #pragma once
 #include "mlp.h"
 

@@ -1,5 +1,5 @@
-// mlp_general_grad.hip -- the backward of the general toy-net forward (mlp_general.hip) on the fp32 MFMA, and the map between torch's
-// flat parameter vector and the packed blob (include/dlpm_amd_mlp_grad.h).
+// mlp_general_grad.hip -- the backward of the general toy-net forward (mlp_general.hip) on the fp32 MFMA (include/dlpm_amd_mlp_grad.h,
+// DESIGN 3.21; the entry points and the flat parameter vector: mlp_train.hip).
 //
 // Row pass (k_mlp_general_backward).  The forward's tile ownership: one workgroup owns 16 MT rows for the whole net, wave w the
 // same NT column tiles of every layer.  It recomputes the forward with the building blocks of mlp_general.h -- the very operations
@@ -31,7 +31,7 @@ struct GradArgs {
     MlpGenLayout L;
     MlpGenGradLayout G;
     MlpGenRecords R;
-    MlpGenFlat f;
+    MlpFlat f;
     const float *x, *t, *dout;
     float *dx;               // nullable
     float *ws;               // the records
@@ -39,12 +39,6 @@ struct GradArgs {
     int64_t B, rows_per_slot;
     int ln, skip, slots;
 };
-
-// d silu(v) / dv with the forward's own sigmoid
-__device__ __forceinline__ float dsilu(float v) {
-    const float sg = 1.0f / (1.0f + __expf(-v));
-    return sg * (1.0f + v * (1.0f - sg));
-}
 
 template <int MT, int NT>
 __global__ void __launch_bounds__(64 * GEN_MAX_WAVES) k_mlp_general_backward(GradArgs a) {
@@ -494,7 +488,7 @@ struct ColJob {
 __device__ MatJob mat_job(const GradArgs &a, int j) {
     const MlpGenLayout &L = a.L;
     const MlpGenRecords &R = a.R;
-    const MlpGenFlat &f = a.f;
+    const MlpFlat &f = a.f;
     const int64_t B = a.B;
     auto rec = [&](int64_t off) { return a.ws + off * B; };
     MatJob b;
@@ -525,7 +519,7 @@ __device__ MatJob mat_job(const GradArgs &a, int j) {
 __device__ ColJob col_job(const GradArgs &a, int j) {
     const MlpGenLayout &L = a.L;
     const MlpGenRecords &R = a.R;
-    const MlpGenFlat &f = a.f;
+    const MlpFlat &f = a.f;
     const int64_t B = a.B;
     auto rec = [&](int64_t off) { return a.ws + off * B; };
     ColJob c;
@@ -632,44 +626,6 @@ __global__ void __launch_bounds__(256) k_gen_wgrad_sum(const double *__restrict_
     grad[i] = (float)s;
 }
 
-// ------------------------------------------------------------------------------------------------ the flat vector
-__global__ void __launch_bounds__(256) k_gen_flat_gather(const float *__restrict__ blob, const int64_t *__restrict__ map,
-                                                         float *__restrict__ flat, int64_t P) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < P) flat[i] = blob[map[i]];
-}
-
-// both regions <- flat; padded elements are never written, so they stay 0
-__global__ void __launch_bounds__(256) k_gen_flat_scatter(const float *__restrict__ flat, const int64_t *__restrict__ map,
-                                                          float *__restrict__ blob, int64_t P) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < P) {
-        const float v = flat[i];
-        blob[map[i]] = v;
-        const int64_t t = map[P + i];
-        if (t >= 0) blob[t] = v;
-    }
-}
-
-MlpGenFlat flat_of(const dlpm_mlp *m) { return mlp_gen_flat(m->F, m->nunits, m->TE, m->nblocks, m->ln); }
-
-// the handle's map, built and uploaded on the first call that needs it
-int ensure_map(dlpm_mlp *m) {
-    if (m->gen_map) return DLPM_OK;
-    const MlpGenFlat f = flat_of(m);
-    const MlpGenGradLayout G = mlp_gen_grad_layout(m->gen);
-    std::vector<int64_t> map((size_t)(2 * f.P));
-    mlp_gen_flat_map(m->gen, G, f, map.data(), map.data() + f.P);
-    for (int64_t i = 0; i < f.P; i++)
-        if (map[i] < 0 || map[i] >= m->gen.total || map[f.P + i] >= m->gen.total + G.total) {
-            set_error("dlpm_mlp_grad: internal error: the flat parameter map has a hole");
-            return DLPM_ERR_STATE;
-        }
-    DLPM_HIP(hipMalloc(&m->gen_map, map.size() * sizeof(int64_t)));
-    DLPM_HIP(hipMemcpy(m->gen_map, map.data(), map.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    return DLPM_OK;
-}
-
 // the tile height of the backward: the forward's choice, but 16 rows where a wave owns 8 column tiles (registers)
 int grad_tile_rows(const dlpm_mlp *m, int64_t rows) {
     if (m->gen.NT == 8 && !(m->flags & DLPM_MLP_TILE_32)) return 16;
@@ -677,7 +633,7 @@ int grad_tile_rows(const dlpm_mlp *m, int64_t rows) {
 }
 
 template <int MT>
-int launch_backward(const dlpm_mlp *m, const GradArgs &a, unsigned grid, size_t lds, hipStream_t st) {
+int launch_backward(const dlpm_mlp *m, const char *name, const GradArgs &a, unsigned grid, size_t lds, hipStream_t st) {
     void (*fn)(GradArgs) = nullptr;
     switch (m->gen.NT) {
         case 1: fn = k_mlp_general_backward<MT, 1>; break;
@@ -686,7 +642,7 @@ int launch_backward(const dlpm_mlp *m, const GradArgs &a, unsigned grid, size_t 
         case 8: fn = k_mlp_general_backward<MT, 8>; break;
     }
     if (!fn) {
-        set_error("dlpm_mlp_grad_backward_f32: no general kernel for %d column tiles per wave", m->gen.NT);
+        set_error("%s: no general kernel for %d column tiles per wave", name, m->gen.NT);
         return DLPM_ERR_UNSUPPORTED;
     }
     const int r = ensure_dynamic_lds(reinterpret_cast<const void *>(fn), GEN_LDS_LIMIT);
@@ -696,92 +652,48 @@ int launch_backward(const dlpm_mlp *m, const GradArgs &a, unsigned grid, size_t 
     return DLPM_OK;
 }
 
-#define GRAD_NEED_FINALIZED(m, name)                               \
-    do {                                                           \
-        if (!(m)->finalized) {                                     \
-            set_error(name ": call dlpm_mlp_finalize first");      \
-            return DLPM_ERR_STATE;                                 \
-        }                                                          \
-    } while (0)
-
 }  // namespace
 
-extern "C" int64_t dlpm_mlp_grad_param_floats(const dlpm_mlp *m) {
-    if (!m) return -1;
-    if (!m->general) return dlpm_mlp_param_floats(m);
-    return flat_of(m).P;
-}
+namespace dlpm {
 
-extern "C" int dlpm_mlp_grad_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t n, dlpm_stream_t stream) {
-    if (m && !m->general) return dlpm_mlp_export_params_f32(m, flat_dev, n, stream);
-    DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_grad_export_params_f32: null argument");
-    const int64_t P = flat_of(m).P;
-    DLPM_CHECK_ARG(n == P, "dlpm_mlp_grad_export_params_f32: n = %lld, the net has %lld parameters", (long long)n, (long long)P);
-    GRAD_NEED_FINALIZED(m, "dlpm_mlp_grad_export_params_f32");
-    if (int rc = ensure_map(m)) return rc;
-    k_gen_flat_gather<<<(unsigned)ceil_div(P, 256), 256, 0, as_stream(stream)>>>(m->gen_dev, m->gen_map, flat_dev, P);
-    DLPM_LAUNCH_CHECK();
-    return DLPM_OK;
-}
-
-extern "C" int dlpm_mlp_grad_import_params_f32(dlpm_mlp *m, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
-    if (m && !m->general) return dlpm_mlp_import_params_f32(m, flat_dev, n, stream);
-    DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_grad_import_params_f32: null argument");
-    const int64_t P = flat_of(m).P;
-    DLPM_CHECK_ARG(n == P, "dlpm_mlp_grad_import_params_f32: n = %lld, the net has %lld parameters", (long long)n, (long long)P);
-    GRAD_NEED_FINALIZED(m, "dlpm_mlp_grad_import_params_f32");
-    if (int rc = ensure_map(m)) return rc;
-    k_gen_flat_scatter<<<(unsigned)ceil_div(P, 256), 256, 0, as_stream(stream)>>>(flat_dev, m->gen_map, m->gen_dev, P);
-    DLPM_LAUNCH_CHECK();
-    return DLPM_OK;
-}
-
-extern "C" int64_t dlpm_mlp_grad_workspace_bytes(const dlpm_mlp *m, int64_t rows) {
-    if (!m || rows <= 0) return -1;
-    if (!m->general) return dlpm_mlp_backward_workspace_bytes(m, rows);
+int64_t mlp_general_workspace_bytes(const dlpm_mlp *m, const char *name, int64_t rows) {
     const int M = grad_tile_rows(m, rows);
     const int64_t lds = mlp_gen_grad_lds_bytes(m->gen, M);
     if ((M != 16 && M != 32) || lds > GEN_LDS_LIMIT) {
-        set_error("dlpm_mlp_grad_workspace_bytes: a %d-row tile of this net's backward takes %lld bytes of LDS, a workgroup has %d", M,
-                  (long long)lds, GEN_LDS_LIMIT);
+        set_error("%s: a %d-row tile of this net's backward takes %lld bytes of LDS, a workgroup has %d", name, M, (long long)lds,
+                  GEN_LDS_LIMIT);
         return DLPM_ERR_UNSUPPORTED;
     }
-    return mlp_gen_grad_workspace_bytes(m->gen, flat_of(m), rows);
+    return mlp_gen_grad_workspace_bytes(m->gen, mlp_flat_of(m), rows);
 }
 
-extern "C" int dlpm_mlp_grad_backward_f32(dlpm_mlp *m, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
-                                          float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes,
-                                          dlpm_stream_t stream) {
-    if (m && !m->general)
-        return dlpm_mlp_backward_f32(m, x_dev, t_dev, dout_dev, rows, grad_flat_dev, dx_dev, workspace_dev, workspace_bytes, stream);
-    DLPM_CHECK_ARG(m && x_dev && t_dev && dout_dev && grad_flat_dev && workspace_dev, "dlpm_mlp_grad_backward_f32: null argument");
-    DLPM_CHECK_ARG(rows > 0, "dlpm_mlp_grad_backward_f32: rows must be positive (got %lld)", (long long)rows);
+int mlp_general_backward(dlpm_mlp *m, const char *name, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
+                         float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes, hipStream_t st) {
     const int M = grad_tile_rows(m, rows);
     const int64_t lds = mlp_gen_grad_lds_bytes(m->gen, M);
     if ((M != 16 && M != 32) || lds > GEN_LDS_LIMIT) {
-        set_error("dlpm_mlp_grad_backward_f32: a %d-row tile of this net's backward takes %lld bytes of LDS, a workgroup has %d", M,
-                  (long long)lds, GEN_LDS_LIMIT);
+        set_error("%s: a %d-row tile of this net's backward takes %lld bytes of LDS, a workgroup has %d", name, M, (long long)lds,
+                  GEN_LDS_LIMIT);
         return DLPM_ERR_UNSUPPORTED;
     }
     const int64_t grid = ceil_div(rows, M);
-    DLPM_CHECK_ARG(grid < (1ll << 31), "dlpm_mlp_grad_backward_f32: rows = %lld is beyond the grid of one call", (long long)rows);
+    DLPM_CHECK_ARG(grid < (1ll << 31), "%s: rows = %lld is beyond the grid of one call", name, (long long)rows);
     GradArgs a;
-    a.f = flat_of(m);
+    a.f = mlp_flat_of(m);
     const int64_t need = mlp_gen_grad_workspace_bytes(m->gen, a.f, rows);
     if (workspace_bytes < need) {
-        set_error("dlpm_mlp_grad_backward_f32: the workspace has %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)need);
+        set_error("%s: the workspace has %lld bytes, %lld are needed", name, (long long)workspace_bytes, (long long)need);
         return DLPM_ERR_NOMEM;
     }
-    DLPM_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace_dev) % 8 == 0, "dlpm_mlp_grad_backward_f32: the workspace must be 8-byte aligned");
-    GRAD_NEED_FINALIZED(m, "dlpm_mlp_grad_backward_f32");
-    hipStream_t st = as_stream(stream);
+    DLPM_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace_dev) % 8 == 0, "%s: the workspace must be 8-byte aligned", name);
+    DLPM_MLP_NEED_FINALIZED(m, name);
     a.P = m->gen_dev; a.L = m->gen; a.G = mlp_gen_grad_layout(m->gen); a.R = mlp_gen_records(m->gen);
     a.x = x_dev; a.t = t_dev; a.dout = dout_dev; a.dx = dx_dev;
     a.ws = static_cast<float *>(workspace_dev);
     a.part = reinterpret_cast<double *>(a.ws + (a.R.per_row * rows + 1) / 2 * 2);
     a.B = rows; a.ln = m->ln; a.skip = m->skip;
     mlp_gen_grad_slots(rows, &a.slots, &a.rows_per_slot);
-    if (int rc = M == 32 ? launch_backward<2>(m, a, (unsigned)grid, (size_t)lds, st) : launch_backward<1>(m, a, (unsigned)grid, (size_t)lds, st))
+    if (int rc = M == 32 ? launch_backward<2>(m, name, a, (unsigned)grid, (size_t)lds, st) : launch_backward<1>(m, name, a, (unsigned)grid, (size_t)lds, st))
         return rc;
     const int nb = m->gen.nblk;
     k_gen_wgrad<<<dim3(4 + 3 * nb, a.slots, WG_ZSPLIT), 256, 0, st>>>(a);
@@ -792,3 +704,5 @@ extern "C" int dlpm_mlp_grad_backward_f32(dlpm_mlp *m, const float *x_dev, const
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
 }
+
+}  // namespace dlpm

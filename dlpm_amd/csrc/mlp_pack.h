@@ -1,7 +1,8 @@
 // mlp_pack.h -- the host side of the general toy-net forward (mlp_general.hip) and of its backward (mlp_general_grad.hip): how a net
 // of any width is cut into MFMA tiles, where every tensor lies in the packed blob, the routine that lays a Linear weight out as the
-// B operand of v_mfma_f32_16x16x4_f32, and for the backward the transposed operands, the flat parameter vector's map, the per-row
-// records and the slots of the weight pass.
+// B operand of v_mfma_f32_16x16x4_f32, and for the backward the transposed operands, the per-row records and the slots of the weight
+// pass.  Also the ONE definition of torch's flat parameter vector (MlpFlat) with its map into the general blob and into the lane
+// kernels' blob (MlpOffsets, mlp.hip).
 // Plain C++ with no HIP in it, so that the packing can be compiled into a stand-alone program and run under a host sanitizer.
 #pragma once
 #include <cstdint>
@@ -144,13 +145,13 @@ inline int64_t mlp_gen_grad_lds_bytes(const MlpGenLayout &L, int M) { return mlp
 
 // the flat parameter vector, parameters_to_vector(model.parameters()): named_parameters() order, torch's [out][in] layout, every
 // alias once; a net without LayerNorm has no group_norm tensors (their offsets are -1)
-struct MlpGenFlat {
+struct MlpFlat {
     int64_t in_g, in_be, te_w, te_b, tm_w, tm_b, in_w, in_b, blk0, blk_stride, out_w, out_b, P;
     int64_t b_g1, b_be1, b_g2, b_be2, b_w1, b_b1, b_tw, b_tb, b_w2, b_b2;
 };
 
-inline MlpGenFlat mlp_gen_flat(int F, int NU, int TE, int nblocks, bool ln) {
-    MlpGenFlat f{};
+inline MlpFlat mlp_flat(int F, int NU, int TE, int nblocks, bool ln) {
+    MlpFlat f{};
     int64_t p = 0;
     auto take = [&](int64_t n) { int64_t r = p; p += n; return r; };
     f.in_g = ln ? take(NU) : -1; f.in_be = ln ? take(NU) : -1;
@@ -171,8 +172,8 @@ inline MlpGenFlat mlp_gen_flat(int F, int NU, int TE, int nblocks, bool ln) {
 }
 
 // fwd[i] = index in the blob of element i of the flat vector; tr[i] = index of its copy in the transposed region (from the start
-// of the blob), -1 for a tensor that has none.  Both arrays hold MlpGenFlat::P entries.
-inline void mlp_gen_flat_map(const MlpGenLayout &L, const MlpGenGradLayout &G, const MlpGenFlat &f, int64_t *fwd, int64_t *tr) {
+// of the blob), -1 for a tensor that has none.  Both arrays hold MlpFlat::P entries.
+inline void mlp_general_flat_map(const MlpGenLayout &L, const MlpGenGradLayout &G, const MlpFlat &f, int64_t *fwd, int64_t *tr) {
     const int F = L.F, NU = L.NU, TE = L.TE;
     for (int64_t i = 0; i < f.P; i++) { fwd[i] = -1; tr[i] = -1; }
     auto vec = [&](int64_t fo, int64_t bo, int n) { if (fo >= 0) for (int i = 0; i < n; i++) fwd[fo + i] = bo + i; };
@@ -202,6 +203,59 @@ inline void mlp_gen_flat_map(const MlpGenLayout &L, const MlpGenGradLayout &G, c
     for (int k = 0; k < F; k++)
         for (int n = 0; n < NU; n++) fwd[f.out_w + (int64_t)k * NU + n] = L.out_w + (int64_t)k * L.NP + n;
     vec(f.out_b, L.out_b, F);
+}
+
+// ------------------------------------------------------------------------------------------------ the lane kernels' blob (mlp.hip)
+constexpr int LANE_NU = 64;   // hidden units of the lane kernels' net == wavefront width (mlp.h: NU)
+
+struct MlpOffsets {      // offsets (floats) into the lane kernels' packed parameter blob; every tensor starts on a 16-byte boundary
+    int te_w, te_b, tm_w, tm_b, in_w, in_b, in_g, in_be, blk0, blk_stride, out_w, out_b;
+    // per block: w1T[64*64] b1 g1 be1 twT[TE*64] tb w2T[64*64] b2 g2 be2; a Linear weight [N][K] lies transposed, [K][64]
+    int b_w1, b_b1, b_g1, b_be1, b_tw, b_tb, b_w2, b_b2, b_g2, b_be2;
+};
+
+// the layout of a net's blob and, through `total`, its size in floats
+inline MlpOffsets mlp_lane_offsets(int F, int TE, int nblocks, int *total) {
+    MlpOffsets o{};
+    int p = 0;
+    auto take = [&](int n) { int r = p; p += (n + 3) / 4 * 4; return r; };
+    o.te_w = take(TE); o.te_b = take(TE); o.tm_w = take(TE * TE); o.tm_b = take(TE);
+    o.in_w = take(F * LANE_NU); o.in_b = take(LANE_NU); o.in_g = take(LANE_NU); o.in_be = take(LANE_NU);
+    int q = 0;
+    auto takeb = [&](int n) { int r = q; q += (n + 3) / 4 * 4; return r; };
+    o.b_w1 = takeb(LANE_NU * LANE_NU); o.b_b1 = takeb(LANE_NU); o.b_g1 = takeb(LANE_NU); o.b_be1 = takeb(LANE_NU);
+    o.b_tw = takeb(TE * LANE_NU); o.b_tb = takeb(LANE_NU);
+    o.b_w2 = takeb(LANE_NU * LANE_NU); o.b_b2 = takeb(LANE_NU); o.b_g2 = takeb(LANE_NU); o.b_be2 = takeb(LANE_NU);
+    o.blk_stride = q;
+    o.blk0 = take(q * (nblocks + 1));
+    o.out_w = take(F * LANE_NU); o.out_b = take(F);
+    *total = p;
+    return o;
+}
+
+// map[i] = index in the lane blob of element i of the flat vector f = mlp_flat(F, 64, TE, nblocks, true); MlpFlat::P entries
+inline void mlp_lane_flat_map(const MlpOffsets &o, const MlpFlat &f, int F, int TE, int nblocks, int64_t *map) {
+    for (int64_t i = 0; i < f.P; i++) map[i] = -1;
+    auto vec = [&](int64_t fo, int bo, int n) { for (int i = 0; i < n; i++) map[fo + i] = bo + i; };
+    // a Linear weight [N][K] in the flat vector, transposed to [K][ld] in the blob
+    auto mat = [&](int64_t fo, int bo, int N, int K, int ld) {
+        for (int n = 0; n < N; n++)
+            for (int k = 0; k < K; k++) map[fo + n * K + k] = bo + k * ld + n;
+    };
+    vec(f.in_g, o.in_g, LANE_NU); vec(f.in_be, o.in_be, LANE_NU);
+    vec(f.te_w, o.te_w, TE); vec(f.te_b, o.te_b, TE);
+    mat(f.tm_w, o.tm_w, TE, TE, TE); vec(f.tm_b, o.tm_b, TE);
+    mat(f.in_w, o.in_w, LANE_NU, F, LANE_NU); vec(f.in_b, o.in_b, LANE_NU);
+    for (int bi = 0; bi <= nblocks; bi++) {
+        const int64_t fb = f.blk0 + bi * f.blk_stride;
+        const int ob = o.blk0 + bi * o.blk_stride;
+        vec(fb + f.b_g1, ob + o.b_g1, LANE_NU); vec(fb + f.b_be1, ob + o.b_be1, LANE_NU);
+        vec(fb + f.b_g2, ob + o.b_g2, LANE_NU); vec(fb + f.b_be2, ob + o.b_be2, LANE_NU);
+        mat(fb + f.b_w1, ob + o.b_w1, LANE_NU, LANE_NU, LANE_NU); vec(fb + f.b_b1, ob + o.b_b1, LANE_NU);
+        mat(fb + f.b_tw, ob + o.b_tw, LANE_NU, TE, LANE_NU); vec(fb + f.b_tb, ob + o.b_tb, LANE_NU);
+        mat(fb + f.b_w2, ob + o.b_w2, LANE_NU, LANE_NU, LANE_NU); vec(fb + f.b_b2, ob + o.b_b2, LANE_NU);
+    }
+    vec(f.out_w, o.out_w, F * LANE_NU); vec(f.out_b, o.out_b, F);      // the blob keeps outblocks_mean.1.weight as [F][64]
 }
 
 // the backward's per-row records in the workspace, in floats per row: record q of width wq lies at ws[off_q rows + row wq + column]
@@ -241,7 +295,7 @@ inline void mlp_gen_grad_slots(int64_t rows, int *slots, int64_t *rows_per_slot)
 }
 
 // bytes of workspace of the backward: the records, then slots x P fp64 partial sums
-inline int64_t mlp_gen_grad_workspace_bytes(const MlpGenLayout &L, const MlpGenFlat &f, int64_t rows) {
+inline int64_t mlp_gen_grad_workspace_bytes(const MlpGenLayout &L, const MlpFlat &f, int64_t rows) {
     int slots;
     int64_t rps;
     mlp_gen_grad_slots(rows, &slots, &rps);

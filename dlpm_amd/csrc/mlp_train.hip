@@ -1,5 +1,6 @@
 // mlp_train.hip -- training of the toy net (include/dlpm_amd_train.h): the backward of k_mlp_forward, the loss gradient, the
-// gradient-norm clip, AdamW with EMA shadows, and the map between torch's flat parameter vector and the packed blob.
+// gradient-norm clip, AdamW with EMA shadows, and torch's flat parameter vector for either kind of handle: the entry points of
+// dlpm_amd_train.h and of dlpm_amd_mlp_grad.h (the general handle's backward itself: mlp_general_grad.hip).
 //
 // Backward.  The net is 55 k parameters; per row the backward is ~210 kFLOP of matrix-vector work plus, per 64x64 matrix, one
 // rank-1 update of its gradient.  The matrix-vector half keeps the forward's mapping (one wavefront owns 4 rows, lanes = hidden
@@ -13,6 +14,7 @@
 #include <cmath>
 
 #include "mlp.h"
+#include "../../include/dlpm_amd_mlp_grad.h"
 #include "../../include/dlpm_amd_train.h"
 
 using namespace dlpm;
@@ -29,7 +31,8 @@ enum { B_H = 0, B_XH1, B_TP, B_Y, B_XH2, B_DLN1, B_DLN2, B_DZ1, B_DZ2, B_DTP, R_
 struct BwdArgs {
     const float *P;      // packed blob ([k][unit])
     const float *W;      // flat vector (torch layout)
-    MlpOffsets o, fo;    // offsets into P, into W
+    MlpOffsets o;        // offsets into P
+    MlpFlat fo;          // offsets into W
     const float *x, *t, *dout;
     float *dx;
     float *rec, *sc, *part;
@@ -40,24 +43,7 @@ struct BwdArgs {
 
 __device__ __forceinline__ float *rec_at(const BwdArgs &a, int q, int64_t row) { return a.rec + ((int64_t)q * a.rows + row) * NU; }
 
-// d silu(v) / dv with the forward's own sigmoid
-__device__ __forceinline__ float dsilu(float v) {
-    const float sg = 1.0f / (1.0f + __expf(-v));
-    return sg * (1.0f + v * (1.0f - sg));
-}
-
-// layer_norm of mlp.h with xhat and 1/sigma kept; v gets the same bits
-__device__ __forceinline__ void layer_norm_keep(float v[SPW], float gam, float bet, float xh[SPW], float rs[SPW]) {
-#pragma unroll
-    for (int s = 0; s < SPW; s++) {
-        const float mean = wave_sum(v[s]) * (1.0f / NU);
-        const float d = v[s] - mean;
-        const float var = wave_sum(d * d) * (1.0f / NU);
-        rs[s] = 1.0f / sqrtf(var + 1e-5f);
-        xh[s] = d * rs[s];
-        v[s] = xh[s] * gam + bet;
-    }
-}
+#define FOR_S for (int s = 0; s < SPW; s++)
 
 // dL/d(LayerNorm input) from dL/d(LayerNorm output) g
 __device__ __forceinline__ void layer_norm_back(const float g[SPW], const float xh[SPW], const float rs[SPW], float gam, float dz[SPW]) {
@@ -70,7 +56,54 @@ __device__ __forceinline__ void layer_norm_back(const float g[SPW], const float 
     }
 }
 
-#define FOR_S for (int s = 0; s < SPW; s++)
+// The per-row records of the wave's 4 rows in the workspace: lane_forward's tap writes what the recomputed forward leaves there,
+// the walk back reads it and adds its own
+struct RowRecords {
+    static constexpr bool KEEP = true;
+    const BwdArgs &a;
+    const int lane;
+    const int64_t s0;
+    bool live[SPW];
+    float a0[SPW], a1[SPW];   // the time embedding's pre-activations
+    __device__ __forceinline__ RowRecords(const BwdArgs &a_, int lane_, int64_t s0_) : a(a_), lane(lane_), s0(s0_) {
+#pragma unroll
+        FOR_S live[s] = s0 + s < a.rows;
+    }
+    __device__ __forceinline__ void put(int q, const float *v) const {
+#pragma unroll
+        FOR_S if (live[s]) rec_at(a, q, s0 + s)[lane] = v[s];
+    }
+    __device__ __forceinline__ void get(int q, float *v) const {
+#pragma unroll
+        FOR_S v[s] = live[s] ? rec_at(a, q, s0 + s)[lane] : 0.f;
+    }
+    // every lane stores and later reads back the same word: each reads its own store
+    __device__ __forceinline__ void put_sc(int q, const float *v) const {
+#pragma unroll
+        FOR_S if (live[s]) a.sc[(int64_t)q * a.rows + s0 + s] = v[s];
+    }
+    __device__ __forceinline__ void get_sc(int q, float *v) const {
+#pragma unroll
+        FOR_S v[s] = live[s] ? a.sc[(int64_t)q * a.rows + s0 + s] : 0.f;
+    }
+    // lane_forward's hooks
+    __device__ __forceinline__ void time_emb0(const float *pre, const float *act) {
+#pragma unroll
+        FOR_S a0[s] = pre[s];
+        put(R_E0, act);
+    }
+    __device__ __forceinline__ void time_emb1(const float *pre, const float *act) {
+#pragma unroll
+        FOR_S a1[s] = pre[s];
+        put(R_TEMB, act);
+    }
+    __device__ __forceinline__ void norm_in(const float *xh, const float *rs) { put(R_XHIN, xh); put_sc(0, rs); }
+    __device__ __forceinline__ void block_in(int bi, const float *h) { put(R_GLOBAL + bi * R_PER_BLOCK + B_H, h); }
+    __device__ __forceinline__ void norm1(int bi, const float *xh, const float *rs) { put(R_GLOBAL + bi * R_PER_BLOCK + B_XH1, xh); put_sc(1 + 2 * bi, rs); }
+    __device__ __forceinline__ void t_proj(int bi, const float *tp) { put(R_GLOBAL + bi * R_PER_BLOCK + B_TP, tp); }
+    __device__ __forceinline__ void block_mid(int bi, const float *y) { put(R_GLOBAL + bi * R_PER_BLOCK + B_Y, y); }
+    __device__ __forceinline__ void norm2(int bi, const float *xh, const float *rs) { put(R_GLOBAL + bi * R_PER_BLOCK + B_XH2, xh); put_sc(2 + 2 * bi, rs); }
+};
 
 __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
     __shared__ __attribute__((aligned(16))) float actT[NU * SPW];
@@ -79,111 +112,15 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
     const int lane = threadIdx.x;
     const int64_t s0 = (int64_t)blockIdx.x * SPW;
     const float *P = a.P;
-    const MlpOffsets &o = a.o, &fo = a.fo;
+    const MlpOffsets &o = a.o;
+    const MlpFlat &fo = a.fo;
     const int TE = a.TE, F = a.F;
-    bool live[SPW];
-#pragma unroll
-    FOR_S live[s] = s0 + s < a.rows;
-    auto put = [&](int q, const float v[SPW]) {
-#pragma unroll
-        FOR_S if (live[s]) rec_at(a, q, s0 + s)[lane] = v[s];
-    };
-    auto get = [&](int q, float v[SPW]) {
-#pragma unroll
-        FOR_S v[s] = live[s] ? rec_at(a, q, s0 + s)[lane] : 0.f;
-    };
-    // every lane stores and later reads back the same word: each reads its own store
-    auto put_sc = [&](int q, const float v[SPW]) {
-#pragma unroll
-        FOR_S if (live[s]) a.sc[(int64_t)q * a.rows + s0 + s] = v[s];
-    };
-    auto get_sc = [&](int q, float v[SPW]) {
-#pragma unroll
-        FOR_S v[s] = live[s] ? a.sc[(int64_t)q * a.rows + s0 + s] : 0.f;
-    };
+    RowRecords recs(a, lane, s0);
 
-    // ================================================================ forward, operation for operation as k_mlp_forward
-    float tv[SPW], a0[SPW], a1[SPW], tmp[SPW];
-#pragma unroll
-    FOR_S { tv[s] = live[s] ? a.t[s0 + s] : 0.f; a0[s] = 0.f; a1[s] = 0.f; tmp[s] = 0.f; }
-    if (lane < TE) {
-        const float w = P[o.te_w + lane], b = P[o.te_b + lane];
-#pragma unroll
-        FOR_S { a0[s] = fmaf(w, tv[s], b); tmp[s] = silu(a0[s]); actT[lane * SPW + s] = tmp[s]; }
-    }
-    put(R_E0, tmp);
-    __syncthreads();
-#pragma unroll
-    FOR_S tmp[s] = 0.f;
-    if (lane < TE) {
-        float acc[SPW];
-        const float b = P[o.tm_b + lane];
-#pragma unroll
-        FOR_S acc[s] = b;
-        for (int k = 0; k < TE; k++) {
-            const float w = P[o.tm_w + k * TE + lane];
-#pragma unroll
-            FOR_S acc[s] = fmaf(w, actT[k * SPW + s], acc[s]);
-        }
-#pragma unroll
-        FOR_S { a1[s] = acc[s]; tmp[s] = silu(acc[s]); tembT[lane * SPW + s] = tmp[s]; }
-    }
-    put(R_TEMB, tmp);
-    __syncthreads();
-
+    // ================================================================ forward: lane_forward, as k_mlp_forward runs it
     float h[SPW], xh[SPW], rs[SPW];
-    {
-        const float b = P[o.in_b + lane];
-#pragma unroll
-        FOR_S h[s] = b;
-        for (int f = 0; f < F; f++) {
-            const float w = P[o.in_w + f * NU + lane];
-#pragma unroll
-            FOR_S h[s] = fmaf(w, live[s] ? a.x[(s0 + s) * F + f] : 0.f, h[s]);
-        }
-        layer_norm_keep(h, P[o.in_g + lane], P[o.in_be + lane], xh, rs);
-        put(R_XHIN, xh);
-        put_sc(0, rs);
-#pragma unroll
-        FOR_S h[s] = silu(h[s]);
-    }
-    for (int bi = 0; bi < a.nblk; bi++) {
-        const float *Q = P + o.blk0 + (int64_t)bi * o.blk_stride;
-        const int rb = R_GLOBAL + bi * R_PER_BLOCK;
-        put(rb + B_H, h);
-#pragma unroll
-        FOR_S actT[lane * SPW + s] = h[s];
-        __syncthreads();
-        float y[SPW], tp[SPW];
-        const float b1 = Q[o.b_b1 + lane], tb = Q[o.b_tb + lane];
-#pragma unroll
-        FOR_S { y[s] = b1; tp[s] = tb; }
-        matvec(Q + o.b_w1, NU, actT, lane, y);
-        layer_norm_keep(y, Q[o.b_g1 + lane], Q[o.b_be1 + lane], xh, rs);
-        put(rb + B_XH1, xh);
-        put_sc(1 + 2 * bi, rs);
-        matvec(Q + o.b_tw, TE, tembT, lane, tp);
-        put(rb + B_TP, tp);
-#pragma unroll
-        FOR_S y[s] = silu(y[s]) + silu(tp[s]);
-        put(rb + B_Y, y);
-        __syncthreads();
-#pragma unroll
-        FOR_S actT[lane * SPW + s] = y[s];
-        __syncthreads();
-        float z[SPW];
-        const float b2 = Q[o.b_b2 + lane];
-#pragma unroll
-        FOR_S z[s] = b2;
-        matvec(Q + o.b_w2, NU, actT, lane, z);
-        layer_norm_keep(z, Q[o.b_g2 + lane], Q[o.b_be2 + lane], xh, rs);
-        put(rb + B_XH2, xh);
-        put_sc(2 + 2 * bi, rs);
-#pragma unroll
-        FOR_S h[s] = silu(z[s] + h[s]);
-        __syncthreads();
-    }
-    put(R_HFIN, h);
+    lane_forward(P, o, a.x, a.t, a.rows, F, TE, a.nblk, lane, s0, actT, tembT, h, recs);
+    recs.put(R_HFIN, h);
 
     // ================================================================ backward
     float dh[SPW], dtemb[SPW];
@@ -192,7 +129,7 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
     for (int f = 0; f < F; f++) {      // out[f] = sum_n out_w[f][n] h[n] + b[f]
         const float w = P[o.out_w + f * NU + lane];
 #pragma unroll
-        FOR_S dh[s] = fmaf(w, live[s] ? a.dout[(s0 + s) * F + f] : 0.f, dh[s]);
+        FOR_S dh[s] = fmaf(w, recs.live[s] ? a.dout[(s0 + s) * F + f] : 0.f, dh[s]);
     }
     for (int bi = a.nblk - 1; bi >= 0; bi--) {
         const float *Q = P + o.blk0 + (int64_t)bi * o.blk_stride;
@@ -200,15 +137,15 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
         const int rb = R_GLOBAL + bi * R_PER_BLOCK;
         float hin[SPW], ds[SPW], dz[SPW];
         // h_out = silu(LN2(W2 y + b2) + h_in)
-        get(rb + B_H, hin);
-        get(rb + B_XH2, xh);
-        get_sc(2 + 2 * bi, rs);
+        recs.get(rb + B_H, hin);
+        recs.get(rb + B_XH2, xh);
+        recs.get_sc(2 + 2 * bi, rs);
         const float g2 = Q[o.b_g2 + lane], be2 = Q[o.b_be2 + lane];
 #pragma unroll
         FOR_S ds[s] = dh[s] * dsilu(xh[s] * g2 + be2 + hin[s]);
-        put(rb + B_DLN2, ds);
+        recs.put(rb + B_DLN2, ds);
         layer_norm_back(ds, xh, rs, g2, dz);
-        put(rb + B_DZ2, dz);
+        recs.put(rb + B_DZ2, dz);
 #pragma unroll
         FOR_S gT[lane * SPW + s] = dz[s];
         __syncthreads();
@@ -218,14 +155,14 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
         matvec(WQ + fo.b_w2, NU, gT, lane, dy);       // dy[k] = sum_n W2[n][k] dz[n]
         // y = silu(LN1(W1 h_in + b1)) + silu(Wt temb + tb)
         float tp[SPW], du[SPW], dtp[SPW];
-        get(rb + B_XH1, xh);
-        get_sc(1 + 2 * bi, rs);
-        get(rb + B_TP, tp);
+        recs.get(rb + B_XH1, xh);
+        recs.get_sc(1 + 2 * bi, rs);
+        recs.get(rb + B_TP, tp);
         const float g1 = Q[o.b_g1 + lane], be1 = Q[o.b_be1 + lane];
 #pragma unroll
         FOR_S { du[s] = dy[s] * dsilu(xh[s] * g1 + be1); dtp[s] = dy[s] * dsilu(tp[s]); }
-        put(rb + B_DLN1, du);
-        put(rb + B_DTP, dtp);
+        recs.put(rb + B_DLN1, du);
+        recs.put(rb + B_DTP, dtp);
         __syncthreads();
 #pragma unroll
         FOR_S gT[lane * SPW + s] = dtp[s];
@@ -242,7 +179,7 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
             }
         }
         layer_norm_back(du, xh, rs, g1, dz);
-        put(rb + B_DZ1, dz);
+        recs.put(rb + B_DZ1, dz);
         __syncthreads();
 #pragma unroll
         FOR_S gT[lane * SPW + s] = dz[s];
@@ -254,29 +191,29 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
     }
     {   // h_0 = silu(LN(W_in x + b))
         float du[SPW], dz[SPW];
-        get(R_XHIN, xh);
-        get_sc(0, rs);
+        recs.get(R_XHIN, xh);
+        recs.get_sc(0, rs);
         const float g = P[o.in_g + lane], be = P[o.in_be + lane];
 #pragma unroll
         FOR_S du[s] = dh[s] * dsilu(xh[s] * g + be);
-        put(R_DLNIN, du);
+        recs.put(R_DLNIN, du);
         layer_norm_back(du, xh, rs, g, dz);
-        put(R_DZIN, dz);
+        recs.put(R_DZIN, dz);
         if (a.dx)
             for (int f = 0; f < F; f++) {
                 const float w = P[o.in_w + f * NU + lane];
 #pragma unroll
                 FOR_S {
                     const float r = wave_sum(w * dz[s]);
-                    if (lane == 0 && live[s]) a.dx[(s0 + s) * F + f] = r;
+                    if (lane == 0 && recs.live[s]) a.dx[(s0 + s) * F + f] = r;
                 }
             }
     }
     {   // temb = silu(a1), a1 = Wtm e0 + b, e0 = silu(a0), a0 = w t + b
         float da1[SPW], da0[SPW];
 #pragma unroll
-        FOR_S { da1[s] = lane < TE ? dtemb[s] * dsilu(a1[s]) : 0.f; da0[s] = 0.f; }
-        put(R_DA1, da1);
+        FOR_S { da1[s] = lane < TE ? dtemb[s] * dsilu(recs.a1[s]) : 0.f; da0[s] = 0.f; }
+        recs.put(R_DA1, da1);
 #pragma unroll
         FOR_S gT[lane * SPW + s] = da1[s];
         __syncthreads();
@@ -289,9 +226,9 @@ __global__ void __launch_bounds__(64) k_mlp_backward_rows(BwdArgs a) {
                 FOR_S de[s] = fmaf(w, gT[n * SPW + s], de[s]);
             }
 #pragma unroll
-            FOR_S da0[s] = de[s] * dsilu(a0[s]);
+            FOR_S da0[s] = de[s] * dsilu(recs.a0[s]);
         }
-        put(R_DA0, da0);
+        recs.put(R_DA0, da0);
     }
 }
 
@@ -306,7 +243,7 @@ struct Job {
 
 __device__ Job job_of(const BwdArgs &a, int j) {
     Job b;
-    const MlpOffsets &fo = a.fo;
+    const MlpFlat &fo = a.fo;
     b.Y = nullptr; b.A = nullptr; b.Ad = nullptr;
     b.ldA = NU; b.K = 0; b.nmax = NU; b.outW = 0; b.sN = 0; b.sK = 0; b.outC = -1; b.outD = -1;
     const int F = a.F, TE = a.TE;
@@ -392,71 +329,28 @@ __global__ void __launch_bounds__(256) k_mlp_wgrad_sum(const float *__restrict__
     grad[i] = (float)s;
 }
 
-// ------------------------------------------------------------------------------------------------ layout
-// the flat offsets, in named_parameters() order; returns P
-int64_t flat_offsets(const dlpm_mlp *m, MlpOffsets &f) {
-    const int TE = m->TE, F = m->F;
-    int p = 0;
-    auto take = [&](int n) { int r = p; p += n; return r; };
-    f.in_g = take(NU); f.in_be = take(NU);
-    f.te_w = take(TE); f.te_b = take(TE);
-    f.tm_w = take(TE * TE); f.tm_b = take(TE);
-    f.in_w = take(NU * F); f.in_b = take(NU);
-    int q = 0;
-    auto takeb = [&](int n) { int r = q; q += n; return r; };
-    f.b_g1 = takeb(NU); f.b_be1 = takeb(NU); f.b_g2 = takeb(NU); f.b_be2 = takeb(NU);
-    f.b_w1 = takeb(NU * NU); f.b_b1 = takeb(NU);
-    f.b_tw = takeb(NU * TE); f.b_tb = takeb(NU);
-    f.b_w2 = takeb(NU * NU); f.b_b2 = takeb(NU);
-    f.blk_stride = q;
-    f.blk0 = take(q * (m->nblocks + 1));
-    f.out_w = take(F * NU); f.out_b = take(F);
-    return p;
-}
-
-// map[i] = index in the blob of element i of the flat vector
-std::vector<int32_t> flat_to_blob(const dlpm_mlp *m) {
-    MlpOffsets f;
-    const int64_t P = flat_offsets(m, f);
-    const MlpOffsets &o = m->off;
-    const int TE = m->TE, F = m->F;
-    std::vector<int32_t> map(P, -1);
-    auto vec = [&](int fo, int bo, int n) { for (int i = 0; i < n; i++) map[fo + i] = bo + i; };
-    // a Linear weight [N][K] in the flat vector, transposed to [K][ld] in the blob
-    auto mat = [&](int fo, int bo, int N, int K, int ld) {
-        for (int n = 0; n < N; n++)
-            for (int k = 0; k < K; k++) map[fo + n * K + k] = bo + k * ld + n;
-    };
-    vec(f.in_g, o.in_g, NU); vec(f.in_be, o.in_be, NU);
-    vec(f.te_w, o.te_w, TE); vec(f.te_b, o.te_b, TE);
-    mat(f.tm_w, o.tm_w, TE, TE, TE); vec(f.tm_b, o.tm_b, TE);
-    mat(f.in_w, o.in_w, NU, F, NU); vec(f.in_b, o.in_b, NU);
-    for (int bi = 0; bi <= m->nblocks; bi++) {
-        const int fb = f.blk0 + bi * f.blk_stride, ob = o.blk0 + bi * o.blk_stride;
-        vec(fb + f.b_g1, ob + o.b_g1, NU); vec(fb + f.b_be1, ob + o.b_be1, NU);
-        vec(fb + f.b_g2, ob + o.b_g2, NU); vec(fb + f.b_be2, ob + o.b_be2, NU);
-        mat(fb + f.b_w1, ob + o.b_w1, NU, NU, NU); vec(fb + f.b_b1, ob + o.b_b1, NU);
-        mat(fb + f.b_tw, ob + o.b_tw, NU, TE, NU); vec(fb + f.b_tb, ob + o.b_tb, NU);
-        mat(fb + f.b_w2, ob + o.b_w2, NU, NU, NU); vec(fb + f.b_b2, ob + o.b_b2, NU);
-    }
-    vec(f.out_w, o.out_w, F * NU); vec(f.out_b, o.out_b, F);      // the blob keeps outblocks_mean.1.weight as [F][64]
-    return map;
-}
-
-__global__ void __launch_bounds__(256) k_flat_gather(const float *__restrict__ blob, const int32_t *__restrict__ map,
+// ------------------------------------------------------------------------------------------------ the flat parameter vector
+// torch's parameters_to_vector(model.parameters()) of either kind of handle (mlp_pack.h: MlpFlat and the two maps into the blobs)
+__global__ void __launch_bounds__(256) k_flat_gather(const float *__restrict__ blob, const int64_t *__restrict__ map,
                                                      float *__restrict__ flat, int64_t P) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < P) flat[i] = blob[map[i]];
 }
 
-// blob <- flat and the handle's own flat copy <- flat
-__global__ void __launch_bounds__(256) k_flat_scatter(const float *__restrict__ flat, const int32_t *__restrict__ map,
-                                                      float *__restrict__ blob, float *__restrict__ keep, int64_t P) {
+// blob <- flat, through map and, where there is one, the second map (a general handle's transposed operands; -1: no second place),
+// then the handle's own flat copy <- flat where it keeps one.  Padded elements are never written, so they stay 0.
+__global__ void __launch_bounds__(256) k_flat_scatter(const float *__restrict__ flat, const int64_t *__restrict__ map,
+                                                      const int64_t *__restrict__ map2, float *__restrict__ blob,
+                                                      float *__restrict__ keep, int64_t P) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < P) {
         const float v = flat[i];
         blob[map[i]] = v;
-        keep[i] = v;
+        if (map2) {
+            const int64_t t = map2[i];
+            if (t >= 0) blob[t] = v;
+        }
+        if (keep) keep[i] = v;
     }
 }
 
@@ -469,115 +363,136 @@ __global__ void __launch_bounds__(256) k_q4_refresh(const float *__restrict__ bl
     q4[i] = make_float4(src[(4 * kq + 0) * NU + u], src[(4 * kq + 1) * NU + u], src[(4 * kq + 2) * NU + u], src[(4 * kq + 3) * NU + u]);
 }
 
-// the handle's flat copy and map, allocated on the first training call; the copy regathered when finalize() made it stale
+// a lane handle's flat copy and map, allocated on the first training call; the copy regathered when finalize() made it stale
 int ensure_flat(dlpm_mlp *m, hipStream_t st) {
-    MlpOffsets f;
-    const int64_t P = flat_offsets(m, f);
+    const MlpFlat f = mlp_flat_of(m);
     if (!m->flat_map) {
-        const std::vector<int32_t> map = flat_to_blob(m);
-        for (int32_t v : map)
-            if (v < 0) {
+        std::vector<int64_t> map((size_t)f.P);
+        mlp_lane_flat_map(m->off, f, m->F, m->TE, m->nblocks, map.data());
+        for (int64_t v : map)
+            if (v < 0 || v >= m->blob_floats) {
                 set_error("dlpm_mlp: internal error: the flat parameter map has a hole");
                 return DLPM_ERR_STATE;
             }
-        DLPM_HIP(hipMalloc(&m->flat_map, P * sizeof(int32_t)));
-        DLPM_HIP(hipMemcpy(m->flat_map, map.data(), P * sizeof(int32_t), hipMemcpyHostToDevice));
+        DLPM_HIP(hipMalloc(&m->flat_map, f.P * sizeof(int64_t)));
+        DLPM_HIP(hipMemcpy(m->flat_map, map.data(), f.P * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     if (!m->flat) {
-        DLPM_HIP(hipMalloc(&m->flat, P * sizeof(float)));
+        DLPM_HIP(hipMalloc(&m->flat, f.P * sizeof(float)));
         m->flat_valid = false;
     }
     if (!m->flat_valid) {
-        k_flat_gather<<<(unsigned)ceil_div(P, 256), 256, 0, st>>>(m->dev, m->flat_map, m->flat, P);
+        k_flat_gather<<<(unsigned)ceil_div(f.P, 256), 256, 0, st>>>(m->dev, m->flat_map, m->flat, f.P);
         DLPM_LAUNCH_CHECK();
         m->flat_valid = true;
     }
     return DLPM_OK;
 }
 
+// a general handle's map into both regions of its blob, built and uploaded on the first call that needs it; it keeps no flat copy
+int ensure_map(dlpm_mlp *m) {
+    if (m->gen_map) return DLPM_OK;
+    const MlpFlat f = mlp_flat_of(m);
+    const MlpGenGradLayout G = mlp_gen_grad_layout(m->gen);
+    std::vector<int64_t> map((size_t)(2 * f.P));
+    mlp_general_flat_map(m->gen, G, f, map.data(), map.data() + f.P);
+    for (int64_t i = 0; i < f.P; i++)
+        if (map[i] < 0 || map[i] >= m->gen.total || map[f.P + i] >= m->gen.total + G.total) {
+            set_error("dlpm_mlp_grad: internal error: the flat parameter map has a hole");
+            return DLPM_ERR_STATE;
+        }
+    DLPM_HIP(hipMalloc(&m->gen_map, map.size() * sizeof(int64_t)));
+    DLPM_HIP(hipMemcpy(m->gen_map, map.data(), map.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    return DLPM_OK;
+}
+
 int64_t backward_floats(const dlpm_mlp *m, int64_t rows, int64_t *rec_floats, int64_t *sc_floats) {
-    MlpOffsets f;
-    const int64_t P = flat_offsets(m, f);
     const int nb = m->nblocks + 1;
     const int64_t rec = (int64_t)(R_GLOBAL + nb * R_PER_BLOCK) * rows * NU;
     const int64_t sc = ((int64_t)(1 + 2 * nb) * rows + 3) / 4 * 4;
     if (rec_floats) *rec_floats = rec;
     if (sc_floats) *sc_floats = sc;
-    return rec + sc + ceil_div(rows, RC) * P;
+    return rec + sc + ceil_div(rows, RC) * mlp_flat_of(m).P;
 }
 
-}  // namespace
-
-extern "C" int64_t dlpm_mlp_param_floats(const dlpm_mlp *m) {
+// ------------------------------------------------------------------------------------------------ the five operations
+// Each serves its entry point of dlpm_amd_train.h (lane_only: the fused trainer's, which refuses a general handle) and of
+// dlpm_amd_mlp_grad.h (either kind of handle); `name` is the entry point, for the messages.
+int64_t param_floats(const dlpm_mlp *m, const char *name, bool lane_only) {
     if (!m) return -1;
-    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_param_floats", "training");
-    MlpOffsets f;
-    return flat_offsets(m, f);
+    if (lane_only) DLPM_MLP_REFUSE_GENERAL(m, name, "training");
+    return mlp_flat_of(m).P;
 }
 
-#define TRAIN_NEED_FINALIZED(m, name)                              \
-    do {                                                           \
-        if (!(m)->finalized) {                                     \
-            set_error(name ": call dlpm_mlp_finalize first");      \
-            return DLPM_ERR_STATE;                                 \
-        }                                                          \
-    } while (0)
-
-extern "C" int dlpm_mlp_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t n, dlpm_stream_t stream) {
-    DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_export_params_f32: null argument");
-    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_export_params_f32", "training");
-    DLPM_CHECK_ARG(n == dlpm_mlp_param_floats(m), "dlpm_mlp_export_params_f32: n = %lld, the net has %lld parameters", (long long)n,
-                   (long long)dlpm_mlp_param_floats(m));
-    TRAIN_NEED_FINALIZED(m, "dlpm_mlp_export_params_f32");
+int export_params(dlpm_mlp *m, const char *name, bool lane_only, float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(m && flat_dev, "%s: null argument", name);
+    if (lane_only) DLPM_MLP_REFUSE_GENERAL(m, name, "training");
+    const int64_t P = mlp_flat_of(m).P;
+    DLPM_CHECK_ARG(n == P, "%s: n = %lld, the net has %lld parameters", name, (long long)n, (long long)P);
+    DLPM_MLP_NEED_FINALIZED(m, name);
     hipStream_t st = as_stream(stream);
-    if (int rc = ensure_flat(m, st)) return rc;
-    DLPM_HIP(hipMemcpyAsync(flat_dev, m->flat, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (m->general) {
+        if (int rc = ensure_map(m)) return rc;
+        k_flat_gather<<<(unsigned)ceil_div(P, 256), 256, 0, st>>>(m->gen_dev, m->gen_map, flat_dev, P);
+        DLPM_LAUNCH_CHECK();
+    } else {
+        if (int rc = ensure_flat(m, st)) return rc;
+        DLPM_HIP(hipMemcpyAsync(flat_dev, m->flat, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
     return DLPM_OK;
 }
 
-extern "C" int dlpm_mlp_import_params_f32(dlpm_mlp *m, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
-    DLPM_CHECK_ARG(m && flat_dev, "dlpm_mlp_import_params_f32: null argument");
-    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_import_params_f32", "training");
-    DLPM_CHECK_ARG(n == dlpm_mlp_param_floats(m), "dlpm_mlp_import_params_f32: n = %lld, the net has %lld parameters", (long long)n,
-                   (long long)dlpm_mlp_param_floats(m));
-    TRAIN_NEED_FINALIZED(m, "dlpm_mlp_import_params_f32");
+int import_params(dlpm_mlp *m, const char *name, bool lane_only, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(m && flat_dev, "%s: null argument", name);
+    if (lane_only) DLPM_MLP_REFUSE_GENERAL(m, name, "training");
+    const int64_t P = mlp_flat_of(m).P;
+    DLPM_CHECK_ARG(n == P, "%s: n = %lld, the net has %lld parameters", name, (long long)n, (long long)P);
+    DLPM_MLP_NEED_FINALIZED(m, name);
     hipStream_t st = as_stream(stream);
-    if (int rc = ensure_flat(m, st)) return rc;
-    k_flat_scatter<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(flat_dev, m->flat_map, m->dev, m->flat, n);
-    DLPM_LAUNCH_CHECK();
-    const int nb = m->nblocks + 1;
-    k_q4_refresh<<<(unsigned)ceil_div((int64_t)nb * 2 * (NU / 4) * NU, 256), 256, 0, st>>>(m->dev, m->off, m->q4, nb);
-    DLPM_LAUNCH_CHECK();
-    m->tp_T = 0;
+    if (m->general) {
+        if (int rc = ensure_map(m)) return rc;
+        k_flat_scatter<<<(unsigned)ceil_div(P, 256), 256, 0, st>>>(flat_dev, m->gen_map, m->gen_map + P, m->gen_dev, nullptr, P);
+        DLPM_LAUNCH_CHECK();
+    } else {
+        if (int rc = ensure_flat(m, st)) return rc;
+        k_flat_scatter<<<(unsigned)ceil_div(P, 256), 256, 0, st>>>(flat_dev, m->flat_map, nullptr, m->dev, m->flat, P);
+        DLPM_LAUNCH_CHECK();
+        const int nb = m->nblocks + 1;
+        k_q4_refresh<<<(unsigned)ceil_div((int64_t)nb * 2 * (NU / 4) * NU, 256), 256, 0, st>>>(m->dev, m->off, m->q4, nb);
+        DLPM_LAUNCH_CHECK();
+        m->tp_T = 0;
+    }
     return DLPM_OK;
 }
 
-extern "C" int64_t dlpm_mlp_backward_workspace_bytes(const dlpm_mlp *m, int64_t rows) {
+int64_t workspace_bytes(const dlpm_mlp *m, const char *name, bool lane_only, int64_t rows) {
     if (!m || rows <= 0) return -1;
-    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_backward_workspace_bytes", "training");
+    if (lane_only) DLPM_MLP_REFUSE_GENERAL(m, name, "training");
+    if (m->general) return mlp_general_workspace_bytes(m, name, rows);
     return backward_floats(m, rows, nullptr, nullptr) * (int64_t)sizeof(float);
 }
 
-extern "C" int dlpm_mlp_backward_f32(dlpm_mlp *m, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
-                                     float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes,
-                                     dlpm_stream_t stream) {
-    DLPM_CHECK_ARG(m && x_dev && t_dev && dout_dev && grad_flat_dev && workspace_dev, "dlpm_mlp_backward_f32: null argument");
-    DLPM_CHECK_ARG(rows > 0, "dlpm_mlp_backward_f32: rows must be positive (got %lld)", (long long)rows);
-    DLPM_MLP_REFUSE_GENERAL(m, "dlpm_mlp_backward_f32", "training");
-    DLPM_CHECK_ARG(ceil_div(rows, SPW) < (1ll << 31) && ceil_div(rows, RC) <= 65535, "dlpm_mlp_backward_f32: rows = %lld is beyond "
-                   "the grid of one call (at most %d)", (long long)rows, 65535 * RC);
+int backward(dlpm_mlp *m, const char *name, bool lane_only, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
+             float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes, dlpm_stream_t stream) {
+    DLPM_CHECK_ARG(m && x_dev && t_dev && dout_dev && grad_flat_dev && workspace_dev, "%s: null argument", name);
+    DLPM_CHECK_ARG(rows > 0, "%s: rows must be positive (got %lld)", name, (long long)rows);
+    if (lane_only) DLPM_MLP_REFUSE_GENERAL(m, name, "training");
+    hipStream_t st = as_stream(stream);
+    if (m->general)
+        return mlp_general_backward(m, name, x_dev, t_dev, dout_dev, rows, grad_flat_dev, dx_dev, workspace_dev, workspace_bytes, st);
+    DLPM_CHECK_ARG(ceil_div(rows, SPW) < (1ll << 31) && ceil_div(rows, RC) <= 65535, "%s: rows = %lld is beyond the grid of one call "
+                   "(at most %d)", name, (long long)rows, 65535 * RC);
     int64_t rec_floats, sc_floats;
     const int64_t need = backward_floats(m, rows, &rec_floats, &sc_floats) * (int64_t)sizeof(float);
     if (workspace_bytes < need) {
-        set_error("dlpm_mlp_backward_f32: the workspace has %lld bytes, %lld are needed", (long long)workspace_bytes, (long long)need);
+        set_error("%s: the workspace has %lld bytes, %lld are needed", name, (long long)workspace_bytes, (long long)need);
         return DLPM_ERR_NOMEM;
     }
-    TRAIN_NEED_FINALIZED(m, "dlpm_mlp_backward_f32");
-    hipStream_t st = as_stream(stream);
+    DLPM_MLP_NEED_FINALIZED(m, name);
     if (int rc = ensure_flat(m, st)) return rc;
     BwdArgs a;
-    a.P = m->dev; a.W = m->flat; a.o = m->off;
-    a.nparam = flat_offsets(m, a.fo);
+    a.P = m->dev; a.W = m->flat; a.o = m->off; a.fo = mlp_flat_of(m);
+    a.nparam = a.fo.P;
     a.x = x_dev; a.t = t_dev; a.dout = dout_dev; a.dx = dx_dev;
     a.rec = static_cast<float *>(workspace_dev); a.sc = a.rec + rec_floats; a.part = a.sc + sc_floats;
     a.rows = rows; a.F = m->F; a.TE = m->TE; a.nblk = m->nblocks + 1;
@@ -589,6 +504,45 @@ extern "C" int dlpm_mlp_backward_f32(dlpm_mlp *m, const float *x_dev, const floa
     k_mlp_wgrad_sum<<<(unsigned)ceil_div(a.nparam, 256), 256, 0, st>>>(a.part, grad_flat_dev, a.nparam, chunks);
     DLPM_LAUNCH_CHECK();
     return DLPM_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t dlpm_mlp_param_floats(const dlpm_mlp *m) { return param_floats(m, "dlpm_mlp_param_floats", true); }
+extern "C" int64_t dlpm_mlp_grad_param_floats(const dlpm_mlp *m) { return param_floats(m, "dlpm_mlp_grad_param_floats", false); }
+
+extern "C" int dlpm_mlp_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    return export_params(m, "dlpm_mlp_export_params_f32", true, flat_dev, n, stream);
+}
+extern "C" int dlpm_mlp_grad_export_params_f32(dlpm_mlp *m, float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    return export_params(m, "dlpm_mlp_grad_export_params_f32", false, flat_dev, n, stream);
+}
+
+extern "C" int dlpm_mlp_import_params_f32(dlpm_mlp *m, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    return import_params(m, "dlpm_mlp_import_params_f32", true, flat_dev, n, stream);
+}
+extern "C" int dlpm_mlp_grad_import_params_f32(dlpm_mlp *m, const float *flat_dev, int64_t n, dlpm_stream_t stream) {
+    return import_params(m, "dlpm_mlp_grad_import_params_f32", false, flat_dev, n, stream);
+}
+
+extern "C" int64_t dlpm_mlp_backward_workspace_bytes(const dlpm_mlp *m, int64_t rows) {
+    return workspace_bytes(m, "dlpm_mlp_backward_workspace_bytes", true, rows);
+}
+extern "C" int64_t dlpm_mlp_grad_workspace_bytes(const dlpm_mlp *m, int64_t rows) {
+    return workspace_bytes(m, "dlpm_mlp_grad_workspace_bytes", false, rows);
+}
+
+extern "C" int dlpm_mlp_backward_f32(dlpm_mlp *m, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
+                                     float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes,
+                                     dlpm_stream_t stream) {
+    return backward(m, "dlpm_mlp_backward_f32", true, x_dev, t_dev, dout_dev, rows, grad_flat_dev, dx_dev, workspace_dev, workspace_bytes,
+                    stream);
+}
+extern "C" int dlpm_mlp_grad_backward_f32(dlpm_mlp *m, const float *x_dev, const float *t_dev, const float *dout_dev, int64_t rows,
+                                          float *grad_flat_dev, float *dx_dev, void *workspace_dev, int64_t workspace_bytes,
+                                          dlpm_stream_t stream) {
+    return backward(m, "dlpm_mlp_grad_backward_f32", false, x_dev, t_dev, dout_dev, rows, grad_flat_dev, dx_dev, workspace_dev,
+                    workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ loss gradient

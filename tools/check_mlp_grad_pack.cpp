@@ -1,5 +1,5 @@
-// check_mlp_grad_pack.cpp -- the host-side layout of the general toy-net backward (dlpm_amd/csrc/mlp_pack.h) as a stand-alone
-// program, meant for a host sanitizer:
+// check_mlp_grad_pack.cpp -- the host-side layout of the toy net's flat parameter vector and backward (dlpm_amd/csrc/mlp_pack.h)
+// as a stand-alone program, meant for a host sanitizer:
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I dlpm_amd/csrc tools/check_mlp_grad_pack.cpp -o check_mlp_grad_pack
 //     ./check_mlp_grad_pack
 // For the 72- and the 264-unit nets of tests/mlp_general_refs.py, with and without LayerNorm, and at the caps it fills a flat
@@ -11,6 +11,9 @@
 //   - the flat map is a bijection onto the real elements of the forward region, and onto those of the transposed region for the
 //     four hidden Linears;
 //   - the per-row records do not overlap, the slots cover every row once, and the LDS budget holds.
+// For the lane kernels' 64-unit net (nfeatures 1, 2, 4 x time_emb_size 8, 32, 64 x nblocks 0, 1, 4) it checks the flat map into the
+// lane blob the same way: every flat element has exactly one blob element, inside the blob, and a scatter through the map puts every
+// tensor where the kernels read it (a Linear weight transposed, [k][unit]).
 // Exit status 0 and "ok" when all of it holds.
 #include <cstdio>
 #include <cstdlib>
@@ -59,7 +62,7 @@ static void check_operand(const std::vector<float> &blob, int64_t off, const cha
 static void check_net(int F, int NU, int TE, int nblocks, bool ln) {
     const MlpGenLayout L = mlp_gen_layout(F, NU, TE, nblocks);
     const MlpGenGradLayout G = mlp_gen_grad_layout(L);
-    const MlpGenFlat f = mlp_gen_flat(F, NU, TE, nblocks, ln);
+    const MlpFlat f = mlp_flat(F, NU, TE, nblocks, ln);
     const int64_t total = L.total + G.total;
     CHECK(G.base == L.total && G.base % 4 == 0, "the second region does not start behind the first on a 16-byte boundary");
 
@@ -72,7 +75,7 @@ static void check_net(int F, int NU, int TE, int nblocks, bool ln) {
 
     // ---- the map: in range, injective into each region
     std::vector<int64_t> fwd((size_t)f.P), tr((size_t)f.P);      // exactly P each: a write past the end is the sanitizer's
-    mlp_gen_flat_map(L, G, f, fwd.data(), tr.data());
+    mlp_general_flat_map(L, G, f, fwd.data(), tr.data());
     std::vector<char> owner((size_t)total, 0);
     int64_t with_t = 0;
     for (int64_t i = 0; i < f.P; i++) {
@@ -192,6 +195,56 @@ static void check_net(int F, int NU, int TE, int nblocks, bool ln) {
                 (long long)mlp_gen_grad_lds_bytes(L, 32));
 }
 
+// the lane kernels' blob (mlp_lane_offsets) and the flat vector's map into it (mlp_lane_flat_map)
+static void check_lane_net(int F, int TE, int nblocks) {
+    int total = 0;
+    const MlpOffsets o = mlp_lane_offsets(F, TE, nblocks, &total);
+    const MlpFlat f = mlp_flat(F, LANE_NU, TE, nblocks, true);
+    constexpr int NU = LANE_NU;
+    const int64_t per_block = 4 * NU + 2 * ((int64_t)NU * NU + NU) + (int64_t)NU * TE + NU;
+    const int64_t P = 2 * NU + 2 * TE + (int64_t)TE * TE + TE + (int64_t)NU * F + NU + per_block * (nblocks + 1) + (int64_t)F * NU + F;
+    CHECK(f.P == P, "lane net: the flat vector has %lld floats, the modules %lld", (long long)f.P, (long long)P);
+    std::vector<int64_t> map((size_t)f.P);                       // exactly P: a write past the end is the sanitizer's
+    mlp_lane_flat_map(o, f, F, TE, nblocks, map.data());
+    std::vector<float> blob((size_t)total, 0.0f);
+    int64_t holes = 0;
+    for (int64_t i = 0; i < f.P; i++) {
+        if (map[i] < 0) { holes++; continue; }
+        CHECK(map[i] < total, "lane net: flat %lld maps to %lld, outside the blob of %d floats", (long long)i, (long long)map[i], total);
+        if (map[i] >= total) continue;
+        CHECK(blob[map[i]] == 0.0f, "lane net: two parameters map to blob float %lld", (long long)map[i]);
+        blob[map[i]] = tag(i);
+    }
+    CHECK(holes == 0, "lane net: the flat map has %lld holes", (long long)holes);
+    int64_t nonzero = 0;
+    for (int i = 0; i < total; i++) nonzero += blob[i] != 0.0f;
+    CHECK(nonzero == f.P, "lane net: %lld floats of the blob are set, %lld expected", (long long)nonzero, (long long)f.P);
+    // every tensor where the kernels read it
+    auto vector = [&](const char *name, int64_t fo, int bo, int n) {
+        for (int i = 0; i < n; i++) CHECK(blob[bo + i] == tag(fo + i), "lane net %s: element %d is %g", name, i, blob[bo + i]);
+    };
+    auto linear = [&](const char *name, int64_t fo, int bo, int N, int K, int ld) {      // W[n][k] at blob[k * ld + n]
+        for (int n = 0; n < N; n++)
+            for (int k = 0; k < K; k++)
+                CHECK(blob[bo + k * ld + n] == tag(fo + (int64_t)n * K + k), "lane net %s: element (%d, %d) is %g", name, n, k, blob[bo + k * ld + n]);
+    };
+    vector("group_norm_in.weight", f.in_g, o.in_g, NU); vector("group_norm_in.bias", f.in_be, o.in_be, NU);
+    vector("time_emb.weight", f.te_w, o.te_w, TE); vector("time_emb.bias", f.te_b, o.te_b, TE);
+    linear("time_mlp.2.weight", f.tm_w, o.tm_w, TE, TE, TE); vector("time_mlp.2.bias", f.tm_b, o.tm_b, TE);
+    linear("linear_in.weight", f.in_w, o.in_w, NU, F, NU); vector("linear_in.bias", f.in_b, o.in_b, NU);
+    for (int bi = 0; bi <= nblocks; bi++) {
+        const int64_t fb = f.blk0 + bi * f.blk_stride;
+        const int b = o.blk0 + bi * o.blk_stride;
+        vector("group_norm1.weight", fb + f.b_g1, b + o.b_g1, NU); vector("group_norm1.bias", fb + f.b_be1, b + o.b_be1, NU);
+        vector("group_norm2.weight", fb + f.b_g2, b + o.b_g2, NU); vector("group_norm2.bias", fb + f.b_be2, b + o.b_be2, NU);
+        linear("mlp_1.1.weight", fb + f.b_w1, b + o.b_w1, NU, NU, NU); vector("mlp_1.1.bias", fb + f.b_b1, b + o.b_b1, NU);
+        linear("t_proj.1.weight", fb + f.b_tw, b + o.b_tw, NU, TE, NU); vector("t_proj.1.bias", fb + f.b_tb, b + o.b_tb, NU);
+        linear("mlp_2.1.weight", fb + f.b_w2, b + o.b_w2, NU, NU, NU); vector("mlp_2.1.bias", fb + f.b_b2, b + o.b_b2, NU);
+    }
+    vector("outblocks_mean.1.weight", f.out_w, o.out_w, F * NU); vector("outblocks_mean.1.bias", f.out_b, o.out_b, F);
+    std::printf("lane net  TE %2d  F %d  blocks %d+1: P %lld, blob %d floats\n", TE, F, nblocks, (long long)f.P, total);
+}
+
 int main() {
     check_net(2, 72, 32, 1, true);       // not a multiple of 16
     check_net(2, 72, 32, 1, false);
@@ -199,6 +252,9 @@ int main() {
     check_net(2, 264, 130, 1, true);
     check_net(64, 1024, 1024, 0, true);  // every cap at once
     check_net(1, 1, 1, 0, true);
+    for (int F : {1, 2, 4})
+        for (int TE : {8, 32, 64})
+            for (int nblocks : {0, 1, 4}) check_lane_net(F, TE, nblocks);
     if (failures) {
         std::printf("%d failures\n", failures);
         return 1;
