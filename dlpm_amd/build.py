@@ -12,6 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
+INCLUDE = os.path.join(HERE, '..', 'include')   # every *.h here and in CSRC is a dependency of every object
 OBJ = os.path.join(HERE, '_obj')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIB_DIR, 'libdlpm_amd.so')
@@ -43,19 +44,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_fd.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_lim.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_toy.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_step.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_chains.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_conv.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_train.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_mlp.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_mlp_grad.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_w1.h'))
-    headers.append(os.path.join(HERE, '..', 'include', 'dlpm_amd_tail.h'))
+    headers = [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in sorted(os.listdir(d)) if f.endswith('.h')]
     jobs = []
     objs = []
     for src in SOURCES:

@@ -4,53 +4,13 @@ cover, which (family, n-tile, split-K) combinations a 3x3 stride-1 layer can rea
 all of them before anything is enqueued."""
 import ctypes as C
 import itertools
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from dlpm_amd import _lib
 from conv_policy_cases import CASES, NARROW, SPLIT, case_route, descriptor, out_size, query, r0_of, route_tuple, slices
 from metric_helpers import buffers
 
-CONV_SYMBOLS = ('dlpm_conv_policy_route', 'dlpm_conv_policy_f32')
-
-
-# ---------------------------------------------------------------- ABI
-def test_conv_policy_symbols_are_declared_exported_and_bound():
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd_conv.h')).read()
-    assert '#include "dlpm_amd.h"' in header
-    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    assert set(re.findall(r'\b(dlpm_conv_policy_[a-z0-9_]+)\s*\(', code)) == set(CONV_SYMBOLS) == set(_lib.SIGNATURES_CONV)
-    integration = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    L = _lib.lib()
-    for name in CONV_SYMBOLS:
-        assert name in integration and list(getattr(L, name).argtypes) == _lib.SIGNATURES_CONV[name][1]
-    assert len(_lib.SIGNATURES) == 100
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_FD, _lib.SIGNATURES_LIM, _lib.SIGNATURES_TOY, _lib.SIGNATURES_CHAINS):
-        assert not set(other) & set(_lib.SIGNATURES_CONV)
-    assert _lib.ABI_VERSION == 6 and L.dlpm_abi_version() == 6
-    assert '+ 2 in `dlpm_amd_conv.h`' in open(os.path.join(ROOT, 'README.md')).read()
-    families = re.search(r'typedef enum dlpm_conv_family \{(.*?)\}', code, flags=re.S).group(1)
-    assert [(n, int(v)) for n, v in re.findall(r'DLPM_CONV_FAMILY_([A-Z0-9_]+) = (\d+)', families)] == list(
-        zip(_lib.CONV_FAMILIES, range(10)))
-
-
-def test_header_compiles_as_plain_c_with_the_mirrored_layout(tmp_path):
-    src = tmp_path / 'conv_header.c'
-    src.write_text('#include <stddef.h>\n#include "dlpm_amd_conv.h"\n'
-                   'typedef char size_is_56[sizeof(dlpm_conv_route) == 56 ? 1 : -1];\n'
-                   'typedef char ksplit_at_24[offsetof(dlpm_conv_route, ksplit) == 24 ? 1 : -1];\n'
-                   'typedef char grid_at_32[offsetof(dlpm_conv_route, grid) == 32 ? 1 : -1];\n'
-                   'typedef char partial_at_48[offsetof(dlpm_conv_route, partial_floats) == 48 ? 1 : -1];\n'
-                   'int use(const dlpm_conv_args *a, dlpm_conv_route *r) { return dlpm_conv_policy_route(a, DLPM_CONV_AUTO, 64, r) +\n'
-                   '    dlpm_conv_policy_f32(a, DLPM_CONV_F4, 0, NULL, NULL, 0, NULL, NULL, r, NULL) + DLPM_CONV_FAMILY_DIRECT; }\n')
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'),
-                           str(src)])
-    R = _lib.ConvRoute
-    assert (C.sizeof(R), R.ksplit.offset, R.grid.offset, R.partial_floats.offset) == (56, 24, 32, 48)
 
 
 # ---------------------------------------------------------------- the case table

